@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: MXFP4 GEMM 4096x4096x4096 (BASELINE.json configs[1]) on N MI355X GPUs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one matmul_mxf4_bf16_tn over pre-quantised, HBM-resident operands ("ideal" provider of the
@@ -9,11 +9,17 @@ reference's own harness, benchmarks/bench_mxfp4_sm120.py:27-31,109-127).  The pa
 contraction with no exchange step, so ranks are independent replicas over the same shapes: `value` is
 the sum of the ranks' work over the max-over-ranks time ("scaling": "weak", no data-path collective).
 
-Prints ONE JSON line on rank 0 with `roofline` (MFMA-bound: FLOP/s of the dominant kernel from HIP
-events on the launch stream vs the FP4 dense peak of MI355X_MICROARCH.md) and `cpu_baseline` (the
-reference's dequantise + torch.matmul oracle path timed on this host's cores, bounded sample).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: `value`, `ms_per_step` and
+`roofline` (MFMA-bound: FLOP/s of the dominant kernel from the HIP events around the same K steps vs the FP4
+dense peak of MI355X_MICROARCH.md).  `--dump-outputs DIR` then writes what the last timed step returned
+(dump_outputs: a fixed sample of its rows as float32), from inputs that are the same in every run.
 
-Round 3: the same line also carries (i) `configs` -- the other BASELINE.json configs (C3 GEMM / C3 step / C4 / C5 TN / C5 NN), each
+`--full` adds every side measurement below to the same line (each after the timed region): `cpu_baseline` (the
+reference's dequantise + torch.matmul oracle path timed on this host's cores) with the parity of the measured op
+against it, `roofline.per_launch_us`, `roofline.same_kernel_on_zero_operands`, `roofline.traffic`, `power` and
+`configs`; `--no-cpu-baseline`, `--no-configs` and `--no-pmc` leave single ones out of a `--full` run.
+
+Round 3: the full line also carries (i) `configs` -- the other BASELINE.json configs (C3 GEMM / C3 step / C4 / C5 TN / C5 NN), each
 timed with HIP events on the launch stream after the headline's timed region, with its own roofline fraction; (ii) `power` -- socket
 power and shader clock sampled through librocm_smi64 on a host thread WHILE the timed region runs (the headline kernel sits at the
 socket power limit: the clock it gets is part of the result); (iii) `roofline.traffic` measured FRESH: after the timed region the
@@ -51,6 +57,7 @@ FP4_SUSTAINED_RANDOM_TFLOPS = 6550.0
 PMC_TRAFFIC_ENV = "QAMD_PMC_TRAFFIC_JSON"
 M = N = K = 4096
 CPU_ROWS = 4096  # cpu_baseline sample: the whole workload (measured 3.2 s per 1024 rows on the 256-thread host)
+DUMP_ROWS = 2048  # --dump-outputs: half the rows of the 4096 x 4096 output (32 MiB as float32; all of it would be 64 MiB)
 
 
 def hadamard(n, device):
@@ -347,6 +354,17 @@ def dominant_kernel_name():
     return names.get(plan[0], f"gemm variant {plan[0]}") if plan else "unknown", plan
 
 
+def dump_outputs(dirname, out):
+    """--dump-outputs DIR: the (M, N) bf16 output of the last timed step as DIR/out.npy, float32 (exact for bf16).  Only the rows
+    sorted(numpy.random.default_rng(0).choice(M, DUMP_ROWS, replace=False)) are written: a fixed sample, the same in every run."""
+    import numpy as np
+
+    rows = np.sort(np.random.default_rng(0).choice(M, DUMP_ROWS, replace=False))
+    sample = out[torch.from_numpy(rows).to(out.device)].float().cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "out.npy"), sample)
+
+
 def percentile(sorted_vals, p):
     if not sorted_vals:
         return None
@@ -376,15 +394,22 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C3 / C4 / C5 side measurements")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child runs (roofline.traffic = null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/out.npy (float32, a fixed sample of rows; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the side measurements after the timed region: per-launch pass, socket power, zero-operand run, rocprofv3 --pmc "
+                         "traffic, C3 / C4 / C5 configs, CPU baseline with the parity slab")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity slab")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C3 / C4 / C5 side measurements and the zero-operand run")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two rocprofv3 --pmc child runs (roofline.traffic = null)")
     ap.add_argument("--pmc-child", type=int, default=0, metavar="N",
                     help="internal: set the headline operands up, launch the headline op N times and exit (the command the --pmc passes profile)")
     ap.add_argument("--ramp-ms", type=float, default=250.0,
                     help="untimed load before the W warmup steps: an idle MI355X needs ~50 ms under load to leave its clock "
                          "ramp (tools/clock_ramp.py: 54 -> 42 -> 38 -> 36.7 us/step over the first 40 ms)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -418,7 +443,7 @@ def main():
             step()
         torch.cuda.synchronize()
         return
-    sampler = PowerSampler(local_rank) if rank == 0 else None
+    sampler = PowerSampler(local_rank) if rank == 0 and args.full else None
 
     # ---- clock ramp (untimed, not part of the W warmup steps): bring the part to its steady clock / power state ----
     ramp_steps = 0
@@ -458,22 +483,26 @@ def main():
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # average launch-to-launch duration of the GEMM kernel
 
     wall = max_over_ranks(wall, dev if world > 1 else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # ---- the reference's protocol as a separate pass: individually timed launches, median / p20 / p80 ----------------
-    nrep = max(200, min(args.steps, 1000))
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(nrep + 1)]
-    for _ in range(25):
-        out = step()
-    evs[0].record(stream)
-    for i in range(nrep):
-        out = step()
-        evs[i + 1].record(stream)
-    torch.cuda.synchronize()
-    per = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(nrep))
-    if sampler:
-        sampler.mark("per_launch_end")
-    per_launch = {"n": nrep, "median": round(percentile(per, 0.5), 3), "p20": round(percentile(per, 0.2), 3), "p80": round(percentile(per, 0.8), 3),
-                  "min": round(per[0], 3), "note": "one HIP event pair per launch, after the timed region (bench_mxfp4_sm120.py:109-125 protocol)"}
+    per_launch = None
+    if args.full:
+        nrep = max(200, min(args.steps, 1000))
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nrep + 1)]
+        for _ in range(25):
+            out = step()
+        evs[0].record(stream)
+        for i in range(nrep):
+            out = step()
+            evs[i + 1].record(stream)
+        torch.cuda.synchronize()
+        per = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(nrep))
+        if sampler:
+            sampler.mark("per_launch_end")
+        per_launch = {"n": nrep, "median": round(percentile(per, 0.5), 3), "p20": round(percentile(per, 0.2), 3), "p80": round(percentile(per, 0.8), 3),
+                      "min": round(per[0], 3), "note": "one HIP event pair per launch, after the timed region (bench_mxfp4_sm120.py:109-125 protocol)"}
 
     kname, kplan = dominant_kernel_name()
     flop_per_step = 2.0 * M * N * K
@@ -537,7 +566,7 @@ def main():
             result["power"] = None
     # [r5] the same kernel, same shape, ALL-ZERO operands under unit scales (nothing toggles in the matrix pipe, the clock stays up): what the SCHEDULE delivers without the
     # socket's power cap.  A reported side figure, after the timed region, never `value` / `roofline.frac` (tools/power_data_probe.py has the longer form).
-    if rank == 0 and world == 1 and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_configs:
         try:
             zq_a, zq_b = torch.zeros_like(a_q), torch.zeros_like(b_q)
             one_a = torch.full_like(a_sf.view(torch.uint8), 127).view(a_sf.dtype)
@@ -556,7 +585,7 @@ def main():
         except Exception as e:   # noqa: BLE001 -- a side measurement must not cost the headline line
             result["roofline"]["same_kernel_on_zero_operands"] = {"error": f"{type(e).__name__}: {e}"}
     # HBM-side bytes per launch of this kernel: fresh PMC passes (see fresh_traffic), rank 0 of a single-GPU run only
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         tj, note = None, "skipped (--no-pmc)"
         fresh = os.environ.get(PMC_TRAFFIC_ENV)
         if fresh:
@@ -585,7 +614,7 @@ def main():
         sampler.stop()
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb, ref = cpu_baseline(a_q, a_s, b_q, b_s, rows=CPU_ROWS)
             result["cpu_baseline"] = cb
             # parity of the measured op against the same slab (exact bf16 equality, as the reference asserts)

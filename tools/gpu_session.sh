@@ -4,7 +4,7 @@
 # writes everything under gpurun_out/<name>/ and prints a one-line verdict per step.  Steps:
 #   testsk    the stream-K parity tests only, short timeout (a wrong flag protocol would hang)
 #   tests4    tests/test_gpu_round4.py (fail-fast)            suite     the whole -m gpu suite
-#   smoke     __graft_entry__.smoke()                         bench     bench.py (driver protocol) + a summary of its JSON line
+#   smoke     __graft_entry__.smoke()                         bench     bench.py --full + a summary of its JSON line
 #   pmc       tools/pmc_bench.sh (kernel-trace + FETCH_SIZE / WRITE_SIZE passes of the bench command + a fresh-traffic bench line)
 #   abnv      tools/ab_nvpk.py --trace (persistent NVFP4 kernel vs per-tile kernel vs torch bf16; stage trace)
 #   vendor    tools/vendor_ab.py (hipBLASLt block-scaled GEMM through torch beside ours, power / clock)
@@ -33,7 +33,7 @@ for step in "$@"; do
     tests4) timeout 900 python -m pytest tests/test_gpu_round4.py -x -q > $O/pytest_round4.log 2>&1; echo "tests4 rc=$?"; tail -3 $O/pytest_round4.log ;;
     suite)  timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "suite rc=$?"; tail -3 $O/pytest_gpu.log ;;
     smoke)  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log ;;
-    bench)  timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+    bench)  timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
             python - $O/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d['roofline']
