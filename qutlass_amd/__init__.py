@@ -6,6 +6,7 @@ meaning, defaults and Python-level error behaviour):
     fusedQuantizeMx, fusedQuantizeNv, matmul_mxf4_bf16_tn, matmul_nvf4_bf16_tn,
     matmul_mxf8_bf16_tn, matmul_mxf8_bf16_nn         (+ qutlass_amd.utils.to_blocked & friends)
     matmul_ada_mxf4_bf16_tn, backward_t_bf16, backward_qt_bf16, backward_bf16_square_double_mxfp8, mxfp4_transpose_mxfp8
+    grouped_matmul_mxf4_bf16_tn                      (extension: mixture-of-experts layers, one launch over all experts)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -54,6 +55,24 @@ def matmul_ada_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor
                             alpha: torch.Tensor) -> torch.Tensor:
     """qutlass/__init__.py:79-86: small-batch MXFP4 GEMM taking the UN-swizzled (rows, K/32) scales."""
     return qutlass_CUDA.matmul_ada_mxf4_bf16_tn(a, b, a_sf, b_sf, alpha)
+
+
+def grouped_matmul_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,
+                                alpha: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): grouped MXFP4 GEMM for mixture-of-experts layers, one launch over all experts.
+
+    a      (M, K/2) uint8 / float4_e2m1fn_x2 -- the tokens, sorted by expert
+    b      (E, N, K/2) uint8 / float4_e2m1fn_x2 -- the stacked expert weights
+    a_sf   float8_e8m0fnu, >= M*K/32 elements, read as row-major (M, K/32): fusedQuantizeMx's scale buffer as is (like matmul_ada_mxf4_bf16_tn)
+    b_sf   float8_e8m0fnu, >= E*N*K/32 elements, read as row-major (E, N, K/32)
+    alpha  float32, 1 element (shared) or E elements (per expert)
+    offs   int32 (E,): the cumulative END rows of the groups (torch._grouped_mm's convention) -- group g is rows [offs[g-1], offs[g]), offs[-1] := 0
+
+    Returns out (M, N) bf16 with out[r] = alpha[g] * (A_r . SFA) (B_g . SFB_g)^T for every row r of group g.  Empty groups are allowed; rows at or
+    past offs[E-1] are not written (their contents are unspecified, as in torch._grouped_mm).  The offsets are read on the device, so the call
+    needs no host sync and works under graph capture and torch.compile; each offset is clamped to [0, M] and a decreasing one is an empty group.
+    K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; one expert's weight below 2 GiB (the stack may exceed it).  M == 0 returns an empty output."""
+    return _ops_amd.grouped_matmul_mxf4(a, b, a_sf, b_sf, alpha, offs)
 
 
 def matmul_nvf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,

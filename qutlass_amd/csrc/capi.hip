@@ -398,6 +398,43 @@ inline int os8_plan(int64_t M, int64_t N, int64_t K) {
   return (T64 <= cus && KT > 16 && KT <= 128) ? 570 : 0;
 }
 
+// ---- grouped MXFP4 GEMM (gemm_mx_grouped.hip.h): one launch over E experts ----------------------------------------------------------------------------------------
+// Forms: 590 = 32x32 tiles of the wave-owned kernel, 591 = 32x16, 592 = 64x32 (one shot while a tile's K extent fits the LDS, wave-owned rings beyond), 593 = the 64x64
+// ring kernel with row-major scale fetch.  Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B (profiles/calib_grouped_r7.txt): the per-workgroup
+// cost of a grouped tile (the offsets' round trip before the first weight request) favours the fewest, largest tiles -- 593 is fastest everywhere except a short K
+// (Qwen3 down, K = 768, 4 rows per expert: 37.6 us against 41.0), where the wave-owned kernel's single round trip wins; 591 and 592 never lead.  So: mean rows per group
+// M / E <= 32 and K <= 1024 -> 590, otherwise 593.  N and the CU count are arguments so that a rule re-taken from more measurements can use them.
+inline int grouped_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M <= 32 * E && K <= 1024) ? 590 : 593;
+}
+// workgroups of a form: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles
+inline int64_t grouped_grid(int v, int64_t M, int64_t N, int64_t E) {
+  const int TM = v == 590 || v == 591 ? 32 : 64, TN = v == 591 ? 16 : v == 593 ? 64 : 32;
+  return (cdiv(M, TM) + E) * cdiv(N, TN);
+}
+template <int TM, int TN>
+int launch_grouped_os(GroupedParams q, hipStream_t s) {
+  q.tiles_m = 1;
+  q.tiles_n = (int)cdiv(q.N, TN);
+  const int64_t KT = cdiv((int64_t)q.K / 2, 128);
+  const dim3 grid((int)((cdiv(q.M, TM) + q.E) * q.tiles_n)), block(256);   // the bound of the real tiles (grouped_tile: the rest return at once)
+  constexpr int SMAX = TM == 32 ? 4 : 3;   // slots per wave that fit the LDS (launch_gemm_os)
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<1, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<2, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
+  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<3, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, 4, TM>, true, true, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  return check_launch("gemm_mx_os_kernel (grouped)");
+}
+template <class C>
+int launch_grouped_ring(GroupedParams q, hipStream_t s) {
+  q.tiles_m = 1;
+  q.tiles_n = (int)cdiv(q.N, C::BN);
+  hipLaunchKernelGGL((gemm_mx_grouped_ring_kernel<C>), dim3((int)((cdiv(q.M, C::BM) + q.E) * q.tiles_n)), dim3(C::THREADS), 0, s, q);
+  return check_launch("gemm_mx_grouped_ring_kernel");
+}
+
 // [r4] stream-K form of the two persistent kernels (lab variant 89): one workgroup per CU; p.ws / p.ctr / p.tag / p.sk_tiles set by gemm_mx
 #if QAMD_BENCH
 template <class C>
@@ -1349,6 +1386,46 @@ int qutlass_amd_matmul_ada_mxf4_bf16_tn(const void* A, const void* B, const void
   return ada_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, 0, stream);
 }
 
+// grouped_matmul_mxf4_bf16_tn: every argument is checked before any HIP call
+static int grouped_check(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                         const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E) {
+  if (!A || !B || !A_sf || !B_sf || !alpha || !offs || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (E < 1 || E > GRP_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, GRP_MAX_E, (long long)E);
+  if (n_alpha != 1 && n_alpha != E) return fail(QAMD_ERR_INVALID, "%s: alpha must have 1 or E = %lld elements (got %lld)", name, (long long)E, (long long)n_alpha);
+  if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
+  if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
+  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
+  if (N * (K / 2) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * K/2 = %lld bytes) must stay below 2 GiB", name, (long long)(N * (K / 2)));
+  if (M * (K / 2) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * K/2 = %lld bytes) must stay below 2 GiB", name, (long long)(M * (K / 2)));
+  if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
+  for (int v = 590; v <= 593; ++v)
+    if (grouped_grid(v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
+  return QAMD_OK;
+}
+
+int qutlass_amd_grouped_matmul_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                            const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  const char* name = "grouped_matmul_mxf4_bf16_tn";
+  if (int rc = grouped_check(name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if (M == 0) return QAMD_OK;
+  const int forced = opt_gemm_variant();   // lab: 590 ... 593 force a form
+  const int v = (forced >= 590 && forced <= 593) ? forced : grouped_plan(M, N, K, E, chip_cus());
+  const int64_t rowbytes = K / 2, KB = K / 32;
+  GroupedParams q;
+  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
+  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
+  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * rowbytes);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
+  q.sfa_bytes = (uint32_t)(M * KB); q.sfb_bytes = (uint32_t)(N * KB);
+  q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
+  q.ws = nullptr; q.splits = 1; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha;
+  hipStream_t s = (hipStream_t)stream;
+  if (v == 590) return launch_grouped_os<32, 32>(q, s);
+  if (v == 591) return launch_grouped_os<32, 16>(q, s);
+  if (v == 592) return launch_grouped_os<64, 32>(q, s);
+  return launch_grouped_ring<GroupedRingCfg>(q, s);   // matmul_ada_mxf4_bf16_tn's ring tiles
+}
+
 int qutlass_amd_matmul_mxf8_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
                                     const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream) {
   return gemm_mx<8>("matmul_mxf8_bf16_tn", A, B, A_sf, B_sf, alpha, D, M, N, K, stream);
@@ -1935,6 +2012,34 @@ int qutlass_amd_debug_raster_decode(int tiles_m, int tiles_n, int t0, int n, int
   const uint32_t magic = qamd::raster_magic(tiles_n);
   for (int i = 0; i < n; ++i) qamd::raster_decode(t0 + i, tiles_m, tiles_n, magic, out[2 * i], out[2 * i + 1]);
   return n;
+}
+
+// debug only (not declared in the public header): the tile decode of grouped_matmul_mxf4_bf16_tn (gemm_mx_grouped.hip.h grouped_tile, the SAME lane functions the
+// device runs) for workgroups [0, nwg) of TM-row tiles and tiles_n column tiles over host offs[0 .. E): out[4 b .. 4 b + 3] = {expert, first row, rows, column tile} of
+// workgroup b ({-1, 0, 0, 0}: no work).  Returns the number of workgroups with work, or -1 when the arguments are rejected.  No GPU touched.
+int qutlass_amd_debug_grouped_decode(const int32_t* offs, int E, int M, int TM, int tiles_n, int nwg, int* out) {
+  if (!offs || !out || E < 1 || E > qamd::GRP_MAX_E || M < 0 || TM <= 0 || tiles_n <= 0 || nwg < 0) return -1;
+  int n = 0;
+  for (int b = 0; b < nwg; ++b) {
+    qamd::GroupTile t;
+    if (qamd::grouped_tile(offs, E, M, TM, tiles_n, b, t)) {
+      out[4 * b] = t.g; out[4 * b + 1] = t.row0; out[4 * b + 2] = t.rows; out[4 * b + 3] = t.nt;
+      ++n;
+    } else {
+      out[4 * b] = -1; out[4 * b + 1] = 0; out[4 * b + 2] = 0; out[4 * b + 3] = 0;
+    }
+  }
+  return n;
+}
+
+// debug only: the form grouped_matmul_mxf4_bf16_tn picks (590 = 32x32, 592 = 64x32 tiles of the wave-owned kernel, 593 = the 64x64 ring kernel) on a 256-CU part,
+// after the entry's own argument checks (-1: rejected); out[0] (optional) = the workgroups it launches.  No GPU touched.
+int qutlass_amd_debug_grouped_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  alignas(16) static char dummy[16];
+  if (grouped_check("debug_grouped_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E)) return -1;
+  const int v = grouped_plan(M, N, K, E, 256);
+  if (out) out[0] = M == 0 ? 0 : grouped_grid(v, M, N, E);
+  return v;
 }
 
 // debug only (not declared in the public header): what matmul_nvf4_bf16_tn's rule picks for an M x N x K problem (gemm_nvf4.hip.h: nvf4_plan; 256 CUs assumed,

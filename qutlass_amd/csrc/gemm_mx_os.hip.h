@@ -17,6 +17,7 @@
 // to the other schedules wherever partial sums are exact (the reference's test regime), one fp32 rounding apart otherwise, like every split-K plan here.
 #pragma once
 #include "gemm_mx.hip.h"
+#include "gemm_mx_grouped.hip.h"
 #include "quantize.hip.h"
 
 namespace qamd {
@@ -53,24 +54,31 @@ struct OsCfg {
 
 // RM: the scale operands are row-major (rows, K / 32) as matmul_ada_mxf4_bf16_tn hands them over (qutlass/csrc/gemm_ada.cu) instead of the to_blocked image
 // RING: any K -- the wave's SPW slots are refilled as they are consumed (false: at most 4 SPW stages, every stage has a slot of its own)
-template <class C, bool RM = false, bool RING = false>
-__global__ __launch_bounds__(256) void gemm_mx_os_kernel(const GemmParams p) {
+// GRP: one launch of grouped_matmul_mxf4_bf16_tn (gemm_mx_grouped.hip.h) -- the workgroup decodes its tile from the group offsets: origin, the group's end row (A / A-scale
+// ranges and stores end there), expert g's B / B-scales / alpha; the rest is this body unchanged (false: the plain kernel, the same code as before the parameter existed)
+template <class C, bool RM = false, bool RING = false, bool GRP = false>
+__global__ __launch_bounds__(256) void gemm_mx_os_kernel(const std::conditional_t<GRP, GroupedParams, GemmParams> p) {
   constexpr int SPW = C::SPW, LPS = C::LPS, MT = C::MT, KSL = C::KSL, E8 = C::EBITS == 8;
   static_assert(!(RM && E8), "row-major scales: matmul_ada_mxf4_bf16_tn only");
+  static_assert(!GRP || (RM && !E8), "grouped: MXFP4 with row-major scales");
   __shared__ __attribute__((aligned(16))) char smem[C::LDS_BYTES];
+  GroupedView gv{};
+  if constexpr (GRP) {
+    if (!grouped_setup<C::TM, C::TN>(p, gv)) return;   // an m-tile slot past the real tiles: no work
+  }
   asm volatile("" :: "s"(p.A), "s"(p.D), "s"(p.K), "s"(p.b_bytes), "s"(p.alpha));   // all scalar argument loads in one round
-  const float alpha = *p.alpha;
+  const float alpha = *(GRP ? gv.alpha : p.alpha);
   const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6), i32 = lane & 31, g = lane >> 5;
   // tile: workgroups that share a B row tile are neighbours (and stay on one XCD: xcd_remap)
   const int nb = p.tiles_m * p.tiles_n;
   const int b2 = xcd_remap((int)blockIdx.x, nb);
-  const int m0 = uniform((b2 % p.tiles_m) * C::TM), n0 = uniform((b2 / p.tiles_m) * C::TN);
+  const int m0 = GRP ? gv.m0 : uniform((b2 % p.tiles_m) * C::TM), n0 = GRP ? gv.n0 : uniform((b2 / p.tiles_m) * C::TN);
   const int rowbytes = E8 ? p.K : p.K >> 1, KT = (rowbytes + C::ROWB - 1) / C::ROWB, CB = (p.K / 32 + 3) >> 2;
   const int tailbytes = rowbytes - (KT - 1) * C::ROWB;   // bytes per row of the last stage
 
   // ---- LDS-DMA sources --------------------------------------------------------------------------------------------------------------
   const uint32_t a_off = (uint32_t)m0 * rowbytes, b_off = (uint32_t)n0 * rowbytes;
-  const __amdgpu_buffer_rsrc_t rA = make_rsrc(p.A + a_off, p.a_bytes - a_off), rB = make_rsrc(p.B + b_off, p.b_bytes - b_off);
+  const __amdgpu_buffer_rsrc_t rA = make_rsrc(p.A + a_off, (GRP ? gv.a_bytes : p.a_bytes) - a_off), rB = make_rsrc((GRP ? gv.B : p.B) + b_off, p.b_bytes - b_off);
   // piece qq of an operand tile = rows 8 qq .. + 7; lane -> row 8 qq + (l >> 3), physical chunk l & 7 = logical chunk ^ ((row >> 1) & 7): only the parity of qq matters
   int vP[2], chP[2];
 #pragma unroll
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(256) void gemm_mx_os_kernel(const GemmParams p) {
   // fp8: the stage is column tile kt; both lane halves fetch the row's dword (TM = 64: lane half g fetches m-tile g's)
   const int KB = p.K >> 5;
   const uint32_t sa_off = RM ? (uint32_t)m0 * KB : (uint32_t)(m0 >> 7) * CB * 512, sb_off = RM ? (uint32_t)n0 * KB : (uint32_t)(n0 >> 7) * CB * 512;
-  const __amdgpu_buffer_rsrc_t rSA = make_rsrc(p.SFA + sa_off, p.sfa_bytes - sa_off), rSB = make_rsrc(p.SFB + sb_off, p.sfb_bytes - sb_off);
+  const __amdgpu_buffer_rsrc_t rSA = make_rsrc(p.SFA + sa_off, (GRP ? gv.sfa_bytes : p.sfa_bytes) - sa_off), rSB = make_rsrc((GRP ? gv.SFB : p.SFB) + sb_off, p.sfb_bytes - sb_off);
   const int rowB = (n0 & 127) + i32;   // row of the 128-row scale tile (TN = 16: n0 is a multiple of 16 only; lanes past the 16 rows fetch some row's dword -- unused)
   const int mq = (m0 & 127) >> 5;      // 32-row slab of the 128-row scale tile the A tile starts in
   const int gcol = E8 ? 0 : g * 512;   // fp4: lane half g takes column tile 2 kt + g
@@ -228,7 +236,7 @@ __global__ __launch_bounds__(256) void gemm_mx_os_kernel(const GemmParams p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) t[e] = ((s[0][e] + s[1][e]) + s[2][e]) + s[3][e];
     const int row = m0 + rr, col = n0 + 4 * cq;
-    if (row < p.M && col < p.N && 4 * cq < C::TN) {
+    if (row < (GRP ? gv.M : p.M) && col < p.N && 4 * cq < C::TN) {
       v2i o;
       o[0] = (int)pack_bf16x2(t[0] * alpha, t[1] * alpha);
       o[1] = (int)pack_bf16x2(t[2] * alpha, t[3] * alpha);

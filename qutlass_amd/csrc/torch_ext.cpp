@@ -173,6 +173,34 @@ Tensor matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor
   return out;
 }
 
+// EXTENSION: grouped MXFP4 GEMM for mixture-of-experts layers (qutlass_amd_grouped_matmul_mxf4_bf16_tn).  A (M, K/2) tokens sorted by expert, B (E, N, K/2) stacked
+// expert weights, row-major e8m0 scales, alpha of 1 or E elements, offs int32 (E,) cumulative end rows.  Rows at or past offs[E-1] are not written (left as allocated).
+Tensor grouped_matmul_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
+  const char* op = "grouped_matmul_mxf4";
+  require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  STD_TORCH_CHECK(has_dtype(A, ScalarType::Byte) || has_dtype(A, ScalarType::Float4_e2m1fn_x2), "A must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), "B must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(A_sf, ScalarType::Float8_e8m0fnu), "A_sf must be float8_e8m0fnu");
+  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e8m0fnu), "B_sf must be float8_e8m0fnu");
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
+  STD_TORCH_CHECK(A.size(1) == B.size(2), "Inner dimensions must match for A @ B[g].T");
+  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * 2;
+  STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
+  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
+  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
+  STD_TORCH_CHECK(A_sf.numel() >= M * (K / 32), "A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * (K / 32));
+  STD_TORCH_CHECK(B_sf.numel() >= E * N * (K / 32), "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * (K / 32));
+  Tensor out = torch::stable::new_empty(A, {M, N}, ScalarType::BFloat16);
+  if (M == 0 || N == 0) return out;   // empty batch: nothing to launch
+
+  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
+  check_rc(qutlass_amd_grouped_matmul_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()),
+                                                   alpha.numel(), static_cast<const int32_t*>(offs.data_ptr()), out.data_ptr(), M, N, K, E, current_stream(A)));
+  return out;
+}
+
 Tensor matmul_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_ada_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::ADA_MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_nvf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::NVF4>(A, B, A_sf, B_sf, alpha); }
@@ -454,6 +482,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("mxfp4_transpose_mxfp8_(Tensor x_fp4, Tensor scales, Tensor(a!) x_fp8, Tensor(b!) shared_exps) -> ()");
 #endif
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
+  m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
 }
 
 // CUDA dispatch key only, as the reference (bindings.cpp:516-535); there is no CPU compute path.
@@ -489,6 +518,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("mxfp4_transpose_mxfp8_", TORCH_BOX(&mxfp4_transpose_mxfp8));
 #endif
   m.impl("fusedQuantizeMatmulMxf4", TORCH_BOX(&fusedQuantizeMatmulMxf4));
+  m.impl("grouped_matmul_mxf4", TORCH_BOX(&grouped_matmul_mxf4));
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module
