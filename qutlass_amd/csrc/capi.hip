@@ -143,22 +143,12 @@ constexpr uint32_t* opt_dbg() { return nullptr; }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Dry run (qutlass_amd_debug_gemm_plan): the dispatch code below runs unchanged, but instead of launching it records
-// which kernels it WOULD launch -- {variant, N of the launch, K splits} per launch -- so the auto rules are testable on a
-// machine without a GPU (tests/test_cabi_and_host.py).
-struct DryRun { bool on = false; int n = 0; int rec[8][3]; };
-#if QAMD_DEF(1)
-thread_local DryRun t_dry;
-#else
-extern thread_local DryRun t_dry;
-#endif
 // Compute units of the current device, asked once per device (hipDeviceAttributeMultiprocessorCount: 256 on an MI355X in SPX
 // mode; fewer in a partitioned / CU-masked configuration).  Every grid size and occupancy threshold below derives from it.
 // (The kernels' blockIdx -> XCD remap assumes the dispatcher's round-robin over 8 XCDs; it is a bijection for any grid, so
-// on another XCD count it only costs L2 locality.)  The dry-run hook describes a full MI355X whatever the machine.
+// on another XCD count it only costs L2 locality.)  The dispatch rules take the count as an argument: the debug entries pass 256.
 #if QAMD_DEF(1)
 int chip_cus() {
-  if (t_dry.on) return 256;
   static std::atomic<int> cache[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -174,13 +164,6 @@ int chip_cus() {
 #else
 int chip_cus();
 #endif
-
-inline bool dry_record(int variant, int n_cols, int splits) {
-  if (!t_dry.on) return false;
-  if (t_dry.n < 8) { t_dry.rec[t_dry.n][0] = variant; t_dry.rec[t_dry.n][1] = n_cols; t_dry.rec[t_dry.n][2] = splits; }
-  ++t_dry.n;
-  return true;
-}
 
 
 template <class C, int PP>
@@ -303,8 +286,7 @@ int launch_gemm_os16(GemmParams p, hipStream_t s) {
   return check_launch("gemm_mx_os16_kernel");
 }
 // columns per workgroup of the decode form for M <= 16: the narrowest of 16 / 32 / 48 / 56 / 64 that leaves at most one workgroup per CU; 0 = none does
-inline int os16_tn(int64_t N) {
-  const int64_t cus = chip_cus();
+inline int os16_tn(int64_t N, int64_t cus) {
   for (int tn : {16, 32, 48, 56, 64})
     if (cdiv(N, tn) <= cus) return tn;
   return 0;
@@ -315,8 +297,8 @@ inline int os16_tn(int64_t N) {
 // 7.5-8.0 -> 5.6-6.1, 16384 x 4096 -7 %; N = 5120 ... 8192 (32 columns against the 32x32 form's 64 rows per stage) -3 ... -7 % at K = 3072 ... 8192, +3 % at K = 2048.
 // Past the one-shot range the wider forms lose (14336 x 8192: +3 %).  MXFP8: 32 columns -6 ... -12 % at K = 2048 ... 8192, 48 columns -9 % at 11008 x 4096; 14336 x 4096 loses.
 // Returns the variant or 0.
-inline int os16_wide_plan(int ebits, int64_t N, int64_t K) {
-  const int tn = os16_tn(N);
+inline int os16_wide_plan(int ebits, int64_t N, int64_t K, int64_t cus) {
+  const int tn = os16_tn(N, cus);
   const int64_t KT = cdiv(K * ebits / 8, 128);
   if (ebits == 4) {
     if (tn == 32) return (KT >= 12 && KT <= 32) ? 572 : 0;
@@ -346,8 +328,8 @@ int launch_gemm_os16_tn(int tn, const GemmParams& p, hipStream_t s) {
 // they fill half of it (N = 1024, K = 14336: 32 workgroups take 7.4 us where the split-K plans take 5.7-6.9); with 32 columns per workgroup the blocked-scale op also keeps
 // M < 8 against more than 32 stages on the LDS-free split-K kernel (4096 x 11008, M = 1: 6.07 vs 6.40 us).  ada: matmul_ada_mxf4_bf16_tn (row-major scales: its other
 // kernels are 25-45 % slower on every such shape).  profiles/calib_os_r6q.txt, calib_osring_r6q.txt, calib_ada_r6q.txt, calib_os16_r6s.txt
-inline int os_plan(int64_t M, int64_t N, int64_t K, bool ada = false) {
-  const int64_t cus = chip_cus(), T32 = cdiv(M, 32) * cdiv(N, 32), T16 = cdiv(M, 32) * cdiv(N, 16), KT = cdiv(K, 256);
+inline int os_plan(int64_t M, int64_t N, int64_t K, int64_t cus, bool ada = false) {
+  const int64_t T32 = cdiv(M, 32) * cdiv(N, 32), T16 = cdiv(M, 32) * cdiv(N, 16), KT = cdiv(K, 256);
   if (T32 > cus) return 0;
   const int tn = T16 <= cus ? 16 : 32;
   if (KT <= 16) return tn;
@@ -364,8 +346,8 @@ inline int os_plan(int64_t M, int64_t N, int64_t K, bool ada = false) {
 // 32 stages on every CU: 11.65 -> 9.66).  profiles/calib_os2_fp4_r7.txt
 // ada: matmul_ada_mxf4_bf16_tn has no scratch argument, so no split-K plan competes -- every measured K wins there (4096 x 4096, M = 96 / 128: 6.5 / 6.7 -> 6.0 / 6.3 us;
 // x 8192: 10.1 -> 8.9; x 14336: 20.9 / 22.6 -> 14.4 / 15.3; profiles/calib_ada_570_r7.txt)
-inline bool os64_plan(int64_t M, int64_t N, int64_t K, bool ada = false) {
-  const int64_t cus = chip_cus(), T32 = cdiv(M, 32) * cdiv(N, 32), T64 = cdiv(M, 64) * cdiv(N, 32), KT = cdiv(K, 256);
+inline bool os64_plan(int64_t M, int64_t N, int64_t K, int64_t cus, bool ada = false) {
+  const int64_t T32 = cdiv(M, 32) * cdiv(N, 32), T64 = cdiv(M, 64) * cdiv(N, 32), KT = cdiv(K, 256);
   if (T32 <= cus || T64 > cus) return false;
   if (ada) return KT <= 64;
   return KT <= 12 || (KT >= 40 && KT <= 64) || (KT >= 32 && KT < 40 && T64 == cus && M <= 64);   // (the last: 8192^2, M = 64; 4096 x 8192, M = 128 -- two tile rows -- loses 3 %)
@@ -379,10 +361,10 @@ inline bool os64_plan(int64_t M, int64_t N, int64_t K, bool ada = false) {
 //     (2048 x 14336, M = 64: a tie); up to 256 stages (K = 32768) for one m-tile.
 //   * 64-row tiles where the 32-row ones overflow the chip: 17 ... 128 stages (4096 x 8192, M = 96 / 128: 15.6 / 14.8 -> 12.0 / 12.5 us; 8192 x 4096, M = 64: 11.3 -> 9.3;
 //     K <= 2048 ties, K = 28672 loses 13 %).
-inline int os8_plan(int64_t M, int64_t N, int64_t K) {
-  const int64_t cus = chip_cus(), T32 = cdiv(M, 32) * cdiv(N, 32), T16 = cdiv(M, 32) * cdiv(N, 16), T64 = cdiv(M, 64) * cdiv(N, 32), KT = cdiv(K, 128);
+inline int os8_plan(int64_t M, int64_t N, int64_t K, int64_t cus) {
+  const int64_t T32 = cdiv(M, 32) * cdiv(N, 32), T16 = cdiv(M, 32) * cdiv(N, 16), T64 = cdiv(M, 64) * cdiv(N, 32), KT = cdiv(K, 128);
   if (M <= 16) {   // the decode form with 32 / 48 columns per workgroup
-    if (const int v = os16_wide_plan(8, N, K)) return v;
+    if (const int v = os16_wide_plan(8, N, K, cus)) return v;
   }
   if (T32 <= cus) {
     const int v = T16 <= cus ? 569 : 568;
@@ -435,7 +417,7 @@ int launch_grouped_ring(GroupedParams q, hipStream_t s) {
   return check_launch("gemm_mx_grouped_ring_kernel");
 }
 
-// [r4] stream-K form of the two persistent kernels (lab variant 89): one workgroup per CU; p.ws / p.ctr / p.tag / p.sk_tiles set by gemm_mx
+// [r4] stream-K form of the two persistent kernels (lab variant 89): one workgroup per CU; p.ws / p.ctr / p.tag / p.sk_tiles set by mx_launch
 #if QAMD_BENCH
 template <class C>
 int launch_gemm_deepp_sk(GemmParams p, hipStream_t s) {
@@ -564,7 +546,6 @@ int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name
     else if (v == 24 || v == 25 || (v >= 27 && v <= 29)) v += 200;
   }
 #endif
-  if (dry_record(v, p.N, ((v >= 70 && v <= 78) || (v >= 170 && v <= 173)) ? p.splits : 1)) return 0;
   switch (v) {
     // pipelined schedule on a 2-deep LDS ring (gemm_mx_ringp with NSTAGE = 2: the LDS footprint of the round-1 "simple" schedule,
     // two workgroups per CU, but the next stage's fragments are read during this stage's MFMAs): -3 .. -13 % against the
@@ -723,7 +704,6 @@ int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name
 int dispatch_variant_a5(int v, const GemmParams& p, hipStream_t s, const char* name)
 #if QAMD_DEF(4)   // (the e5m2-operand MXFP8 kernels ride with the NVFP4 unit: balances the parallel build)
 {
-  if (dry_record(v, p.N, (v >= 70 && v <= 78) ? p.splits : 1)) return 0;
   switch (v) {
     case 24: return launch_gemm<GemmCfg<128, 128, 2, 2, 8, true, 0, 2, 1>, 9>(p, s);
     case 25: return launch_gemm<GemmCfg<256, 128, 4, 2, 8, true, 0, 2, 1>, 9>(p, s);
@@ -785,7 +765,6 @@ int launch_nvf4_host(const NvGemmParams& p, hipStream_t s, int variant, int* spl
 #endif
 
 #if QAMD_DEF(1)
-// EBITS: 4 = MXFP4, 8 = MXFP8 (TN)
 // Small-output regime: ring schedule (one workgroup per CU with several stages in flight beats the 2-stage simple schedule
 // whenever the tiles do not fill the chip twice), plus split-K over grid.y when 64x64 tiles leave CUs idle and K is long
 // enough to pay for the second pass (>= 32 stages: fp4 K >= 8192).  One function so that the launcher and qutlass_amd_gemm_splitk_workspace_bytes
@@ -812,8 +791,7 @@ inline int64_t splitk_ws_bytes(int variant, int64_t M, int64_t N, int splits) {
 }
 // the round-1/2 rule: thresholds on the tile counts (fitted on sweeps of the in-stream C++ harness, profiles/native_r1_ring.log, native_r2_tilesplit.log)
 template <int EBITS>
-SmallPlan plan_small_rule(int64_t M, int64_t N, int64_t K, bool may_split) {
-  const int64_t cus = chip_cus();
+SmallPlan plan_small_rule(int64_t M, int64_t N, int64_t K, int64_t cus, bool may_split) {
   const int64_t T64 = cdiv(M, 64) * cdiv(N, 64), T128 = cdiv(M, 128) * cdiv(N, 128);
   if (T64 <= cus) {
     const int64_t KT = cdiv(K * EBITS / 8, 128);
@@ -847,10 +825,9 @@ SmallPlan plan_small_rule(int64_t M, int64_t N, int64_t K, bool may_split) {
 // 28.2 / 30.5 us, x 5120 x 25600 27.5 / 28.0 -> 19.5 / 21.1; MXFP8 192 / 256 x 4096 x 14336 30.9 / 31.5 -> 23.0 / 25.3, 96 ... 384 x 5120 x 25600 50 ... 68 -> 30 ... 54,
 // 96 ... 256 x 8192 x 28672 59 ... 84 -> 44 ... 70; three shapes lose 2 - 4 % (MXFP8 16 / 32 x 8192 x 8192, MXFP4 64 x 8192 x 28672).
 template <int EBITS>
-SmallPlan plan_small(int64_t M, int64_t N, int64_t K, bool may_split = true) {
-  const SmallPlan cur = plan_small_rule<EBITS>(M, N, K, may_split);
+SmallPlan plan_small(int64_t M, int64_t N, int64_t K, int64_t cus, bool may_split) {
+  const SmallPlan cur = plan_small_rule<EBITS>(M, N, K, cus, may_split);
   if (cur.variant != 70 && cur.variant != 72 && cur.variant != 73) return cur;      // (71: M > N, not calibrated)
-  const int64_t cus = chip_cus();
   //                                   64x64  64x128 128x128
   static constexpr double A4[3] = {6.07, 6.04, 6.30}, B4[3] = {3.41, 4.80, 6.58}, E4[3] = {0.99, 1.2, 1.2};
   static constexpr double A8[3] = {3.31, 3.79, 2.91}, B8[3] = {3.87, 4.83, 6.41}, E8[3] = {0.90, 1.2, 1.2};
@@ -897,130 +874,77 @@ SmallPlan plan_small(int64_t M, int64_t N, int64_t K, bool may_split = true) {
 // Where it applies it is 11 ... 30 % faster (N = K = 4096: M <= 64 4.9-5.3 -> 4.1-4.5 us; 8192^2: M <= 32 8.8-11.1 -> 7.4-7.8 us), M = 1 ... 8 included (the LDS-free
 // split-K kernel: 4.55-4.92 us at N = K = 4096).  32x64 tiles: only where 32x32 tiles just overflow the chip and 32x64 nearly fill it (N = 14336: -6 %).
 // Returns the variant (568 / 569 / 570 / 571 / 561 / 562) or 0.
-inline int ks_plan(int64_t M, int64_t N, int64_t K) {
-  const int64_t cus = chip_cus(), KT = cdiv(K, 256);
+inline int ks_plan(int64_t M, int64_t N, int64_t K, int64_t cus) {
+  const int64_t KT = cdiv(K, 256);
   const int64_t T32 = cdiv(M, 32) * cdiv(N, 32);
   // [r6] K <= 4096: the tile's whole K extent fits the LDS -- the one-shot kernel (gemm_mx_os.hip.h), no ring and no barrier in the K walk: N = K = 4096, M = 1 ... 64
   // 4.05-4.39 -> 3.34-3.67 us, N = K = 2048 3.15-3.26 -> 2.62-2.77 (profiles/calib_os_r6q.txt); its wave-owned-ring form for longer K and 16 columns per workgroup where os_plan says so
   // (4096 x 8192, M <= 32: 5.8-7.1 -> 5.5-5.7 us); past one tile per CU the ring plans below keep the shape
   if (M <= 16) {   // [r6] the decode form with wider column tiles (os16_wide_plan)
-    if (const int v = os16_wide_plan(4, N, K)) return v;
+    if (const int v = os16_wide_plan(4, N, K, cus)) return v;
   }
-  if (const int tn = os_plan(M, N, K)) {
+  if (const int tn = os_plan(M, N, K, cus)) {
     // [r6] decode form (gemm_mx_os16_kernel, 16x16 tiles on the 16x16x128 MFMA) wherever those fit one per CU: a third fewer bytes through each CU's LDS-DMA path
     // (N = K = 4096, M <= 16: 3.25-3.31 -> 2.86-2.92 us; K = 8192 5.0-5.2 -> 3.7-4.1; K = 14336 6.8-7.0 -> 6.1-6.5; two per CU (N = 8192) lose 9 %; profiles/calib_os16_r7.txt)
     if (cdiv(M, 16) * cdiv(N, 16) <= cus) return 571;
     return tn == 16 ? 569 : 568;
   }
-  if (os64_plan(M, N, K)) return 570;   // [r6] 64x32 tiles on wave-owned K stages where 32x32 tiles overflow the chip
+  if (os64_plan(M, N, K, cus)) return 570;   // [r6] 64x32 tiles on wave-owned K stages where 32x32 tiles overflow the chip
   if (T32 <= cus && (KT <= 24 || (2 * T32 > cus && KT <= 64))) return 561;   // (K > 16384 was not calibrated, and a split-K plan on larger tiles moves fewer bytes per CU there)
   const int64_t T64 = cdiv(M, 32) * cdiv(N, 64);
   if (M <= 32 && T32 > cus && T64 <= cus && 8 * T64 >= 7 * cus && KT <= 24) return 562;
   return 0;
 }
 
-// a_fmt (MXFP8 only): QAMD_FP8_E4M3 / QAMD_FP8_E5M2 element format of A
+// ---- the MX GEMM plan: pure host functions of the shape, the caller's scratch and the CU count, shared by the launchers, the workspace query and the debug entries
+
+// The kernels address an operand through 32-bit buffer-descriptor offsets (< 2 GiB); the reference's CUTLASS kernels use 64-bit strides.  A larger operand runs as
+// ranges of whole gran-row / gran-column tiles with rebased operand / scale / D pointers: column ranges of B (e.g. a 262400 x 16384 fp4 weight), each writing its
+// columns of the same D (row stride N) with A shared, and inside each of them row ranges of A (large batch x long K, e.g. 262144 x 16384 fp4) with B shared.  Every
+// output element is computed by exactly one launch, in the same K order.  f(r0, c0, m, n) runs once per range; returns the first non-zero code.
+template <class F>
+int for_each_range(const char* name, int64_t M, int64_t N, int64_t rowbytes, int gran, F&& f) {
+  const int64_t lim = ((1ll << 31) - 1) / rowbytes / gran * gran;
+  const bool split_n = N * rowbytes >= (1ll << 31), split_m = M * rowbytes >= (1ll << 31);
+  if (split_n && lim < gran) return fail(QAMD_ERR_INVALID, "%s: K too large for a %d-column range of B to stay below 2 GiB", name, gran);
+  if (split_m && lim < gran) return fail(QAMD_ERR_INVALID, "%s: K too large for a %d-row range of A to stay below 2 GiB", name, gran);
+  const int64_t cols = split_n ? lim : N, rows = split_m ? lim : M;
+  for (int64_t c0 = 0; c0 < N; c0 += cols)
+    for (int64_t r0 = 0; r0 < M; r0 += rows)
+      if (int rc = f(r0, c0, std::min(rows, M - r0), std::min(cols, N - c0))) return rc;
+  return QAMD_OK;
+}
+
+// One launch of a range: `variant` (dispatch_variant's numbering) over columns [c0, c0 + n) of the range, K in `splits` ranges (> 1: fp32 partials in the
+// caller's scratch, then the reduce pass).  A range takes at most two launches (the lab's two-launch experiment, "pp_flags" bit 13).
+// ws: split-K scratch of the range's split form, what the caller's scratch must hold for the split to be taken (0: none)
+struct MxLaunch { int variant; int64_t c0, n; int splits; };
+struct MxPlan {
+  int n = 0; MxLaunch l[2]; int64_t ws = 0;
+  MxPlan& add(int variant, int64_t c0, int64_t n_cols, int splits = 1) { l[n++] = {variant, c0, n_cols, splits}; return *this; }
+};
+
+// a_fmt (MXFP8 only): QAMD_FP8_E4M3 / QAMD_FP8_E5M2 element format of A; ldd: row stride of D (the whole output's N); avail: bytes of the caller's scratch (0: none)
 template <int EBITS>
-int gemm_mx(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf,
-            const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream, void* ws = nullptr, int64_t ws_bytes = 0, int a_fmt = 0,
-            int64_t ldd = 0) {   // ldd: row stride of D in elements when this call covers a column range of a wider output (0 = N)
-  // one place decides which instantiation family a variant number is looked up in
-  auto dispatch = [&](int v, const GemmParams& q, hipStream_t st) -> int {
-    if (EBITS == 8 && a_fmt == 1) return dispatch_variant_a5(v, q, st, name);
-    return dispatch_variant<EBITS, EBITS == 8>(v, q, st, name);
-  };
-  if (!A || !B || !A_sf || !B_sf || !alpha || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  // [r5] operands are fetched as 16-byte LDS-DMA pieces and the output leaves as 16-byte stores (the reference's CUTLASS kernels ask for 128-bit alignment as well, via TMA)
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)A_sf | (uintptr_t)B_sf | (uintptr_t)D) % 16)
-    return fail(QAMD_ERR_INVALID, "%s: A, B, the scale operands and D must be 16-byte aligned", name);
-  if (M <= 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M and N must be positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
-  const int kalign = (EBITS == 4) ? 128 : 32;
-  if (K < 32 || K % kalign) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of %d (got %lld)", name, kalign, (long long)K);
-  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  const int64_t rowbytes = K * EBITS / 8;
-  const int64_t CB = cdiv(K / 32, 4);
-  const int64_t a_bytes = M * rowbytes, b_bytes = N * rowbytes;
-  const int64_t sfa_bytes = cdiv(M, 128) * CB * 512, sfb_bytes = cdiv(N, 128) * CB * 512;
-  if (M * N >= (1ll << 40) || M >= (1ll << 31) || N >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
-  if (ldd == 0) ldd = N;
-  if (b_bytes >= (1ll << 31)) {
-    // B of >= 2 GiB (e.g. a 262400 x 16384 fp4 weight): column ranges of whole 256-column tiles, each writing its columns of the
-    // same D (row stride ldd); A is shared.  Every output element is computed by exactly one launch, in the same K order.
-    const int64_t cols = ((1ll << 31) - 1) / rowbytes / 256 * 256;
-    if (cols < 256) return fail(QAMD_ERR_INVALID, "%s: K too large for a 256-column range of B to stay below 2 GiB", name);
-    for (int64_t c0 = 0; c0 < N; c0 += cols) {
-      const int64_t nc = std::min(cols, N - c0);
-      if (int rc = gemm_mx<EBITS>(name, A, (const uint8_t*)B + c0 * rowbytes, A_sf, (const uint8_t*)B_sf + (c0 / 128) * CB * 512, alpha,
-                                  (uint16_t*)D + c0, M, nc, K, stream, ws, ws_bytes, a_fmt, ldd))
-        return rc;
-    }
-    return QAMD_OK;
-  }
-  if (a_bytes >= (1ll << 31)) {
-    // The kernels address an operand through 32-bit buffer-descriptor offsets (< 2 GiB); the reference's CUTLASS kernels use
-    // 64-bit strides.  A larger A (large batch x long K, e.g. 262144 x 16384 fp4) runs as row ranges of whole 256-row tiles:
-    // rebased A / scale / D pointers, same B -- every output element is computed by exactly one launch, in the same K order.
-    const int64_t rows = ((1ll << 31) - 1) / rowbytes / 256 * 256;
-    if (rows < 256) return fail(QAMD_ERR_INVALID, "%s: K too large for a 256-row range of A to stay below 2 GiB", name);
-    for (int64_t r0 = 0; r0 < M; r0 += rows) {
-      const int64_t mc = std::min(rows, M - r0);
-      if (int rc = gemm_mx<EBITS>(name, (const uint8_t*)A + r0 * rowbytes, B, (const uint8_t*)A_sf + (r0 / 128) * CB * 512, B_sf, alpha,
-                                  (uint16_t*)D + r0 * ldd, mc, N, K, stream, ws, ws_bytes, a_fmt, ldd))
-        return rc;
-    }
-    return QAMD_OK;
-  }
-  GemmParams p;
-  p.A = (const uint8_t*)A; p.B = (const uint8_t*)B; p.SFA = (const uint8_t*)A_sf; p.SFB = (const uint8_t*)B_sf;
-  p.alpha = alpha; p.D = (uint16_t*)D; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.ldd = (int)ldd;
-  p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
-  p.sfa_bytes = (uint32_t)sfa_bytes; p.sfb_bytes = (uint32_t)sfb_bytes;
-  p.pp_shift = opt_pp_shift();
-  p.pp_flags = opt_pp_flags();
-  p.dbg = opt_dbg();
-  p.ws = nullptr; p.splits = 1; p.ctr = nullptr; p.tag = 0; p.sk_tiles = 0;
-  hipStream_t s = (hipStream_t)stream;
+MxPlan mx_plan(int a_fmt, int64_t M, int64_t N, int64_t K, int64_t ldd, int64_t avail, int cus) {
+  MxPlan r;
+  const int pp = opt_pp_flags();
   int variant = opt_gemm_variant();
   if (variant >= 61 && variant <= 66) variant = 0;   // these select the NN operand path only (matmul_mxf8_bf16_nn)
   // ring schedule + optional split-K (needs caller scratch; "pp_flags" bit 7 turns split-K off, bit 8 the ring rule)
   // the plan with K ranges needs the caller's scratch; without it (or with too little) the best single-pass plan
-  SmallPlan pl = plan_small<EBITS>(M, N, K, true);
-  if (pl.variant && pl.splits > 1 && !(ws && ws_bytes >= splitk_ws_bytes(pl.variant, M, N, pl.splits) && !(opt_pp_flags() & 128))) pl = plan_small<EBITS>(M, N, K, false);
-  auto ring_launch = [&](int v, int splits) -> int {
-    {   // every split non-empty (a forced count may not divide the K stages)
-      const int64_t KT = cdiv(K * EBITS / 8, 128);
-      splits = (int)std::min<int64_t>(std::max(splits, 1), std::min<int64_t>(KT, 8));
-      splits = (int)cdiv(KT, cdiv(KT, splits));
-    }
-    if (splits > 1 && ws && ws_bytes >= splitk_ws_bytes(v, M, N, splits) && !(p.pp_flags & 128)) {
-      p.ws = (float*)ws; p.splits = splits; p.ctr = nullptr; p.tag = 0;
-#if QAMD_BENCH
-      if (p.pp_flags & 512) {   // lab: ONE launch, the last split to arrive for a tile reduces it (gemm_mx.hip.h epilogue_splitk_fused);
-                                // measured slower than the reduce kernel below, see there
-        p.ctr = (unsigned long long*)((char*)ws + splitk_ctr_offset(M, N, splits));
-        p.tag = (next_launch_tag() & ((1ull << 56) - 1)) << 8;
-        return dispatch(v, p, s);
-      }
-#endif
-      // second launch: sum the partials in fixed z order, alpha, bf16 (deterministic)
-      if (int rc = dispatch(v, p, s)) return rc;
-      if (t_dry.on) return 0;
-      const int64_t quads = M * (N / 4);
-      const int grid = (int)std::min<int64_t>(cdiv(quads, 256), 2048);
-      switch (splits) {
-#define QAMD_RED(S_) case S_: hipLaunchKernelGGL(splitk_reduce_kernel<S_>, dim3(grid), dim3(256), 0, s, (const float*)ws, p.D, alpha, (int)M, (int)N, p.ldd); break;
-        QAMD_RED(2) QAMD_RED(3) QAMD_RED(4) QAMD_RED(5) QAMD_RED(6) QAMD_RED(7) QAMD_RED(8)
-#undef QAMD_RED
-        default: return fail(QAMD_ERR_INVALID, "%s: unsupported split count %d", name, splits);
-      }
-      return check_launch("splitk_reduce_kernel");
-    }
-    p.ws = nullptr; p.splits = 1; p.ctr = nullptr; p.tag = 0;
-    return dispatch(v, p, s);
+  auto can_split = [&](int v, int splits) { return splits > 1 && avail >= splitk_ws_bytes(v, M, N, splits) && !(pp & 128); };
+  SmallPlan pl = plan_small<EBITS>(M, N, K, cus, true);
+  if (pl.variant && pl.splits > 1) r.ws = splitk_ws_bytes(pl.variant, M, N, pl.splits);
+  if (pl.variant && pl.splits > 1 && !can_split(pl.variant, pl.splits)) pl = plan_small<EBITS>(M, N, K, cus, false);
+  auto ring = [&](int v, int splits) -> MxPlan& {
+    const int64_t KT = cdiv(K * EBITS / 8, 128);   // every split non-empty (a forced count may not divide the K stages)
+    splits = (int)std::min<int64_t>(std::max(splits, 1), std::min<int64_t>(KT, 8));
+    splits = (int)cdiv(KT, cdiv(KT, splits));
+    return r.add(v, 0, N, can_split(v, splits) ? splits : 1);
   };
-  const bool can_split = pl.variant && pl.splits > 1 && ws && ws_bytes >= splitk_ws_bytes(pl.variant, M, N, pl.splits) && !(p.pp_flags & 128);
-  if (variant == 77) return ring_launch(70, pl.variant == 70 ? pl.splits : 1);   // lab: 64x64 ring (+ split-K) whatever M
-  if (variant >= 70 && variant <= 73 && opt_splitk_force() > 0) return ring_launch(variant, opt_splitk_force());   // lab: forced tile x forced split
+  if (variant == 77) return ring(70, pl.variant == 70 ? pl.splits : 1);   // lab: 64x64 ring (+ split-K) whatever M
+  if (variant >= 70 && variant <= 73 && opt_splitk_force() > 0) return ring(variant, opt_splitk_force());   // lab: forced tile x forced split
   // small batch (M <= 32): weight-bandwidth bound.  With fewer than 128 64-row tiles (N < 8192) the split-K kernel without
   // LDS staging wins (gemm_mx_skinny.hip.h: N = K = 4096, M = 16: 5.9 us vs 7.1 us for the ring kernel on 64 CUs); from
   // 128 tiles on, the 64x64 ring kernel streams the weight through full-line LDS-DMA and wins (N = 14336, K = 4096: 6.9 us
@@ -1030,39 +954,19 @@ int gemm_mx(const char* name, const void* A, const void* B, const void* A_sf, co
   // grows with M (N = K = 4096: 4.65 us at M = 1, 5.4 at 16, 6.1 at 32) while the 3-deep ring stays at 5.0 -- it keeps M <= 8 (now including N = 8192: 8.9 us against
   // the ring's 10.8 at K = 8192) and M <= 24 only against small weights (N <= 2048: 3.7 against 3.9 us)
   // [r6] small batches against a weight that fills the chip with 32x32 tiles: the in-workgroup K-split kernel (gemm_mx_ks.hip.h; ks_plan above)
-  if (EBITS == 4 && variant == 0 && !(p.pp_flags & 256)) {
-    if (const int kv = ks_plan(M, N, K)) return dispatch(kv, p, s);
-  }
   // [r6] MXFP8 small batches (e4m3 and e5m2 A): the wave-owned kernel where os8_plan says so
-  if (EBITS == 8 && variant == 0 && !(p.pp_flags & 256)) {
-    if (const int kv = os8_plan(M, N, K)) return dispatch(kv, p, s);
+  if (variant == 0 && !(pp & 256)) {
+    if (const int kv = EBITS == 4 ? ks_plan(M, N, K, cus) : os8_plan(M, N, K, cus)) { r.ws = 0; return r.add(kv, 0, N); }
   }
-  const bool skinny_auto = variant == 0 && !can_split && ((M <= 8 && cdiv(N, 64) <= chip_cus() / 2) || (M <= 24 && cdiv(N, 64) <= chip_cus() / 8));
-  if (EBITS == 4 && (variant == 60 || (variant >= 44 && variant <= 49) || skinny_auto)) {
-    if (dry_record(variant ? variant : 60, p.N, 1)) return 0;
-    SkinnyParams q;
-    q.A = p.A; q.B = p.B; q.SFA = p.SFA; q.SFB = p.SFB; q.alpha = alpha; q.D = p.D; q.M = p.M; q.N = p.N; q.K = p.K;
-    q.a_bytes = p.a_bytes; q.b_bytes = p.b_bytes; q.sfa_bytes = p.sfa_bytes; q.sfb_bytes = p.sfb_bytes; q.ldd = p.ldd;
-    switch (variant) {   // 44..49: lab-only shapes of the split-K kernel (waves, segments per trip, chunk mapping)
-#if QAMD_BENCH
-      case 44: launch_skinny<true, 8, 2, true>(q, s); break;
-      case 45: launch_skinny<true, 4, 2, false>(q, s); break;
-      case 46: launch_skinny<true, 4, 2, true>(q, s); break;
-      case 47: launch_skinny<true, 8, 2, false>(q, s); break;
-      case 48: launch_skinny<true, 8, 1, true>(q, s); break;
-      case 49: launch_skinny<true, 4, 4, true>(q, s); break;
-#endif
-      default: launch_skinny<true, 8, 4, false>(q, s);   // 4 segments per wave per trip: 32 b128 loads in flight per wave
-    }
-    return check_launch("gemm_mx_skinny_kernel");
-  }
-  if (variant == 0 && !(p.pp_flags & 256) && pl.variant) return ring_launch(pl.variant, pl.splits);
+  const bool split = pl.variant && can_split(pl.variant, pl.splits);
+  const bool skinny_auto = variant == 0 && !split && ((M <= 8 && cdiv(N, 64) <= cus / 2) || (M <= 24 && cdiv(N, 64) <= cus / 8));
+  if (EBITS == 4 && (variant == 60 || (variant >= 44 && variant <= 49) || skinny_auto)) return r.add(variant ? variant : 60, 0, N);
+  if (variant == 0 && !(pp & 256) && pl.variant) return ring(pl.variant, pl.splits);
   if (variant == 0) {
     // auto (measured, profiles/native_r1_schedules.log, profiles/bench_sweep_*.txt): the largest tile that still gives
     // every CU work -- 256x256 ("deep" schedule, 4 waves of 128x128), then 128x128, 128x64 / 64x128, 64x64 (simple
     // schedule, several workgroups per CU).  (fp4 with M <= 32 went to the split-K kernel above.)
     auto tiles = [&](int bm, int bn) { return cdiv(M, bm) * cdiv(N, bn); };
-    const int cus = chip_cus();
     const int64_t want = cus * 3 / 4;   // 3/4 of the CUs
     // no point in tiles taller than the problem; 64x64 until 64x128 tiles fill the chip 1.5 times (weight-bandwidth
     // bound: N = 28672, K = 4096, M = 32: 12.6 us with 448 tiles of 64x64 vs 14.3 us with 224 of 64x128)
@@ -1086,26 +990,17 @@ int gemm_mx(const char* name, const void* A, const void* B, const void* A_sf, co
       // (gemm_mx_hetero_kernel: dispatched CU by CU as the persistent workgroups retire) whenever the cost model says so;
       // otherwise ONE persistent launch with balanced rounds (deepp_grid).
       const int64_t tm = cdiv(M, 256), tn = cdiv(N, 256), T = tm * tn;
-      bool hetero_ok = big == 90 && !(opt_pp_flags() & 64);   // (lab, "pp_flags" bit 6: balanced rounds only)
+      bool hetero_ok = big == 90 && !(pp & 64);   // (lab, "pp_flags" bit 6: balanced rounds only)
 #if QAMD_BENCH
       // lab, "pp_flags" bit 13: the round-1/2 form of the same idea INSTEAD -- the trailing tile columns as a SECOND launch of smaller
       // tiles (kept for the A/B in profiles/native_r3_heterobench.log)
       const int64_t full = (T / cus) * cus, main_cols = (tm > 0) ? full / tm : 0;
-      const bool two_launch = (opt_pp_flags() & 8192) != 0;
+      const bool two_launch = (pp & 8192) != 0;
       if (two_launch && hetero_ok && full >= cus && full < 3 * cus && main_cols >= 1 && main_cols < tn && (T - main_cols * tm) <= 80) {
-        const int64_t n1 = main_cols * 256;
-        GemmParams pm = p;
-        pm.N = (int)n1; pm.b_bytes = (uint32_t)(n1 * rowbytes); pm.sfb_bytes = (uint32_t)(cdiv(n1, 128) * CB * 512);
-        if (int rc = dispatch(big, pm, s)) return rc;
-        GemmParams pt = p;
-        pt.N = (int)(N - n1);
-        pt.B = p.B + n1 * rowbytes; pt.b_bytes = (uint32_t)((N - n1) * rowbytes);
-        pt.SFB = p.SFB + (n1 / 128) * CB * 512; pt.sfb_bytes = (uint32_t)(cdiv(N - n1, 128) * CB * 512);
-        pt.D = p.D + n1;
-        const int64_t Nt = N - n1;
+        const int64_t n1 = main_cols * 256, Nt = N - n1;
         auto tt = [&](int bm, int bn) { return cdiv(M, bm) * cdiv(Nt, bn); };
         const int vt = (tt(256, 128) >= want) ? 25 : (tt(128, 128) >= want) ? 24 : (tt(128, 64) >= want) ? 27 : 29;
-        return dispatch(vt, pt, s);
+        return r.add(big, 0, n1).add(vt, n1, Nt);
       }
       if (two_launch) hetero_ok = false;
 #endif
@@ -1127,18 +1022,163 @@ int gemm_mx(const char* name, const void* A, const void* B, const void* A_sf, co
     else variant = 29;
   }
   if (variant == 89) {   // (lab: forced stream-K; falls back to the persistent kernel when the shape has nothing to cut or the scratch is missing)
-    const int cus = chip_cus();
     const int64_t T = cdiv(M, 256) * cdiv(N, 256), KTe = (cdiv(K * EBITS / 8, 128) + 1) / 2 * 2;
-    const bool ok = a_fmt == 0 && ws && ws_bytes >= sk_ws_bytes(cus) && (uintptr_t)ws % 16 == 0 && T % cus != 0 && T > cus && KTe >= 8 && (K * EBITS / 8) % 256 == 0 && ldd < (1ll << 22);
+    const bool ok = a_fmt == 0 && avail >= sk_ws_bytes(cus) && T % cus != 0 && T > cus && KTe >= 8 && (K * EBITS / 8) % 256 == 0 && ldd < (1ll << 22);
     if (!ok) variant = 90;
-    else {
-      p.sk_tiles = (int)(cus + T % cus);
-      p.ws = (float*)ws;
-      p.ctr = (unsigned long long*)((char*)ws + (int64_t)cus * SK_PART_BYTES);
-      p.tag = next_launch_tag();
-    }
   }
-  return dispatch(variant, p, s);
+  return r.add(variant, 0, N);
+}
+
+// matmul_ada_mxf4_bf16_tn (row-major scales): the variant of the kernel with row-major scale fetch, in dispatch_variant's numbering -- 60 the LDS-free split-K
+// kernel, 70 the 64x64 ring (lab: 178 = its round-1 schedule), 568 / 569 / 570 the wave-owned kernel with 32x32 / 32x16 / 64x32 tiles, 571 ... 575 its decode form
+// with 16 / 32 / 48 / 56 / 64 columns per workgroup.  Never split-K: the op has no scratch argument.
+inline int ada_plan(int64_t M, int64_t N, int64_t K, int cus) {
+  // Same regimes as matmul_mxf4_bf16_tn: the LDS-free split-K kernel while the weight has fewer than 128 64-row tiles;
+  // from 128 tiles on (N >= 8192) the 64x64 ring kernel with row-major scale fetch streams the weight through full-line
+  // LDS-DMA (M = 16: N = 14336, K = 4096 9.7 -> 6.9 us; N = 57344, K = 8192 62.6 -> 39.9 us), and any M > 32 goes there
+  // too ("gemm_variant" 60 / 70 force either).
+  const int forced = opt_gemm_variant();
+  const int64_t T64 = cdiv(N, 64);   // (no split-K here -- the op has no scratch argument -- so a long K on few tiles stays with the split-K kernel:
+                                     //  8 x 8192 x 28672: 27.9 us vs 34.2 us on 128 workgroups of the ring kernel)
+  const bool ring = forced == 70 || (forced != 60 && (M > 32 || T64 >= cus || (T64 >= cus / 2 && K < 16384)));
+  // [r6] K <= 4096 and at most one 32x32 tile per CU: the one-shot kernel with row-major scale pieces (gemm_mx_os.hip.h; "gemm_variant" 568 forces it where it fits)
+  const int os_tn = forced == 0 ? os_plan(M, N, K, cus, true) : 0;
+  const bool os16 = forced == 569 || os_tn == 16;   // 16 columns per workgroup
+  // [r6] ... its decode form (16x16 tiles on the 16x16x128 MFMA) where those fit one per CU (matmul_mxf4_bf16_tn's rule, ks_plan)
+  if (forced >= 571 && forced <= 575) return forced;
+  if (os_tn != 0 && cdiv(M, 16) * cdiv(N, 16) <= cus) return 571;
+  if (forced == 0 && M <= 16) {
+    if (const int v = os16_wide_plan(4, N, K, cus)) return v;   // (wider column tiles: matmul_mxf4_bf16_tn's rule)
+  }
+  const bool os64 = forced == 570 || (forced == 0 && os_tn == 0 && os64_plan(M, N, K, cus, true));   // 64x32 tiles where the 32-row tiles overflow the chip (os64_plan)
+  const bool oneshot = (forced >= 568 && forced <= 570) ? cdiv(M, 32) * cdiv(N, 32) <= 4 * cus : (os_tn != 0 || os64);
+  if (oneshot) return os64 ? 570 : os16 ? 569 : 568;
+  if (ring) return forced == 178 ? 178 : 70;
+  return 60;
+}
+
+// ---- the executor.  The operands of one MX GEMM: scales in the to_blocked layout (128-row blocks of ceil(K / 128) 512-byte pieces: the TN and NN ops) or row-major (rows, K / 32)
+// (rm: matmul_ada_mxf4_bf16_tn); ldd: row stride of D in elements
+struct MxArgs { const void *A, *B, *A_sf, *B_sf; const float* alpha; void* D; int64_t K, ldd; int ebits; bool rm; };
+// the GemmParams of rows [r0, r0 + m) x columns [c0, c0 + n) of the output (with blocked scales r0 and c0 are multiples of 128)
+inline GemmParams mx_params(const MxArgs& x, int64_t r0, int64_t c0, int64_t m, int64_t n) {
+  const int64_t rowbytes = x.K * x.ebits / 8, KB = x.K / 32, CB = cdiv(KB, 4);
+  auto sf_offset = [&](int64_t row) { return x.rm ? row * KB : (row / 128) * CB * 512; };
+  auto sf_bytes = [&](int64_t rows) { return (uint32_t)(x.rm ? rows * KB : cdiv(rows, 128) * CB * 512); };
+  GemmParams p{};
+  p.A = (const uint8_t*)x.A + r0 * rowbytes; p.B = (const uint8_t*)x.B + c0 * rowbytes;
+  p.SFA = (const uint8_t*)x.A_sf + sf_offset(r0); p.SFB = (const uint8_t*)x.B_sf + sf_offset(c0);
+  p.alpha = x.alpha; p.D = (uint16_t*)x.D + r0 * x.ldd + c0; p.M = (int)m; p.N = (int)n; p.K = (int)x.K; p.ldd = (int)x.ldd;
+  p.a_bytes = (uint32_t)(m * rowbytes); p.b_bytes = (uint32_t)(n * rowbytes);
+  p.sfa_bytes = sf_bytes(m); p.sfb_bytes = sf_bytes(n);
+  p.pp_shift = opt_pp_shift(); p.pp_flags = opt_pp_flags(); p.dbg = opt_dbg();
+  p.splits = 1;
+  return p;
+}
+inline SkinnyParams skinny_params(const GemmParams& p) {
+  SkinnyParams q;
+  q.A = p.A; q.B = p.B; q.SFA = p.SFA; q.SFB = p.SFB; q.alpha = p.alpha; q.D = p.D; q.M = p.M; q.N = p.N; q.K = p.K;
+  q.a_bytes = p.a_bytes; q.b_bytes = p.b_bytes; q.sfa_bytes = p.sfa_bytes; q.sfb_bytes = p.sfb_bytes; q.ldd = p.ldd;
+  return q;
+}
+
+// one planned launch of matmul_mx{f4,f8}_bf16_tn, then the reduce pass of a split
+template <int EBITS>
+int mx_launch(const char* name, const MxLaunch& l, GemmParams p, void* ws, int a_fmt, hipStream_t s) {
+  // one place decides which instantiation family a variant number is looked up in
+  auto dispatch = [&](int v) -> int {
+    if (EBITS == 8 && a_fmt == 1) return dispatch_variant_a5(v, p, s, name);
+    return dispatch_variant<EBITS, EBITS == 8>(v, p, s, name);
+  };
+  if (EBITS == 4 && (l.variant == 60 || (l.variant >= 44 && l.variant <= 49))) {
+    const SkinnyParams q = skinny_params(p);
+    switch (l.variant) {   // 44..49: lab-only shapes of the split-K kernel (waves, segments per trip, chunk mapping)
+#if QAMD_BENCH
+      case 44: launch_skinny<true, 8, 2, true>(q, s); break;
+      case 45: launch_skinny<true, 4, 2, false>(q, s); break;
+      case 46: launch_skinny<true, 4, 2, true>(q, s); break;
+      case 47: launch_skinny<true, 8, 2, false>(q, s); break;
+      case 48: launch_skinny<true, 8, 1, true>(q, s); break;
+      case 49: launch_skinny<true, 4, 4, true>(q, s); break;
+#endif
+      default: launch_skinny<true, 8, 4, false>(q, s);   // 4 segments per wave per trip: 32 b128 loads in flight per wave
+    }
+    return check_launch("gemm_mx_skinny_kernel");
+  }
+#if QAMD_BENCH
+  if (l.variant == 89) {   // lab: stream-K over the caller's scratch (the persistent kernel when that is not 16-byte aligned)
+    if ((uintptr_t)ws % 16) return dispatch(90);
+    const int cus = chip_cus();
+    p.sk_tiles = (int)(cus + cdiv(p.M, 256) * cdiv(p.N, 256) % cus);
+    p.ws = (float*)ws;
+    p.ctr = (unsigned long long*)((char*)ws + (int64_t)cus * SK_PART_BYTES);
+    p.tag = next_launch_tag();
+    return dispatch(89);
+  }
+#endif
+  if (l.splits == 1) return dispatch(l.variant);
+  p.ws = (float*)ws; p.splits = l.splits;
+#if QAMD_BENCH
+  if (p.pp_flags & 512) {   // lab: ONE launch, the last split to arrive for a tile reduces it (gemm_mx.hip.h epilogue_splitk_fused);
+                            // measured slower than the reduce kernel below, see there
+    p.ctr = (unsigned long long*)((char*)ws + splitk_ctr_offset(p.M, p.N, l.splits));
+    p.tag = (next_launch_tag() & ((1ull << 56) - 1)) << 8;
+    return dispatch(l.variant);
+  }
+#endif
+  // second launch: sum the partials in fixed z order, alpha, bf16 (deterministic)
+  if (int rc = dispatch(l.variant)) return rc;
+  const int64_t quads = (int64_t)p.M * (p.N / 4);
+  const int grid = (int)std::min<int64_t>(cdiv(quads, 256), 2048);
+  switch (l.splits) {
+#define QAMD_RED(S_) case S_: hipLaunchKernelGGL(splitk_reduce_kernel<S_>, dim3(grid), dim3(256), 0, s, (const float*)ws, p.D, p.alpha, p.M, p.N, p.ldd); break;
+    QAMD_RED(2) QAMD_RED(3) QAMD_RED(4) QAMD_RED(5) QAMD_RED(6) QAMD_RED(7) QAMD_RED(8)
+#undef QAMD_RED
+    default: return fail(QAMD_ERR_INVALID, "%s: unsupported split count %d", name, l.splits);
+  }
+  return check_launch("splitk_reduce_kernel");
+}
+
+// the argument checks of matmul_mx{f4,f8}_bf16_tn (EBITS 4 / 8)
+inline int mx_check(const char* name, int ebits, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, const void* D,
+                    int64_t M, int64_t N, int64_t K) {
+  if (!A || !B || !A_sf || !B_sf || !alpha || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  // [r5] operands are fetched as 16-byte LDS-DMA pieces and the output leaves as 16-byte stores (the reference's CUTLASS kernels ask for 128-bit alignment as well, via TMA)
+  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)A_sf | (uintptr_t)B_sf | (uintptr_t)D) % 16)
+    return fail(QAMD_ERR_INVALID, "%s: A, B, the scale operands and D must be 16-byte aligned", name);
+  if (M <= 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M and N must be positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
+  const int kalign = (ebits == 4) ? 128 : 32;
+  if (K < 32 || K % kalign) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of %d (got %lld)", name, kalign, (long long)K);
+  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
+  if (M * N >= (1ll << 40) || M >= (1ll << 31) || N >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
+  return QAMD_OK;
+}
+
+// EBITS: 4 = MXFP4, 8 = MXFP8 (TN); a_fmt (MXFP8 only): QAMD_FP8_E4M3 / QAMD_FP8_E5M2 element format of A
+template <int EBITS>
+int gemm_mx(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf,
+            const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream, void* ws = nullptr, int64_t ws_bytes = 0, int a_fmt = 0) {
+  if (int rc = mx_check(name, EBITS, A, B, A_sf, B_sf, alpha, D, M, N, K)) return rc;
+  const MxArgs x{A, B, A_sf, B_sf, alpha, D, K, N, EBITS, false};
+  return for_each_range(name, M, N, K * EBITS / 8, 256, [&](int64_t r0, int64_t c0, int64_t m, int64_t n) -> int {
+    const MxPlan pl = mx_plan<EBITS>(a_fmt, m, n, K, N, ws ? ws_bytes : 0, chip_cus());
+    for (int i = 0; i < pl.n; ++i)
+      if (int rc = mx_launch<EBITS>(name, pl.l[i], mx_params(x, r0, c0 + pl.l[i].c0, m, pl.l[i].n), ws, a_fmt, (hipStream_t)stream)) return rc;
+    return QAMD_OK;
+  });
+}
+
+// debug entries: plan(m, n) of every range; out[3 i .. 3 i + 2] = {variant, N of the launch, K splits} of launch i (the first min(cap, 8)); returns the launch count
+template <class P>
+int debug_plan(const char* name, int64_t M, int64_t N, int64_t rowbytes, int gran, int* out, int cap, P&& plan) {
+  int cnt = 0;
+  const int rc = for_each_range(name, M, N, rowbytes, gran, [&](int64_t, int64_t, int64_t m, int64_t n) {
+    const MxPlan pl = plan(m, n);
+    for (int i = 0; i < pl.n; ++i, ++cnt)
+      if (cnt < 8 && cnt < cap) { out[3 * cnt] = pl.l[i].variant; out[3 * cnt + 1] = (int)pl.l[i].n; out[3 * cnt + 2] = pl.l[i].splits; }
+    return QAMD_OK;
+  });
+  return rc == QAMD_OK ? cnt : -1;
 }
 
 #endif   // QAMD_DEF(1)
@@ -1279,14 +1319,13 @@ int qutlass_amd_matmul_mxf4_bf16_tn(const void* A, const void* B, const void* A_
   return gemm_mx<4>("matmul_mxf4_bf16_tn", A, B, A_sf, B_sf, alpha, D, M, N, K, stream);
 }
 
+// the split-K scratch of the plan with unlimited scratch
 int64_t qutlass_amd_gemm_splitk_workspace_bytes(int ebits, int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0 || (ebits != 4 && ebits != 8)) return 0;
-  const SmallPlan pl = (ebits == 4) ? plan_small<4>(M, N, K) : plan_small<8>(M, N, K);
-  int64_t need = (pl.variant && pl.splits > 1) ? splitk_ws_bytes(pl.variant, M, N, pl.splits) : 0;
-  if (ebits == 4 && opt_gemm_variant() == 0 && !(opt_pp_flags() & 256) && ks_plan(M, N, K)) need = 0;   // [r6] the in-workgroup K-split kernel takes the shape: no scratch
-  if (ebits == 8 && opt_gemm_variant() == 0 && !(opt_pp_flags() & 256) && os8_plan(M, N, K)) need = 0;  // [r6] ... the wave-owned kernel an MXFP8 one
+  const int cus = chip_cus();
+  int64_t need = (ebits == 4 ? mx_plan<4>(0, M, N, K, N, INT64_MAX, cus) : mx_plan<8>(0, M, N, K, N, INT64_MAX, cus)).ws;
 #if QAMD_BENCH
-  if (opt_gemm_variant() == 89) need = std::max<int64_t>(need, sk_ws_bytes(chip_cus()));   // lab: forced stream-K
+  if (opt_gemm_variant() == 89) need = std::max<int64_t>(need, sk_ws_bytes(cus));   // lab: forced stream-K
   if (opt_splitk_force() > 1) need = std::max<int64_t>(need, splitk_ws_bytes(70, M, N, 8));   // lab: room for any forced tile x split
 #endif
   return need;
@@ -1304,86 +1343,38 @@ int qutlass_amd_matmul_mxf8_bf16_tn_ws(const void* A, const void* B, const void*
   return gemm_mx<8>("matmul_mxf8_bf16_tn", A, B, A_sf, B_sf, alpha, D, M, N, K, stream, workspace, workspace_bytes);
 }
 
-static int ada_impl(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, void* D, int64_t M, int64_t N, int64_t K,
-                    int64_t ldd, void* stream) {
-  const char* name = "matmul_ada_mxf4_bf16_tn";
+// the argument checks of matmul_ada_mxf4_bf16_tn
+static int ada_check(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, const void* D, int64_t M, int64_t N,
+                     int64_t K) {
   if (!A || !B || !A_sf || !B_sf || !alpha || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   if (M <= 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M and N must be positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
   if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
   if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
   if (M >= (1ll << 31) || N >= (1ll << 31) || M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
-  if (ldd == 0) ldd = N;
-  const int64_t rowbytes = K / 2, KB = K / 32;
-  // operands of >= 2 GiB (32-bit buffer-descriptor offsets; the reference hands 64-bit strides to CUTLASS): ranges of whole 64-row
-  // tiles with rebased operand / row-major scale / D pointers -- every output element is computed by exactly one launch
-  if (N * rowbytes >= (1ll << 31)) {
-    const int64_t cols = ((1ll << 31) - 1) / rowbytes / 64 * 64;
-    if (cols < 64) return fail(QAMD_ERR_INVALID, "%s: K too large for a 64-column range of B to stay below 2 GiB", name);
-    for (int64_t c0 = 0; c0 < N; c0 += cols)
-      if (int rc = ada_impl(A, (const uint8_t*)B + c0 * rowbytes, A_sf, (const uint8_t*)B_sf + c0 * KB, alpha, (uint16_t*)D + c0, M, std::min(cols, N - c0), K, ldd, stream)) return rc;
-    return QAMD_OK;
-  }
-  if (M * rowbytes >= (1ll << 31)) {
-    const int64_t rows = ((1ll << 31) - 1) / rowbytes / 64 * 64;
-    if (rows < 64) return fail(QAMD_ERR_INVALID, "%s: K too large for a 64-row range of A to stay below 2 GiB", name);
-    for (int64_t r0 = 0; r0 < M; r0 += rows)
-      if (int rc = ada_impl((const uint8_t*)A + r0 * rowbytes, B, (const uint8_t*)A_sf + r0 * KB, B_sf, alpha, (uint16_t*)D + r0 * ldd, std::min(rows, M - r0), N, K, ldd, stream)) return rc;
-    return QAMD_OK;
-  }
-  // Same regimes as matmul_mxf4_bf16_tn: the LDS-free split-K kernel while the weight has fewer than 128 64-row tiles;
-  // from 128 tiles on (N >= 8192) the 64x64 ring kernel with row-major scale fetch streams the weight through full-line
-  // LDS-DMA (M = 16: N = 14336, K = 4096 9.7 -> 6.9 us; N = 57344, K = 8192 62.6 -> 39.9 us), and any M > 32 goes there
-  // too ("gemm_variant" 60 / 70 force either).
-  const int forced = opt_gemm_variant();
-  const int64_t T64 = cdiv(N, 64);   // (no split-K here -- the op has no scratch argument -- so a long K on few tiles stays with the split-K kernel:
-                                     //  8 x 8192 x 28672: 27.9 us vs 34.2 us on 128 workgroups of the ring kernel)
-  const int cus = chip_cus();
-  const bool ring = forced == 70 || (forced != 60 && (M > 32 || T64 >= cus || (T64 >= cus / 2 && K < 16384)));
-  // [r6] K <= 4096 and at most one 32x32 tile per CU: the one-shot kernel with row-major scale pieces (gemm_mx_os.hip.h; "gemm_variant" 568 forces it where it fits)
-  const int os_tn = forced == 0 ? os_plan(M, N, K, true) : 0;
-  const bool os16 = forced == 569 || os_tn == 16;   // 16 columns per workgroup
-  // [r6] ... its decode form (16x16 tiles on the 16x16x128 MFMA) where those fit one per CU (matmul_mxf4_bf16_tn's rule, ks_plan)
-  const int ada_tn16 = (forced >= 571 && forced <= 575) ? (forced == 571 ? 16 : forced == 572 ? 32 : forced == 573 ? 48 : forced == 574 ? 56 : 64)
-                       : (os_tn != 0 && cdiv(M, 16) * cdiv(N, 16) <= cus) ? 16
-                       : (forced == 0 && M <= 16 && os16_wide_plan(4, N, K)) ? os16_tn(N) : 0;   // (wider column tiles: matmul_mxf4_bf16_tn's rule)
-  if (ada_tn16) {
-    GemmParams p;
-    p.A = (const uint8_t*)A; p.B = (const uint8_t*)B; p.SFA = (const uint8_t*)A_sf; p.SFB = (const uint8_t*)B_sf;
-    p.alpha = alpha; p.D = (uint16_t*)D; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.ldd = (int)ldd;
-    p.a_bytes = (uint32_t)(M * rowbytes); p.b_bytes = (uint32_t)(N * rowbytes);
-    p.sfa_bytes = (uint32_t)(M * KB); p.sfb_bytes = (uint32_t)(N * KB);
-    p.pp_shift = opt_pp_shift(); p.pp_flags = opt_pp_flags(); p.dbg = opt_dbg();
-    return launch_gemm_os16_tn<4, 0, true>(ada_tn16, p, (hipStream_t)stream);
-  }
-  const bool os64 = forced == 570 || (forced == 0 && os_tn == 0 && os64_plan(M, N, K, true));   // 64x32 tiles where the 32-row tiles overflow the chip (os64_plan)
-  const bool oneshot = (forced >= 568 && forced <= 570) ? cdiv(M, 32) * cdiv(N, 32) <= 4 * cus : (os_tn != 0 || os64);
-  if (ring || oneshot) {
-    GemmParams p;
-    p.A = (const uint8_t*)A; p.B = (const uint8_t*)B; p.SFA = (const uint8_t*)A_sf; p.SFB = (const uint8_t*)B_sf;
-    p.alpha = alpha; p.D = (uint16_t*)D; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.ldd = (int)ldd;
-    p.a_bytes = (uint32_t)(M * rowbytes); p.b_bytes = (uint32_t)(N * rowbytes);
-    p.sfa_bytes = (uint32_t)(M * KB); p.sfb_bytes = (uint32_t)(N * KB);   // row-major (rows, K/32), un-swizzled
-    p.pp_shift = opt_pp_shift(); p.pp_flags = opt_pp_flags(); p.dbg = opt_dbg();
-    p.ws = nullptr; p.splits = 1; p.ctr = nullptr; p.tag = 0;
-    if (oneshot && os64) return launch_gemm_os<true, 32, 4, 64>(p, (hipStream_t)stream);
-    if (oneshot) return os16 ? launch_gemm_os<true, 16>(p, (hipStream_t)stream) : launch_gemm_os<true>(p, (hipStream_t)stream);
-#if QAMD_BENCH
-    if (opt_gemm_variant() == 178) return launch_gemm<GemmCfg<64, 64, 2, 2, 4, false, 0, 3>, 8>(p, (hipStream_t)stream);   // round-1 ring schedule
-#endif
-    return launch_gemm<GemmCfg<64, 64, 2, 2, 4, false, 0, 3>, 10>(p, (hipStream_t)stream);
-  }
-  SkinnyParams q;
-  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
-  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)ldd;
-  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * rowbytes);
-  q.sfa_bytes = (uint32_t)(M * KB); q.sfb_bytes = (uint32_t)(N * KB);   // row-major (rows, K/32), un-swizzled
-  launch_skinny<false, 8, 4, false>(q, (hipStream_t)stream);
-  return check_launch("gemm_mx_skinny_kernel");
+  return QAMD_OK;
 }
 
+// the plan of each range (ada_plan; operands of >= 2 GiB: ranges of whole 64-row / 64-column tiles) on the row-major-scale kernels
 int qutlass_amd_matmul_ada_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
                                         const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream) {
-  return ada_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, 0, stream);
+  const char* name = "matmul_ada_mxf4_bf16_tn";
+  if (int rc = ada_check(name, A, B, A_sf, B_sf, alpha, D, M, N, K)) return rc;
+  const MxArgs x{A, B, A_sf, B_sf, alpha, D, K, N, 4, true};
+  const hipStream_t s = (hipStream_t)stream;
+  return for_each_range(name, M, N, K / 2, 64, [&](int64_t r0, int64_t c0, int64_t m, int64_t n) -> int {
+    const GemmParams p = mx_params(x, r0, c0, m, n);
+    switch (const int v = ada_plan(m, n, K, chip_cus())) {
+      case 60: launch_skinny<false, 8, 4, false>(skinny_params(p), s); return check_launch("gemm_mx_skinny_kernel");
+      case 70: return launch_gemm<GemmCfg<64, 64, 2, 2, 4, false, 0, 3>, 10>(p, s);
+#if QAMD_BENCH
+      case 178: return launch_gemm<GemmCfg<64, 64, 2, 2, 4, false, 0, 3>, 8>(p, s);   // round-1 ring schedule
+#endif
+      case 568: return launch_gemm_os<true>(p, s);
+      case 569: return launch_gemm_os<true, 16>(p, s);
+      case 570: return launch_gemm_os<true, 32, 4, 64>(p, s);
+      default: return launch_gemm_os16_tn<4, 0, true>(v == 571 ? 16 : v == 572 ? 32 : v == 573 ? 48 : v == 574 ? 56 : 64, p, s);
+    }
+  });
 }
 
 // grouped_matmul_mxf4_bf16_tn: every argument is checked before any HIP call
@@ -1432,7 +1423,7 @@ int qutlass_amd_matmul_mxf8_bf16_tn(const void* A, const void* B, const void* A_
 }
 
 // one rule for the launcher and the workspace query: the persistent kernel on the (K, M) operand wherever the TN op would
-// pick the persistent 256x256 kernel for the whole problem (gemm_mx auto rule); everything smaller goes through the
+// pick the persistent 256x256 kernel for the whole problem (mx_plan auto rule); everything smaller goes through the
 // byte-transpose pre-pass and the TN dispatch with its smaller tiles / split-K
 // (operands of >= 2 GiB also take the pre-pass: the in-place path walks the (K, M) operand with 32-bit offsets k * M + m, which only a
 //  per-K-chunk descriptor could extend; the (M, K) copy in the workspace then runs as row ranges of the TN dispatch, gemm_mx)
@@ -1465,15 +1456,7 @@ static int mxf8_nn_impl(const void* A, const void* B, const void* A_sf, const vo
   if (fused) {
     if (!B || !A_sf || !B_sf || !alpha || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
     if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-    const int64_t CB = cdiv(K / 32, 4);
-    GemmParams p;
-    p.A = (const uint8_t*)A; p.B = (const uint8_t*)B; p.SFA = (const uint8_t*)A_sf; p.SFB = (const uint8_t*)B_sf;
-    p.alpha = alpha; p.D = (uint16_t*)D; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.ldd = (int)N;
-    p.a_bytes = (uint32_t)(M * K); p.b_bytes = (uint32_t)(N * K);
-    p.sfa_bytes = (uint32_t)(cdiv(M, 128) * CB * 512); p.sfb_bytes = (uint32_t)(cdiv(N, 128) * CB * 512);
-    p.pp_shift = opt_pp_shift(); p.pp_flags = opt_pp_flags(); p.dbg = opt_dbg();
-    p.ws = nullptr; p.splits = 1; p.ctr = nullptr; p.tag = 0;
-    if (dry_record(forced == 61 ? 61 : 63, p.N, 1)) return 0;
+    const GemmParams p = mx_params({A, B, A_sf, B_sf, alpha, D, K, N, 8, false}, 0, 0, M, N);   // (A is (K, M): M * K bytes all the same)
     if (a_fmt == 1) return launch_nn_fused_a5(p, (hipStream_t)stream, forced == 61);
 #if QAMD_BENCH
     if (forced == 61) return launch_gemm<GemmCfg<256, 256, 2, 2, 8, true>, 6>(p, (hipStream_t)stream);
@@ -1532,7 +1515,7 @@ static int nvf4_impl(const void* A, const void* B, const void* A_sf, const void*
                      int64_t K, int64_t ldd, void* stream, void* ws = nullptr, int64_t ws_bytes = 0) {
   const char* name = "matmul_nvf4_bf16_tn";
   if (!A || !B || !A_sf || !B_sf || !alpha || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)A_sf | (uintptr_t)B_sf | (uintptr_t)D) % 16)   // [r5] as in gemm_mx
+  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)A_sf | (uintptr_t)B_sf | (uintptr_t)D) % 16)   // [r5] as in mx_check
     return fail(QAMD_ERR_INVALID, "%s: A, B, the scale operands and D must be 16-byte aligned", name);
   if (M <= 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M and N must be positive", name);
   if (K < 16 || K % 32) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 32 (got %lld)", name, (long long)K);
@@ -1697,7 +1680,7 @@ int qutlass_amd_fused_quantize_nv_blocked(const void* x, const void* h, int rot,
 //      0.2 ... 0.8 us more than the flat one and saves the 1.9 ... 3.2 us to_blocked launch: 2.2 vs 4.5 us at 256 x 4096, 7.3 vs 10.4 at 4096^2, 27.9 vs 31.4 at
 //      8192^2, 23.4 vs 26.5 at 4096 x 14336 -- device time, every size measured (profiles/ab_blocked_quant_r3y.txt); with the GEMM behind it: 4096 x 14336 x 4096
 //      123.2 vs 124.5 us (profiles/bench_r4c.json).  It never returns 3: the reference's three-launch flow stays available as fusedQuantizeMx + to_blocked + matmul.
-// Thresholds scale with the CU count of the current device.  No GPU work; the dry-run hook describes a 256-CU part.
+// Thresholds scale with the CU count of the current device.  No GPU work.
 int qutlass_amd_activation_path_launches(int64_t M, int64_t N, int64_t K, int rot) {
   if (M <= 0 || N <= 0 || K <= 0) return 2;
   const int cus = chip_cus();
@@ -1723,7 +1706,7 @@ int qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn(const void* x, const void* h,
 #if QAMD_BENCH
   // [r6] lab ("gemm_variant" 580): the hand-off form of the one-launch layer (gemm_mx_os16_fq_kernel: the quantizer's body on the first workgroups, the decode form's K walk
   // behind one arrival counter) on a scratch buffer the LAB library allocates once -- an experiment's plumbing, not an API (the product would take caller scratch)
-  if (opt_gemm_variant() == 580 && M <= 16 && K <= 8192 && os16_tn(N) != 0) {
+  if (opt_gemm_variant() == 580 && M <= 16 && K <= 8192 && os16_tn(N, chip_cus()) != 0) {
     static void* scratch = nullptr;
     if (!scratch && hipMalloc(&scratch, 1 << 20) != hipSuccess) return fail(QAMD_ERR_HIP, "%s: lab scratch", name);
     const int64_t CB = cdiv(K / 32, 4);
@@ -1735,7 +1718,7 @@ int qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn(const void* x, const void* h,
     g.M = (int)M; g.N = (int)N; g.K = (int)K; g.ldd = (int)N;
     g.a_bytes = (uint32_t)(M * (K / 2)); g.b_bytes = (uint32_t)(N * (K / 2)); g.sfa_bytes = (uint32_t)(CB * 512); g.sfb_bytes = (uint32_t)(cdiv(N, 128) * CB * 512);
     g.pp_shift = 0; g.pp_flags = 0; g.dbg = nullptr; g.ws = nullptr; g.splits = 1; g.ctr = nullptr; g.tag = 0; g.sk_tiles = 0;
-    const int tn = os16_tn(N);
+    const int tn = os16_tn(N, chip_cus());
     g.tiles_m = 1; g.tiles_n = (int)cdiv(N, tn); g.raster_magic = 0;
     P.flag = (unsigned long long*)((uint8_t*)scratch + (512 << 10));
     P.tag = (next_launch_tag() & ((1ull << 56) - 1)) << 8;
@@ -1976,21 +1959,25 @@ int qutlass_amd_to_blocked(const void* in, int64_t rows, int64_t cols, void* out
   return check_launch("to_blocked_kernel");
 }
 
-// debug only (not declared in the public header): which kernels would matmul_mx{f4,f8}_bf16_tn(_ws) launch for this shape?
+// debug only (not declared in the public header): which kernels would matmul_mx{f4,f8}_bf16_tn(_ws) launch for this shape on a 256-CU part?
 // out[3 * i + {0, 1, 2}] = {gemm_variant, N of the launch, K splits} of launch i; returns the number of launches (the split-K
 // reduce pass is implied by splits > 1), or -1 when the arguments are rejected.  No GPU is touched.
 int qutlass_amd_debug_gemm_plan(int ebits, int64_t M, int64_t N, int64_t K, int64_t workspace_bytes, int* out, int cap) {
   alignas(16) static char dummy[16];
-  t_dry = DryRun{};
-  t_dry.on = true;
-  void* ws = workspace_bytes > 0 ? (void*)dummy : nullptr;
-  const int rc = (ebits == 4) ? gemm_mx<4>("debug_gemm_plan", dummy, dummy, dummy, dummy, (const float*)dummy, dummy, M, N, K, nullptr, ws, workspace_bytes)
-               : (ebits == 8) ? gemm_mx<8>("debug_gemm_plan", dummy, dummy, dummy, dummy, (const float*)dummy, dummy, M, N, K, nullptr, ws, workspace_bytes)
-                              : QAMD_ERR_INVALID;
-  const int n = t_dry.n;
-  for (int i = 0; i < n && i < 8 && i < cap; ++i) { out[3 * i] = t_dry.rec[i][0]; out[3 * i + 1] = t_dry.rec[i][1]; out[3 * i + 2] = t_dry.rec[i][2]; }
-  t_dry = DryRun{};
-  return rc == QAMD_OK ? n : -1;
+  const char* name = "debug_gemm_plan";
+  if ((ebits != 4 && ebits != 8) || mx_check(name, ebits, dummy, dummy, dummy, dummy, (const float*)dummy, dummy, M, N, K)) return -1;
+  const int64_t avail = std::max<int64_t>(workspace_bytes, 0);
+  return debug_plan(name, M, N, K * ebits / 8, 256, out, cap, [&](int64_t m, int64_t n) {
+    return ebits == 4 ? mx_plan<4>(0, m, n, K, N, avail, 256) : mx_plan<8>(0, m, n, K, N, avail, 256);
+  });
+}
+
+// debug only (not declared in the public header): the same for matmul_ada_mxf4_bf16_tn (ada_plan; K splits are always 1)
+int qutlass_amd_debug_ada_plan(int64_t M, int64_t N, int64_t K, int* out, int cap) {
+  alignas(16) static char dummy[16];
+  const char* name = "debug_ada_plan";
+  if (ada_check(name, dummy, dummy, dummy, dummy, (const float*)dummy, dummy, M, N, K)) return -1;
+  return debug_plan(name, M, N, K / 2, 64, out, cap, [&](int64_t m, int64_t n) { return MxPlan().add(ada_plan(m, n, K, 256), 0, n); });
 }
 
 // [r4] debug only (not declared in the public header): the kernel rules of the QAT-backward data-prep ops on a 256-CU part, no GPU touched.

@@ -453,8 +453,8 @@ def test_small_output_plans_against_the_gpu_only_calibrations(lib):
 
 
 def test_auto_dispatch_rules_dry_run(lib):
-    """The tile / schedule choice of the MX GEMMs (DESIGN.md sections 3.3, 3.7, 3.8) through the library's dry-run hook:
-    the real dispatch code runs, launches are recorded instead of issued.  (variant, N of the launch, K splits)."""
+    """The tile / schedule choice of the MX GEMMs (DESIGN.md sections 3.3, 3.7, 3.8) through the library's plan entry: the
+    plan the launcher executes, on a 256-CU part, no GPU touched.  (variant, N of the launch, K splits)."""
     f = lib.qutlass_amd_debug_gemm_plan   # debug entry, deliberately not in the public header
     f.restype = ctypes.c_int
     f.argtypes = [ctypes.c_int] + [ctypes.c_int64] * 4 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
@@ -556,6 +556,37 @@ def test_auto_dispatch_rules_dry_run(lib):
     assert plan(4, 4096, 262400, 16384) == [(DEEPP, 261888, 1), (71, 512, 1)]
     # rejected arguments never reach the dispatch
     assert plan(4, 128, 128, 96) is None and plan(5, 128, 128, 128) is None
+
+
+def test_ada_dispatch_rule(lib):
+    """matmul_ada_mxf4_bf16_tn's kernel choice (capi.hip ada_plan: row-major scales, no scratch so no split-K) on a 256-CU part, through its debug entry:
+    (variant, N of the launch, K splits) per launch, in dispatch_variant's numbering."""
+    f = lib.qutlass_amd_debug_ada_plan   # debug entry, deliberately not in the public header
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_int64] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+
+    def plan(m, n, k):
+        out = (ctypes.c_int * 24)()
+        cnt = f(m, n, k, out, 8)
+        return None if cnt < 0 else [(out[3 * i], out[3 * i + 1], out[3 * i + 2]) for i in range(cnt)]
+
+    SKINNY, RING64, OS32, OS16, OS64 = 60, 70, 568, 569, 570
+    # the LDS-free split-K kernel: M <= 32 against fewer than 128 64-row weight tiles, or fewer than 256 with K >= 16384 (8 x 8192 x 28672: 27.9 us vs 34.2 on the ring)
+    assert plan(8, 2048, 28672) == [(SKINNY, 2048, 1)] and plan(8, 8192, 28672) == [(SKINNY, 8192, 1)]
+    # the 64x64 ring kernel: M > 32 past the wave-owned kernels' reach, or a weight of >= 256 64-row tiles
+    assert plan(256, 4096, 4096) == [(RING64, 4096, 1)] and plan(16, 57344, 8192) == [(RING64, 57344, 1)] and plan(17, 14336, 4096) == [(RING64, 14336, 1)]
+    # the wave-owned kernel (os_plan, ada: every K up to 64 stages of 256): 32x32 tiles, 32x16 while those still fit one per CU, 64x32 where 32-row tiles overflow (os64_plan)
+    assert plan(64, 4096, 4096) == [(OS32, 4096, 1)] and plan(32, 4096, 4096) == [(OS16, 4096, 1)]
+    assert plan(128, 4096, 4096) == [(OS64, 4096, 1)] and plan(96, 4096, 14336) == [(OS64, 4096, 1)]
+    # its 16-row decode form: 16 columns per workgroup where 16x16 tiles fit one per CU, 32 / 48 / 56 / 64 for wider weights inside os16_wide_plan's K ranges
+    assert plan(1, 4096, 4096) == [(571, 4096, 1)] and plan(16, 4096, 4096) == [(571, 4096, 1)] and plan(8, 8192, 8192) == [(572, 8192, 1)]
+    assert plan(1, 12288, 4096) == [(573, 12288, 1)] and plan(16, 14336, 4096) == [(574, 14336, 1)] and plan(8, 16384, 4096) == [(575, 16384, 1)]
+    assert plan(16, 14336, 8192) == [(RING64, 14336, 1)]   # 56 columns past 16 stages: the ring
+    # operands of >= 2 GiB: ranges of whole 64-row tiles of A (262080 rows, then 64) and 64-column tiles of B (262080 columns, then 320), each planned on its own
+    assert plan(262144, 4096, 16384) == [(RING64, 4096, 1), (OS32, 4096, 1)] and plan(262143, 4096, 16384) == [(RING64, 4096, 1)]
+    assert plan(16, 262400, 16384) == [(RING64, 262080, 1), (SKINNY, 320, 1)]
+    # rejected arguments never reach the rule
+    assert plan(128, 128, 96) is None and plan(128, 130, 128) is None and plan(1, 64, 1 << 27) is None   # (the last: K too long for a 64-column range of B)
 
 
 def test_new_round3_entry_points_validate_their_arguments(lib):
