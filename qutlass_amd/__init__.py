@@ -7,6 +7,7 @@ meaning, defaults and Python-level error behaviour):
     matmul_mxf8_bf16_tn, matmul_mxf8_bf16_nn         (+ qutlass_amd.utils.to_blocked & friends)
     matmul_ada_mxf4_bf16_tn, backward_t_bf16, backward_qt_bf16, backward_bf16_square_double_mxfp8, mxfp4_transpose_mxfp8
     grouped_matmul_mxf4_bf16_tn                      (extension: mixture-of-experts layers, one launch over all experts)
+    grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -73,6 +74,25 @@ def grouped_matmul_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Te
     needs no host sync and works under graph capture and torch.compile; each offset is clamped to [0, M] and a decreasing one is an empty group.
     K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; one expert's weight below 2 GiB (the stack may exceed it).  M == 0 returns an empty output."""
     return _ops_amd.grouped_matmul_mxf4(a, b, a_sf, b_sf, alpha, offs)
+
+
+def grouped_matmul_mxf8_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,
+                                alpha: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): grouped MXFP8 GEMM for mixture-of-experts layers, one launch over all experts.
+
+    a      (M, K) float8_e4m3fn or float8_e5m2 -- the tokens, sorted by expert (e5m2 selects the e5m2-A path, as in matmul_mxf8_bf16_tn: MoE dgrad)
+    b      (E, N, K) float8_e4m3fn -- the stacked expert weights
+    a_sf   float8_e8m0fnu, >= M*K/32 elements, read as row-major (M, K/32)
+    b_sf   float8_e8m0fnu, >= E*N*K/32 elements, read as row-major (E, N, K/32)
+    alpha  float32, 1 element (shared) or E elements (per expert)
+    offs   int32 (E,): the cumulative END rows of the groups (torch._grouped_mm's convention) -- group g is rows [offs[g-1], offs[g]), offs[-1] := 0
+
+    Returns out (M, N) bf16 with out[r] = alpha[g] * (A_r . SFA) (B_g . SFB_g)^T for every row r of group g.  Empty groups are allowed; rows at or
+    past offs[E-1] are not written (their contents are unspecified, as in torch._grouped_mm).  The offsets are read on the device, so the call
+    needs no host sync and works under graph capture and torch.compile; each offset is clamped to [0, M] and a decreasing one is an empty group.
+    K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; the token matrix and one expert's weight below 2 GiB (the stack may exceed it).  M == 0 returns an
+    empty output."""
+    return _ops_amd.grouped_matmul_mxf8(a, b, a_sf, b_sf, alpha, offs)
 
 
 def matmul_nvf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,

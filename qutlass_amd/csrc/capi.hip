@@ -395,18 +395,19 @@ inline int64_t grouped_grid(int v, int64_t M, int64_t N, int64_t E) {
   const int TM = v == 590 || v == 591 ? 32 : 64, TN = v == 591 ? 16 : v == 593 ? 64 : 32;
   return (cdiv(M, TM) + E) * cdiv(N, TN);
 }
-template <int TM, int TN>
+// (EBITS 8: grouped_matmul_mxf8_bf16_tn, AFMT 1: e5m2 A)
+template <int TM, int TN, int EBITS = 4, int AFMT = 0>
 int launch_grouped_os(GroupedParams q, hipStream_t s) {
   q.tiles_m = 1;
   q.tiles_n = (int)cdiv(q.N, TN);
-  const int64_t KT = cdiv((int64_t)q.K / 2, 128);
+  const int64_t KT = cdiv((int64_t)q.K * EBITS / 8, 128);
   const dim3 grid((int)((cdiv(q.M, TM) + q.E) * q.tiles_n)), block(256);   // the bound of the real tiles (grouped_tile: the rest return at once)
   constexpr int SMAX = TM == 32 ? 4 : 3;   // slots per wave that fit the LDS (launch_gemm_os)
-  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<1, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
-  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<2, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
-  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<3, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
-  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, 4, TM>, true, false, true>), grid, block, 0, s, q);
-  else hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, 4, TM>, true, true, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<1, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<2, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
+  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<3, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, true, true, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
   return check_launch("gemm_mx_os_kernel (grouped)");
 }
 template <class C>
@@ -415,6 +416,30 @@ int launch_grouped_ring(GroupedParams q, hipStream_t s) {
   q.tiles_n = (int)cdiv(q.N, C::BN);
   hipLaunchKernelGGL((gemm_mx_grouped_ring_kernel<C>), dim3((int)((cdiv(q.M, C::BM) + q.E) * q.tiles_n)), dim3(C::THREADS), 0, s, q);
   return check_launch("gemm_mx_grouped_ring_kernel");
+}
+
+// ---- grouped MXFP8 GEMM: the same two tile bodies on 8-bit elements (a stage is 128 elements, so a row has twice the stages of an MXFP4 row of the same K) ----------
+// Forms: 594 = 32x32 tiles of the wave-owned kernel, 595 = 32x16, 596 = 64x32 (one shot while a tile's K extent fits the LDS, wave-owned rings beyond), 597 = the 64x64
+// ring kernel with row-major scale fetch (matmul_mxf8_bf16_tn's ring tiles).
+// Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B (profiles/calib_grouped_mxf8_r7.txt; these are not the MXFP4 thresholds): 597 is fastest
+// everywhere but one case, a short K included (Qwen3 down, K = 768, 4 rows per expert: 53.1 us against 66.4 for 594 -- where MXFP4's 590 won); 595 and 596 never lead.
+// The exception is a long K at few rows per expert (Mixtral down, K = 14336, 16 rows per expert: 594 takes 107.8 / 112.6 us uniform / skewed against 106.9 / 145.8 for
+// 597), while the same rows at K = 4096 stay with 597 (Mixtral gate/up: 224.6 / 240.5 against 275.9 / 295.9).  So: mean rows per group M / E <= 32 and K >= 8192 -> 594,
+// otherwise 597.  N and the CU count are arguments so that a rule re-taken from more measurements can use them.
+inline int grouped8_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M <= 32 * E && K >= 8192) ? 594 : 597;
+}
+inline int64_t grouped8_grid(int v, int64_t M, int64_t N, int64_t E) {
+  const int TM = v == 594 || v == 595 ? 32 : 64, TN = v == 595 ? 16 : v == 597 ? 64 : 32;
+  return (cdiv(M, TM) + E) * cdiv(N, TN);
+}
+template <int AFMT>
+int launch_grouped8(int v, const GroupedParams& q, hipStream_t s) {
+  if (v == 594) return launch_grouped_os<32, 32, 8, AFMT>(q, s);
+  if (v == 595) return launch_grouped_os<32, 16, 8, AFMT>(q, s);
+  if (v == 596) return launch_grouped_os<64, 32, 8, AFMT>(q, s);
+  return launch_grouped_ring<GroupedRing8Cfg<AFMT>>(q, s);
 }
 
 // [r4] stream-K form of the two persistent kernels (lab variant 89): one workgroup per CU; p.ws / p.ctr / p.tag / p.sk_tiles set by mx_launch
@@ -1417,6 +1442,45 @@ int qutlass_amd_grouped_matmul_mxf4_bf16_tn(const void* A, const void* B, const 
   return launch_grouped_ring<GroupedRingCfg>(q, s);   // matmul_ada_mxf4_bf16_tn's ring tiles
 }
 
+// grouped_matmul_mxf8_bf16_tn: every argument is checked before any HIP call (grouped_check's checks with one byte per element, plus the A format)
+static int grouped8_check(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                          const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E, int a_format) {
+  if (!A || !B || !A_sf || !B_sf || !alpha || !offs || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (E < 1 || E > GRP_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, GRP_MAX_E, (long long)E);
+  if (n_alpha != 1 && n_alpha != E) return fail(QAMD_ERR_INVALID, "%s: alpha must have 1 or E = %lld elements (got %lld)", name, (long long)E, (long long)n_alpha);
+  if (a_format != QAMD_FP8_E4M3 && a_format != QAMD_FP8_E5M2) return fail(QAMD_ERR_INVALID, "%s: invalid a_format %d", name, a_format);
+  if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
+  if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
+  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
+  const int64_t rows_2g = ((1ll << 31) + K - 1) / K;   // rows of K bytes that reach 2 GiB (no product that can overflow)
+  if (N >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * K bytes, N=%lld K=%lld) must stay below 2 GiB", name, (long long)N, (long long)K);
+  if (M >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * K bytes, M=%lld K=%lld) must stay below 2 GiB", name, (long long)M, (long long)K);
+  if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
+  for (int v = 594; v <= 597; ++v)
+    if (grouped8_grid(v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
+  return QAMD_OK;
+}
+
+int qutlass_amd_grouped_matmul_mxf8_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                            const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, int a_format, void* stream) {
+  const char* name = "grouped_matmul_mxf8_bf16_tn";
+  if (int rc = grouped8_check(name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E, a_format)) return rc;
+  if (M == 0) return QAMD_OK;
+  const int forced = opt_gemm_variant();   // lab: 594 ... 597 force a form
+  const int v = (forced >= 594 && forced <= 597) ? forced : grouped8_plan(M, N, K, E, chip_cus());
+  const int64_t KB = K / 32;
+  GroupedParams q;
+  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
+  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
+  q.a_bytes = (uint32_t)(M * K); q.b_bytes = (uint32_t)(N * K);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
+  q.sfa_bytes = (uint32_t)(M * KB); q.sfb_bytes = (uint32_t)(N * KB);
+  q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
+  q.ws = nullptr; q.splits = 1; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha;
+  hipStream_t s = (hipStream_t)stream;
+  return a_format == QAMD_FP8_E5M2 ? launch_grouped8<1>(v, q, s) : launch_grouped8<0>(v, q, s);
+}
+
 int qutlass_amd_matmul_mxf8_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
                                     const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream) {
   return gemm_mx<8>("matmul_mxf8_bf16_tn", A, B, A_sf, B_sf, alpha, D, M, N, K, stream);
@@ -2026,6 +2090,16 @@ int qutlass_amd_debug_grouped_plan(int64_t M, int64_t N, int64_t K, int64_t E, i
   if (grouped_check("debug_grouped_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E)) return -1;
   const int v = grouped_plan(M, N, K, E, 256);
   if (out) out[0] = M == 0 ? 0 : grouped_grid(v, M, N, E);
+  return v;
+}
+
+// debug only (not declared in the public header): the form grouped_matmul_mxf8_bf16_tn picks (594 = 32x32 tiles of the wave-owned kernel, 597 = the 64x64 ring
+// kernel) on a 256-CU part, after the entry's own argument checks (-1: rejected); out[0] (optional) = the workgroups it launches.  No GPU touched.
+int qutlass_amd_debug_grouped_mxf8_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  alignas(16) static char dummy[16];
+  if (grouped8_check("debug_grouped_mxf8_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E, QAMD_FP8_E4M3)) return -1;
+  const int v = grouped8_plan(M, N, K, E, 256);
+  if (out) out[0] = M == 0 ? 0 : grouped8_grid(v, M, N, E);
   return v;
 }
 

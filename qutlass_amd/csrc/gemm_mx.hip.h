@@ -631,22 +631,32 @@ __device__ __forceinline__ void gemm_mx_ringp(char* smem, const GemmParams& p, i
   constexpr int LPS = C::NA + C::NB + 1;            // DMA instructions per wave per stage
   constexpr int U = (D % 2 == 0) ? D : 2 * D;       // unroll: slot = u % D, register set = u & 1
   static_assert(D >= 2 && (D - 2) * LPS <= 63, "vmcnt immediate");   // D = 2: one stage in flight, LDS of the simple schedule (two workgroups per CU)
-  static_assert(!RM || (C::EBITS == 4 && C::BM == 64 && C::BN == 64 && C::NWAVES == 4), "row-major scales: 64x64 fp4 tiles");
+  static_assert(!RM || (C::BM == 64 && C::BN == 64 && C::NWAVES == 4 && (C::EBITS == 4 || C::F8SPLIT)), "row-major scales: 64x64 tiles (fp8: split fragments)");
   static_assert((C::ABL & ~ABL_READS_FIRST) == 0, "no ablation builds of this schedule");
   GemmCtx<C> cx(smem, p, bid, fm0, fn0);
   __amdgpu_buffer_rsrc_t rSrm = cx.rS;
   int vSrm = 0x7fffffff;
   const int KBr = p.K >> 5;                         // scale bytes per row (row-major)
+  constexpr int RMW = C::EBITS == 4 ? 8 : 4;        // RM: scale bytes per row and stage (fp4: two dwords, fp8: one)
   if (RM) {
+    // waves 0, 1: A's 64 rows, waves 2, 3: B's; each wave one dword piece of 256 bytes at OFF_S + 256 wave (the same DMA count for every wave).
+    // fp4: wave & 1 = which of the row's two dwords, lane = row; fp8: wave & 1 = which 32 rows, lane half 0 carries them (half 1: out of range -> zeros)
     const int opB = cx.wave >> 1, dw = cx.wave & 1;
     const uint32_t row0 = opB ? (uint32_t)cx.n0 : (uint32_t)cx.m0;
     const uint32_t total = opB ? p.sfb_bytes : p.sfa_bytes, off = row0 * (uint32_t)KBr;
     rSrm = make_rsrc((opB ? p.SFB : p.SFA) + off, total > off ? total - off : 0);   // rows past M / N fall off the end -> 0
-    vSrm = cx.lane * KBr + dw * 4;
+    if (C::EBITS == 4) vSrm = cx.lane * KBr + dw * 4;
+    else vSrm = cx.g ? 0x7fffffff : (32 * dw + cx.i32) * KBr;
 #pragma unroll
-    for (int t = 0; t < MT; ++t) cx.rdSA[t] = C::OFF_S + cx.g * 256 + (cx.wave_m * C::WTM + 32 * t + cx.i32) * 4;
+    for (int t = 0; t < MT; ++t) {
+      const int r = cx.wave_m * C::WTM + 32 * t + cx.i32;
+      cx.rdSA[t] = C::OFF_S + (C::EBITS == 4 ? cx.g * 256 + r * 4 : (r >> 5) * 256 + (r & 31) * 4);   // fp8: both lane halves read the row's dword
+    }
 #pragma unroll
-    for (int t = 0; t < NT; ++t) cx.rdSB[t] = C::OFF_S + 512 + cx.g * 256 + (cx.wave_n * C::WTN + 32 * t + cx.i32) * 4;
+    for (int t = 0; t < NT; ++t) {
+      const int r = cx.wave_n * C::WTN + 32 * t + cx.i32;
+      cx.rdSB[t] = C::OFF_S + 512 + (C::EBITS == 4 ? cx.g * 256 + r * 4 : (r >> 5) * 256 + (r & 31) * 4);
+    }
   }
   auto fence = [&]() __attribute__((always_inline)) { __builtin_amdgcn_sched_barrier(0); };
   int kt0 = 0, kt1 = cx.KT;
@@ -686,8 +696,8 @@ __device__ __forceinline__ void gemm_mx_ringp(char* smem, const GemmParams& p, i
       const int t = item - C::NA, v = (vBT[t] & d_last) | (vB[t] & ~d_last);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.rB, (lds_ptr_t)(st + C::OFF_B + (cx.wave * C::NB + t) * 1024), 16, v, d_soff, 0, QAMD_DMA_AUX);
     } else if (RM) {
-      const int vs = (d_ktc * 8 + (cx.wave & 1) * 4 < KBr) ? vSrm : 0x7fffffff;   // K tail: the stage's second scale dword does not exist
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rSrm, (lds_ptr_t)(st + C::OFF_S + cx.wave * 256), 4, vs, d_ktc * 8, 0, 0);
+      const int vs = (d_ktc * RMW + (C::EBITS == 4 ? (cx.wave & 1) * 4 : 0) < KBr) ? vSrm : 0x7fffffff;   // K tail: the stage's second scale dword does not exist
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rSrm, (lds_ptr_t)(st + C::OFF_S + cx.wave * 256), 4, vs, d_ktc * RMW, 0, 0);
     } else {
       const int vs = (d_ktc * C::SCT + cx.colS < cx.CB) ? cx.voffS : 0x7fffffff;   // K tail: no such scale column tile
       __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.rS, (lds_ptr_t)(st + C::OFF_S + cx.wave * 1024), 16, vs, d_ktc * C::SCT * 512, 0, 0);

@@ -1,4 +1,5 @@
-// Grouped MXFP4 GEMM for mixture-of-experts layers (extension: grouped_matmul_mxf4_bf16_tn).  Tokens sorted by expert, A (M, K/2) with row-major scales (M, K/32)
+// Grouped MXFP4 / MXFP8 GEMM for mixture-of-experts layers (extensions: grouped_matmul_mxf4_bf16_tn, grouped_matmul_mxf8_bf16_tn -- the same with (M, K) /
+// (E, N, K) fp8 operands, A e4m3 or e5m2, B e4m3).  Tokens sorted by expert, A (M, K/2) with row-major scales (M, K/32)
 // as fusedQuantizeMx writes them; the stacked expert weights B (E, N, K/2) with row-major scales (E, N, K/32); offs (E,) int32 = the cumulative END rows of the groups
 // (torch._grouped_mm's convention).  out[r] = alpha[g] (A_r . SFA) (B_g . SFB_g)^T for every row r of group g; rows at or past offs[E - 1] are not written.
 //
@@ -163,13 +164,13 @@ struct GroupedView {
   const uint8_t* SFB;
   const float* alpha;
 };
-// workgroup -> the grouped parts of its tile's view, false: no work
-template <int TM, int TN>
+// workgroup -> the grouped parts of its tile's view, false: no work (EBITS: element width, 4 = MXFP4, 8 = MXFP8)
+template <int TM, int TN, int EBITS = 4>
 __device__ __forceinline__ bool grouped_setup(const GroupedParams& pk, GroupedView& v) {
   GroupTile t;
   if (!grouped_tile(pk.offs, pk.E, pk.M, TM, pk.tiles_n, (int)blockIdx.x, t)) return false;
   const int g = uniform(t.g), gend = uniform(t.row0 + t.rows);
-  const uint32_t rowbytes = (uint32_t)pk.K >> 1, KB = (uint32_t)pk.K >> 5;
+  const uint32_t rowbytes = EBITS == 8 ? (uint32_t)pk.K : (uint32_t)pk.K >> 1, KB = (uint32_t)pk.K >> 5;
   v.M = gend;                                      // stores masked to the group's rows ...
   v.a_bytes = (uint32_t)gend * rowbytes;           // ... and reads past them return zeros
   v.sfa_bytes = (uint32_t)gend * KB;
@@ -185,13 +186,16 @@ __device__ __forceinline__ bool grouped_setup(const GroupedParams& pk, GroupedVi
 // type of its own (same constants): the body's templates are instantiated for this kernel alone, so the compiler's view of the plain kernel's instantiation -- called
 // from that kernel only -- and with it that kernel's code stay exactly as they were.
 struct GroupedRingCfg : GemmCfg<64, 64, 2, 2, 4, false, 0, 3> {};
+// grouped_matmul_mxf8_bf16_tn's: the tiles of matmul_mxf8_bf16_tn's product ring (split 8-bit fragments, dispatch_variant<8, true>), A e4m3 (AFMT 0) or e5m2 (1)
+template <int AFMT>
+struct GroupedRing8Cfg : GemmCfg<64, 64, 2, 2, 8, true, 0, 3, AFMT> {};
 template <class C>
 __global__ __launch_bounds__(C::THREADS, (gemm_min_waves_per_eu<C, SCHED_RINGP_RM>())) void gemm_mx_grouped_ring_kernel(const GroupedParams pk) {
-  static_assert(C::BM == 64 && C::BN == 64 && C::EBITS == 4, "64x64 MXFP4 tiles");
+  static_assert(C::BM == 64 && C::BN == 64, "64x64 tiles");
   __shared__ __attribute__((aligned(16))) char smem[C::LDS_BYTES];
 #if defined(__HIP_DEVICE_COMPILE__)   // (the host pass of this unit does not resolve the body's device templates; it only needs the kernel's symbol)
   GroupedView v;
-  if (!grouped_setup<C::BM, C::BN>(pk, v)) return;
+  if (!grouped_setup<C::BM, C::BN, C::EBITS>(pk, v)) return;
   GemmParams p = pk;
   p.M = v.M; p.a_bytes = v.a_bytes; p.sfa_bytes = v.sfa_bytes; p.B = v.B; p.SFB = v.SFB; p.alpha = v.alpha;
   p.tiles_m = 1; p.tiles_n = 1;

@@ -53,18 +53,19 @@ struct OsCfg {
 };
 
 // RM: the scale operands are row-major (rows, K / 32) as matmul_ada_mxf4_bf16_tn hands them over (qutlass/csrc/gemm_ada.cu) instead of the to_blocked image
+// (fp8: grouped_matmul_mxf8_bf16_tn only -- row r's dword of stage kt is bytes 4 kt .. + 3 of its K / 32, the same four bytes in the same order as its dword of column
+// tile kt in the to_blocked image, so the fragments, op_sel and shifts are those of the blocked path)
 // RING: any K -- the wave's SPW slots are refilled as they are consumed (false: at most 4 SPW stages, every stage has a slot of its own)
-// GRP: one launch of grouped_matmul_mxf4_bf16_tn (gemm_mx_grouped.hip.h) -- the workgroup decodes its tile from the group offsets: origin, the group's end row (A / A-scale
+// GRP: one launch of grouped_matmul_mxf4_bf16_tn / grouped_matmul_mxf8_bf16_tn (gemm_mx_grouped.hip.h) -- the workgroup decodes its tile from the group offsets: origin, the group's end row (A / A-scale
 // ranges and stores end there), expert g's B / B-scales / alpha; the rest is this body unchanged (false: the plain kernel, the same code as before the parameter existed)
 template <class C, bool RM = false, bool RING = false, bool GRP = false>
 __global__ __launch_bounds__(256) void gemm_mx_os_kernel(const std::conditional_t<GRP, GroupedParams, GemmParams> p) {
   constexpr int SPW = C::SPW, LPS = C::LPS, MT = C::MT, KSL = C::KSL, E8 = C::EBITS == 8;
-  static_assert(!(RM && E8), "row-major scales: matmul_ada_mxf4_bf16_tn only");
-  static_assert(!GRP || (RM && !E8), "grouped: MXFP4 with row-major scales");
+  static_assert(!GRP || RM, "grouped: row-major scales");
   __shared__ __attribute__((aligned(16))) char smem[C::LDS_BYTES];
   GroupedView gv{};
   if constexpr (GRP) {
-    if (!grouped_setup<C::TM, C::TN>(p, gv)) return;   // an m-tile slot past the real tiles: no work
+    if (!grouped_setup<C::TM, C::TN, C::EBITS>(p, gv)) return;   // an m-tile slot past the real tiles: no work
   }
   asm volatile("" :: "s"(p.A), "s"(p.D), "s"(p.K), "s"(p.b_bytes), "s"(p.alpha));   // all scalar argument loads in one round
   const float alpha = *(GRP ? gv.alpha : p.alpha);
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(256) void gemm_mx_os_kernel(const std::conditional_
   const int rstep = 8 * rowbytes;
   // scale dwords.  fp4: row (m0 | n0) + i32 of column tile 2 kt + g -- byte ((r % 32) * 16 + ((r % 128) / 32) * 4) of the 512-byte tile (qutlass/utils.py:60-64)
   // (RM: row r's eight scale bytes of stage kt are bytes 8 kt .. + 7 of its K / 32 -- the lane's dword is bytes 8 kt + 4 g .. + 3; rows past M / N lie past the descriptor).
-  // fp8: the stage is column tile kt; both lane halves fetch the row's dword (TM = 64: lane half g fetches m-tile g's)
+  // fp8: the stage is column tile kt; both lane halves fetch the row's dword (TM = 64: lane half g fetches m-tile g's) -- RM: bytes 4 kt .. + 3 of the row's K / 32
   const int KB = p.K >> 5;
   const uint32_t sa_off = RM ? (uint32_t)m0 * KB : (uint32_t)(m0 >> 7) * CB * 512, sb_off = RM ? (uint32_t)n0 * KB : (uint32_t)(n0 >> 7) * CB * 512;
   const __amdgpu_buffer_rsrc_t rSA = make_rsrc(p.SFA + sa_off, (GRP ? gv.sfa_bytes : p.sfa_bytes) - sa_off), rSB = make_rsrc((GRP ? gv.SFB : p.SFB) + sb_off, p.sfb_bytes - sb_off);
@@ -100,10 +101,11 @@ __global__ __launch_bounds__(256) void gemm_mx_os_kernel(const std::conditional_
 #pragma unroll
   for (int t = 0; t < C::NSA; ++t) {
     const int slab = E8 ? (MT == 2 ? g : 0) : t;   // m-tile whose dword this lane fetches with piece t
-    vSA[t] = RM ? (32 * slab + i32) * KB + 4 * g : gcol + i32 * 16 + (mq + slab) * 4;
+    vSA[t] = RM ? (32 * slab + i32) * KB + (E8 ? 0 : 4 * g) : gcol + i32 * 16 + (mq + slab) * 4;
   }
-  const int vSB = RM ? i32 * KB + 4 * g : gcol + (rowB & 31) * 16 + ((rowB & 127) >> 5) * 4;
+  const int vSB = RM ? i32 * KB + (E8 ? 0 : 4 * g) : gcol + (rowB & 31) * 16 + ((rowB & 127) >> 5) * 4;
   constexpr int SCW = E8 ? 512 : 1024;   // scale bytes per stage and 128-row tile
+  constexpr int RMW = E8 ? 4 : 8;        // RM: scale bytes per stage and row
 
   auto issue = [&](const int kt, const int slot) __attribute__((always_inline)) {   // stage kt into slot `slot` of this wave (kt >= KT: every piece out of range -> zeros)
     char* st = smem + (wave * SPW + slot) * C::STAGE;
@@ -120,11 +122,11 @@ __global__ __launch_bounds__(256) void gemm_mx_os_kernel(const std::conditional_
       __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rB : rA, (lds_ptr_t)(st + (isB ? C::OFF_B : 0) + qq * 1024), 16, v, soff, 0, 0);
     }
     // a column tile past the operand's last one would read the next row tile's bytes (RM: K-blocks past K / 32 the next row's)
-    const int os = (kt < KT && (RM ? 8 * kt + 4 * g < KB : (E8 ? kt : 2 * kt + g) < CB)) ? 0 : -1;
+    const int os = (kt < KT && (RM ? (E8 ? 4 * kt : 8 * kt + 4 * g) < KB : (E8 ? kt : 2 * kt + g) < CB)) ? 0 : -1;
 #pragma unroll
     for (int t = 0; t < C::NSA; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rSA, (lds_ptr_t)(st + C::OFF_S + t * 256), 4, (vSA[t] & ~os) | ((int)0x80000000 & os), RM ? kt * 8 : kt * SCW, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rSB, (lds_ptr_t)(st + C::OFF_SB), 4, (vSB & ~os) | ((int)0x80000000 & os), RM ? kt * 8 : kt * SCW, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rSA, (lds_ptr_t)(st + C::OFF_S + t * 256), 4, (vSA[t] & ~os) | ((int)0x80000000 & os), RM ? kt * RMW : kt * SCW, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rSB, (lds_ptr_t)(st + C::OFF_SB), 4, (vSB & ~os) | ((int)0x80000000 & os), RM ? kt * RMW : kt * SCW, 0, 0);
   };
 
   // ---- everything this wave will ever read (RING: its first SPW stages), requested now ---------------------------------------------------------
