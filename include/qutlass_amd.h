@@ -183,6 +183,22 @@ int qutlass_amd_grouped_matmul_mxf8_bf16_tn(const void* A, const void* B, const 
                                             const float* alpha, int64_t n_alpha, const int32_t* offs, void* D,
                                             int64_t M, int64_t N, int64_t K, int64_t E, int a_format, void* stream);
 
+/*
+ * EXTENSION (no counterpart in the reference): grouped NVFP4 GEMM for mixture-of-experts layers, one launch over E experts.
+ * A: (M, K/2) packed e2m1 tokens sorted by expert, A_sf: ROW-MAJOR (M, K/16) e4m3 (the quantizer's buffer as it is, no to_blocked).
+ * B: (E, N, K/2) stacked expert weights, B_sf: row-major (E, N, K/16).  alpha: device fp32[n_alpha], n_alpha = 1 (shared)
+ * or E (per expert).  offs: device int32[E], the cumulative END rows of the groups (torch._grouped_mm's convention): group g =
+ * rows [offs[g-1], offs[g]), offs[-1] := 0.  D[r] = alpha[g] * (A_r . SFA_r) (B_g . SFB_g)^T for every row r of group g, in
+ * qutlass_amd_matmul_nvf4_bf16_tn's arithmetic; rows at or past offs[E-1] are not written.  The offsets are read on the device
+ * (graph capture works); each is clamped to [0, M] and a decreasing one is an empty group, so malformed offsets never address
+ * outside the operands.
+ * K % 128 == 0, N % 8 == 0, 1 <= E <= 1024, M * K/2 and N * K/2 (one expert) below 2 GiB; the stack may exceed 2 GiB.
+ * M == 0 returns QAMD_OK without a launch.
+ */
+int qutlass_amd_grouped_matmul_nvf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
+                                            const float* alpha, int64_t n_alpha, const int32_t* offs, void* D,
+                                            int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
+
 /* ---- fused rotate + quantize ------------------------------------------------------------------ */
 
 /*

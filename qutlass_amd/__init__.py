@@ -8,6 +8,7 @@ meaning, defaults and Python-level error behaviour):
     matmul_ada_mxf4_bf16_tn, backward_t_bf16, backward_qt_bf16, backward_bf16_square_double_mxfp8, mxfp4_transpose_mxfp8
     grouped_matmul_mxf4_bf16_tn                      (extension: mixture-of-experts layers, one launch over all experts)
     grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
+    grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -93,6 +94,25 @@ def grouped_matmul_mxf8_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Te
     K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; the token matrix and one expert's weight below 2 GiB (the stack may exceed it).  M == 0 returns an
     empty output."""
     return _ops_amd.grouped_matmul_mxf8(a, b, a_sf, b_sf, alpha, offs)
+
+
+def grouped_matmul_nvf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,
+                                alpha: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): grouped NVFP4 GEMM for mixture-of-experts layers, one launch over all experts.
+
+    a      (M, K/2) uint8 or float4_e2m1fn_x2 -- the tokens, sorted by expert
+    b      (E, N, K/2) uint8 or float4_e2m1fn_x2 -- the stacked expert weights
+    a_sf   float8_e4m3fn, >= M*K/16 elements, read as ROW-MAJOR (M, K/16): fusedQuantizeNv's scale buffer as it is (no to_blocked)
+    b_sf   float8_e4m3fn, >= E*N*K/16 elements, read as row-major (E, N, K/16)
+    alpha  float32, 1 element (shared) or E elements (per expert: alpha[g] = 1 / (global_scale_a * global_scale_b[g]))
+    offs   int32 (E,): the cumulative END rows of the groups (torch._grouped_mm's convention) -- group g is rows [offs[g-1], offs[g]), offs[-1] := 0
+
+    Returns out (M, N) bf16 with out[r] = alpha[g] * (A_r . SFA_r) (B_g . SFB_g)^T for every row r of group g, in matmul_nvf4_bf16_tn's arithmetic (e2m1 x e4m3
+    exact in f16, fp32 sums).  Empty groups are allowed; rows at or past offs[E-1] are not written (their contents are unspecified, as in torch._grouped_mm).
+    The offsets are read on the device, so the call needs no host sync and works under graph capture and torch.compile; each offset is clamped to [0, M]
+    and a decreasing one is an empty group.  K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; the token matrix and one expert's weight below 2 GiB (the stack may
+    exceed it).  M == 0 returns an empty output."""
+    return _ops_amd.grouped_matmul_nvf4(a, b, a_sf, b_sf, alpha, offs)
 
 
 def matmul_nvf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,

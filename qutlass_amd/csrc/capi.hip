@@ -785,8 +785,10 @@ extern template int launch_gemm<GemmCfg<256, 256, 2, 2, 8, true>, 6>(GemmParams,
 int launch_nvf4_host(const NvGemmParams& p, hipStream_t s, int variant, int* splits_out) {
   return launch_nvf4_gemm(p, s, variant, chip_cus(), splits_out) == hipSuccess ? 0 : 1;
 }
+int launch_nvf4_grouped_host(const NvGroupedParams& q, hipStream_t s, int form) { return launch_nvf4_grouped(q, s, form) == hipSuccess ? 0 : 1; }
 #else
 int launch_nvf4_host(const NvGemmParams& p, hipStream_t s, int variant, int* splits_out);
+int launch_nvf4_grouped_host(const NvGroupedParams& q, hipStream_t s, int form);
 #endif
 
 #if QAMD_DEF(1)
@@ -1481,6 +1483,63 @@ int qutlass_amd_grouped_matmul_mxf8_bf16_tn(const void* A, const void* B, const 
   return a_format == QAMD_FP8_E5M2 ? launch_grouped8<1>(v, q, s) : launch_grouped8<0>(v, q, s);
 }
 
+// ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
+// Forms: 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles, 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.
+// Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B and on token counts between them (profiles/calib_grouped_nvf4_r7.txt; these are not the MX
+// thresholds).  NVFP4 is bound by dequantisation instructions per MFMA, so the larger tile wins as soon as the groups fill it: at a mean of 64 rows per group and
+// beyond 601 leads (Qwen3 gate/up, 64 rows: 90.6 us against 111.8 for 600; Mixtral gate/up, 1024 rows: 1823 against 2791), at 48 rows and below 600 does (Qwen3 gate/up,
+// 48 rows: 84.1 against 94.2; 4 rows: 70.9 against 82.7 and 84.2 for 598; Qwen3 down, K = 768, 4 rows: 44.1 against 50.3 and 105.7 for 598).  The wave-owned kernel
+// leads only where few 64x64 tiles would each walk a long K: at most 16 rows per group and K >= 8192 (Mixtral down, K = 14336, 16 rows: 598 takes 69.6 / 83.1 us
+// uniform / skewed against 82.8 / 115.5 for 600; cut to K = 8192: 48.6 / 58.6 against 49.5 / 68.8; cut to K = 6144 the two cross, 42.7 / 49.7 against 38.1 / 53.0,
+// and at K = 4096 600 leads, Mixtral gate/up 166.0 / 181.6 against 215.3 / 238.4); at 32 rows per group 600 leads at every K measured.  599 never leads.
+// N and the CU count are arguments so that a rule re-taken from more measurements can use them.
+inline int grouped_nv_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  if (M <= 16 * E && K >= 8192) return 598;
+  return M <= 48 * E ? 600 : 601;
+}
+inline int64_t grouped_nv_grid(int v, int64_t M, int64_t N, int64_t E) {
+  const int TM = v == 598 ? 32 : v == 601 ? 128 : 64, TN = v == 600 ? 64 : v == 601 ? 128 : 32;
+  return (cdiv(M, TM) + E) * cdiv(N, TN);
+}
+
+// grouped_matmul_nvf4_bf16_tn: every argument is checked before any HIP call (grouped_check's checks; the grid bound covers every form)
+static int grouped_nv_check(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                            const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E) {
+  if (!A || !B || !A_sf || !B_sf || !alpha || !offs || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (E < 1 || E > GRP_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, GRP_MAX_E, (long long)E);
+  if (n_alpha != 1 && n_alpha != E) return fail(QAMD_ERR_INVALID, "%s: alpha must have 1 or E = %lld elements (got %lld)", name, (long long)E, (long long)n_alpha);
+  if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
+  if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
+  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
+  const int64_t rows_2g = ((1ll << 31) + K / 2 - 1) / (K / 2);   // rows of K/2 bytes that reach 2 GiB (no product that can overflow)
+  if (N >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * K/2 bytes, N=%lld K=%lld) must stay below 2 GiB", name, (long long)N, (long long)K);
+  if (M >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * K/2 bytes, M=%lld K=%lld) must stay below 2 GiB", name, (long long)M, (long long)K);
+  if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
+  for (int v = 598; v <= 601; ++v)
+    if (grouped_nv_grid(v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
+  return QAMD_OK;
+}
+
+int qutlass_amd_grouped_matmul_nvf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                            const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  const char* name = "grouped_matmul_nvf4_bf16_tn";
+  if (int rc = grouped_nv_check(name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if (M == 0) return QAMD_OK;
+  const int forced = opt_gemm_variant();   // lab: 598 ... 601 force a form
+  const int v = (forced >= 598 && forced <= 601) ? forced : grouped_nv_plan(M, N, K, E, chip_cus());
+  const int64_t rowbytes = K / 2, G16 = K / 16;
+  qamd::NvGroupedParams q{};
+  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
+  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
+  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * rowbytes);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
+  q.sfa_bytes = (uint32_t)(M * G16); q.sfb_bytes = (uint32_t)(N * G16);
+  q.splits = 1;
+  q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha;
+  if (launch_nvf4_grouped_host(q, (hipStream_t)stream, v)) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", name, v);
+  return check_launch("grouped_matmul_nvf4_bf16_tn");
+}
+
 int qutlass_amd_matmul_mxf8_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
                                     const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream) {
   return gemm_mx<8>("matmul_mxf8_bf16_tn", A, B, A_sf, B_sf, alpha, D, M, N, K, stream);
@@ -2100,6 +2159,17 @@ int qutlass_amd_debug_grouped_mxf8_plan(int64_t M, int64_t N, int64_t K, int64_t
   if (grouped8_check("debug_grouped_mxf8_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E, QAMD_FP8_E4M3)) return -1;
   const int v = grouped8_plan(M, N, K, E, 256);
   if (out) out[0] = M == 0 ? 0 : grouped8_grid(v, M, N, E);
+  return v;
+}
+
+// debug only (not declared in the public header): the form grouped_matmul_nvf4_bf16_tn picks (598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 =
+// 64x64 / 128x128 tiles of the tile kernel) on a 256-CU part, after the entry's own argument checks (-1: rejected); out[0] (optional) = the workgroups it launches.
+// No GPU touched.
+int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  alignas(16) static char dummy[16];
+  if (grouped_nv_check("debug_grouped_nvf4_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E)) return -1;
+  const int v = grouped_nv_plan(M, N, K, E, 256);
+  if (out) out[0] = M == 0 ? 0 : grouped_nv_grid(v, M, N, E);
   return v;
 }
 

@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "common.hip.h"
+#include "gemm_mx_grouped.hip.h"   // grouped_tile: the tile decode of the grouped ops (generic in TM, one function for the host and the device)
 
 namespace qamd {
 
@@ -48,6 +49,37 @@ struct NvGemmParams {
   unsigned long long* sk_flags;  //      one arrival flag per slot; == sk_tag: parked (the consumer resets it to 0)
   unsigned long long sk_tag;     //      per-launch number (capi.hip next_launch_tag): the flags need no initialisation
 };
+
+// ---- grouped NVFP4 GEMM for mixture-of-experts layers (extension: grouped_matmul_nvf4_bf16_tn) ----------------------------------------------------------------------
+// The contract of the MX grouped ops (gemm_mx_grouped.hip.h) on NVFP4 operands: A (M, K/2) tokens sorted by expert with ROW-MAJOR e4m3 scales (M, K/16) as
+// fusedQuantizeNv writes them, B (E, N, K/2) with row-major scales (E, N, K/16), offs (E,) the cumulative end rows.  A workgroup decodes (expert, first row, rows,
+// column tile) with grouped_tile and runs an existing NVFP4 tile body at that origin (GRP = true below and in gemm_nvf4_os.hip.h).  Row r's scale dword of column tile
+// c in the to_blocked image holds the same four bytes as the row-major dword at byte r (K/16) + 4 c, so the LDS image of a stage's scales stays byte for byte what the
+// consumers read: only the source offsets of the scale pieces change.  K % 128 == 0, so a row's K/16 scale bytes are whole dwords (no partial column tile).
+struct NvGroupedParams : NvGemmParams {   // A, SFA, alpha, D, M, N, K, ldd, a_bytes, sfa_bytes as for one GEMM over all M rows; B / SFB: expert 0, b_bytes / sfb_bytes: ONE
+                                          // expert's weight / scales; tiles_n = column tiles of the form
+  const int* offs;  // (E,) cumulative end rows
+  int E;
+  int n_alpha;      // 1: alpha[0] for every group, E: alpha[g]
+};
+#if defined(__HIPCC__)
+// workgroup -> the grouped parts of its tile's view (GroupedView: origin, the group's end row, expert g's B / B-scales / alpha), false: no work
+template <int TM, int TN>
+__device__ __forceinline__ bool grouped_nv_setup(const NvGroupedParams& pk, GroupedView& v) {
+  GroupTile t;
+  if (!grouped_tile(pk.offs, pk.E, pk.M, TM, pk.tiles_n, (int)blockIdx.x, t)) return false;
+  const int g = uniform(t.g), gend = uniform(t.row0 + t.rows);
+  v.M = gend;                                               // stores masked to the group's rows ...
+  v.a_bytes = (uint32_t)gend * ((uint32_t)pk.K >> 1);       // ... and reads past them return zeros
+  v.sfa_bytes = (uint32_t)gend * ((uint32_t)pk.K >> 4);
+  v.B = pk.B + (size_t)g * pk.b_bytes;                      // 64-bit: the stacked weight may exceed 2 GiB
+  v.SFB = pk.SFB + (size_t)g * pk.sfb_bytes;
+  v.alpha = pk.alpha + (pk.n_alpha > 1 ? g : 0);
+  v.m0 = uniform(t.row0);
+  v.n0 = uniform(t.nt * TN);
+  return true;
+}
+#endif
 
 template <int BM_, int BN_, int WAVES_M_, int WAVES_N_>
 struct NvCfg {
@@ -90,14 +122,24 @@ __device__ __forceinline__ h8_t dq8(uint32_t w, h2_t s) {
 // SPLIT: the workgroup walks K stages [z kt_per, (z + 1) kt_per) of its tile only and stores the raw fp32 accumulators to ws[z] (splitk_reduce_kernel sums
 // the ranges in z order, applies alpha and rounds: gemm_mx.hip.h).  For outputs of a few dozen 128x128 tiles and a long K, where the only other way to
 // give every CU work is 64x64 tiles whose 32x32 wave tiles dequantise two fragments per MFMA.
-template <class C, bool SPLIT = false, bool FENCED = false>
-__global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const NvGemmParams p) {
+// GRP: one launch of grouped_matmul_nvf4_bf16_tn -- the workgroup decodes its tile from the group offsets (origin, the group's end row: A / A-scale ranges and stores
+// end there; expert g's B / B-scales / alpha) and fetches ROW-MAJOR scales: per operand and stage eight dword pieces (column tile c, half h), lane l of a piece = row
+// 32 (l & 3) + 16 h + (l >> 2) of the tile, so row r's dword lands at (r & 31) 16 + (r >> 5) 4 of column tile c's 512 bytes -- the blocked image; load_scale1 and
+// everything after it are untouched.  The tile's rows are counted from its own origin (rbaseA = rbaseB = 0).  false: the plain kernel, the same code as before the
+// parameter existed.
+template <class C, bool SPLIT = false, bool FENCED = false, bool GRP = false>
+__global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const std::conditional_t<GRP, NvGroupedParams, NvGemmParams> p) {
   constexpr int BM = C::BM, BN = C::BN, MT = C::MT, NT = C::NT;
+  static_assert(!GRP || (!SPLIT && C::NWAVES == 4 && BM == BN && (BM == 64 || BM == 128)), "grouped: 64x64 / 128x128 tiles on four waves, no split");
   __shared__ __attribute__((aligned(16))) char smem[C::LDS_BYTES];
+  GroupedView gv{};
+  if constexpr (GRP) {
+    if (!grouped_nv_setup<BM, BN>(p, gv)) return;   // an m-tile slot past the real tiles: no work
+  }
 #if QAMD_NV_KERNARG_EARLY   // one scalar-load round for the kernel arguments (as gemm_mx_deepp_kernel); prepared at the end of round 4, off in the product, not measured yet
   asm volatile("" :: "s"(p.A), "s"(p.D), "s"(p.K), "s"(p.b_bytes), "s"(p.ws), "s"(p.splits), "s"(p.kt_per));
 #endif
-  const float alpha_k = SPLIT ? 1.0f : *p.alpha;       // [r4] fetched here, not where the epilogue starts (a memory round trip on every workgroup's critical path)
+  const float alpha_k = SPLIT ? 1.0f : *(GRP ? gv.alpha : p.alpha);       // [r4] fetched here, not where the epilogue starts (a memory round trip on every workgroup's critical path)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -105,10 +147,10 @@ __global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const NvGemmParam
   const int wave_m = wave / C::WAVES_N, wave_n = wave % C::WAVES_N;
   const int i32 = lane & 31, g = lane >> 5;
 
-  int tile_m, tile_n;
+  int tile_m = 0, tile_n = 0;
   const int nb = p.tiles_m * p.tiles_n;
   const int z = SPLIT ? (int)blockIdx.x / nb : 0;
-  {
+  if constexpr (!GRP) {
     const int b2 = xcd_remap((int)blockIdx.x - z * nb, nb);
 #if QAMD_CTX_MAGIC_DECODE   // (prepared at the end of round 4, not the product's choice yet: gemm_mx.hip.h GemmCtx)
     raster_decode(b2, p.tiles_m, p.tiles_n, p.raster_magic, tile_m, tile_n);
@@ -122,18 +164,19 @@ __global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const NvGemmParam
     tile_n = (b2 % group) / gsz;
 #endif
   }
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int m0 = GRP ? gv.m0 : tile_m * BM, n0 = GRP ? gv.n0 : tile_n * BN;
   const int rowbytes = p.K >> 1;
   const int KT = (rowbytes + C::ROWB - 1) / C::ROWB;
   const int CB = (p.K / 16 + 3) >> 2;
   const bool ktail = (rowbytes % C::ROWB) != 0;
 
   const uint32_t a_off = (uint32_t)m0 * rowbytes, b_off = (uint32_t)n0 * rowbytes;
-  const __amdgpu_buffer_rsrc_t rA = make_rsrc(p.A + a_off, p.a_bytes - a_off);
-  const __amdgpu_buffer_rsrc_t rB = make_rsrc(p.B + b_off, p.b_bytes - b_off);
-  const uint32_t sa_off = (uint32_t)(m0 >> 7) * CB * 512, sb_off = (uint32_t)(n0 >> 7) * CB * 512;
-  const __amdgpu_buffer_rsrc_t rSA = make_rsrc(p.SFA + sa_off, p.sfa_bytes - sa_off);
-  const __amdgpu_buffer_rsrc_t rSB = make_rsrc(p.SFB + sb_off, p.sfb_bytes - sb_off);
+  const __amdgpu_buffer_rsrc_t rA = make_rsrc(p.A + a_off, (GRP ? gv.a_bytes : p.a_bytes) - a_off);
+  const __amdgpu_buffer_rsrc_t rB = make_rsrc((GRP ? gv.B : p.B) + b_off, p.b_bytes - b_off);
+  // (GRP: row-major scales, K / 16 bytes per row, from the tile's first row)
+  const uint32_t sa_off = GRP ? (uint32_t)m0 * (p.K >> 4) : (uint32_t)(m0 >> 7) * CB * 512, sb_off = GRP ? (uint32_t)n0 * (p.K >> 4) : (uint32_t)(n0 >> 7) * CB * 512;
+  const __amdgpu_buffer_rsrc_t rSA = make_rsrc(p.SFA + sa_off, (GRP ? gv.sfa_bytes : p.sfa_bytes) - sa_off);
+  const __amdgpu_buffer_rsrc_t rSB = make_rsrc((GRP ? gv.SFB : p.SFB) + sb_off, p.sfb_bytes - sb_off);
 
   int voffA[C::NA], voffB[C::NB], chA[C::NA], chB[C::NB];
 #pragma unroll
@@ -162,6 +205,20 @@ __global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const NvGemmParam
       voffS[e] = ((pp / C::SCT) * CB + colS[e]) * 512 + i32 * 16;
     }
   }
+  // GRP: wave w carries four of the sixteen dword pieces of a stage -- operand w >> 1, column tiles 2 (w & 1), + 1, both halves; rows of the 128-row image past a
+  // 64-row tile are not fetched (rows past the group's end / past N lie past the descriptor: zeros)
+  int voffG[4];
+  __amdgpu_buffer_rsrc_t rSG = rSA;
+  if constexpr (GRP) {
+    const bool opB = wave >> 1;
+    const uint32_t total = opB ? p.sfb_bytes : gv.sfa_bytes, off = opB ? sb_off : sa_off;
+    rSG = make_rsrc((opB ? gv.SFB : p.SFA) + off, total - off);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r = (lane & 3) * 32 + 16 * (e & 1) + (lane >> 2);
+      voffG[e] = r < BM ? r * (p.K >> 4) + (2 * (wave & 1) + (e >> 1)) * 4 : 0x7fffffff;
+    }
+  }
 
   auto issue_stage = [&](int kt, int buf) {
     char* st = smem + buf * C::STAGE_BYTES;
@@ -178,6 +235,16 @@ __global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const NvGemmParam
       int v = voffB[t];
       if (tail && (soff + chB[t] * 16 >= rowbytes)) v = 0x7fffffff;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr_t)(st + C::OFF_B + (wave * C::NB + t) * 1024), 16, v, soff, 0, 0);
+    }
+    if constexpr (GRP) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = 2 * (wave & 1) + (e >> 1);
+        // a scale column past K is the NEXT ROW's first scales in the row-major layout (K % 256 == 128: the last stage's upper two dwords): out of range -> 0
+        const int v = (kt * C::SCT + c < CB) ? voffG[e] : 0x7fffffff;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rSG, (lds_ptr_t)(st + (wave >> 1 ? C::OFF_SB : C::OFF_SA) + c * 512 + (e & 1) * 256), 4, v, kt * 16, 0, 0);
+      }
+      return;
     }
 #pragma unroll
     for (int e = 0; e < C::SPW; ++e) {
@@ -204,7 +271,7 @@ __global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const NvGemmParam
     rdA[j] = (wave_m * C::WTM + i32) * C::ROWB + ((c ^ sw) << 4);
     rdB[j] = C::OFF_B + (wave_n * C::WTN + i32) * C::ROWB + ((c ^ sw) << 4);
   }
-  const int rbaseA = (BM >= 128) ? 0 : (m0 & 127), rbaseB = (BN >= 128) ? 0 : (n0 & 127);
+  const int rbaseA = (BM >= 128 || GRP) ? 0 : (m0 & 127), rbaseB = (BN >= 128 || GRP) ? 0 : (n0 & 127);
   int rdSA[MT], rdSB[NT];   // address of column tile 2g; tile 2g+1 is +512
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -375,7 +442,7 @@ __global__ __launch_bounds__(C::THREADS) void gemm_nvf4_kernel(const NvGemmParam
   for (int pss = 0; pss < BM / RPP; ++pss) {
     const int row = pss * RPP + r0;
     const int grow = m0 + row;
-    if (grow < p.M && gcol < p.N) {
+    if (grow < (GRP ? gv.M : p.M) && gcol < p.N) {
       v4i v = *(const v4i*)(smem + row * C::SROW + ((((2 * chunk) ^ (row & 15)) & ~1) << 3));
       if (row & 1) v = v4i{v[2], v[3], v[0], v[1]};
       *(v4i*)(p.D + (size_t)grow * p.ldd + gcol) = v;
@@ -859,6 +926,7 @@ inline int nv_os_plan(int64_t M, int64_t N, int64_t K, int cus) {
   return 0;
 }
 hipError_t launch_nvf4_os(NvGemmParams p, hipStream_t s, int tn);   // capi.hip (the NVFP4 unit)
+hipError_t launch_nvf4_grouped(NvGroupedParams q, hipStream_t s, int form);   // capi.hip (the NVFP4 unit; gemm_nvf4_os.hip.h): form 598 ... 601
 inline NvPlan nvf4_plan(int64_t M, int64_t N, int64_t K, int cus, bool may_split) {
   if (const int tn = nv_os_plan(M, N, K, cus)) return {tn == 856 ? -9 : tn == 1656 ? -8 : tn == 1648 ? -7 : tn == 1632 ? -6 : tn == 3216 ? -5 : tn == 1616 ? -4 : tn == 16 ? -3 : -2, 1, 0};
   if (M <= 32) {   // one m-tile: the wave-owned 32x32 kernel in up to four rounds of tiles (1.75 + 4.05 us per round and 16 stages, K <= 8192) or the split-K kernel (2.53 + 4.66)

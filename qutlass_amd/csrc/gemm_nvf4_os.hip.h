@@ -33,23 +33,33 @@ struct NvOsCfg {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-template <class C, bool RING = false>
-__global__ __launch_bounds__(512) void gemm_nvf4_os_kernel(const NvGemmParams p) {
+// GRP: one launch of grouped_matmul_nvf4_bf16_tn (gemm_nvf4.hip.h) -- the workgroup decodes its tile from the group offsets: origin, the group's end row (A / A-scale
+// ranges and stores end there), expert g's B / B-scales / alpha, and the scale operands are ROW-MAJOR (rows, K / 16): lane (row i32, half g) fetches bytes
+// 16 kt + 8 g + 4 jj .. + 3 of its row -- the same four bytes as its dword of column tile 4 kt + 2 g + jj in the to_blocked image, so the LDS image, the K guard
+// (K % 128 == 0: a row is K / 64 whole dwords, column tile c exists iff c < CB) and everything after the fetch are unchanged; a column tile past K would be the NEXT
+// ROW's first scales and is sent out of range (reads 0).  false: the plain kernel, the same code as before the parameter existed.
+template <class C, bool RING = false, bool GRP = false>
+__global__ __launch_bounds__(512) void gemm_nvf4_os_kernel(const std::conditional_t<GRP, NvGroupedParams, NvGemmParams> p) {
   constexpr int SPW = C::SPW, LPS = C::LPS, NW = C::NW, MT = C::MT;
+  static_assert(!GRP || C::TN == 32, "grouped: 32-column tiles");
   __shared__ __attribute__((aligned(16))) char smem[C::LDS_BYTES];
+  GroupedView gv{};
+  if constexpr (GRP) {
+    if (!grouped_nv_setup<C::TM, C::TN>(p, gv)) return;   // an m-tile slot past the real tiles: no work
+  }
   asm volatile("" :: "s"(p.A), "s"(p.D), "s"(p.K), "s"(p.b_bytes), "s"(p.alpha));   // all scalar argument loads in one round
-  const float alpha = *p.alpha;
+  const float alpha = *(GRP ? gv.alpha : p.alpha);
   const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6), i32 = lane & 31, g = lane >> 5;
   const int nb = p.tiles_m * p.tiles_n;
-  const int b2 = xcd_remap((int)blockIdx.x, nb);
-  const int m0 = uniform((b2 % p.tiles_m) * C::TM), n0 = uniform((b2 / p.tiles_m) * C::TN);
+  const int b2 = GRP ? 0 : xcd_remap((int)blockIdx.x, nb);
+  const int m0 = GRP ? gv.m0 : uniform((b2 % p.tiles_m) * C::TM), n0 = GRP ? gv.n0 : uniform((b2 / p.tiles_m) * C::TN);
   const int rowbytes = p.K >> 1, KT = (rowbytes + C::ROWB - 1) / C::ROWB;
   const int G16 = p.K >> 4, CB = (G16 + 3) >> 2;   // scale groups per row, column tiles of 4 groups
   const int tailbytes = rowbytes - (KT - 1) * C::ROWB;
 
   // ---- LDS-DMA sources (gemm_mx_os.hip.h) ------------------------------------------------------------------------------------------------
   const uint32_t a_off = (uint32_t)m0 * rowbytes, b_off = (uint32_t)n0 * rowbytes;
-  const __amdgpu_buffer_rsrc_t rA = make_rsrc(p.A + a_off, p.a_bytes - a_off), rB = make_rsrc(p.B + b_off, p.b_bytes - b_off);
+  const __amdgpu_buffer_rsrc_t rA = make_rsrc(p.A + a_off, (GRP ? gv.a_bytes : p.a_bytes) - a_off), rB = make_rsrc((GRP ? gv.B : p.B) + b_off, p.b_bytes - b_off);
   int vP[2], chP[2];
 #pragma unroll
   for (int par = 0; par < 2; ++par) {
@@ -57,16 +67,18 @@ __global__ __launch_bounds__(512) void gemm_nvf4_os_kernel(const NvGemmParams p)
     vP[par] = (lane >> 3) * rowbytes + (chP[par] << 4);
   }
   const int rstep = 8 * rowbytes;
-  const uint32_t sb_off = (uint32_t)(n0 >> 7) * CB * 512;
-  const __amdgpu_buffer_rsrc_t rSA = make_rsrc(p.SFA, p.sfa_bytes), rSB = make_rsrc(p.SFB + sb_off, p.sfb_bytes - sb_off);
+  // (GRP: both scale operands from the tile's first row, G16 bytes per row; rows past the group's end / past N lie past the descriptor)
+  const uint32_t sa_off = GRP ? (uint32_t)m0 * G16 : 0u, sb_off = GRP ? (uint32_t)n0 * G16 : (uint32_t)(n0 >> 7) * CB * 512;
+  const __amdgpu_buffer_rsrc_t rSA = make_rsrc(p.SFA + sa_off, (GRP ? gv.sfa_bytes : p.sfa_bytes) - sa_off), rSB = make_rsrc((GRP ? gv.SFB : p.SFB) + sb_off, p.sfb_bytes - sb_off);
   const int rowB = (n0 & 127) + i32;   // (TN = 16: n0 is a multiple of 16 only; lanes past the 16 rows fetch some row's dword -- unused)
   int vSA[MT];   // A scale rows are addressed from the operand's start: a 96-row tile's m-tiles may lie in two 128-row scale tiles
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     const int rabs = m0 + 32 * t;
-    vSA[t] = (rabs >> 7) * CB * 512 + 2 * g * 512 + i32 * 16 + ((rabs & 127) >> 5) * 4;
+    vSA[t] = GRP ? (32 * t + i32) * G16 + 8 * g : (rabs >> 7) * CB * 512 + 2 * g * 512 + i32 * 16 + ((rabs & 127) >> 5) * 4;
   }
-  const int vSB = 2 * g * 512 + (rowB & 31) * 16 + ((rowB & 127) >> 5) * 4;
+  const int vSB = GRP ? i32 * G16 + 8 * g : 2 * g * 512 + (rowB & 31) * 16 + ((rowB & 127) >> 5) * 4;
+  constexpr int SJJ = GRP ? 4 : 512, SKT = GRP ? 16 : 2048;   // source step of a piece's second dword (jj) and of a stage
 
   auto issue = [&](const int kt, const int slot) __attribute__((always_inline)) {   // stage kt into slot `slot` of this wave (kt >= KT: every piece out of range -> zeros)
     char* st = smem + (wave * SPW + slot) * C::STAGE;
@@ -87,8 +99,8 @@ __global__ __launch_bounds__(512) void gemm_nvf4_os_kernel(const NvGemmParams p)
       const int os = (kt < KT && 4 * kt + 2 * g + jj < CB) ? 0 : -1;   // a column tile past the operand's last one would read the next row tile's bytes
 #pragma unroll
       for (int t = 0; t < MT; ++t)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rSA, (lds_ptr_t)(st + C::OFF_S + t * 512 + jj * 256), 4, ((vSA[t] + jj * 512) & ~os) | ((int)0x80000000 & os), kt * 2048, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rSB, (lds_ptr_t)(st + C::OFF_SB + jj * 256), 4, ((vSB + jj * 512) & ~os) | ((int)0x80000000 & os), kt * 2048, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rSA, (lds_ptr_t)(st + C::OFF_S + t * 512 + jj * 256), 4, ((vSA[t] + jj * SJJ) & ~os) | ((int)0x80000000 & os), kt * SKT, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rSB, (lds_ptr_t)(st + C::OFF_SB + jj * 256), 4, ((vSB + jj * SJJ) & ~os) | ((int)0x80000000 & os), kt * SKT, 0, 0);
     }
   };
 
@@ -197,7 +209,7 @@ __global__ __launch_bounds__(512) void gemm_nvf4_os_kernel(const NvGemmParams p)
       for (int e = 0; e < 4; ++e) t[e] += s[e];
     }
     const int row = m0 + rr, col = n0 + 4 * cq;
-    if (row < p.M && col < p.N && 4 * cq < C::TN) {
+    if (row < (GRP ? gv.M : p.M) && col < p.N && 4 * cq < C::TN) {
       v2i o;
       o[0] = (int)pack_bf16x2(t[0] * alpha, t[1] * alpha);
       o[1] = (int)pack_bf16x2(t[2] * alpha, t[3] * alpha);
@@ -488,6 +500,34 @@ hipError_t launch_nvf4_os(NvGemmParams p, hipStream_t s, int tn) {
   else if (KT <= 16) QAMD_NVOS(2, false);
   else QAMD_NVOS(2, true);
 #undef QAMD_NVOS
+  return hipSuccess;
+}
+
+// grouped_matmul_nvf4_bf16_tn's forms (capi.hip grouped_nv_plan): 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles (one shot while the tile's K extent
+// fits the LDS, refilled slots beyond -- launch_nvf4_os's K rule), 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.  The grid is the
+// bound (cdiv(M, TM) + E) tiles_n of the real tiles (grouped_tile: the rest return at once).
+hipError_t launch_nvf4_grouped(NvGroupedParams q, hipStream_t s, int form) {
+  const int TM = form == 598 ? 32 : form == 601 ? 128 : 64, TN = form == 600 ? 64 : form == 601 ? 128 : 32;
+  q.tiles_m = 1;
+  q.tiles_n = (q.N + TN - 1) / TN;
+  const int KT = (q.K / 2 + 127) / 128;
+  const dim3 grid(((q.M + TM - 1) / TM + q.E) * q.tiles_n);
+  if (form == 598) {
+    if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32>, false, true>), grid, dim3(512), 0, s, q);
+    else if (KT <= 16) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<2, 32>, false, true>), grid, dim3(512), 0, s, q);
+    else hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<2, 32>, true, true>), grid, dim3(512), 0, s, q);
+  } else if (form == 599) {
+    if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32, 2>, false, true>), grid, dim3(512), 0, s, q);
+    else hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32, 2>, true, true>), grid, dim3(512), 0, s, q);
+  } else if (form == 600) {
+    using C = NvCfg<64, 64, 2, 2>;
+    hipLaunchKernelGGL((gemm_nvf4_kernel<C, false, false, true>), grid, dim3(C::THREADS), 0, s, q);
+  } else if (form == 601) {
+    using C = NvCfg<128, 128, 2, 2>;
+    hipLaunchKernelGGL((gemm_nvf4_kernel<C, false, false, true>), grid, dim3(C::THREADS), 0, s, q);
+  } else {
+    return hipErrorInvalidValue;
+  }
   return hipSuccess;
 }
 #endif

@@ -201,6 +201,34 @@ Tensor grouped_matmul_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf,
   return out;
 }
 
+// EXTENSION: grouped NVFP4 GEMM for mixture-of-experts layers (qutlass_amd_grouped_matmul_nvf4_bf16_tn).  A (M, K/2) tokens sorted by expert, B (E, N, K/2) stacked
+// expert weights, row-major e4m3 scales per 16 elements (fusedQuantizeNv's buffer as it is); the rest as grouped_matmul_nvf4.
+Tensor grouped_matmul_nvf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
+  const char* op = "grouped_matmul_nvf4";
+  require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  STD_TORCH_CHECK(has_dtype(A, ScalarType::Byte) || has_dtype(A, ScalarType::Float4_e2m1fn_x2), "A must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), "B must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(A_sf, ScalarType::Float8_e4m3fn), "A_sf must be float8_e4m3fn");
+  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e4m3fn), "B_sf must be float8_e4m3fn");
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
+  STD_TORCH_CHECK(A.size(1) == B.size(2), "Inner dimensions must match for A @ B[g].T");
+  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * 2;
+  STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
+  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
+  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
+  STD_TORCH_CHECK(A_sf.numel() >= M * (K / 16), "A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * (K / 16));
+  STD_TORCH_CHECK(B_sf.numel() >= E * N * (K / 16), "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * (K / 16));
+  Tensor out = torch::stable::new_empty(A, {M, N}, ScalarType::BFloat16);
+  if (M == 0 || N == 0) return out;   // empty batch: nothing to launch
+
+  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
+  check_rc(qutlass_amd_grouped_matmul_nvf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()),
+                                                   alpha.numel(), static_cast<const int32_t*>(offs.data_ptr()), out.data_ptr(), M, N, K, E, current_stream(A)));
+  return out;
+}
+
 // EXTENSION: grouped MXFP8 GEMM for mixture-of-experts layers (qutlass_amd_grouped_matmul_mxf8_bf16_tn).  A (M, K) e4m3 / e5m2 tokens sorted by expert (e5m2 selects the
 // e5m2-A path, as matmul_mxf8_bf16_tn), B (E, N, K) e4m3 stacked expert weights; the rest as grouped_matmul_mxf4.
 Tensor grouped_matmul_mxf8(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
@@ -513,6 +541,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
+  m.def("grouped_matmul_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
 }
 
 // CUDA dispatch key only, as the reference (bindings.cpp:516-535); there is no CPU compute path.
@@ -550,6 +579,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("fusedQuantizeMatmulMxf4", TORCH_BOX(&fusedQuantizeMatmulMxf4));
   m.impl("grouped_matmul_mxf4", TORCH_BOX(&grouped_matmul_mxf4));
   m.impl("grouped_matmul_mxf8", TORCH_BOX(&grouped_matmul_mxf8));
+  m.impl("grouped_matmul_nvf4", TORCH_BOX(&grouped_matmul_nvf4));
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module

@@ -94,6 +94,10 @@ def _register_fakes() -> None:
     def _(A, B, A_sf, B_sf, alpha, offs):   # A (M, K), B (E, N, K)
         return A.new_empty((A.size(0), B.size(1)), dtype=torch.bfloat16)
 
+    @rf("qutlass_amd::grouped_matmul_nvf4")
+    def _(A, B, A_sf, B_sf, alpha, offs):   # A (M, K/2), B (E, N, K/2)
+        return A.new_empty((A.size(0), B.size(1)), dtype=torch.bfloat16)
+
 
 def _define_functional_ops() -> None:
     """FUNCTIONAL forms of the output-filling ops (`qutlass_amd::quantize_mx` ...: allocate, call the in-place twin, return fresh tensors), defined in Python with
