@@ -240,6 +240,28 @@ int qutlass_amd_fused_quantize_nv_blocked(const void* x, const void* h, int rot,
                                           void* stream);
 
 /*
+ * EXTENSION (no reference counterpart): the activation of a gated MLP, alone and fused into the quantizers above.
+ * x: bf16 (rows, 2 * inter), contiguous, 16-byte aligned; gate = x[:, :inter], up = x[:, inter:] (what a GEMM against stacked [W1; W3] returns).
+ *     s   = bf16_rne(g / (1 + exp(-g)))      g widened to fp32; the CORRECTLY rounded bf16 of silu(g): fp32 arithmetic, redone in fp64 where that lands within
+ *                                            12 fp32 ulp of a bf16 tie and for g < -16; a large negative g (below about -97) gives -0
+ *     act = bf16_rne(float(s) * float(u))    -- what silu(gate) * up gives in bf16
+ * qutlass_amd_silu_mul_bf16 writes act, bf16 (rows, inter); inter % 8 == 0; rows, inter < 2^31 (64-bit addressing: no byte limit).
+ * qutlass_amd_fused_silu_mul_quantize_{mx,nv}: qutlass_amd_fused_quantize_{mx,nv}[_blocked] applied to act viewed as (rows, inter), byte for byte (same
+ * rotation, scale rules, encoder, layouts and padding contracts: blocked == 0 writes the scales flat and leaves the rest of the caller's buffer untouched,
+ * blocked != 0 writes the to_blocked layout of the (rows, inter / gs) scale matrix, padding zero-filled) -- without act ever being written to memory.
+ * inter % max(rot, 32) == 0; rot as in the plain entries; hardware e2m1 convert, no clip mask.
+ * LIMIT: the fused kernels address x with 32-bit offsets from one buffer descriptor: x must stay below 2 GiB (rows * inter < 2^29), QAMD_ERR_INVALID beyond
+ * (run such an input as row ranges).  Non-finite gate / up values (the unwritten tail rows of a grouped GEMM's output, say) give unspecified bytes for their
+ * own rotation groups only.  rows == 0 returns QAMD_OK without a launch.
+ */
+int qutlass_amd_silu_mul_bf16(const void* x, int64_t rows, int64_t inter, void* out, void* stream);
+int qutlass_amd_fused_silu_mul_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
+                                           int blocked, void* out_e2m1, void* out_e8m0, void* stream);
+int qutlass_amd_fused_silu_mul_quantize_nv(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
+                                           const float* global_scale, int blocked, void* out_e2m1, void* out_e4m3,
+                                           void* stream);
+
+/*
  * EXTENSION: the measured launch-count rule of the activation path y = Q(x h) W^T of one linear layer (reference flow: qutlass/__init__.py:149-180 ->
  * qutlass/utils.py:160-193 -> qutlass/__init__.py:34-76, three launches): returns 1 where the one-launch decode kernel below wins (M <= 16, R = 32, short K,
  * a weight of fewer than 32 x CUs rows), else 2 (quantizer with GEMM-ready scales + GEMM).  Pure host arithmetic on the current device's CU count; what

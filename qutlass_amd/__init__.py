@@ -9,6 +9,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_mxf4_bf16_tn                      (extension: mixture-of-experts layers, one launch over all experts)
     grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
+    silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -210,6 +211,85 @@ def fusedQuantizeNvBlocked(a: torch.Tensor, b: torch.Tensor, global_scale: torch
     xh_e2m1, xh_e4m3 = _alloc_nv(a, blocked=True)
     _ops_amd.fusedQuantizeNvBlocked(a, b, xh_e2m1, xh_e4m3, global_scale, _METHOD_CODE[method])
     return xh_e2m1, xh_e4m3
+
+
+def _act_meta(x: torch.Tensor) -> torch.Tensor:
+    """The (.., I) bf16 activation of a (.., 2 I) gate | up tensor, as a meta tensor: shapes for the allocators, no memory."""
+    if x.size(-1) % 2:
+        raise ValueError(f"the last dimension of x must be 2 * I (got {x.size(-1)})")
+    return torch.empty(*x.shape[:-1], x.size(-1) // 2, dtype=x.dtype, device="meta")
+
+
+def _alloc_gated(x: torch.Tensor, nv: bool, blocked: bool):
+    """The outputs the plain quantizers allocate for a (.., I) tensor (_alloc_mx / _alloc_nv), for x = (.., 2 I)."""
+    act = _act_meta(x)
+    padded_rows, padded_cols = get_padded_shape_nv(act) if nv else get_padded_shape_mx(act)
+    xh_e2m1 = torch.empty(*act.shape[:-1], act.size(-1) // 2, dtype=torch.uint8, device=x.device)
+    sf_shape = (padded_rows * padded_cols,) if blocked else (padded_rows, padded_cols)
+    return xh_e2m1, torch.empty(*sf_shape, dtype=torch.float8_e4m3fn if nv else torch.float8_e8m0fnu, device=x.device)
+
+
+def silu_and_mul(x: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): the activation of a gated MLP as one streaming HIP kernel.  x is (.., 2 I) bf16, contiguous, with
+    gate = x[..., :I] and up = x[..., I:] (what a GEMM against stacked [W1; W3] returns); the result is (.., I) bf16,
+
+        s = bf16(g / (1 + exp(-g)))  (correctly rounded: fp32 arithmetic, fp64 near a bf16 tie),   act = bf16(float(s) * float(u))
+
+    i.e. what ``torch.nn.functional.silu(gate) * up`` computes in bf16.  I % 8 == 0; no size limit below 2^31 rows / columns."""
+    if torch.compiler.is_compiling():
+        return _ops_amd.silu_and_mul(x)
+    out = torch.empty(*x.shape[:-1], x.size(-1) // 2, dtype=x.dtype, device=x.device)
+    _ops_amd.siluAndMul_(x, out)
+    return out
+
+
+def _silu_mul_quantize_mx(x, h, method, blocked):
+    if method not in _METHOD_CODE:
+        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
+    if torch.compiler.is_compiling():
+        return _ops_amd.silu_mul_quantize_mx(x, h, _METHOD_CODE[method], blocked)
+    xh_e2m1, xh_e8m0 = _alloc_gated(x, False, blocked)
+    _ops_amd.fusedSiluMulQuantizeMx_(x, h, xh_e2m1, xh_e8m0, _METHOD_CODE[method], blocked)
+    return xh_e2m1, xh_e8m0
+
+
+def _silu_mul_quantize_nv(x, h, global_scale, method, blocked):
+    if method not in _METHOD_CODE:
+        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
+    if torch.compiler.is_compiling():
+        return _ops_amd.silu_mul_quantize_nv(x, h, global_scale, _METHOD_CODE[method], blocked)
+    xh_e2m1, xh_e4m3 = _alloc_gated(x, True, blocked)
+    _ops_amd.fusedSiluMulQuantizeNv_(x, h, xh_e2m1, xh_e4m3, global_scale, _METHOD_CODE[method], blocked)
+    return xh_e2m1, xh_e4m3
+
+
+def fusedSiluMulQuantizeMx(x: torch.Tensor, h: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): ``fusedQuantizeMx(silu_and_mul(x), h, method=method)`` in ONE launch, byte for byte -- the quantizer reads gate and up
+    itself and applies the activation in registers, so the (.., I) bf16 activation never goes through memory (4.5 B instead of 8.5 B moved per element).
+    x is (.., 2 I) bf16, contiguous; I % max(R, 32) == 0 for the R x R rotation h.  Returns e2m1 (.., I/2) and e8m0 (padded_rows, padded_cols) exactly as
+    fusedQuantizeMx does for a (.., I) tensor (scales flat in the first rows * I / 32 bytes, padding untouched).  x must stay below 2 GiB (the kernel addresses
+    it with 32-bit offsets; larger inputs raise -- split them by rows).  Non-finite gate / up values give unspecified bytes in their own groups only.
+    Measured faster than the two calls for R <= 32 (1.15-1.45x); at R = 128 it is not: keep silu_and_mul + fusedQuantizeMx there."""
+    return _silu_mul_quantize_mx(x, h, method, False)
+
+
+def fusedSiluMulQuantizeMxBlocked(x: torch.Tensor, h: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMxBlocked(silu_and_mul(x), h, method=method)`` in one launch (see fusedSiluMulQuantizeMx): the scales come out flat in the
+    ``to_blocked`` layout, zero padded -- what the dense ``matmul_mxf4_bf16_tn`` takes.  x below 2 GiB."""
+    return _silu_mul_quantize_mx(x, h, method, True)
+
+
+def fusedSiluMulQuantizeNv(x: torch.Tensor, h: torch.Tensor, global_scale: torch.Tensor, *,
+                           method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeNv(silu_and_mul(x), h, global_scale, method=method)`` in one launch, byte for byte (see fusedSiluMulQuantizeMx); R may be 16.
+    x below 2 GiB."""
+    return _silu_mul_quantize_nv(x, h, global_scale, method, False)
+
+
+def fusedSiluMulQuantizeNvBlocked(x: torch.Tensor, h: torch.Tensor, global_scale: torch.Tensor, *,
+                                  method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeNvBlocked(silu_and_mul(x), h, global_scale, method=method)`` in one launch (see fusedSiluMulQuantizeMxBlocked).  x below 2 GiB."""
+    return _silu_mul_quantize_nv(x, h, global_scale, method, True)
 
 
 def _decode_single_launch_wins(m: int, n: int, k: int, rot: int, device: torch.device | None = None) -> bool:

@@ -1257,6 +1257,39 @@ QAMD_ROT_BOTH(true, METHOD_ABSMAX, false)
 #undef QAMD_ROT_INST
 #endif
 
+// the gated quantizers (fused_silu_mul_quantize_kernel: act = silu(gate) * up computed in the tile loads): unit 5 as well
+template <bool NV, int METHOD, bool BLK>
+int dispatch_rot_gated(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
+#define QAMD_GATED_GO(R_) hipLaunchKernelGGL((fused_silu_mul_quantize_kernel<R_, NV, METHOD, BLK>), dim3(grid), dim3(256), 0, s, p); return check_launch("fused_silu_mul_quantize_kernel")
+  switch (rot) {
+    case 16:
+      if constexpr (NV) { QAMD_GATED_GO(16); }
+      break;
+    case 32: QAMD_GATED_GO(32);
+    case 64: QAMD_GATED_GO(64);
+    case 128: QAMD_GATED_GO(128);
+  }
+#undef QAMD_GATED_GO
+  return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, NV ? "16, " : "");
+}
+
+#if QAMD_TU != 0
+#if QAMD_TU == 5
+#define QAMD_ROT_INST template
+#else
+#define QAMD_ROT_INST extern template
+#endif
+#define QAMD_ROT_BOTH(NV_, M_) \
+  QAMD_ROT_INST int dispatch_rot_gated<NV_, M_, false>(int, const QuantParams&, hipStream_t, int, const char*); \
+  QAMD_ROT_INST int dispatch_rot_gated<NV_, M_, true>(int, const QuantParams&, hipStream_t, int, const char*);
+QAMD_ROT_BOTH(false, METHOD_QUEST)
+QAMD_ROT_BOTH(false, METHOD_ABSMAX)
+QAMD_ROT_BOTH(true, METHOD_QUEST)
+QAMD_ROT_BOTH(true, METHOD_ABSMAX)
+#undef QAMD_ROT_BOTH
+#undef QAMD_ROT_INST
+#endif
+
 // backward_t_bf16 / backward_qt_bf16 kernels live in unit 5 with the other rotation quantizers (MFMA results straight in VGPRs: a
 // v_accvgpr_read per accumulator register is 32 more VALU issues per tile)
 //   which: 1 = the round-3 kernel (8 waves per unit of 8 groups x 64 m, two barriers per unit); 2 = wave-owned 64-byte segments (units of 4
@@ -1790,6 +1823,68 @@ int qutlass_amd_fused_quantize_nv_blocked(const void* x, const void* h, int rot,
   const char* name = "fusedQuantizeNvBlocked";
   if (rows <= 0 || k <= 0 || rows >= (1ll << 31) || k >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld, %lld)", name, (long long)rows, (long long)k);
   return fused_quantize_nv_impl(name, x, h, rot, rows * k, k, method, global_scale, out_e2m1, out_e4m3_blocked, stream);
+}
+
+// ---- gated MLP: act = silu(gate) * up of x = (rows, 2 * inter) [gate | up], alone or fused into the rotate + quantize ops ----------------------------------
+// The fused kernels read gate and up where the plain quantizer reads its operand (4 B instead of 2 B per element, and no (rows, inter) bf16 round trip through
+// memory in between); workgroups per CU as quant_grid's rule for the act tiles (calibrated with the doubled read stream: profiles/calib_gated_quantize_*.txt).
+static int gated_common_check(const char* name, const void* x, int64_t rows, int64_t inter, int64_t align) {
+  if (rows < 0 || inter <= 0 || rows >= (1ll << 31) || inter >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld, 2 * %lld)", name, (long long)rows, (long long)inter);
+  if (inter % align) return fail(QAMD_ERR_INVALID, "%s: the gate / up width %lld must be a multiple of %lld", name, (long long)inter, (long long)align);
+  if ((uintptr_t)x % 16) return fail(QAMD_ERR_INVALID, "%s: x must be 16-byte aligned", name);
+  return QAMD_OK;
+}
+
+int qutlass_amd_silu_mul_bf16(const void* x, int64_t rows, int64_t inter, void* out, void* stream) {
+  const char* name = "silu_and_mul";
+  if (int rc = gated_common_check(name, x, rows, inter, 8)) return rc;
+  if ((uintptr_t)out % 16) return fail(QAMD_ERR_INVALID, "%s: out must be 16-byte aligned", name);
+  if (rows == 0) return QAMD_OK;
+  if (!x || !out) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  SiluMulParams p;
+  p.x = (const uint16_t*)x; p.out = (uint16_t*)out; p.chunks = rows * (inter / 8); p.cpr = (uint32_t)(inter / 8);
+  const int grid = (int)std::min<int64_t>(cdiv(p.chunks, 256), (int64_t)chip_cus() * 8);
+  hipLaunchKernelGGL(silu_mul_bf16_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  return check_launch("silu_mul_bf16_kernel");
+}
+
+// nv: 0 = MX (e8m0 per 32), 1 = NV (e4m3 per 16, global_scale)
+static int fused_silu_mul_quantize_impl(const char* name, bool nv, const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
+                                        const float* global_scale, int blocked, void* out_e2m1, void* out_sf, void* stream) {
+  if (nv ? (rot != 16 && rot != 32 && rot != 64 && rot != 128) : (rot != 32 && rot != 64 && rot != 128))
+    return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, nv ? "16, " : "");
+  if (method != QAMD_METHOD_QUEST && method != QAMD_METHOD_ABSMAX) return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
+  const int rp = rot < 32 ? 32 : rot;
+  if (int rc = gated_common_check(name, x, rows, inter, rp)) return rc;
+  // x is addressed with 32-bit offsets from one buffer descriptor (quantize.hip.h, GATED): no silent wrap beyond it
+  if (rows * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: x (rows * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(rows * inter * 4));
+  if (rows == 0) return QAMD_OK;
+  if (!x || !h || !out_e2m1 || !out_sf || (nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (rot >= 64 && (uintptr_t)h % 16) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 16-byte aligned for rotation sizes >= 64", name);
+  QuantParams p;
+  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
+  p.out_mask = nullptr; p.global_scale = global_scale; p.numel = rows * inter; p.inter = (int)inter;
+  p.ntiles = (int)cdiv(p.numel, (int64_t)rp * 32);
+  p.sf_rows = blocked ? (int)rows : 0; p.sf_cols = blocked ? (int)(inter / (nv ? 16 : 32)) : 0;
+  int grid = quant_grid(p.ntiles, rot);
+  if (blocked) grid = blocked_pad_grid(grid, p.sf_rows, p.sf_cols);
+  hipStream_t s = (hipStream_t)stream;
+#define QAMD_GATED_ARM(NV_, M_) (blocked ? dispatch_rot_gated<NV_, M_, true>(rot, p, s, grid, name) : dispatch_rot_gated<NV_, M_, false>(rot, p, s, grid, name))
+  if (nv) return method == QAMD_METHOD_QUEST ? QAMD_GATED_ARM(true, METHOD_QUEST) : QAMD_GATED_ARM(true, METHOD_ABSMAX);
+  return method == QAMD_METHOD_QUEST ? QAMD_GATED_ARM(false, METHOD_QUEST) : QAMD_GATED_ARM(false, METHOD_ABSMAX);
+#undef QAMD_GATED_ARM
+}
+
+int qutlass_amd_fused_silu_mul_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, int blocked, void* out_e2m1,
+                                           void* out_e8m0, void* stream) {
+  return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeMxBlocked" : "fusedSiluMulQuantizeMx", false, x, h, rot, rows, inter, method, nullptr, blocked,
+                                      out_e2m1, out_e8m0, stream);
+}
+
+int qutlass_amd_fused_silu_mul_quantize_nv(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, const float* global_scale, int blocked,
+                                           void* out_e2m1, void* out_e4m3, void* stream) {
+  return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", true, x, h, rot, rows, inter, method, global_scale,
+                                      blocked, out_e2m1, out_e4m3, stream);
 }
 
 // How many launches should the activation path y = Q(x h) W^T of one linear layer take (the rule behind qutlass_amd.fused_quantize_matmul_mxf4_bf16_tn;

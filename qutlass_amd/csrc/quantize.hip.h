@@ -35,6 +35,9 @@ struct QuantParams {
   // BLK kernels only (fusedQuantize{Mx,Nv}Blocked): the scales go straight into the to_blocked() layout of the logical
   // (sf_rows, sf_cols) scale matrix -- sf_rows = numel / K, sf_cols = K / 32 (MX) or K / 16 (NV) -- padding zero-filled
   int sf_rows, sf_cols;
+  // GATED kernels only (fusedSiluMulQuantize*): x is (rows, 2 * inter) -- gate | up halves of every row -- and the operand that is rotated and quantized is
+  // act = silu(gate) * up, (rows, inter); numel counts act.  The plain kernels never read it.  (Sits in the struct's tail padding: no other field moves.)
+  int inter = 0;
 };
 
 // byte offset of scale (row, col) in the 128x4-tiled block-scale layout (qutlass/utils.py:60-64, :190-193); CB = ceil(cols / 4)
@@ -178,6 +181,69 @@ __device__ __forceinline__ float e4m3_decode_pos(uint32_t b) {
   return e ? __uint_as_float(((e + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
 }
 
+// --- gated-MLP activation --------------------------------------------------------------------------
+// act = bf16_rne(float(s) * float(u)), s = bf16_rne(g / (1 + exp(-g))): what a model that runs `silu(gate) * up` in bf16 computes.  s is the CORRECTLY rounded bf16 of
+// silu(g): a mis-rounded s (fp32 arithmetic misses a bf16 tie about once in 2^11 values) is off by up to 2^-8 of its value, which can come out as TWO bf16 steps of
+// act -- and would make the result depend on the accuracy of one chip's v_exp_f32.  So:
+//   fast path  fp32.  exp(-g) = v_exp_f32(-g * c_hi) * (1 - ln 2 * c_lo * g) with log2 e = c_hi + c_lo, c_hi of 16 bits: g has 8, the product is exact, and the
+//              rest (|ln 2 c_lo g| < 2^-13 for |g| <= 16) enters to first order.  v_exp_f32, v_rcp_f32: 1 ulp each; in all s is within 2^-21.2 of silu(g), 7 fp32 ulp.
+//   slow path  the values whose fast result lies within 12 fp32 ulp of a bf16 tie (2^-11.4 of them), and g < -16, where a relative bound on exp no longer gives one
+//              on s (and fp32's exp overflows from -88.7 on, where silu(g) is still a bf16 number; it rounds to -0 below about -97, as fp32's g / inf does): fp64, rounded to bf16 once.
+// The product float(s) * float(u) is exact in fp32 (8 x 8 bits), so its one rounding is the definition's.
+__device__ __forceinline__ float silu_f32(float g) {
+  const float e0 = __builtin_amdgcn_exp2f(g * -1.44268798828125f);             // c_hi = 0x3FB8AA00: exact product
+  const float e = fmaf(e0, g * -4.8884952e-06f, e0);                          // ln 2 * c_lo, c_lo = log2 e - c_hi = 7.0526077e-06
+  return g * __builtin_amdgcn_rcpf(1.0f + e);
+}
+// fp64 -> bf16 bits, round-to-nearest-even in ONE rounding: through fp32, and where that lands exactly on a bf16 tie the fp64 value says which side it came from
+__device__ __forceinline__ uint32_t f64_to_bf16_bits(double v) {
+  const float f = (float)v;
+  uint32_t b = __float_as_uint(f);
+  if ((b & 0xffffu) == 0x8000u) {
+    const double d = fabs(v) - fabs((double)f);
+    b += d > 0.0 ? 1u : (d < 0.0 ? 0xffffffffu : 0u);
+  }
+  return (f != f) ? ((b >> 16) | 0x40u) : ((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ bool silu_needs_fp64(float g, float s) {
+  return ((__float_as_uint(s) & 0xffffu) - (0x8000u - 12u) <= 24u) || g < -16.0f;
+}
+// 8 gate bf16 + 8 up bf16 (one 16-byte load each) -> 8 packed act bf16.  The ONE definition of the activation: silu_mul_bf16_kernel stores its result, the gated
+// quantizers feed it to the rotation MFMA -- which is what makes fusedSiluMulQuantize* bit-equal to silu_and_mul followed by fusedQuantize*.
+__device__ __forceinline__ v4i silu_mul8(const v4i g, const v4i u) {
+  uint32_t sw[4], need = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t gw = (uint32_t)g[i];
+    const float g0 = __uint_as_float(gw << 16), g1 = __uint_as_float(gw & 0xffff0000u);
+    const float s0 = silu_f32(g0), s1 = silu_f32(g1);
+    sw[i] = pack_bf16x2(s0, s1);
+    need |= (silu_needs_fp64(g0, s0) ? 1u : 0u) << (2 * i) | (silu_needs_fp64(g1, s1) ? 1u : 0u) << (2 * i + 1);
+  }
+  if (__builtin_expect(need != 0, 0)) {
+    // one copy of the fp64 code: a loop over the eight positions, taken by the lanes that flagged that position
+#pragma nounroll
+    for (int i = 0; i < 8; ++i) {
+      if (need & (1u << i)) {
+        const int w = i >> 1;
+        const uint32_t gw = (uint32_t)(w == 0 ? g[0] : w == 1 ? g[1] : w == 2 ? g[2] : g[3]);
+        const double gd = (double)__uint_as_float((i & 1) ? (gw & 0xffff0000u) : (gw << 16));
+        const uint32_t r = f64_to_bf16_bits(gd / (1.0 + exp(-gd)));
+        const uint32_t keep = (i & 1) ? 0x0000ffffu : 0xffff0000u, val = (i & 1) ? (r << 16) : r;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sw[k] = (k == w) ? ((sw[k] & keep) | val) : sw[k];
+      }
+    }
+  }
+  v4i r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t uw = (uint32_t)u[i];
+    r[i] = (int)pack_bf16x2(__uint_as_float(sw[i] << 16) * __uint_as_float(uw << 16), __uint_as_float(sw[i] & 0xffff0000u) * __uint_as_float(uw & 0xffff0000u));
+  }
+  return r;
+}
+
 // -------------------------------------------------------------------------------------------------
 // Kernel.  One wave owns one 32-row tile at a time (grid-stride over tiles).
 //   R      : rotation size (MX: 32/64/128, NV: 16/32/64/128)
@@ -186,11 +252,14 @@ __device__ __forceinline__ float e4m3_decode_pos(uint32_t b) {
 //   MASK   : MX quest only: also emit the clip mask
 //   HWCVT  : use v_cvt_scalef32_pk_fp4_f32 for the final RTNE
 //   BLK    : scale bytes are written in the to_blocked() layout (GEMM-ready: no separate swizzle launch) instead of flat
+//   GATED  : the operand is act = silu(gate) * up of an x that holds (rows, 2 I): the tile's loads fetch gate and up (two 16-byte loads where the plain kernel has
+//            one) and silu_mul8 turns them into the bf16 the plain kernel would have loaded; everything after that is the plain kernel.  The input is addressed with
+//            32-bit offsets from one descriptor: x must stay below 2 GiB (rows * I < 2^29; the host checks).
 // -------------------------------------------------------------------------------------------------
 // The kernel's body as a device function of (workgroup index, workgroup count): fused_quantize_kernel below is its plain launch; [r6] the one-launch decode layer
 // (gemm_mx_os.hip.h gemm_mx_os16_fq_kernel) runs it on its first few workgroups.  PAD = false: the zero padding of the blocked scale layout is left out (a reader that
 // only looks at the rows it wrote).
-template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true>
+template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false>
 __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const int bid, const int nblk) {
   constexpr int RP = (R < 32) ? 32 : R;         // rotation padded to one MFMA j-tile (R=16: block-diag)
   constexpr int KC = RP / 16;                   // 16-wide k chunks per row
@@ -216,16 +285,70 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
 
   // x as rows of RP elements (for R = 16 two rotation rows share one 32-element "row")
   const int64_t ngroups = p.numel / (NV ? 16 : 32);
-  const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, (uint32_t)(p.numel * 2));
+  const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, (uint32_t)(p.numel * (GATED ? 4 : 2)));
 
   const int wave_global = bid * 4 + wave, nwaves = nblk * 4;
   v4i xnext[RP / 16];
+  v4i unext[GATED ? RP / 16 : 1];   // GATED: xnext holds the gate chunks, unext the up chunks of the same elements
   // per-lane byte offset inside a tile and the step between a lane's loads: MFMA layout (row, half; 32 bytes apart) or,
   // staged, chunk lane + 64 i of the tile's contiguous 32 * RP * 2 bytes
   const int lane_off = STAGED ? lane * 16 : row * RP * 2 + half * 16;
   constexpr int LSTEP = STAGED ? 1024 : 32;
   char* xs = xs_all + (STAGED ? wave * 32 * XROW : 0);
-  {   // [r2] the first tile's loads go out BEFORE H is staged: the two memory round trips overlap (4096^2 cold: 9.03 -> 8.46 us at
+  // GATED: the act tile is the plain kernel's tile -- 32 "rows" of RP elements, contiguous in act -- but its RP-element rows sit 2 I elements apart in x where
+  // they belong to different logical rows.  (g_row, g_rem) = logical row and RP-row within it of the first RP-row of the NEXT tile this wave loads: wave-uniform,
+  // one division here and a carry-propagating add per tile.  A lane's chunk is RP-row `lrow` of the tile (the MFMA layout: lane & 31; staged: chunk / CPR, so that
+  // consecutive lanes walk along a row -- whole lines -- before stepping to the next): x = g_rem + lrow < I / RP + 32 is split into (rows to carry, RP-row) with a
+  // reciprocal multiply and a fix-up of one either way.
+  uint32_t g_row = 0, g_rem = 0, g_qstep = 0, g_rstep = 0, g_rpr = 1, g_nrows = 0;
+  float g_rc = 1.0f;
+  if constexpr (GATED) {
+    g_rpr = (uint32_t)p.inter / RP;
+    g_rc = __builtin_amdgcn_rcpf((float)g_rpr);
+    g_nrows = (uint32_t)(p.numel / RP);
+    const uint32_t r0 = (uint32_t)wave_global * 32u, step = (uint32_t)nwaves * 32u;
+    g_row = r0 / g_rpr;
+    g_rem = r0 - g_row * g_rpr;
+    g_qstep = step / g_rpr;
+    g_rstep = step - g_qstep * g_rpr;
+  }
+  // byte offset of the gate chunk (RP-row lrow of the tile at (g_row, g_rem), byte cb of that RP-row); up sits 2 I bytes further.  RP-rows past the end of act
+  // (the last tile's tail, tiles past the end) get an offset off the descriptor: they read 0, as in the plain kernel.
+  auto gated_off = [&](const int t, const uint32_t lrow, const uint32_t cb) -> int {
+    const uint32_t x = g_rem + lrow;
+    uint32_t q = (uint32_t)((float)x * g_rc);
+    int32_t r = (int32_t)(x - q * g_rpr);
+    if (r < 0) { q -= 1; r += (int32_t)g_rpr; }
+    if (r >= (int32_t)g_rpr) { q += 1; r -= (int32_t)g_rpr; }
+    const uint32_t off = (g_row + q) * ((uint32_t)p.inter * 4u) + (uint32_t)r * (RP * 2u) + cb;
+    return ((uint32_t)t * 32u + lrow < g_nrows) ? (int)off : (int)0xfffffff0u;
+  };
+  auto gated_loads = [&](const int t) {   // issue tile t's loads (the tile (g_row, g_rem) stands at), then advance to this wave's next tile
+    if constexpr (STAGED) {
+      constexpr int CPR = RP / 8;
+#pragma unroll
+      for (int i = 0; i < RP / 16; ++i) {
+        const int q = i * 64 + lane;
+        const int off = gated_off(t, (uint32_t)(q / CPR), (uint32_t)(q % CPR) * 16u);
+        xnext[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0);
+        unext[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, off, p.inter * 2, 0);
+      }
+    } else {
+      const int off = gated_off(t, (uint32_t)row, (uint32_t)half * 16u);
+#pragma unroll
+      for (int kc = 0; kc < RP / 16; ++kc) {
+        xnext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rx, off + kc * 32, 0, 0);
+        unext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rx, off + kc * 32, p.inter * 2, 0);
+      }
+    }
+    g_rem += g_rstep;
+    const uint32_t carry = g_rem >= g_rpr ? 1u : 0u;
+    g_rem -= carry ? g_rpr : 0u;
+    g_row += g_qstep + carry;
+  };
+  if constexpr (GATED) {
+    gated_loads(wave_global);   // (before H is staged, as below)
+  } else {   // [r2] the first tile's loads go out BEFORE H is staged: the two memory round trips overlap (4096^2 cold: 9.03 -> 8.46 us at
       // R = 32, 10.08 -> 9.31 at R = 64, 13.18 -> 12.54 at R = 128; profiles/ab_stream_ops_r2.txt)
     const int xoff0 = (wave_global < p.ntiles) ? (int)((int64_t)wave_global * 32 * RP * 2) + lane_off : 0x7f000000;
 #pragma unroll
@@ -323,6 +446,10 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     // loads of the wave's NEXT tile are issued before this tile is computed (tiles past the end fall off the buffer
     // descriptor and read 0), so the HBM latency of tile i+1 hides behind the MFMAs / epilogue of tile i.
     v8bf xf[KC];
+    if constexpr (GATED) {   // gate, up -> the act chunk the plain kernel would have loaded
+#pragma unroll
+      for (int i = 0; i < KC; ++i) xnext[i] = silu_mul8(xnext[i], unext[i]);
+    }
     if (STAGED) {
       constexpr int CPR = RP / 8;                // 16-byte chunks per row
 #pragma unroll
@@ -338,7 +465,9 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) xf[kc] = __builtin_bit_cast(v8bf, xnext[kc]);
     }
-    {
+    if constexpr (GATED) {
+      gated_loads(tile + nwaves);
+    } else {
       const int64_t on = (int64_t)(tile + nwaves) * 32 * RP * 2 + lane_off;
       const int xoffn = (tile + nwaves < p.ntiles) ? (int)on : 0x7f000000;
 #pragma unroll
@@ -557,6 +686,37 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
 template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false>
 __global__ __launch_bounds__(256) void fused_quantize_kernel(const QuantParams p) {
   fused_quantize_body<R, NV, METHOD, MASK, HWCVT, BLK>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// the gated quantizers (fusedSiluMulQuantize{Mx,Nv}[Blocked]): the hardware e2m1 convert only, no clip mask
+template <int R, bool NV, int METHOD, bool BLK>
+__global__ __launch_bounds__(256) void fused_silu_mul_quantize_kernel(const QuantParams p) {
+  fused_quantize_body<R, NV, METHOD, false, true, BLK, true, true>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// silu_and_mul: x (rows, 2 I) bf16 -> out (rows, I) bf16, out[r][c] = act(x[r][c], x[r][I + c]) (silu_mul8 above).  Streaming, 4 B in + 2 B out per element: a
+// thread takes 16-byte chunks (8 elements; I % 8 == 0) chunk = first + k * step, kept as (row, chunk within the row) with a carry-propagating add -- no division in
+// the loop -- and 64-bit addresses, so neither operand has a size limit below rows, I < 2^31.
+struct SiluMulParams {
+  const uint16_t* x;
+  uint16_t* out;
+  int64_t chunks;    // rows * I / 8
+  uint32_t cpr;      // chunks per row, I / 8
+};
+template <int UNUSED = 0>   // (a template so that only the unit that launches it holds a copy)
+__global__ __launch_bounds__(256) void silu_mul_bf16_kernel(const SiluMulParams p) {
+  const uint32_t first = blockIdx.x * 256u + threadIdx.x, step = gridDim.x * 256u;
+  uint32_t row = first / p.cpr, cc = first - row * p.cpr;
+  const uint32_t qstep = step / p.cpr, rstep = step - qstep * p.cpr;
+  for (int64_t c = first; c < p.chunks; c += step) {
+    const uint16_t* g = p.x + ((int64_t)row * 2 * p.cpr + cc) * 8;
+    const v4i gv = *(const v4i*)g, uv = *(const v4i*)(g + (int64_t)p.cpr * 8);
+    *(v4i*)(p.out + c * 8) = silu_mul8(gv, uv);
+    cc += rstep;
+    const uint32_t carry = cc >= p.cpr ? 1u : 0u;
+    cc -= carry ? p.cpr : 0u;
+    row += qstep + carry;
+  }
 }
 
 }  // namespace qamd

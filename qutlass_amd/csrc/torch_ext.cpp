@@ -402,6 +402,67 @@ void fusedQuantizeNvBlocked(const Tensor& A, const Tensor& R, Tensor OUT, Tensor
                                                  OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
 }
 
+// ---- EXTENSION: the gated-MLP activation act = silu(gate) * up of X = (.., 2 I) [gate | up], alone and fused into the quantizers ----------
+// OUT / OUT_sf are sized as for the plain quantizers on a (.., I) tensor.  method: 0 quest, 1 abs_max; blocked: scales in the to_blocked layout.
+void siluAndMul_(const Tensor& X, Tensor OUT) {
+  const char* op = "siluAndMul_";
+  require_contiguous(op, {{X, "X"}, {OUT, "OUT"}});
+  require_gpu(op, {{X, "X"}, {OUT, "OUT"}});
+  require_same_gpu(op, {{X, "X"}, {OUT, "OUT"}});
+  STD_TORCH_CHECK(has_dtype(X, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "X and OUT must be bf16");
+  STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of X must be 2 * I");
+  const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
+  STD_TORCH_CHECK(inter % 8 == 0, "the gate / up width must be divisible by", 8);
+  STD_TORCH_CHECK(OUT.numel() >= rows * inter, "OUT is too small");
+  const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
+  check_rc(qutlass_amd_silu_mul_bf16(X.data_ptr(), rows, inter, OUT.data_ptr(), current_stream(X)));
+}
+
+void silu_mul_quantize(const char* op, bool nv, const Tensor& X, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method, bool blocked) {
+  require_contiguous(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
+  if (nv) {
+    require_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
+    require_same_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
+  } else {
+    require_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
+    require_same_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
+  }
+  quant_prologue(op, X, R);
+  if (nv) {
+    STD_TORCH_CHECK(has_dtype(*gscale, ScalarType::Float), "global_scale must be float");
+    STD_TORCH_CHECK(gscale->dim() == 1 && gscale->size(0) == 1, "global_scale must be a scalar");
+  }
+  STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
+  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
+  STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of A must be 2 * I");
+  const int64_t rot = R.size(0), inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter), numel = rows * inter, gs = nv ? 16 : 32;
+  if (nv) {
+    STD_TORCH_CHECK(rot == 16 || rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 16, 32, 64, or 128.");
+  } else {
+    STD_TORCH_CHECK(rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 32, 64, or 128.");
+  }
+  STD_TORCH_CHECK(inter % (rot < 32 ? 32 : rot) == 0, "the gate / up width must be divisible by", rot < 32 ? 32 : rot);
+  STD_TORCH_CHECK(nbytes(OUT) >= numel / 2, "OUT is too small");
+  if (blocked) {
+    STD_TORCH_CHECK(nbytes(OUT_sf) >= (rows + 127) / 128 * 128 * ((inter / gs + 3) / 4 * 4), "OUT_sf is too small for the blocked scale layout");
+  } else {
+    STD_TORCH_CHECK(nbytes(OUT_sf) >= numel / gs, "OUT_sf is too small");
+  }
+  const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
+  if (nv)
+    check_rc(qutlass_amd_fused_silu_mul_quantize_nv(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, static_cast<const float*>(gscale->data_ptr()),
+                                                    blocked ? 1 : 0, OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
+  else
+    check_rc(qutlass_amd_fused_silu_mul_quantize_mx(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, blocked ? 1 : 0, OUT.data_ptr(), OUT_sf.data_ptr(),
+                                                    current_stream(X)));
+}
+void fusedSiluMulQuantizeMx_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, int64_t method, bool blocked) {
+  silu_mul_quantize(blocked ? "fusedSiluMulQuantizeMxBlocked" : "fusedSiluMulQuantizeMx", false, A, R, OUT, OUT_sf, nullptr, method, blocked);
+}
+void fusedSiluMulQuantizeNv_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale, int64_t method, bool blocked) {
+  silu_mul_quantize(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", true, A, R, OUT, OUT_sf, &global_scale, method, blocked);
+}
+
 // ---- EXTENSION: rotate + quantize + MXFP4 GEMM in one launch for decode batches (M <= 32) ---------------------------------------
 Tensor fusedQuantizeMatmulMxf4(const Tensor& X, const Tensor& R, const Tensor& B, const Tensor& B_sf, const Tensor& alpha, int64_t method) {
   const char* op = "fusedQuantizeMatmulMxf4";
@@ -538,6 +599,9 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("backward_bf16_square_double_mxfp8_(Tensor x_bf16, Tensor(a!) x_fp8, Tensor(b!) row_scales, Tensor(c!) column_scales) -> ()");
   m.def("mxfp4_transpose_mxfp8_(Tensor x_fp4, Tensor scales, Tensor(a!) x_fp8, Tensor(b!) shared_exps) -> ()");
 #endif
+  m.def("siluAndMul_(Tensor X, Tensor(a!) OUT) -> ()");   // inference ops: in the minimal library too
+  m.def("fusedSiluMulQuantizeMx_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, int method, bool blocked) -> ()");
+  m.def("fusedSiluMulQuantizeNv_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method, bool blocked) -> ()");
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
@@ -576,6 +640,9 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("backward_bf16_square_double_mxfp8_", TORCH_BOX(&backward_bf16_square_double_mxfp8));
   m.impl("mxfp4_transpose_mxfp8_", TORCH_BOX(&mxfp4_transpose_mxfp8));
 #endif
+  m.impl("siluAndMul_", TORCH_BOX(&siluAndMul_));
+  m.impl("fusedSiluMulQuantizeMx_", TORCH_BOX(&fusedSiluMulQuantizeMx_));
+  m.impl("fusedSiluMulQuantizeNv_", TORCH_BOX(&fusedSiluMulQuantizeNv_));
   m.impl("fusedQuantizeMatmulMxf4", TORCH_BOX(&fusedQuantizeMatmulMxf4));
   m.impl("grouped_matmul_mxf4", TORCH_BOX(&grouped_matmul_mxf4));
   m.impl("grouped_matmul_mxf8", TORCH_BOX(&grouped_matmul_mxf8));

@@ -73,7 +73,7 @@ def _register_fakes() -> None:
         return None
 
     for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
-                 "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -155,6 +155,34 @@ def _define_functional_ops() -> None:
         return o
 
     quantize_nv_blocked.register_fake(lambda A, R, global_scale, method: _nv(A, True))
+
+    # gated MLP: X is (.., 2 I) [gate | up]; the results have the shapes of the plain quantizers on a (.., I) tensor
+    def _act(x):
+        return x.new_empty((*x.shape[:-1], x.size(-1) // 2))
+
+    @custom_op("qutlass_amd::silu_and_mul", mutates_args=(), schema="(Tensor X) -> Tensor")
+    def silu_and_mul(X):
+        o = _act(X)
+        amd.siluAndMul_(X, o)
+        return o
+
+    silu_and_mul.register_fake(_act)
+
+    @custom_op("qutlass_amd::silu_mul_quantize_mx", mutates_args=(), schema="(Tensor A, Tensor R, int method, bool blocked) -> (Tensor, Tensor)")
+    def silu_mul_quantize_mx(A, R, method, blocked):
+        o = _mx(_act(A), blocked)
+        amd.fusedSiluMulQuantizeMx_(A, R, o[0], o[1], method, blocked)
+        return o
+
+    silu_mul_quantize_mx.register_fake(lambda A, R, method, blocked: _mx(_act(A), blocked))
+
+    @custom_op("qutlass_amd::silu_mul_quantize_nv", mutates_args=(), schema="(Tensor A, Tensor R, Tensor global_scale, int method, bool blocked) -> (Tensor, Tensor)")
+    def silu_mul_quantize_nv(A, R, global_scale, method, blocked):
+        o = _nv(_act(A), blocked)
+        amd.fusedSiluMulQuantizeNv_(A, R, o[0], o[1], global_scale, method, blocked)
+        return o
+
+    silu_mul_quantize_nv.register_fake(lambda A, R, global_scale, method, blocked: _nv(_act(A), blocked))
 
     if not have_training_ops:   # QUTLASS_MINIMAL_BUILD: inference ops only
         return
