@@ -35,6 +35,22 @@ extern "C" {
 /* ---- block-scaled GEMMs:  D[M,N] (bf16, row-major) = alpha[0] * (A.SFA) (B.SFB)^T ------------- */
 
 /*
+ * Input contract of the MX GEMMs below (MXFP4 / MXFP8, TN / NN, row-major-scale and grouped entries, every kernel form behind them;
+ * pinned by tests/test_gpu_mx_scale_range.py and tests/test_gpu_gemm_footprint.py):
+ *   * e8m0 scale bytes 0 ... 254 are the powers 2^-127 ... 2^127, each on its own: a block whose two scales are far apart
+ *     (0 against 254) but whose product is ordinary contributes exactly that product.  Byte 255 is NaN: it makes NaN exactly the
+ *     outputs of its A row / B column (every K group, the last one and the rows next to a tile or expert boundary included) and
+ *     no other output.
+ *   * fp8 operand codes follow IEEE / OCP propagation: the e4m3 NaN codes 0x7f / 0xff and the e5m2 NaN codes give NaN, e5m2 +-inf
+ *     gives +-inf by the sign of the product, inf x 0 and inf - inf give NaN.
+ *   * Nothing outside [D, D + M N) is written (grouped: rows past offs[E-1] are left alone), nor outside the workspace_bytes
+ *     handed to an entry that takes a workspace.
+ *   * Bytes outside the operands and outside the extents of the scale operands (row-major: rows x K/32; blocked: the padded
+ *     to_blocked image) are never consumed.  The padding ROWS of a blocked image may hold anything; its scale COLUMNS past K
+ *     (K % 128 != 0) meet masked-out operand bytes only, so any finite byte there contributes nothing.
+ */
+
+/*
  * MXFP4.  A: (M, K/2) bytes, B: (N, K/2) bytes, two e2m1 per byte (element 2j = low nibble), K % 128 == 0.
  * A_sf / B_sf: e8m0, one per 32 K-elements, in the to_blocked layout of a
  * (ceil(M/128)*128, ceil(K/128)*4) matrix (resp. N).  alpha: device fp32[1].  N % 8 == 0.
