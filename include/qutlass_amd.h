@@ -278,6 +278,34 @@ int qutlass_amd_fused_silu_mul_quantize_nv(const void* x, const void* h, int rot
                                            void* stream);
 
 /*
+ * EXTENSION (no reference counterpart): the two ends of a mixture-of-experts MLP around the grouped GEMMs -- dispatch (tokens -> rows sorted by expert, quantized)
+ * and combine (sorted rows -> tokens, weighted).
+ *
+ * qutlass_amd_fused_gather_quantize_{mx,nv}: qutlass_amd_fused_quantize_{mx,nv} applied to xg = x[src_row], byte for byte, without xg ever being written to memory.
+ *   x        bf16 (t, k), contiguous, 16-byte aligned; k % max(rot, 32) == 0; rot as in the plain entries; hardware e2m1 convert, no clip mask
+ *   src_row  int32 (m), device memory, read by the kernel (no host sync: the call is graph-capturable).  An index outside [0, t) -- -1 as a padding
+ *            sentinel, INT32_MIN, INT32_MAX -- gives the bytes of an all-zero row; it cannot fault and cannot read another row.
+ *   out_e2m1 (m, k / 2) codes; scales FLAT and row-major in the first m * k / 32 (MX) or m * k / 16 (NV) bytes of the caller's buffer, the rest untouched: what
+ *            the grouped GEMMs read as it is.
+ * LIMIT: x is addressed with 32-bit offsets from one buffer descriptor: x must stay below 2 GiB (t * k < 2^30), QAMD_ERR_INVALID beyond; m * k < 2^31.
+ * m == 0 returns QAMD_OK without a launch.
+ *
+ * qutlass_amd_moe_combine_bf16: out (t, hdim) bf16 from y (m, hdim) bf16, pos (t, topk) int32 and weights (t, topk) float32, all contiguous:
+ *     acc = +0.0f
+ *     for k = 0 .. topk - 1, in this order:  if 0 <= pos[t][k] < m:  acc = fadd_rn(acc, fmul_rn(weights[t][k], float(y[pos[t][k]][c])))      (two roundings, no fma)
+ *     out[t][c] = bf16_rne(acc)
+ * A slot whose pos lies outside [0, m) is skipped, not multiplied by zero: whatever an unreferenced row of y holds (the unwritten tail rows of a grouped GEMM's
+ * output) never reaches out.  A gather without atomics: deterministic, independent of the launch geometry.  hdim % 8 == 0, 1 <= topk <= 32; y and out 16-byte
+ * aligned; m, t, hdim < 2^31 (64-bit addressing: no byte limit).  t == 0 returns QAMD_OK without a launch.
+ */
+int qutlass_amd_fused_gather_quantize_mx(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method,
+                                         void* out_e2m1, void* out_e8m0, void* stream);
+int qutlass_amd_fused_gather_quantize_nv(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method,
+                                         const float* global_scale, void* out_e2m1, void* out_e4m3, void* stream);
+int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, void* out,
+                                 void* stream);
+
+/*
  * EXTENSION: the measured launch-count rule of the activation path y = Q(x h) W^T of one linear layer (reference flow: qutlass/__init__.py:149-180 ->
  * qutlass/utils.py:160-193 -> qutlass/__init__.py:34-76, three launches): returns 1 where the one-launch decode kernel below wins (M <= 16, R = 32, short K,
  * a weight of fewer than 32 x CUs rows), else 2 (quantizer with GEMM-ready scales + GEMM).  Pure host arithmetic on the current device's CU count; what

@@ -10,6 +10,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
+    moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -290,6 +291,84 @@ def fusedSiluMulQuantizeNvBlocked(x: torch.Tensor, h: torch.Tensor, global_scale
                                   method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION: ``fusedQuantizeNvBlocked(silu_and_mul(x), h, global_scale, method=method)`` in one launch (see fusedSiluMulQuantizeMxBlocked).  x below 2 GiB."""
     return _silu_mul_quantize_nv(x, h, global_scale, method, True)
+
+
+def moe_sort(topk_ids: torch.Tensor, num_experts: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): the routing metadata of a mixture-of-experts layer from the router's (T, topk) integer expert ids.
+
+    src_row  (T * topk,) int32 -- the token of every sorted row: rows are ordered by expert, and within an expert by (token, slot) (a stable sort)
+    offs     (num_experts,) int32 -- the cumulative END rows of the experts, the grouped GEMMs' convention; dropped rows are not counted
+    pos      (T, topk) int32 -- the sorted row of every routed slot, or -1 where the id was dropped
+
+    An id outside [0, num_experts) is DROPPED (an expert that lives on another rank): its row sorts behind every real expert, past offs[-1], where the grouped
+    GEMMs write nothing, and moe_combine skips its -1.  Plain torch ops without a host sync or a data-dependent shape (stable argsort, searchsorted, scatter): it
+    runs under graph capture and torch.compile, and on CPU tensors.  Feed src_row to fusedGatherQuantize*, offs to grouped_matmul_*, pos to moe_combine."""
+    if topk_ids.dim() != 2:
+        raise ValueError(f"topk_ids must be (T, topk) (got {tuple(topk_ids.shape)})")
+    topk = topk_ids.size(1)
+    ids = topk_ids.reshape(-1).to(torch.int64)
+    key = torch.where((ids >= 0) & (ids < num_experts), ids, num_experts)
+    order = torch.argsort(key, stable=True)
+    rows = torch.arange(ids.numel(), device=ids.device)
+    offs = torch.searchsorted(key[order], torch.arange(num_experts, device=ids.device), right=True)
+    pos = torch.empty_like(order).scatter_(0, order, rows)
+    pos = torch.where(key < num_experts, pos, -1).view_as(topk_ids)
+    return torch.div(order, topk, rounding_mode="floor").to(torch.int32), offs.to(torch.int32), pos.to(torch.int32)
+
+
+def _alloc_gathered(x: torch.Tensor, src_row: torch.Tensor, nv: bool):
+    """The outputs the plain quantizers allocate for x[src_row], an (M, K) tensor (_alloc_mx / _alloc_nv)."""
+    g = torch.empty(src_row.size(0), x.size(-1), dtype=x.dtype, device="meta")
+    padded_rows, padded_cols = get_padded_shape_nv(g) if nv else get_padded_shape_mx(g)
+    xh_e2m1 = torch.empty(g.size(0), g.size(1) // 2, dtype=torch.uint8, device=x.device)
+    return xh_e2m1, torch.empty(padded_rows, padded_cols, dtype=torch.float8_e4m3fn if nv else torch.float8_e8m0fnu, device=x.device)
+
+
+def fusedGatherQuantizeMx(x: torch.Tensor, h: torch.Tensor, src_row: torch.Tensor, *,
+                          method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): ``fusedQuantizeMx(x.index_select(0, src_row), h, method=method)`` in ONE launch, byte for byte -- the MoE dispatch: the
+    quantizer reads every routed row through the index, so the (M, K) bf16 copy of the tokens is never written (about 2.5 B moved per routed element instead of 6.5).
+    x is (T, K) bf16, contiguous; src_row is (M,) int32 on the device (moe_sort's first result); K % max(R, 32) == 0 for the R x R rotation h.  Returns e2m1 (M, K/2)
+    and e8m0 (padded_rows, padded_cols) exactly as fusedQuantizeMx does for an (M, K) tensor: scales flat in the first M * K / 32 bytes, padding untouched -- what
+    grouped_matmul_mxf4_bf16_tn reads as it is.  The indices are read on the device (no host sync: graph-capturable); an index outside [0, T) -- -1 padding included --
+    gives the bytes of an all-zero row and can neither fault nor read another row.  x must stay below 2 GiB (32-bit offsets; larger inputs raise).
+    Speed against index_select + fusedQuantizeMx: not measured yet (benchmarks/bench_moe_dispatch_mi355x.py)."""
+    if method not in _METHOD_CODE:
+        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
+    if torch.compiler.is_compiling():
+        return _ops_amd.gather_quantize_mx(x, h, src_row, _METHOD_CODE[method])
+    xh_e2m1, xh_e8m0 = _alloc_gathered(x, src_row, False)
+    _ops_amd.fusedGatherQuantizeMx_(x, h, src_row, xh_e2m1, xh_e8m0, _METHOD_CODE[method])
+    return xh_e2m1, xh_e8m0
+
+
+def fusedGatherQuantizeNv(x: torch.Tensor, h: torch.Tensor, global_scale: torch.Tensor, src_row: torch.Tensor, *,
+                          method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeNv(x.index_select(0, src_row), h, global_scale, method=method)`` in one launch, byte for byte (see fusedGatherQuantizeMx); R may be
+    16; e4m3 scales flat in the first M * K / 16 bytes -- what grouped_matmul_nvf4_bf16_tn reads as it is.  x below 2 GiB."""
+    if method not in _METHOD_CODE:
+        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
+    if torch.compiler.is_compiling():
+        return _ops_amd.gather_quantize_nv(x, h, src_row, global_scale, _METHOD_CODE[method])
+    xh_e2m1, xh_e4m3 = _alloc_gathered(x, src_row, True)
+    _ops_amd.fusedGatherQuantizeNv_(x, h, src_row, xh_e2m1, xh_e4m3, global_scale, _METHOD_CODE[method])
+    return xh_e2m1, xh_e4m3
+
+
+def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): the weighted sum that ends a mixture-of-experts layer, one streaming HIP kernel.  y is (M, H) bf16 (the down projection's
+    sorted rows), pos (T, topk) int32 (moe_sort's third result), weights (T, topk) float32; the result is (T, H) bf16 with, for every column c,
+
+        acc = +0.0f;  for k in 0 .. topk-1, in this order:  if 0 <= pos[t, k] < M:  acc = acc + weights[t, k] * float(y[pos[t, k], c]);   out[t, c] = bf16(acc)
+
+    every product and every sum rounded to fp32 on its own (no fma: numpy.float32 reproduces it bit for bit), bf16 by round-to-nearest-even.  A slot with pos outside
+    [0, M) is SKIPPED, not multiplied by zero: the unspecified rows a grouped GEMM leaves past offs[-1] (NaN, inf, garbage) never reach the result, and a token
+    whose slots are all dropped gives +0.  A gather without atomics: deterministic.  H % 8 == 0, 1 <= topk <= 32; no size limit below 2^31 rows / columns."""
+    if torch.compiler.is_compiling():
+        return _ops_amd.moe_combine(y, pos, weights)
+    out = torch.empty(pos.size(0), y.size(-1), dtype=y.dtype, device=y.device)
+    _ops_amd.moeCombine_(y, pos, weights, out)
+    return out
 
 
 def _decode_single_launch_wins(m: int, n: int, k: int, rot: int, device: torch.device | None = None) -> bool:

@@ -1290,6 +1290,35 @@ QAMD_ROT_BOTH(true, METHOD_ABSMAX)
 #undef QAMD_ROT_INST
 #endif
 
+// the gathering quantizers (fused_gather_quantize_kernel: the tile loads go through a row index): unit 5 as well
+template <bool NV, int METHOD>
+int dispatch_rot_gather(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
+#define QAMD_GATHER_GO(R_) hipLaunchKernelGGL((fused_gather_quantize_kernel<R_, NV, METHOD>), dim3(grid), dim3(256), 0, s, p); return check_launch("fused_gather_quantize_kernel")
+  switch (rot) {
+    case 16:
+      if constexpr (NV) { QAMD_GATHER_GO(16); }
+      break;
+    case 32: QAMD_GATHER_GO(32);
+    case 64: QAMD_GATHER_GO(64);
+    case 128: QAMD_GATHER_GO(128);
+  }
+#undef QAMD_GATHER_GO
+  return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, NV ? "16, " : "");
+}
+
+#if QAMD_TU != 0
+#if QAMD_TU == 5
+#define QAMD_ROT_INST template
+#else
+#define QAMD_ROT_INST extern template
+#endif
+QAMD_ROT_INST int dispatch_rot_gather<false, METHOD_QUEST>(int, const QuantParams&, hipStream_t, int, const char*);
+QAMD_ROT_INST int dispatch_rot_gather<false, METHOD_ABSMAX>(int, const QuantParams&, hipStream_t, int, const char*);
+QAMD_ROT_INST int dispatch_rot_gather<true, METHOD_QUEST>(int, const QuantParams&, hipStream_t, int, const char*);
+QAMD_ROT_INST int dispatch_rot_gather<true, METHOD_ABSMAX>(int, const QuantParams&, hipStream_t, int, const char*);
+#undef QAMD_ROT_INST
+#endif
+
 // backward_t_bf16 / backward_qt_bf16 kernels live in unit 5 with the other rotation quantizers (MFMA results straight in VGPRs: a
 // v_accvgpr_read per accumulator register is 32 more VALU issues per tile)
 //   which: 1 = the round-3 kernel (8 waves per unit of 8 groups x 64 m, two barriers per unit); 2 = wave-owned 64-byte segments (units of 4
@@ -1885,6 +1914,69 @@ int qutlass_amd_fused_silu_mul_quantize_nv(const void* x, const void* h, int rot
                                            void* out_e2m1, void* out_e4m3, void* stream) {
   return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", true, x, h, rot, rows, inter, method, global_scale,
                                       blocked, out_e2m1, out_e4m3, stream);
+}
+
+// ---- MoE dispatch and combine: the two ends of a mixture-of-experts MLP around the grouped GEMMs ---------------------------------------------------------
+// Dispatch: fusedQuantize{Mx,Nv}(x.index_select(0, src_row)) in one launch, byte for byte -- the quantizer's tile loads go through the row index (quantize.hip.h,
+// GATHER), so the (M, K) bf16 copy of the routed tokens is never written.  nv: 0 = MX (e8m0 per 32), 1 = NV (e4m3 per 16, global_scale).
+static int fused_gather_quantize_impl(const char* name, bool nv, const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m,
+                                      int method, const float* global_scale, void* out_e2m1, void* out_sf, void* stream) {
+  if (nv ? (rot != 16 && rot != 32 && rot != 64 && rot != 128) : (rot != 32 && rot != 64 && rot != 128))
+    return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, nv ? "16, " : "");
+  if (method != QAMD_METHOD_QUEST && method != QAMD_METHOD_ABSMAX) return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
+  const int rp = rot < 32 ? 32 : rot;
+  if (t < 0 || m < 0 || k <= 0 || t >= (1ll << 31) || m >= (1ll << 31) || k >= (1ll << 31))
+    return fail(QAMD_ERR_INVALID, "%s: bad shape (x (%lld, %lld), %lld indices)", name, (long long)t, (long long)k, (long long)m);
+  if (k % rp) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of %d", name, (long long)k, rp);
+  if ((uintptr_t)x % 16 || (uintptr_t)src_row % 4) return fail(QAMD_ERR_INVALID, "%s: x must be 16-byte aligned (and src_row 4-byte aligned)", name);
+  // x is addressed with 32-bit offsets from one buffer descriptor, and offset 2^31 is the kernel's "zero row" (quantize.hip.h, GATHER): no silent wrap beyond it
+  if (t * k >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: x (rows * k * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(t * k * 2));
+  if (m * k >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: more than 2^31 elements is not supported", name);
+  if (m == 0) return QAMD_OK;
+  if ((!x && t > 0) || !h || !src_row || !out_e2m1 || !out_sf || (nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (rot >= 64 && (uintptr_t)h % 16) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 16-byte aligned for rotation sizes >= 64", name);
+  QuantParams p;
+  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
+  p.out_mask = nullptr; p.global_scale = global_scale; p.numel = m * k; p.inter = (int)k;
+  p.ntiles = (int)cdiv(p.numel, (int64_t)rp * 32);
+  p.sf_rows = 0; p.sf_cols = 0;
+  p.src_row = src_row; p.src_n = (int)t;
+  const int grid = quant_grid(p.ntiles, rot);
+  hipStream_t s = (hipStream_t)stream;
+  if (nv) return method == QAMD_METHOD_QUEST ? dispatch_rot_gather<true, METHOD_QUEST>(rot, p, s, grid, name) : dispatch_rot_gather<true, METHOD_ABSMAX>(rot, p, s, grid, name);
+  return method == QAMD_METHOD_QUEST ? dispatch_rot_gather<false, METHOD_QUEST>(rot, p, s, grid, name) : dispatch_rot_gather<false, METHOD_ABSMAX>(rot, p, s, grid, name);
+}
+
+int qutlass_amd_fused_gather_quantize_mx(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method, void* out_e2m1,
+                                         void* out_e8m0, void* stream) {
+  return fused_gather_quantize_impl("fusedGatherQuantizeMx", false, x, h, rot, t, k, src_row, m, method, nullptr, out_e2m1, out_e8m0, stream);
+}
+
+int qutlass_amd_fused_gather_quantize_nv(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method,
+                                         const float* global_scale, void* out_e2m1, void* out_e4m3, void* stream) {
+  return fused_gather_quantize_impl("fusedGatherQuantizeNv", true, x, h, rot, t, k, src_row, m, method, global_scale, out_e2m1, out_e4m3, stream);
+}
+
+// Combine: out[t] = sum_k w[t][k] * y[pos[t][k]] in the order and with the roundings moe_combine_bf16_kernel states (quantize.hip.h); slots outside [0, m) are skipped.
+int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, void* out, void* stream) {
+  const char* name = "moe_combine";
+  if (m < 0 || t < 0 || hdim <= 0 || m >= (1ll << 31) || t >= (1ll << 31) || hdim >= (1ll << 31))
+    return fail(QAMD_ERR_INVALID, "%s: bad shape (y (%lld, %lld), %lld tokens)", name, (long long)m, (long long)hdim, (long long)t);
+  if (hdim % 8) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of 8", name, (long long)hdim);
+  if (topk < 1 || topk > 32) return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, 32] (got %lld)", name, (long long)topk);
+  if (((uintptr_t)y | (uintptr_t)out) % 16) return fail(QAMD_ERR_INVALID, "%s: y and out must be 16-byte aligned", name);
+  if (t == 0) return QAMD_OK;
+  if ((!y && m > 0) || !pos || !weights || !out) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (m == 0) {   // no row to name: every slot is skipped and every sum is its start, +0 (the kernel reads row 0 for a skipped slot, so it wants one row)
+    if (hipMemsetAsync(out, 0, (size_t)(t * hdim * 2), (hipStream_t)stream) != hipSuccess) return fail(QAMD_ERR_HIP, "%s: hipMemsetAsync failed", name);
+    return QAMD_OK;
+  }
+  MoeCombineParams p;
+  p.y = (const uint16_t*)y; p.pos = pos; p.w = weights; p.out = (uint16_t*)out;
+  p.chunks = t * (hdim / 8); p.cpr = (uint32_t)(hdim / 8); p.m = (uint32_t)m; p.topk = (int)topk;
+  const int grid = (int)std::min<int64_t>(cdiv(p.chunks, 256), (int64_t)chip_cus() * 8);
+  hipLaunchKernelGGL(moe_combine_bf16_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  return check_launch("moe_combine_bf16_kernel");
 }
 
 // How many launches should the activation path y = Q(x h) W^T of one linear layer take (the rule behind qutlass_amd.fused_quantize_matmul_mxf4_bf16_tn;

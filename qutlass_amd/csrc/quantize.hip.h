@@ -38,6 +38,10 @@ struct QuantParams {
   // GATED kernels only (fusedSiluMulQuantize*): x is (rows, 2 * inter) -- gate | up halves of every row -- and the operand that is rotated and quantized is
   // act = silu(gate) * up, (rows, inter); numel counts act.  The plain kernels never read it.  (Sits in the struct's tail padding: no other field moves.)
   int inter = 0;
+  // GATHER kernels only (fusedGatherQuantize*): the operand is xg = x[src_row] -- row m of the (numel / inter, inter) operand is row src_row[m] of x = (src_n, inter);
+  // inter is the row length K here.  An index outside [0, src_n) stands for an all-zero row.  The plain and the gated kernels never read these.
+  const int32_t* src_row = nullptr;
+  int src_n = 0;
 };
 
 // byte offset of scale (row, col) in the 128x4-tiled block-scale layout (qutlass/utils.py:60-64, :190-193); CB = ceil(cols / 4)
@@ -255,11 +259,18 @@ __device__ __forceinline__ v4i silu_mul8(const v4i g, const v4i u) {
 //   GATED  : the operand is act = silu(gate) * up of an x that holds (rows, 2 I): the tile's loads fetch gate and up (two 16-byte loads where the plain kernel has
 //            one) and silu_mul8 turns them into the bf16 the plain kernel would have loaded; everything after that is the plain kernel.  The input is addressed with
 //            32-bit offsets from one descriptor: x must stay below 2 GiB (rows * I < 2^29; the host checks).
+//   GATHER : the operand is xg = x[src_row], (M, K): RP-row (m, c) of a tile is read from row src_row[m] of x = (T, K) -- again only the tile loads' address differs, the
+//            rest is the plain kernel, so the result is fusedQuantize*(x.index_select(0, src_row)) byte for byte.  A tile spans at most 32 logical rows; lane l of the
+//            wave fetches src_row[first row of the tile + (l & 31)] and every chunk load picks its row's index out of that register with a cross-lane read
+//            (ds_bpermute: no LDS memory, one per chunk load).  The x loads depend on the indices, so the indices run one tile ahead of the x loads, which
+//            run one tile ahead of the MFMAs: gather_loads(t) issues tile t's x loads from the indices fetched a tile earlier, then tile t + nwaves' index load.  The
+//            first tile's index load goes out before H's loads and its x loads before H's LDS writes.  An index is compared with T before any offset is formed from
+//            it; out of range (or an RP-row past the end) the offset is 2^31, off the descriptor (x stays below 2 GiB; the host checks): the load returns zeros.
 // -------------------------------------------------------------------------------------------------
 // The kernel's body as a device function of (workgroup index, workgroup count): fused_quantize_kernel below is its plain launch; [r6] the one-launch decode layer
 // (gemm_mx_os.hip.h gemm_mx_os16_fq_kernel) runs it on its first few workgroups.  PAD = false: the zero padding of the blocked scale layout is left out (a reader that
 // only looks at the rows it wrote).
-template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false>
+template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false, bool GATHER = false>
 __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const int bid, const int nblk) {
   constexpr int RP = (R < 32) ? 32 : R;         // rotation padded to one MFMA j-tile (R=16: block-diag)
   constexpr int KC = RP / 16;                   // 16-wide k chunks per row
@@ -285,7 +296,8 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
 
   // x as rows of RP elements (for R = 16 two rotation rows share one 32-element "row")
   const int64_t ngroups = p.numel / (NV ? 16 : 32);
-  const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, (uint32_t)(p.numel * (GATED ? 4 : 2)));
+  static_assert(!(GATED && GATHER) && !(GATHER && (BLK || MASK)), "the gathering form: plain operand, flat scales, no clip mask");
+  const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, GATHER ? (uint32_t)p.src_n * (uint32_t)p.inter * 2u : (uint32_t)(p.numel * (GATED ? 4 : 2)));
 
   const int wave_global = bid * 4 + wave, nwaves = nblk * 4;
   v4i xnext[RP / 16];
@@ -302,7 +314,7 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   // reciprocal multiply and a fix-up of one either way.
   uint32_t g_row = 0, g_rem = 0, g_qstep = 0, g_rstep = 0, g_rpr = 1, g_nrows = 0;
   float g_rc = 1.0f;
-  if constexpr (GATED) {
+  if constexpr (GATED || GATHER) {
     g_rpr = (uint32_t)p.inter / RP;
     g_rc = __builtin_amdgcn_rcpf((float)g_rpr);
     g_nrows = (uint32_t)(p.numel / RP);
@@ -346,7 +358,43 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     g_rem -= carry ? g_rpr : 0u;
     g_row += g_qstep + carry;
   };
-  if constexpr (GATED) {
+  // GATHER: the same walk over (g_row, g_rem); gidx = src_row[g_row + (lane & 31)] of the tile the walk stands at (rows past the end of src_row read 0: only RP-rows
+  // past the end of the operand name them, and those get the off-descriptor offset)
+  const __amdgpu_buffer_rsrc_t ri = make_rsrc(GATHER ? (const void*)p.src_row : (const void*)p.x, GATHER ? (uint32_t)(p.numel / p.inter) * 4u : 0u);
+  int gidx = 0;
+  auto gather_index_load = [&]() { gidx = __builtin_amdgcn_raw_buffer_load_b32(ri, (int)((g_row + (uint32_t)row) * 4u), 0, 0); };
+  auto gather_off = [&](const int t, const uint32_t lrow, const uint32_t cb) -> int {
+    const uint32_t x = g_rem + lrow;
+    uint32_t q = (uint32_t)((float)x * g_rc);
+    int32_t r = (int32_t)(x - q * g_rpr);
+    if (r < 0) { q -= 1; r += (int32_t)g_rpr; }
+    if (r >= (int32_t)g_rpr) { q += 1; r -= (int32_t)g_rpr; }
+    const uint32_t idx = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), gidx);   // q <= lrow <= 31: the lane that fetched src_row[g_row + q]
+    const bool ok = idx < (uint32_t)p.src_n && (uint32_t)t * 32u + lrow < g_nrows;       // the range check comes first: no offset is formed from a bad index
+    return ok ? (int)(idx * ((uint32_t)p.inter * 2u) + (uint32_t)r * (RP * 2u) + cb) : (int)0x80000000u;
+  };
+  auto gather_loads = [&](const int t) {   // tile t's x loads (gidx holds its indices), advance, then the index load of this wave's next tile
+    if constexpr (STAGED) {
+      constexpr int CPR = RP / 8;
+#pragma unroll
+      for (int i = 0; i < RP / 16; ++i) {
+        const int q = i * 64 + lane;
+        xnext[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, gather_off(t, (uint32_t)(q / CPR), (uint32_t)(q % CPR) * 16u), 0, 0);
+      }
+    } else {
+      const int off = gather_off(t, (uint32_t)row, (uint32_t)half * 16u);
+#pragma unroll
+      for (int kc = 0; kc < RP / 16; ++kc) xnext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rx, off + kc * 32, 0, 0);
+    }
+    g_rem += g_rstep;
+    const uint32_t carry = g_rem >= g_rpr ? 1u : 0u;
+    g_rem -= carry ? g_rpr : 0u;
+    g_row += g_qstep + carry;
+    gather_index_load();
+  };
+  if constexpr (GATHER) {
+    gather_index_load();        // the x loads that depend on it go out between H's loads and H's LDS writes, below
+  } else if constexpr (GATED) {
     gated_loads(wave_global);   // (before H is staged, as below)
   } else {   // [r2] the first tile's loads go out BEFORE H is staged: the two memory round trips overlap (4096^2 cold: 9.03 -> 8.46 us at
       // R = 32, 10.08 -> 9.31 at R = 64, 13.18 -> 12.54 at R = 128; profiles/ab_stream_ops_r2.txt)
@@ -385,6 +433,7 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
       const int idx = i * 256 + tid, k = idx / RP, j = idx % RP;
       hv[i] = p.h[(k & 15) * R + (j & 15)];                      // (always in range: R x R entries)
     }
+    if constexpr (GATHER) gather_loads(wave_global);
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
       const int idx = i * 256 + tid, k = idx / RP, j = idx % RP;
@@ -401,6 +450,7 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
       v4i hc[NCH];
 #pragma unroll
       for (int i = 0; i < NCH; ++i) hc[i] = *(const v4i*)(p.h + (i * 256 + tid) * 8);
+      if constexpr (GATHER) gather_loads(wave_global);
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
         const int c = i * 256 + tid;
@@ -411,6 +461,7 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
       uint16_t hv[NE];
 #pragma unroll
       for (int i = 0; i < NE; ++i) hv[i] = p.h[i * 256 + tid];           // idx = i * 256 + tid = k * RP + j, R == RP here
+      if constexpr (GATHER) gather_loads(wave_global);
 #pragma unroll
       for (int i = 0; i < NE; ++i) {
         const int idx = i * 256 + tid, k = idx / RP, j = idx % RP;
@@ -465,7 +516,9 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) xf[kc] = __builtin_bit_cast(v8bf, xnext[kc]);
     }
-    if constexpr (GATED) {
+    if constexpr (GATHER) {
+      gather_loads(tile + nwaves);
+    } else if constexpr (GATED) {
       gated_loads(tile + nwaves);
     } else {
       const int64_t on = (int64_t)(tile + nwaves) * 32 * RP * 2 + lane_off;
@@ -694,6 +747,12 @@ __global__ __launch_bounds__(256) void fused_silu_mul_quantize_kernel(const Quan
   fused_quantize_body<R, NV, METHOD, false, true, BLK, true, true>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// the gathering quantizers (fusedGatherQuantize{Mx,Nv}): the hardware e2m1 convert only, flat scales, no clip mask
+template <int R, bool NV, int METHOD>
+__global__ __launch_bounds__(256) void fused_gather_quantize_kernel(const QuantParams p) {
+  fused_quantize_body<R, NV, METHOD, false, true, false, true, false, true>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
 // silu_and_mul: x (rows, 2 I) bf16 -> out (rows, I) bf16, out[r][c] = act(x[r][c], x[r][I + c]) (silu_mul8 above).  Streaming, 4 B in + 2 B out per element: a
 // thread takes 16-byte chunks (8 elements; I % 8 == 0) chunk = first + k * step, kept as (row, chunk within the row) with a carry-propagating add -- no division in
 // the loop -- and 64-bit addresses, so neither operand has a size limit below rows, I < 2^31.
@@ -712,6 +771,67 @@ __global__ __launch_bounds__(256) void silu_mul_bf16_kernel(const SiluMulParams 
     const uint16_t* g = p.x + ((int64_t)row * 2 * p.cpr + cc) * 8;
     const v4i gv = *(const v4i*)g, uv = *(const v4i*)(g + (int64_t)p.cpr * 8);
     *(v4i*)(p.out + c * 8) = silu_mul8(gv, uv);
+    cc += rstep;
+    const uint32_t carry = cc >= p.cpr ? 1u : 0u;
+    cc -= carry ? p.cpr : 0u;
+    row += qstep + carry;
+  }
+}
+
+// moe_combine: out[t][c] = bf16_rne(sum over k = 0 .. topk - 1, in that order, of w[t][k] * float(y[pos[t][k]][c])), the sum starting from +0 and every product and every
+// sum rounded to fp32 on its own (no fma: numpy.float32 reproduces it bit for bit).  A slot whose pos lies outside [0, M) is SKIPPED -- its load goes to row 0 and the
+// loaded value is dropped by a select, never multiplied -- so a NaN in a row that no slot names cannot reach out.  Written as a gather: no atomics, the result does
+// not depend on the launch geometry.  Streaming like silu_mul_bf16_kernel: 16-byte chunks (H % 8 == 0), (row, chunk) carried without a division, 64-bit addresses
+// (rows, columns < 2^31 is the only limit).  Slots go four at a time so that four row loads are in flight per thread.  y needs one row (the host never launches M == 0).
+struct MoeCombineParams {
+  const uint16_t* y;     // (M, H) bf16
+  const int32_t* pos;    // (T, topk)
+  const float* w;        // (T, topk)
+  uint16_t* out;         // (T, H) bf16
+  int64_t chunks;        // T * H / 8
+  uint32_t cpr;          // chunks per row, H / 8
+  uint32_t m;            // rows of y
+  int topk;
+};
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void moe_combine_bf16_kernel(const MoeCombineParams p) {
+#pragma clang fp contract(off)
+  const uint32_t first = blockIdx.x * 256u + threadIdx.x, step = gridDim.x * 256u;
+  uint32_t row = first / p.cpr, cc = first - row * p.cpr;
+  const uint32_t qstep = step / p.cpr, rstep = step - qstep * p.cpr;
+  for (int64_t c = first; c < p.chunks; c += step) {
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    const int64_t slot0 = (int64_t)row * p.topk;
+    for (int k0 = 0; k0 < p.topk; k0 += 4) {
+      float w[4];
+      bool ok[4];
+      v4i v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = k0 + j < p.topk ? k0 + j : p.topk - 1;   // (past the last slot: a second read of it, dropped below)
+        const uint32_t ps = (uint32_t)p.pos[slot0 + k];
+        w[j] = p.w[slot0 + k];
+        ok[j] = k0 + j < p.topk && ps < p.m;
+        v[j] = *(const v4i*)(p.y + ((int64_t)(ok[j] ? ps : 0u) * p.cpr + cc) * 8);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t yw = (uint32_t)v[j][e];
+          const float lo = w[j] * __uint_as_float(yw << 16), hi = w[j] * __uint_as_float(yw & 0xffff0000u);
+          const float slo = acc[2 * e] + lo, shi = acc[2 * e + 1] + hi;
+          acc[2 * e] = ok[j] ? slo : acc[2 * e];
+          acc[2 * e + 1] = ok[j] ? shi : acc[2 * e + 1];
+        }
+      }
+    }
+    v4i o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
+    *(v4i*)(p.out + c * 8) = o;
     cc += rstep;
     const uint32_t carry = cc >= p.cpr ? 1u : 0u;
     cc -= carry ? p.cpr : 0u;

@@ -463,6 +463,71 @@ void fusedSiluMulQuantizeNv_(const Tensor& A, const Tensor& R, Tensor OUT, Tenso
   silu_mul_quantize(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", true, A, R, OUT, OUT_sf, &global_scale, method, blocked);
 }
 
+// ---- EXTENSION: MoE dispatch and combine around the grouped GEMMs ---------------------------------------------------------------------
+// fusedGatherQuantize{Mx,Nv}_: fusedQuantize{Mx,Nv}_ of A.index_select(0, src_row) in one launch, byte for byte; A (T, K) bf16, src_row (M) int32 read on the device (no
+// host sync).  OUT / OUT_sf are sized as for the plain quantizers on an (M, K) tensor; flat scales.
+void gather_quantize(const char* op, bool nv, const Tensor& X, const Tensor& R, const Tensor& src_row, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method) {
+  require_contiguous(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
+  if (nv) {
+    require_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
+    require_same_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
+  } else {
+    require_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
+    require_same_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
+  }
+  quant_prologue(op, X, R);
+  if (nv) {
+    STD_TORCH_CHECK(has_dtype(*gscale, ScalarType::Float), "global_scale must be float");
+    STD_TORCH_CHECK(gscale->dim() == 1 && gscale->size(0) == 1, "global_scale must be a scalar");
+  }
+  STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
+  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
+  STD_TORCH_CHECK(X.dim() == 2 && X.size(1) > 0, "A must be 2D (T, K)");
+  STD_TORCH_CHECK(has_dtype(src_row, ScalarType::Int) && src_row.dim() == 1, "src_row must be a 1D int32 tensor");
+  const int64_t rot = R.size(0), T = X.size(0), K = X.size(1), M = src_row.size(0), gs = nv ? 16 : 32;
+  if (nv) {
+    STD_TORCH_CHECK(rot == 16 || rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 16, 32, 64, or 128.");
+  } else {
+    STD_TORCH_CHECK(rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 32, 64, or 128.");
+  }
+  STD_TORCH_CHECK(K % (rot < 32 ? 32 : rot) == 0, "the last dimension of A must be divisible by", rot < 32 ? 32 : rot);
+  STD_TORCH_CHECK(nbytes(OUT) >= M * K / 2, "OUT is too small");
+  STD_TORCH_CHECK(nbytes(OUT_sf) >= M * K / gs, "OUT_sf is too small");
+  const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
+  if (nv)
+    check_rc(qutlass_amd_fused_gather_quantize_nv(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, (int)method,
+                                                  static_cast<const float*>(gscale->data_ptr()), OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
+  else
+    check_rc(qutlass_amd_fused_gather_quantize_mx(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, (int)method,
+                                                  OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
+}
+void fusedGatherQuantizeMx_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf, int64_t method) {
+  gather_quantize("fusedGatherQuantizeMx", false, A, R, src_row, OUT, OUT_sf, nullptr, method);
+}
+void fusedGatherQuantizeNv_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale, int64_t method) {
+  gather_quantize("fusedGatherQuantizeNv", true, A, R, src_row, OUT, OUT_sf, &global_scale, method);
+}
+
+// moeCombine_: OUT[t] = sum_k weights[t][k] * Y[pos[t][k]] (the arithmetic is spelled out at qutlass_amd_moe_combine_bf16); slots with pos outside [0, M) are skipped
+void moeCombine_(const Tensor& Y, const Tensor& pos, const Tensor& weights, Tensor OUT) {
+  const char* op = "moeCombine_";
+  require_contiguous(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
+  require_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
+  require_same_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
+  STD_TORCH_CHECK(has_dtype(Y, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "Y and OUT must be bf16");
+  STD_TORCH_CHECK(has_dtype(pos, ScalarType::Int), "pos must be int32");
+  STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
+  STD_TORCH_CHECK(Y.dim() == 2 && Y.size(1) > 0, "Y must be 2D (M, H)");
+  STD_TORCH_CHECK(pos.dim() == 2 && weights.dim() == 2 && pos.size(0) == weights.size(0) && pos.size(1) == weights.size(1), "pos and weights must both be (T, topk)");
+  const int64_t M = Y.size(0), H = Y.size(1), T = pos.size(0), topk = pos.size(1);
+  STD_TORCH_CHECK(H % 8 == 0, "the row length of Y must be divisible by", 8);
+  STD_TORCH_CHECK(topk >= 1 && topk <= 32, "topk must be in [1, 32] (got ", topk, ")");
+  STD_TORCH_CHECK(OUT.numel() >= T * H, "OUT is too small");
+  const torch::stable::accelerator::DeviceGuard guard(Y.get_device_index());
+  check_rc(qutlass_amd_moe_combine_bf16(Y.data_ptr(), M, H, static_cast<const int32_t*>(pos.data_ptr()), static_cast<const float*>(weights.data_ptr()), T, topk,
+                                        OUT.data_ptr(), current_stream(Y)));
+}
+
 // ---- EXTENSION: rotate + quantize + MXFP4 GEMM in one launch for decode batches (M <= 32) ---------------------------------------
 Tensor fusedQuantizeMatmulMxf4(const Tensor& X, const Tensor& R, const Tensor& B, const Tensor& B_sf, const Tensor& alpha, int64_t method) {
   const char* op = "fusedQuantizeMatmulMxf4";
@@ -602,6 +667,9 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("siluAndMul_(Tensor X, Tensor(a!) OUT) -> ()");   // inference ops: in the minimal library too
   m.def("fusedSiluMulQuantizeMx_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, int method, bool blocked) -> ()");
   m.def("fusedSiluMulQuantizeNv_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method, bool blocked) -> ()");
+  m.def("fusedGatherQuantizeMx_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, int method) -> ()");
+  m.def("fusedGatherQuantizeNv_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method) -> ()");
+  m.def("moeCombine_(Tensor Y, Tensor pos, Tensor weights, Tensor(a!) OUT) -> ()");
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
@@ -643,6 +711,9 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("siluAndMul_", TORCH_BOX(&siluAndMul_));
   m.impl("fusedSiluMulQuantizeMx_", TORCH_BOX(&fusedSiluMulQuantizeMx_));
   m.impl("fusedSiluMulQuantizeNv_", TORCH_BOX(&fusedSiluMulQuantizeNv_));
+  m.impl("fusedGatherQuantizeMx_", TORCH_BOX(&fusedGatherQuantizeMx_));
+  m.impl("fusedGatherQuantizeNv_", TORCH_BOX(&fusedGatherQuantizeNv_));
+  m.impl("moeCombine_", TORCH_BOX(&moeCombine_));
   m.impl("fusedQuantizeMatmulMxf4", TORCH_BOX(&fusedQuantizeMatmulMxf4));
   m.impl("grouped_matmul_mxf4", TORCH_BOX(&grouped_matmul_mxf4));
   m.impl("grouped_matmul_mxf8", TORCH_BOX(&grouped_matmul_mxf8));

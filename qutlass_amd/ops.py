@@ -73,7 +73,8 @@ def _register_fakes() -> None:
         return None
 
     for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
-                 "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
+                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "moeCombine_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -183,6 +184,37 @@ def _define_functional_ops() -> None:
         return o
 
     silu_mul_quantize_nv.register_fake(lambda A, R, global_scale, method, blocked: _nv(_act(A), blocked))
+
+    # MoE dispatch / combine: the gathered operand is A[src_row], (M, K) for M indices; the results have the shapes of the plain quantizers on such a tensor
+    def _gathered(A, src_row):
+        return A.new_empty((src_row.size(0), A.size(-1)))
+
+    @custom_op("qutlass_amd::gather_quantize_mx", mutates_args=(), schema="(Tensor A, Tensor R, Tensor src_row, int method) -> (Tensor, Tensor)")
+    def gather_quantize_mx(A, R, src_row, method):
+        o = _mx(_gathered(A, src_row))
+        amd.fusedGatherQuantizeMx_(A, R, src_row, o[0], o[1], method)
+        return o
+
+    gather_quantize_mx.register_fake(lambda A, R, src_row, method: _mx(_gathered(A, src_row)))
+
+    @custom_op("qutlass_amd::gather_quantize_nv", mutates_args=(), schema="(Tensor A, Tensor R, Tensor src_row, Tensor global_scale, int method) -> (Tensor, Tensor)")
+    def gather_quantize_nv(A, R, src_row, global_scale, method):
+        o = _nv(_gathered(A, src_row))
+        amd.fusedGatherQuantizeNv_(A, R, src_row, o[0], o[1], global_scale, method)
+        return o
+
+    gather_quantize_nv.register_fake(lambda A, R, src_row, global_scale, method: _nv(_gathered(A, src_row)))
+
+    def _combined(Y, pos):
+        return Y.new_empty((pos.size(0), Y.size(-1)))
+
+    @custom_op("qutlass_amd::moe_combine", mutates_args=(), schema="(Tensor Y, Tensor pos, Tensor weights) -> Tensor")
+    def moe_combine(Y, pos, weights):
+        o = _combined(Y, pos)
+        amd.moeCombine_(Y, pos, weights, o)
+        return o
+
+    moe_combine.register_fake(lambda Y, pos, weights: _combined(Y, pos))
 
     if not have_training_ops:   # QUTLASS_MINIMAL_BUILD: inference ops only
         return
