@@ -306,6 +306,38 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
                                  void* stream);
 
 /*
+ * EXTENSION (no reference counterpart): MoE routing, the step in front of the dispatch above -- router logits to expert ids and weights, and expert ids to the
+ * sorted-row metadata the gathering quantizers, the grouped GEMMs and moe_combine read.  Every argument check happens before any HIP call.
+ *
+ * qutlass_amd_moe_topk_softmax: logits (t, e), contiguous, bf16 (elem_bytes 2) or float32 (4) -> weights (t, topk) float32 and ids (t, topk) int32.
+ *   selection  the first topk experts in the order (logit descending, expert index ascending), ids[t] in that order; logits compare as floating-point numbers
+ *              (-0 and +0 tie, the lower index wins); -inf is legal and sorts last.  Made on the logits, never on the probabilities.
+ *   weights    fp32: m = max_j x_j, e_j = exp(x_j - m), p_j = e_j / sum_j e_j; renormalize != 0: w_k = p_k / sum over the selected p.  The order of the sums is not
+ *              part of the contract.  A row holding a NaN or +inf, or nothing but -inf, gets unspecified weights; its ids are still distinct and in [0, e), and no
+ *              other row is affected.
+ *   1 <= e <= 1024, 1 <= topk <= min(e, 32), t < 2^31; pointers aligned to their element size (rows that start on 16-byte boundaries are read with 16-byte
+ *   loads).  One launch, one wave per token, no workspace, no host sync.  t == 0 returns QAMD_OK without a launch.
+ *
+ * qutlass_amd_moe_sort: topk_ids (t, topk), int32 (id_bytes 4) or int64 (8) -> src_row (t * topk), offs (num_experts), pos (t, topk), all int32: a STABLE sort of
+ * the n = t * topk slots by expert.
+ *   key        the slot's id g; with expert_map (g_entries int32, or NULL for none): expert_map[g] for g in [0, g_entries), dropped otherwise WITHOUT reading the
+ *              map.  A key outside [0, num_experts) -- -1 by convention, an expert of another rank -- DROPS the slot.
+ *   src_row    the token (slot / topk) of every sorted row: rows ordered by expert, within an expert by slot; dropped slots behind every real expert
+ *   offs       the cumulative END rows of the experts (the grouped GEMMs' convention); dropped slots are not counted
+ *   pos        the sorted row of every slot, -1 where it was dropped
+ *   A counting sort without atomics: the result does not depend on the launch geometry or on timing, and no workgroup waits on another.  Up to the one-launch
+ *   bound (qutlass_amd_moe_sort_workspace_bytes(n, .) == 0) it is ONE launch of one workgroup; beyond it three launches (count, scan, scatter) over `workspace`,
+ *   which must hold qutlass_amd_moe_sort_workspace_bytes(n, num_experts) bytes, 4-byte aligned (never more than 257 * 1025 * 4 bytes); its contents need not be
+ *   initialised and are not kept.  1 <= num_experts <= 1024, topk >= 1, n < 2^31.  n == 0 returns QAMD_OK without a launch and writes nothing: the caller
+ *   zero-fills offs (an empty sort has every offset at 0).
+ */
+int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids,
+                                 void* stream);
+int64_t qutlass_amd_moe_sort_workspace_bytes(int64_t n, int64_t num_experts);
+int qutlass_amd_moe_sort(const void* topk_ids, int id_bytes, int64_t t, int64_t topk, int64_t num_experts, const int32_t* expert_map, int64_t g_entries,
+                         int32_t* src_row, int32_t* offs, int32_t* pos, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * EXTENSION: the measured launch-count rule of the activation path y = Q(x h) W^T of one linear layer (reference flow: qutlass/__init__.py:149-180 ->
  * qutlass/utils.py:160-193 -> qutlass/__init__.py:34-76, three launches): returns 1 where the one-launch decode kernel below wins (M <= 16, R = 32, short K,
  * a weight of fewer than 32 x CUs rows), else 2 (quantizer with GEMM-ready scales + GEMM).  Pure host arithmetic on the current device's CU count; what

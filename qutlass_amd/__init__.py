@@ -11,6 +11,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
+    moe_topk_softmax, moe_sort_fused, moe_route           (extension: MoE routing in HIP -- router logits to ids, weights and the sorted-row metadata)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -314,6 +315,52 @@ def moe_sort(topk_ids: torch.Tensor, num_experts: int) -> tuple[torch.Tensor, to
     pos = torch.empty_like(order).scatter_(0, order, rows)
     pos = torch.where(key < num_experts, pos, -1).view_as(topk_ids)
     return torch.div(order, topk, rounding_mode="floor").to(torch.int32), offs.to(torch.int32), pos.to(torch.int32)
+
+
+def moe_topk_softmax(logits: torch.Tensor, topk: int, *, renormalize: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): the router's (T, E) logits -> (weights (T, topk) float32, ids (T, topk) int32) in ONE HIP launch, one wave per token.
+
+    Selection is exact and part of the contract: the first topk experts in the order (logit descending, expert index ascending), ids[t] in that order.  Logits
+    compare as floating-point numbers (-0.0 and +0.0 tie; the lower index wins); the choice is made on the logits, never on the probabilities (exp can merge two
+    logits).  -inf is a legal logit (a masked expert): probability 0, sorts last.  Weights in fp32: m = max_j x_j, e_j = exp(x_j - m), p_j = e_j / sum_j e_j, and
+    with renormalize w_k = p_k / sum over the selected p (the order of the sums is the kernel's business).  A token whose row holds a NaN or +inf, or nothing but
+    -inf, gets unspecified weights; its ids are still distinct and inside [0, E), and no other token is affected.
+
+    logits bf16 or float32, contiguous; 1 <= E <= 1024 (the grouped GEMMs' limit), 1 <= topk <= min(E, 32) (moe_combine's limit); T == 0 returns empty tensors.  No
+    host sync, no workspace: graph-capturable.  ids feed moe_sort / moe_sort_fused, weights and ids feed moe_combine, as they are."""
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be (T, E) (got {tuple(logits.shape)})")
+    if not 1 <= topk <= min(logits.size(1), 32):
+        raise ValueError(f"topk must be in [1, min(E, 32)] (got topk = {topk} for E = {logits.size(1)})")
+    if torch.compiler.is_compiling():
+        return _ops_amd.moe_topk_softmax(logits, topk, renormalize)
+    weights, ids = ops._alloc_topk(logits, topk)
+    _ops_amd.moeTopkSoftmax_(logits, weights, ids, renormalize)
+    return weights, ids
+
+
+def moe_sort_fused(topk_ids: torch.Tensor, num_experts: int, *, expert_map: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): ``moe_sort(topk_ids, num_experts)`` -- the same three int32 results, bit for bit -- as a counting sort in HIP: one launch
+    of one workgroup up to the one-launch bound of T * topk slots, three launches (count, scan, scatter) over scratch allocated here beyond it.  No atomics and no
+    workgroup waiting on another: the result does not depend on the launch geometry or on timing.  topk_ids (T, topk) int32 or int64 on the device; 1 <=
+    num_experts <= 1024; T * topk < 2^31.
+
+    expert_map (G,) int32, G >= 1, for expert parallelism: an id g in [0, G) is replaced by expert_map[g] before anything else; a value outside [0, num_experts)
+    (conventionally -1, "not on this rank") drops the slot, and an id outside [0, G) is dropped without reading the map.  Dropped slots sort behind every real
+    expert with pos = -1 and are not counted in offs, as in moe_sort.  No host sync: graph-capturable; traces under torch.compile."""
+    if topk_ids.dim() != 2:
+        raise ValueError(f"topk_ids must be (T, topk) (got {tuple(topk_ids.shape)})")
+    if torch.compiler.is_compiling():
+        return _ops_amd.moe_sort_fused(topk_ids, expert_map, num_experts)
+    return ops.run_moe_sort(topk_ids, expert_map, num_experts)
+
+
+def moe_route(logits: torch.Tensor, topk: int, num_experts: int | None = None, *, renormalize: bool = True,
+              expert_map: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """EXTENSION: the whole routing of a mixture-of-experts layer from the router's logits: ``moe_topk_softmax`` then ``moe_sort_fused`` -- two launches for decode-sized
+    inputs.  Returns (weights, ids, src_row, offs, pos).  num_experts defaults to E, the logits' second dimension; with expert_map pass the number of LOCAL experts."""
+    weights, ids = moe_topk_softmax(logits, topk, renormalize=renormalize)
+    return (weights, ids) + tuple(moe_sort_fused(ids, logits.size(1) if num_experts is None else num_experts, expert_map=expert_map))
 
 
 def _alloc_gathered(x: torch.Tensor, src_row: torch.Tensor, nv: bool):

@@ -23,6 +23,7 @@
 #include "gemm_nvf4_pk.hip.h"
 #include "gemm_nvf4_os.hip.h"
 #include "quantize.hip.h"
+#include "moe_route.hip.h"
 #include "to_blocked.hip.h"
 #include "transpose_u8.hip.h"
 #include "quartet_bwd.hip.h"
@@ -71,6 +72,7 @@ std::atomic<int> g_pp_flags{1};
 std::atomic<int> g_quant_wg_per_cu{0};  // 0 = auto
 std::atomic<int> g_deepp_grid{0};       // lab: workgroups of the persistent deep kernels (0 = the balanced-rounds rule)
 std::atomic<int> g_bwd_variant{0};      // lab: 1 = the round-3 backward_t / backward_qt kernel (8 waves meeting at two barriers per tile) instead of the wave-owned-lines one
+std::atomic<int> g_moe_sort_one_launch_max{0};   // lab: moe_sort's one-workgroup bound in slots (0 = the product's; 1 forces the three-launch form from two slots on)
 std::atomic<int> g_splitk_force{0};     // lab: K splits for a FORCED ring variant ("gemm_variant" 70..73); 0 = the plan's
 std::atomic<uint32_t*> g_dbg{nullptr};
 #endif
@@ -102,7 +104,7 @@ unsigned long long next_launch_tag() {
 #else
 unsigned long long next_launch_tag();
 #if QAMD_BENCH
-extern std::atomic<int> g_hw_fp4_cvt, g_gemm_variant, g_nvf4_variant, g_splitk_wg, g_splitk_min_kt, g_transpose_nc, g_pp_shift, g_pp_flags, g_quant_wg_per_cu, g_splitk_force, g_deepp_grid, g_bwd_variant;
+extern std::atomic<int> g_hw_fp4_cvt, g_gemm_variant, g_nvf4_variant, g_splitk_wg, g_splitk_min_kt, g_transpose_nc, g_pp_shift, g_pp_flags, g_quant_wg_per_cu, g_splitk_force, g_deepp_grid, g_bwd_variant, g_moe_sort_one_launch_max;
 extern std::atomic<uint32_t*> g_dbg;
 #endif
 int fail(int code, const char* fmt, ...);
@@ -124,6 +126,7 @@ inline int opt_quant_wg_per_cu() { return g_quant_wg_per_cu.load(); }
 inline int opt_splitk_force() { return g_splitk_force.load(); }
 inline int opt_deepp_grid() { return g_deepp_grid.load(); }
 inline int opt_bwd_variant() { return g_bwd_variant.load(); }
+inline int opt_moe_sort_one_launch_max() { return g_moe_sort_one_launch_max.load(); }
 inline uint32_t* opt_dbg() { return g_dbg.load(); }
 #else
 constexpr bool opt_hw_fp4() { return true; }   // the product ships ONE e2m1 encoder: the hardware convert
@@ -138,6 +141,7 @@ constexpr int opt_quant_wg_per_cu() { return 0; }
 constexpr int opt_splitk_force() { return 0; }
 constexpr int opt_deepp_grid() { return 0; }
 constexpr int opt_bwd_variant() { return 0; }
+constexpr int opt_moe_sort_one_launch_max() { return 0; }
 constexpr uint32_t* opt_dbg() { return nullptr; }
 #endif
 
@@ -1979,6 +1983,97 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
   return check_launch("moe_combine_bf16_kernel");
 }
 
+// ---- MoE routing: the front of the chain (moe_route.hip.h) ---------------------------------------------------------------------------------------------------
+// Router logits -> top-k ids (exact: logit descending, expert index ascending) and softmax weights; one wave per token, one launch, no workspace.
+extern "C++" {
+template <typename T, bool LOADV>
+static void launch_topk_softmax(const MoeTopkParams& p, int grid, hipStream_t s) {
+  const int per_lane = (p.e + 63) / 64;   // columns a lane has to hold: 1 .. 16, in whole vectors of 16 bytes
+#define QAMD_TOPK_ARM(R_) hipLaunchKernelGGL((moe_topk_softmax_kernel<T, R_, LOADV>), dim3(grid), dim3(256), 0, s, p)
+  if constexpr (sizeof(T) == 4) { if (per_lane <= 4) { QAMD_TOPK_ARM(4); return; } }
+  if (per_lane <= 8) { QAMD_TOPK_ARM(8); return; }
+  QAMD_TOPK_ARM(16);
+#undef QAMD_TOPK_ARM
+}
+}   // extern "C++"
+
+int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids, void* stream) {
+  const char* name = "moe_topk_softmax";
+  if (elem_bytes != 2 && elem_bytes != 4) return fail(QAMD_ERR_INVALID, "%s: logits must be bf16 (elem_bytes 2) or float32 (4), got elem_bytes %d", name, elem_bytes);
+  if (t < 0 || t >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld tokens)", name, (long long)t);
+  if (e < 1 || e > 1024) return fail(QAMD_ERR_INVALID, "%s: bad shape: the number of experts must be in [1, 1024] (got %lld)", name, (long long)e);
+  if (topk < 1 || topk > 32 || topk > e) return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, min(E, 32)] (got %lld for E = %lld)", name, (long long)topk, (long long)e);
+  if ((uintptr_t)logits % elem_bytes || (uintptr_t)weights % 4 || (uintptr_t)ids % 4) return fail(QAMD_ERR_INVALID, "%s: logits, weights and ids must be aligned to their element size", name);
+  if (t == 0) return QAMD_OK;
+  if (!logits || !weights || !ids) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  MoeTopkParams p;
+  p.logits = logits; p.weights = weights; p.ids = ids; p.t = t; p.e = (int)e; p.topk = (int)topk; p.renorm = renormalize ? 1 : 0;
+  const int grid = (int)std::min<int64_t>(cdiv(t, 4), (int64_t)chip_cus() * 16);
+  const bool vec = (e * elem_bytes) % 16 == 0 && (uintptr_t)logits % 16 == 0;   // every row starts on a 16-byte boundary: 16-byte loads (same layout, same bits, either way)
+  hipStream_t s = (hipStream_t)stream;
+  if (elem_bytes == 2) { if (vec) launch_topk_softmax<uint16_t, true>(p, grid, s); else launch_topk_softmax<uint16_t, false>(p, grid, s); }
+  else { if (vec) launch_topk_softmax<float, true>(p, grid, s); else launch_topk_softmax<float, false>(p, grid, s); }
+  return check_launch("moe_topk_softmax_kernel");
+}
+
+// Expert sort.  Up to MOE_SORT_ONE_LAUNCH_MAX slots: one workgroup, one launch.  Beyond: count, scan, scatter -- three launches over caller scratch, workgroups of
+// `spb` consecutive slots (at least 4096 = 8 chunks of 64 per wave, and never more than 256 workgroups: the scratch stays below 1.01 MiB however large n is).
+// The bound is measured (profiles/bench_moe_route_mi355x.txt): one workgroup costs 2.6 + 2.2 us per 1024 slots (E = 8; 2.7 + 3.2 at E = 128),
+// three launches 18-19 us (24-25) from 4096 to 16384 slots; at 6144 slots one workgroup still wins (15.9 vs 18.5, 22.2 vs 23.9 us), at 8192 it has lost
+// (20.4 vs 19.0, 28.6 vs 24.7).  6144 is the largest measured size at which one launch is faster for both expert counts.
+constexpr int64_t MOE_SORT_ONE_LAUNCH_MAX = 6144;
+static int64_t moe_sort_one_launch_max() { return opt_moe_sort_one_launch_max() > 0 ? opt_moe_sort_one_launch_max() : MOE_SORT_ONE_LAUNCH_MAX; }
+static void moe_sort_geometry(int64_t n, int64_t& spb, int& rows) {
+  spb = cdiv(std::max<int64_t>(4096, cdiv(n, 256)), 512) * 512;
+  rows = (int)cdiv(n, spb);
+}
+
+int64_t qutlass_amd_moe_sort_workspace_bytes(int64_t n, int64_t num_experts) {
+  if (n <= moe_sort_one_launch_max() || n >= (1ll << 31) || num_experts < 1 || num_experts > 1024) return 0;
+  // sized by min(256, ceil(n / 4096)) rows, which the geometry never exceeds and which, unlike its row count, never shrinks as n grows
+  return (std::min<int64_t>(256, cdiv(n, 4096)) + 1) * (num_experts + 1) * 4;
+}
+
+extern "C++" {
+template <typename IdT>
+static void launch_moe_sort(MoeSortParams& p, hipStream_t s) {
+  if (!p.ws) {
+    hipLaunchKernelGGL((moe_sort_kernel<IdT, 0>), dim3(1), dim3(MOE_SORT_NT), 0, s, p);
+    return;
+  }
+  hipLaunchKernelGGL((moe_sort_kernel<IdT, 1>), dim3(p.rows), dim3(MOE_SORT_NT), 0, s, p);
+  hipLaunchKernelGGL(moe_sort_scan_kernel<0>, dim3(1), dim3(MOE_SORT_NT), 0, s, p);
+  hipLaunchKernelGGL((moe_sort_kernel<IdT, 3>), dim3(p.rows), dim3(MOE_SORT_NT), 0, s, p);
+}
+}   // extern "C++"
+
+int qutlass_amd_moe_sort(const void* topk_ids, int id_bytes, int64_t t, int64_t topk, int64_t num_experts, const int32_t* expert_map, int64_t g, int32_t* src_row,
+                         int32_t* offs, int32_t* pos, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* name = "moe_sort";
+  if (id_bytes != 4 && id_bytes != 8) return fail(QAMD_ERR_INVALID, "%s: topk_ids must be int32 (id_bytes 4) or int64 (8), got id_bytes %d", name, id_bytes);
+  if (t < 0 || topk < 1 || t >= (1ll << 31) || topk >= (1ll << 31) || t * topk >= (1ll << 31))
+    return fail(QAMD_ERR_INVALID, "%s: bad shape (topk_ids (%lld, %lld)): topk >= 1 and T * topk < 2^31", name, (long long)t, (long long)topk);
+  if (num_experts < 1 || num_experts > 1024) return fail(QAMD_ERR_INVALID, "%s: bad shape: the number of experts must be in [1, 1024] (got %lld)", name, (long long)num_experts);
+  if (g < 0 || g >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (expert_map of %lld entries)", name, (long long)g);
+  if ((uintptr_t)topk_ids % id_bytes || ((uintptr_t)expert_map | (uintptr_t)src_row | (uintptr_t)offs | (uintptr_t)pos | (uintptr_t)workspace) % 4)
+    return fail(QAMD_ERR_INVALID, "%s: topk_ids, expert_map, the results and the workspace must be aligned to their element size", name);
+  const int64_t n = t * topk, need = qutlass_amd_moe_sort_workspace_bytes(n, num_experts);
+  if (need > 0 && (!workspace || workspace_bytes < need))
+    return fail(QAMD_ERR_INVALID, "%s: %lld slots need a workspace of %lld bytes (qutlass_amd_moe_sort_workspace_bytes), got %lld", name, (long long)n, (long long)need,
+                (long long)(workspace ? workspace_bytes : 0));
+  if (n == 0) return QAMD_OK;
+  if (!topk_ids || !src_row || !offs || !pos) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  MoeSortParams p;
+  p.ids = topk_ids; p.map = expert_map; p.src_row = src_row; p.offs = offs; p.pos = pos; p.ws = need > 0 ? (uint32_t*)workspace : nullptr;
+  p.n = n; p.g = (int)g; p.e = (int)num_experts; p.topk = (int)topk;
+  p.nbits = 0;
+  while ((num_experts >> p.nbits) != 0) ++p.nbits;   // keys are 0 .. E
+  if (need > 0) moe_sort_geometry(n, p.spb, p.rows);
+  else { p.spb = cdiv(n, 512) * 512; p.rows = 1; }
+  if (id_bytes == 8) launch_moe_sort<int64_t>(p, (hipStream_t)stream); else launch_moe_sort<int32_t>(p, (hipStream_t)stream);
+  return check_launch("moe_sort_kernel");
+}
+
 // How many launches should the activation path y = Q(x h) W^T of one linear layer take (the rule behind qutlass_amd.fused_quantize_matmul_mxf4_bf16_tn;
 // reference flow: qutlass/__init__.py:149-180 -> qutlass/utils.py:160-193 -> qutlass/__init__.py:34-76 = three launches)?
 //   1  ONE launch, qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn (gemm_mx_fusedq.hip.h: the small-batch GEMM rotates and quantises its own A operand).  It repeats
@@ -2425,6 +2520,7 @@ int qutlass_amd_set_option(const char* key, int value) {
   if (!strcmp(key, "deepp_grid")) return g_deepp_grid.exchange(value);
   if (!strcmp(key, "bwd_variant")) return g_bwd_variant.exchange(value);
   if (!strcmp(key, "quant_wg_per_cu")) return g_quant_wg_per_cu.exchange(value);
+  if (!strcmp(key, "moe_sort_one_launch_max")) return g_moe_sort_one_launch_max.exchange(value);
   if (!strcmp(key, "pp_shift")) return g_pp_shift.exchange(value);
   if (!strcmp(key, "pp_flags")) return g_pp_flags.exchange(value);
 #endif

@@ -1,0 +1,300 @@
+// MoE routing: the step in front of the dispatch -> grouped GEMM -> combine chain.
+//   moe_topk_softmax_kernel   router logits (T, E) -> the top-k expert ids (exact, ties to the lower index) and their softmax weights, one wave per token
+//   moe_sort_kernel           (T, topk) expert ids -> src_row / offs / pos of a STABLE sort by expert: a counting sort without atomics and without any
+//                             workgroup waiting on another (one workgroup in one launch, or count / scan / scatter in three launches ordered by the stream)
+// Both are plain wave64 code: no LDS in the first, 33 KiB of LDS counters in the second.
+#pragma once
+#include "common.hip.h"
+
+namespace qamd {
+
+// ---- top-k softmax ----------------------------------------------------------------------------------------------------------------------------------------
+// Selection runs on an order-preserving integer image of the logit, never on a probability: key(x) is monotone in x as a floating-point number, -0 and +0 share
+// one key (so they tie and the lower index wins), -inf has the lowest key of all numbers, and a NaN gets SOME key (its row's weights are unspecified, its ids
+// are still distinct and in range).  Real elements have key >= 1; 0 marks "not a candidate": a column past E, or an expert already taken.
+__device__ __forceinline__ uint32_t route_key(uint32_t bits) {
+  const uint32_t u = bits == 0x80000000u ? 0u : bits;
+  const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return k ? k : 1u;
+}
+__device__ __forceinline__ float route_key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+__device__ __forceinline__ float wave_sum(float v) {   // every lane ends with the same bits: a + b and b + a round alike
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+struct MoeTopkParams {
+  const void* logits;   // (T, E) bf16 or float32
+  float* weights;       // (T, topk)
+  int32_t* ids;         // (T, topk)
+  int64_t t;
+  int e, topk, renorm;
+};
+
+// One wave per token, four tokens per workgroup, the whole row in registers: lane l holds R candidates, column ((r / VEC) * 64 + l) * VEC + r % VEC for r < R --
+// VEC = 8 bf16 / 4 float consecutive columns, one 16-byte load when LOADV (every row starts on a 16-byte boundary), VEC loads of one column otherwise.  The
+// columns a lane holds do not depend on LOADV or on R, so neither do the sums: a row gives the same bits wherever it lies in memory.
+// R * 64 >= E.  Then topk rounds of an arg-max over (key descending, column ascending): R compares in the lane, six butterfly steps across the wave on the
+// 64-bit pair (key, ~column), and the owner strikes the winner out.  Round 0's winner is the row maximum m; the denominator sum_j exp(x_j - m) is taken right
+// there, before anything is struck out.  Lane k keeps round k's pick and writes slot k.  No LDS, no barrier, no workspace.
+template <typename T, int R, bool LOADV>
+__global__ __launch_bounds__(256) void moe_topk_softmax_kernel(const MoeTopkParams p) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  static_assert(R % VEC == 0, "whole vectors per lane");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t e = (uint32_t)p.e;
+  auto column = [lane](int r) { return (uint32_t)(((r / VEC) * 64 + lane) * VEC + r % VEC); };
+  for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < p.t; t += (int64_t)gridDim.x * 4) {
+    const T* row = (const T*)p.logits + t * p.e;
+    uint32_t key[R];
+    if constexpr (!LOADV) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint32_t j = column(r);
+        uint32_t bits = 0;
+        if (j < e) {
+          if constexpr (sizeof(T) == 2) bits = (uint32_t)((const uint16_t*)row)[j] << 16;
+          else bits = ((const uint32_t*)row)[j];
+        }
+        key[r] = j < e ? route_key(bits) : 0u;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < R / VEC; ++c) {
+        const uint32_t j0 = column(c * VEC);
+        v4i raw = {0, 0, 0, 0};
+        if (j0 < e) raw = *(const v4i*)(row + j0);   // E % VEC == 0: a vector is all inside the row or all outside
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+          uint32_t bits;
+          if constexpr (sizeof(T) == 2) bits = (i & 1) ? ((uint32_t)raw[i / 2] & 0xffff0000u) : ((uint32_t)raw[i / 2] << 16);
+          else bits = (uint32_t)raw[i];
+          key[c * VEC + i] = j0 < e ? route_key(bits) : 0u;
+        }
+      }
+    }
+    float m = 0.f, denom = 1.f, my_x = 0.f;
+    uint32_t my_id = 0;
+    for (int k = 0; k < p.topk; ++k) {
+      uint32_t hi = key[0];
+      int br = 0;
+#pragma unroll
+      for (int r = 1; r < R; ++r) {   // strictly greater: the lane's lowest column wins a tie
+        const bool g = key[r] > hi;
+        hi = g ? key[r] : hi;
+        br = g ? r : br;
+      }
+      uint32_t lo = 0;
+#pragma unroll
+      for (int r = 0; r < R; ++r) lo = br == r ? ~column(r) : lo;
+      lo = hi ? lo : 0u;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {   // max of (hi, lo): the largest key, then the smallest column
+        const uint32_t oh = (uint32_t)__shfl_xor((int)hi, off), ol = (uint32_t)__shfl_xor((int)lo, off);
+        const bool g = oh > hi || (oh == hi && ol > lo);
+        hi = g ? oh : hi;
+        lo = g ? ol : lo;
+      }
+      const uint32_t win = ~lo;   // (topk <= E: a candidate is always left, so win < E)
+      const float x = route_key_value(hi);
+      if (k == 0) {
+        m = x;
+        float s = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) s += key[r] ? expf(route_key_value(key[r]) - m) : 0.f;
+        denom = wave_sum(s);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) key[r] = column(r) == win ? 0u : key[r];
+      if (lane == k) {
+        my_id = win;
+        my_x = x;
+      }
+    }
+    float w = lane < p.topk ? expf(my_x - m) / denom : 0.f;
+    if (p.renorm) w = w / wave_sum(w);
+    if (lane < p.topk) {
+      p.weights[t * p.topk + lane] = w;
+      p.ids[t * p.topk + lane] = (int32_t)my_id;
+    }
+  }
+}
+
+// ---- expert sort ------------------------------------------------------------------------------------------------------------------------------------------
+// A counting sort on key = expert id, or E for a dropped slot (an id outside [0, E), before or after expert_map).  Stability comes from the order of the counts,
+// not from any order of execution: a workgroup takes `spb` consecutive slots, each of its 8 waves a consecutive run of 64-slot chunks, and
+//   pass 1   every wave counts its own slots into its OWN row of LDS counters: the lanes of a chunk that hold one key are found with nbits = bits(E) ballots,
+//            the lowest such lane adds their number -- one writer per counter, no atomic;
+//   scan     the counters are replaced by their exclusive prefix in (key, workgroup, wave) order;
+//   pass 2   every wave walks its chunks again: row = counter[wave][key] + (lanes below me with my key); the lowest lane moves the counter on.
+// MODE 0 is all of it in one workgroup (offs too).  MODE 1 is pass 1 of every workgroup, summed over its waves into row `blockIdx.x` of the workspace;
+// moe_sort_scan_kernel turns the workspace into prefixes and writes offs; MODE 3 repeats pass 1, starts its scan from the workspace and runs pass 2.  The three
+// are ordered by the stream; no workgroup ever waits on another.
+constexpr int MOE_SORT_NT = 512, MOE_SORT_W = 8, MOE_SORT_MAXK = 1025;
+
+struct MoeSortParams {
+  const void* ids;        // (n) int32 or int64
+  const int32_t* map;     // (g) or null
+  int32_t* src_row;       // (n)
+  int32_t* offs;          // (e)
+  int32_t* pos;           // (n)
+  uint32_t* ws;           // (rows + 1, e + 1): per-workgroup counts, then prefixes; row `rows` holds every key's first row
+  int64_t n, spb;         // slots; slots per workgroup (a multiple of 512)
+  int g, e, topk, nbits, rows;
+};
+
+template <typename IdT>
+__device__ __forceinline__ int moe_sort_key(const MoeSortParams& p, int64_t slot) {
+  long long id = (long long)((const IdT*)p.ids)[slot];
+  if (p.map) id = (id >= 0 && id < p.g) ? (long long)p.map[id] : -1ll;   // an id outside [0, g) is dropped without reading the map
+  return (id >= 0 && id < p.e) ? (int)id : p.e;
+}
+
+// the lanes of the wave that are active and hold this lane's key
+__device__ __forceinline__ unsigned long long moe_sort_peers(int key, bool active, int nbits) {
+  unsigned long long m = __ballot(active);
+  for (int b = 0; b < nbits; ++b) {
+    const bool bit = (key >> b) & 1;
+    const unsigned long long bal = __ballot(active && bit);
+    m &= bit ? bal : ~bal;
+  }
+  return m;
+}
+
+// exclusive prefix of v over the 512 threads of the workgroup, in thread order (every thread calls it, once per kernel)
+__device__ __forceinline__ uint32_t moe_sort_block_scan(uint32_t v, uint32_t* wsum) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_up((int)inc, off);
+    inc += lane >= off ? o : 0u;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0;
+  for (int w = 0; w < wave; ++w) base += wsum[w];
+  return base + inc - v;
+}
+
+template <typename IdT, int MODE>
+__global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_kernel(const MoeSortParams p) {
+  __shared__ uint32_t cnt[MOE_SORT_W * MOE_SORT_MAXK];
+  __shared__ uint32_t wsum[MOE_SORT_W];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nk = p.e + 1;
+  const int64_t b0 = (int64_t)blockIdx.x * p.spb, b1 = b0 + p.spb < p.n ? b0 + p.spb : p.n;
+  const int chunks = b1 > b0 ? (int)((b1 - b0 + 63) >> 6) : 0;
+  const int wact = chunks < MOE_SORT_W ? (chunks > 0 ? chunks : 1) : MOE_SORT_W;   // waves with work: the others' counter rows are not even cleared
+  const int cpw = (chunks + wact - 1) / wact;
+  const int c_begin = wave * cpw, c_end = c_begin + cpw < chunks ? c_begin + cpw : chunks;
+  uint32_t* mine = cnt + (wave < wact ? wave : 0) * nk;
+  const unsigned long long below = (1ull << lane) - 1ull;
+
+  for (int i = tid; i < wact * nk; i += MOE_SORT_NT) cnt[i] = 0;
+  __syncthreads();
+  for (int c = c_begin; c < c_end; ++c) {
+    const int64_t slot = b0 + (int64_t)c * 64 + lane;
+    const bool active = slot < b1;
+    const int key = active ? moe_sort_key<IdT>(p, slot) : 0;
+    const unsigned long long peers = moe_sort_peers(key, active, p.nbits);
+    if (active && (peers & below) == 0) mine[key] += (uint32_t)__popcll(peers);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  }
+  __syncthreads();
+
+  const int kpt = (nk + MOE_SORT_NT - 1) / MOE_SORT_NT;   // 1 .. 3 consecutive keys per thread
+  const int k0 = tid * kpt;
+  if constexpr (MODE == 1) {
+    for (int i = 0; i < kpt; ++i) {
+      const int k = k0 + i;
+      if (k < nk) {
+        uint32_t s = 0;
+        for (int w = 0; w < wact; ++w) s += cnt[w * nk + k];
+        p.ws[(int64_t)blockIdx.x * nk + k] = s;
+      }
+    }
+    return;
+  } else {
+    uint32_t run = 0;
+    if constexpr (MODE == 0) {
+      uint32_t s = 0;
+      for (int i = 0; i < kpt; ++i)
+        if (k0 + i < nk)
+          for (int w = 0; w < wact; ++w) s += cnt[w * nk + k0 + i];
+      run = moe_sort_block_scan(s, wsum);
+    }
+    for (int i = 0; i < kpt; ++i) {
+      const int k = k0 + i;
+      if (k < nk) {
+        if constexpr (MODE == 3) run = p.ws[(int64_t)p.rows * nk + k] + p.ws[(int64_t)blockIdx.x * nk + k];
+        for (int w = 0; w < wact; ++w) {
+          const uint32_t c = cnt[w * nk + k];
+          cnt[w * nk + k] = run;
+          run += c;
+        }
+        if (MODE == 0 && k < p.e) p.offs[k] = (int32_t)run;
+      }
+    }
+    __syncthreads();
+    for (int c = c_begin; c < c_end; ++c) {
+      const int64_t slot = b0 + (int64_t)c * 64 + lane;
+      const bool active = slot < b1;
+      const int key = active ? moe_sort_key<IdT>(p, slot) : 0;
+      const unsigned long long peers = moe_sort_peers(key, active, p.nbits);
+      const uint32_t first = mine[key];
+      if (active) {
+        const uint32_t r = first + (uint32_t)__popcll(peers & below);
+        if ((int64_t)r < p.n) p.src_row[r] = (int32_t)((uint32_t)slot / (uint32_t)p.topk);   // (r < n unless the ids changed between the launches)
+        p.pos[slot] = key < p.e ? (int32_t)r : -1;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      if (active && (peers & below) == 0) mine[key] = first + (uint32_t)__popcll(peers);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+  }
+}
+
+// One workgroup: ws[r][k] (the count of key k in workgroup r's slots) -> the number of slots with key k in the workgroups before r; row `rows` gets every key's
+// first sorted row and offs its end.  A thread owns 1 .. 3 consecutive keys and walks the rows eight loads at a time.  (A template only so that this header can be
+// included from several translation units: the parameter is not used.)
+template <int UNUSED = 0>
+__global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_scan_kernel(const MoeSortParams p) {
+  __shared__ uint32_t wsum[MOE_SORT_W];
+  const int nk = p.e + 1, kpt = (nk + MOE_SORT_NT - 1) / MOE_SORT_NT, k0 = threadIdx.x * kpt;
+  uint32_t tot[3] = {0, 0, 0}, s = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int k = k0 + i;
+    if (i < kpt && k < nk) {
+      uint32_t run = 0;
+      for (int r = 0; r < p.rows; r += 8) {
+        uint32_t c[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) c[j] = r + j < p.rows ? p.ws[(int64_t)(r + j) * nk + k] : 0u;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (r + j < p.rows) {
+            p.ws[(int64_t)(r + j) * nk + k] = run;
+            run += c[j];
+          }
+      }
+      tot[i] = run;
+      s += run;
+    }
+  }
+  uint32_t run = moe_sort_block_scan(s, wsum);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int k = k0 + i;
+    if (i < kpt && k < nk) {
+      p.ws[(int64_t)p.rows * nk + k] = run;
+      run += tot[i];
+      if (k < p.e) p.offs[k] = (int32_t)run;
+    }
+  }
+}
+
+}  // namespace qamd

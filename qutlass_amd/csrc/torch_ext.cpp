@@ -528,6 +528,53 @@ void moeCombine_(const Tensor& Y, const Tensor& pos, const Tensor& weights, Tens
                                         OUT.data_ptr(), current_stream(Y)));
 }
 
+// ---- EXTENSION: MoE routing in front of the dispatch ---------------------------------------------------------------------------------------------
+// moeTopkSoftmax_: router logits (T, E) bf16 / float32 -> weights (T, topk) float32 and ids (T, topk) int32; topk is the outputs' second dimension
+void moeTopkSoftmax_(const Tensor& logits, Tensor weights, Tensor ids, bool renormalize) {
+  const char* op = "moeTopkSoftmax_";
+  require_contiguous(op, {{logits, "logits"}, {weights, "weights"}, {ids, "ids"}});
+  require_gpu(op, {{logits, "logits"}, {weights, "weights"}, {ids, "ids"}});
+  require_same_gpu(op, {{logits, "logits"}, {weights, "weights"}, {ids, "ids"}});
+  const bool f32 = has_dtype(logits, ScalarType::Float);
+  STD_TORCH_CHECK(f32 || has_dtype(logits, ScalarType::BFloat16), "logits must be bf16 or float32");
+  STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
+  STD_TORCH_CHECK(has_dtype(ids, ScalarType::Int), "ids must be int32");
+  STD_TORCH_CHECK(logits.dim() == 2, "logits must be 2D (T, E)");
+  STD_TORCH_CHECK(weights.dim() == 2 && ids.dim() == 2 && weights.size(0) == logits.size(0) && ids.size(0) == logits.size(0) && weights.size(1) == ids.size(1),
+                  "weights and ids must both be (T, topk)");
+  const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
+  check_rc(qutlass_amd_moe_topk_softmax(logits.data_ptr(), f32 ? 4 : 2, logits.size(0), logits.size(1), ids.size(1), renormalize ? 1 : 0,
+                                        static_cast<float*>(weights.data_ptr()), static_cast<int32_t*>(ids.data_ptr()), current_stream(logits)));
+}
+
+// moeSort_: the stable sort of the (T, topk) slots by expert (qutlass_amd_moe_sort); an EMPTY expert_map means "no map" (a map has at least one entry); workspace is
+// caller scratch of at least qutlass_amd_moe_sort_workspace_bytes bytes (it may be empty below the one-launch bound)
+void moeSort_(const Tensor& topk_ids, const Tensor& expert_map, int64_t num_experts, Tensor src_row, Tensor offs, Tensor pos, Tensor workspace) {
+  const char* op = "moeSort_";
+  require_contiguous(op, {{topk_ids, "topk_ids"}, {src_row, "src_row"}, {offs, "offs"}, {pos, "pos"}, {workspace, "workspace"}});
+  require_gpu(op, {{topk_ids, "topk_ids"}, {src_row, "src_row"}, {offs, "offs"}, {pos, "pos"}, {workspace, "workspace"}});
+  require_same_gpu(op, {{topk_ids, "topk_ids"}, {src_row, "src_row"}, {offs, "offs"}, {pos, "pos"}, {workspace, "workspace"}});
+  const bool i64 = has_dtype(topk_ids, ScalarType::Long);
+  STD_TORCH_CHECK(i64 || has_dtype(topk_ids, ScalarType::Int), "topk_ids must be int32 or int64");
+  STD_TORCH_CHECK(topk_ids.dim() == 2, "topk_ids must be 2D (T, topk)");
+  STD_TORCH_CHECK(has_dtype(src_row, ScalarType::Int) && has_dtype(offs, ScalarType::Int) && has_dtype(pos, ScalarType::Int), "src_row, offs and pos must be int32");
+  const int64_t T = topk_ids.size(0), topk = topk_ids.size(1);
+  STD_TORCH_CHECK(src_row.numel() >= T * topk && pos.numel() >= T * topk && offs.numel() >= num_experts, "src_row, offs or pos is too small");
+  const bool use_map = expert_map.numel() > 0;
+  int64_t G = 0;
+  if (use_map) {
+    require_contiguous(op, {{expert_map, "expert_map"}});
+    require_gpu(op, {{expert_map, "expert_map"}});
+    require_same_gpu(op, {{topk_ids, "topk_ids"}, {expert_map, "expert_map"}});
+    STD_TORCH_CHECK(has_dtype(expert_map, ScalarType::Int) && expert_map.dim() == 1, "expert_map must be a 1D int32 tensor");
+    G = expert_map.size(0);
+  }
+  const torch::stable::accelerator::DeviceGuard guard(topk_ids.get_device_index());
+  check_rc(qutlass_amd_moe_sort(topk_ids.data_ptr(), i64 ? 8 : 4, T, topk, num_experts, use_map ? static_cast<const int32_t*>(expert_map.data_ptr()) : nullptr, G,
+                                static_cast<int32_t*>(src_row.data_ptr()), static_cast<int32_t*>(offs.data_ptr()), static_cast<int32_t*>(pos.data_ptr()),
+                                workspace.numel() > 0 ? workspace.data_ptr() : nullptr, nbytes(workspace), current_stream(topk_ids)));
+}
+
 // ---- EXTENSION: rotate + quantize + MXFP4 GEMM in one launch for decode batches (M <= 32) ---------------------------------------
 Tensor fusedQuantizeMatmulMxf4(const Tensor& X, const Tensor& R, const Tensor& B, const Tensor& B_sf, const Tensor& alpha, int64_t method) {
   const char* op = "fusedQuantizeMatmulMxf4";
@@ -670,6 +717,8 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("fusedGatherQuantizeMx_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, int method) -> ()");
   m.def("fusedGatherQuantizeNv_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method) -> ()");
   m.def("moeCombine_(Tensor Y, Tensor pos, Tensor weights, Tensor(a!) OUT) -> ()");
+  m.def("moeTopkSoftmax_(Tensor logits, Tensor(a!) weights, Tensor(b!) ids, bool renormalize) -> ()");
+  m.def("moeSort_(Tensor topk_ids, Tensor expert_map, int num_experts, Tensor(a!) src_row, Tensor(b!) offs, Tensor(c!) pos, Tensor(d!) workspace) -> ()");
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
@@ -714,6 +763,8 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("fusedGatherQuantizeMx_", TORCH_BOX(&fusedGatherQuantizeMx_));
   m.impl("fusedGatherQuantizeNv_", TORCH_BOX(&fusedGatherQuantizeNv_));
   m.impl("moeCombine_", TORCH_BOX(&moeCombine_));
+  m.impl("moeTopkSoftmax_", TORCH_BOX(&moeTopkSoftmax_));
+  m.impl("moeSort_", TORCH_BOX(&moeSort_));
   m.impl("fusedQuantizeMatmulMxf4", TORCH_BOX(&fusedQuantizeMatmulMxf4));
   m.impl("grouped_matmul_mxf4", TORCH_BOX(&grouped_matmul_mxf4));
   m.impl("grouped_matmul_mxf8", TORCH_BOX(&grouped_matmul_mxf8));

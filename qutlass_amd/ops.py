@@ -74,7 +74,7 @@ def _register_fakes() -> None:
 
     for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
                  "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
-                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "moeCombine_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "moeCombine_", "moeTopkSoftmax_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -216,6 +216,21 @@ def _define_functional_ops() -> None:
 
     moe_combine.register_fake(lambda Y, pos, weights: _combined(Y, pos))
 
+    # MoE routing: (T, E) logits -> (T, topk) weights and ids; (T, topk) ids -> src_row (T * topk), offs (num_experts), pos (T, topk)
+    @custom_op("qutlass_amd::moe_topk_softmax", mutates_args=(), schema="(Tensor logits, int topk, bool renormalize) -> (Tensor, Tensor)")
+    def moe_topk_softmax(logits, topk, renormalize):
+        o = _alloc_topk(logits, topk)
+        amd.moeTopkSoftmax_(logits, o[0], o[1], renormalize)
+        return o
+
+    moe_topk_softmax.register_fake(lambda logits, topk, renormalize: _alloc_topk(logits, topk))
+
+    @custom_op("qutlass_amd::moe_sort_fused", mutates_args=(), schema="(Tensor topk_ids, Tensor? expert_map, int num_experts) -> (Tensor, Tensor, Tensor)")
+    def moe_sort_fused(topk_ids, expert_map, num_experts):
+        return run_moe_sort(topk_ids, expert_map, num_experts)
+
+    moe_sort_fused.register_fake(lambda topk_ids, expert_map, num_experts: _alloc_sort(topk_ids, num_experts))
+
     if not have_training_ops:   # QUTLASS_MINIMAL_BUILD: inference ops only
         return
 
@@ -280,6 +295,28 @@ def _define_functional_ops() -> None:
         return o
 
     transpose_mxfp8.register_fake(lambda x_fp4, scales: _tr(x_fp4, scales))
+
+
+def _alloc_topk(logits: torch.Tensor, topk: int):
+    return logits.new_empty((logits.size(0), topk), dtype=torch.float32), logits.new_empty((logits.size(0), topk), dtype=torch.int32)
+
+
+def _alloc_sort(topk_ids: torch.Tensor, num_experts: int):
+    """src_row, offs, pos; the kernels write every element, except that an empty sort launches nothing: offs is allocated as zeros always (one tiny fill), so no
+    branch on the number of slots is traced"""
+    return (topk_ids.new_empty((topk_ids.numel(),), dtype=torch.int32), topk_ids.new_zeros((num_experts,), dtype=torch.int32),
+            topk_ids.new_empty(tuple(topk_ids.shape), dtype=torch.int32))
+
+
+def run_moe_sort(topk_ids: torch.Tensor, expert_map: torch.Tensor | None, num_experts: int):
+    """Allocate the three results and the scratch of the three-launch form (none up to the one-launch bound), then the in-place op."""
+    if expert_map is not None and expert_map.numel() == 0:
+        raise ValueError("expert_map must have at least one entry")
+    out = _alloc_sort(topk_ids, num_experts)
+    ws = topk_ids.new_empty((_lib.load().qutlass_amd_moe_sort_workspace_bytes(topk_ids.numel(), num_experts) // 4,), dtype=torch.int32)
+    no_map = topk_ids.new_empty((0,), dtype=torch.int32)   # the in-place op's "no map"
+    torch.ops.qutlass_amd.moeSort_(topk_ids, no_map if expert_map is None else expert_map, num_experts, out[0], out[1], out[2], ws)
+    return out
 
 
 def to_blocked(input_matrix: torch.Tensor) -> torch.Tensor:
