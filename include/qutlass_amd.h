@@ -333,6 +333,33 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
  */
 int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids,
                                  void* stream);
+
+/*
+ * EXTENSION: the grouped router of DeepSeek-V2 / V3 and Kimi-K2 -- scores, a selection bias, a top-k over the experts of the best groups -- in one launch, on
+ * moe_topk_softmax's skeleton.  logits (t, e), contiguous, bf16 (elem_bytes 2) or float32 (4) -> weights (t, topk) float32, ids (t, topk) int32 and, with scores
+ * != NULL, scores (t, e) float32.  All arithmetic is fp32.  x is a row, G = n_group, S = e / G.
+ *   scores     scoring QAMD_MOE_SCORING_SIGMOID: s_j = 1 / (1 + exp(-x_j)) (-inf gives 0, +inf gives 1); QAMD_MOE_SCORING_SOFTMAX: moe_topk_softmax's p_j
+ *              (m = max, e_j = exp(x_j - m), p_j = e_j / sum e).  The order of the sum is not part of the contract.
+ *   choice     c_j = s_j + bias_j (one fp32 add, round to nearest) with a bias -- (e) float32, every entry finite or -inf --, c_j = s_j with bias == NULL.
+ *              c alone decides what is selected; the bias never reaches a weight.
+ *   groups     (G > 1) group g is the experts [g * S, (g + 1) * S).  Its score is the sum of its two largest c (one fp32 add; a group of one expert scores that
+ *              value) with a bias, its largest c without.  The first topk_group groups in the order (score descending, group index ascending) survive; the
+ *              experts of the others are NOT candidates, whatever the sign of c (a -inf mask, not a zero fill).
+ *   selection  the first topk candidates in the order (c descending, expert index ascending), ids[t] in that order; c compares as a floating-point number
+ *              (-0 and +0 tie).  Made on c, NOT on the logits: with a bias the two orders differ, and that is the point.
+ *   weights    w_k = s_{id_k}; renormalize != 0: w_k = w_k / sum over the selected w (the order of the sum is free; a row whose selected scores sum to 0 gets
+ *              unspecified weights); last w_k = w_k * routed_scaling_factor (one fp32 multiply).
+ *   scores     the s_j the kernel selected on, bit for bit; asking for them changes no bit of ids or weights.
+ * A row holding a NaN, or a +inf + -inf in the choice or the group score, gets unspecified weights; its ids are still distinct and in [0, e), and no other row is
+ * affected.  1 <= e <= 1024, 1 <= n_group <= 64, e % n_group == 0, 1 <= topk_group <= n_group, 1 <= topk <= min(32, topk_group * S), t < 2^31; pointers aligned
+ * to their element size (16-byte loads and stores where every row starts on a 16-byte boundary; same bits either way).  One launch, one wave per token, no
+ * workspace, no host sync.  Every argument check happens before any HIP call.  t == 0 returns QAMD_OK without a launch.
+ */
+#define QAMD_MOE_SCORING_SIGMOID 0
+#define QAMD_MOE_SCORING_SOFTMAX 1
+int qutlass_amd_moe_topk_grouped(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
+                                 const float* bias /* nullable */, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids,
+                                 float* scores /* nullable */, void* stream);
 int64_t qutlass_amd_moe_sort_workspace_bytes(int64_t n, int64_t num_experts);
 int qutlass_amd_moe_sort(const void* topk_ids, int id_bytes, int64_t t, int64_t topk, int64_t num_experts, const int32_t* expert_map, int64_t g_entries,
                          int32_t* src_row, int32_t* offs, int32_t* pos, void* workspace, int64_t workspace_bytes, void* stream);

@@ -12,6 +12,7 @@ meaning, defaults and Python-level error behaviour):
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
     moe_topk_softmax, moe_sort_fused, moe_route           (extension: MoE routing in HIP -- router logits to ids, weights and the sorted-row metadata)
+    moe_topk_grouped, moe_route_grouped                   (extension: the grouped router of DeepSeek-V2 / V3 and Kimi-K2 -- sigmoid / softmax scores, selection bias, group-limited top-k)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -360,6 +361,66 @@ def moe_route(logits: torch.Tensor, topk: int, num_experts: int | None = None, *
     """EXTENSION: the whole routing of a mixture-of-experts layer from the router's logits: ``moe_topk_softmax`` then ``moe_sort_fused`` -- two launches for decode-sized
     inputs.  Returns (weights, ids, src_row, offs, pos).  num_experts defaults to E, the logits' second dimension; with expert_map pass the number of LOCAL experts."""
     weights, ids = moe_topk_softmax(logits, topk, renormalize=renormalize)
+    return (weights, ids) + tuple(moe_sort_fused(ids, logits.size(1) if num_experts is None else num_experts, expert_map=expert_map))
+
+
+def _check_grouped(logits, topk, n_group, topk_group, bias, scoring):
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be (T, E) (got {tuple(logits.shape)})")
+    E = logits.size(1)
+    if scoring not in _lib.MOE_SCORING:
+        raise ValueError(f"scoring must be 'sigmoid' or 'softmax' (got {scoring!r})")
+    if not 1 <= E <= 1024:
+        raise ValueError(f"the number of experts must be in [1, 1024] (got {E})")
+    if not 1 <= n_group <= 64:
+        raise ValueError(f"n_group must be in [1, 64] (got {n_group})")
+    if E % n_group != 0:
+        raise ValueError(f"n_group must divide E (got n_group = {n_group} for E = {E})")
+    if not 1 <= topk_group <= n_group:
+        raise ValueError(f"topk_group must be in [1, n_group] (got {topk_group} for n_group = {n_group})")
+    if not 1 <= topk <= min(32, topk_group * (E // n_group)):
+        raise ValueError(f"topk must be in [1, min(32, topk_group * E / n_group)] (got topk = {topk} for E = {E}, n_group = {n_group}, topk_group = {topk_group})")
+    if bias is not None and (bias.dim() != 1 or bias.size(0) != E or bias.dtype != torch.float32):
+        raise ValueError(f"bias must be a float32 tensor of (E,) = ({E},) (got {bias.dtype} {tuple(bias.shape)})")
+
+
+def moe_topk_grouped(logits: torch.Tensor, topk: int, *, n_group: int = 1, topk_group: int = 1, bias: torch.Tensor | None = None, scoring: str = "sigmoid",
+                     renormalize: bool = True, routed_scaling_factor: float = 1.0, return_scores: bool = False):
+    """EXTENSION (no reference counterpart): the grouped router of DeepSeek-V3 / R1 (E 256, sigmoid, bias, top-8 of the top-4 of 8 groups, x 2.5), Kimi-K2 (E 384,
+    one group, x 2.827) and DeepSeek-V2 (softmax, 8 groups of 20, no bias) in ONE HIP launch: (T, E) logits -> (weights (T, topk) float32, ids (T, topk) int32),
+    and with return_scores a third result, scores (T, E) float32.  All arithmetic is fp32; G = n_group, S = E / G.
+
+      scores     "sigmoid": s_j = 1 / (1 + exp(-x_j)) (-inf gives 0, +inf gives 1); "softmax": moe_topk_softmax's p_j.  The order of the sum is free.
+      choice     c_j = s_j + bias_j (one fp32 add) with a bias -- (E,) float32, every entry finite or -inf --, else c_j = s_j.  c alone decides what is selected;
+                 the bias never reaches a weight.
+      groups     (G > 1) group g = experts [g S, (g + 1) S); its score is the sum of its two largest c with a bias (one fp32 add; one expert: that value), its
+                 largest c without.  The first topk_group groups in (score descending, group index ascending) survive; experts of the other groups are not
+                 candidates, whatever the sign of c (vLLM's -inf mask, not the zero fill of the Hugging Face model code).
+      selection  the first topk candidates in (c descending, expert index ascending), ids[t] in that order; -0 ties with +0.
+      weights    w_k = s_{id_k}, the UNBIASED score; renormalize: divided by their sum (a sum of 0 gives unspecified weights); last multiplied by
+                 routed_scaling_factor (one fp32 multiply).
+      scores     the s_j the kernel selected on, bit for bit (balance losses and the bias update of auxiliary-loss-free balancing need them; every choice can be
+                 repeated exactly from them).  Asking for them changes no bit of ids or weights.
+
+    Selection runs on c, NOT on the logits: this differs on purpose from moe_topk_softmax, where there is no bias and selecting on the logits is exact -- here a
+    bias reorders the experts, and two logits that round to one score tie (the lower index wins).  A row holding a NaN (or a +inf + -inf in c or a group score) gets
+    unspecified weights; its ids are still distinct and inside [0, E), and no other row is affected.
+
+    logits bf16 or float32, contiguous; 1 <= E <= 1024, 1 <= n_group <= 64, E % n_group == 0, 1 <= topk_group <= n_group, 1 <= topk <= min(32, topk_group * S);
+    T == 0 returns empty tensors.  No host sync, no workspace: graph-capturable; traces under torch.compile."""
+    _check_grouped(logits, topk, n_group, topk_group, bias, scoring)
+    run = _ops_amd.moe_topk_grouped if torch.compiler.is_compiling() else ops.run_moe_topk_grouped
+    weights, ids, scores = run(logits, bias, topk, n_group, topk_group, _lib.MOE_SCORING[scoring], renormalize, float(routed_scaling_factor), return_scores)
+    return (weights, ids, scores) if return_scores else (weights, ids)
+
+
+def moe_route_grouped(logits: torch.Tensor, topk: int, num_experts: int | None = None, *, n_group: int = 1, topk_group: int = 1, bias: torch.Tensor | None = None,
+                      scoring: str = "sigmoid", renormalize: bool = True, routed_scaling_factor: float = 1.0,
+                      expert_map: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``moe_route`` with the grouped router in front: ``moe_topk_grouped`` then ``moe_sort_fused`` -- two launches for decode-sized inputs.  Returns
+    (weights, ids, src_row, offs, pos), what moe_route returns.  num_experts defaults to E; with expert_map pass the number of LOCAL experts."""
+    weights, ids = moe_topk_grouped(logits, topk, n_group=n_group, topk_group=topk_group, bias=bias, scoring=scoring, renormalize=renormalize,
+                                    routed_scaling_factor=routed_scaling_factor)
     return (weights, ids) + tuple(moe_sort_fused(ids, logits.size(1) if num_experts is None else num_experts, expert_map=expert_map))
 
 

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libqutlass_amd.so")
 
 QAMD_OK, QAMD_ERR_INVALID, QAMD_ERR_HIP = 0, 1, 2
 METHOD_QUEST, METHOD_ABSMAX = 0, 1
+MOE_SCORING = {"sigmoid": 0, "softmax": 1}   # QAMD_MOE_SCORING_*
 
 _vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 _GEMM_ARGS = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]
@@ -46,6 +47,7 @@ SYMBOLS = {
     "qutlass_amd_fused_gather_quantize_nv": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "qutlass_amd_moe_combine_bf16": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "qutlass_amd_moe_topk_softmax": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "qutlass_amd_moe_topk_grouped": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "qutlass_amd_moe_sort_workspace_bytes": (_i64, [_i64, _i64]),
     "qutlass_amd_moe_sort": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),

@@ -2016,6 +2016,54 @@ int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, 
   return check_launch("moe_topk_softmax_kernel");
 }
 
+// Grouped top-k (DeepSeek-V2 / V3, Kimi-K2 routers): scores, a selection bias, a top-k inside the best groups; the same launch shape as moe_topk_softmax.
+extern "C++" {
+template <typename T, bool LOADV>
+static void launch_topk_grouped(const MoeGroupedParams& p, int grid, hipStream_t s) {
+  const int per_lane = (p.e + 63) / 64;
+#define QAMD_TOPKG_ARM(R_) hipLaunchKernelGGL((moe_topk_grouped_kernel<T, R_, LOADV>), dim3(grid), dim3(256), 0, s, p)
+  if constexpr (sizeof(T) == 4) { if (per_lane <= 4) { QAMD_TOPKG_ARM(4); return; } }
+  if (per_lane <= 8) { QAMD_TOPKG_ARM(8); return; }
+  QAMD_TOPKG_ARM(16);
+#undef QAMD_TOPKG_ARM
+}
+}   // extern "C++"
+
+int qutlass_amd_moe_topk_grouped(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
+                                 const float* bias, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids, float* scores, void* stream) {
+  const char* name = "moe_topk_grouped";
+  if (elem_bytes != 2 && elem_bytes != 4) return fail(QAMD_ERR_INVALID, "%s: logits must be bf16 (elem_bytes 2) or float32 (4), got elem_bytes %d", name, elem_bytes);
+  if (t < 0 || t >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld tokens)", name, (long long)t);
+  if (e < 1 || e > 1024) return fail(QAMD_ERR_INVALID, "%s: bad shape: the number of experts must be in [1, 1024] (got %lld)", name, (long long)e);
+  if (n_group < 1 || n_group > 64) return fail(QAMD_ERR_INVALID, "%s: bad shape: n_group must be in [1, 64] (got %lld)", name, (long long)n_group);
+  if (e % n_group != 0) return fail(QAMD_ERR_INVALID, "%s: bad shape: n_group must divide E (got n_group = %lld for E = %lld)", name, (long long)n_group, (long long)e);
+  if (topk_group < 1 || topk_group > n_group)
+    return fail(QAMD_ERR_INVALID, "%s: bad shape: topk_group must be in [1, n_group] (got %lld for n_group = %lld)", name, (long long)topk_group, (long long)n_group);
+  if (topk < 1 || topk > 32 || topk > topk_group * (e / n_group))
+    return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, min(32, topk_group * E / n_group)] (got %lld for E = %lld, n_group = %lld, topk_group = %lld)", name,
+                (long long)topk, (long long)e, (long long)n_group, (long long)topk_group);
+  if (scoring != QAMD_MOE_SCORING_SIGMOID && scoring != QAMD_MOE_SCORING_SOFTMAX)
+    return fail(QAMD_ERR_INVALID, "%s: scoring must be QAMD_MOE_SCORING_SIGMOID (0) or QAMD_MOE_SCORING_SOFTMAX (1), got %d", name, scoring);
+  if ((uintptr_t)logits % elem_bytes || ((uintptr_t)bias | (uintptr_t)weights | (uintptr_t)ids | (uintptr_t)scores) % 4)
+    return fail(QAMD_ERR_INVALID, "%s: logits, bias, weights, ids and scores must be aligned to their element size", name);
+  if (t == 0) return QAMD_OK;
+  if (!logits || !weights || !ids) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  MoeGroupedParams p;
+  p.logits = logits; p.bias = bias; p.weights = weights; p.ids = ids; p.scores = scores; p.t = t; p.e = (int)e; p.topk = (int)topk; p.renorm = renormalize ? 1 : 0;
+  p.sigmoid = scoring == QAMD_MOE_SCORING_SIGMOID; p.n_group = (int)n_group; p.topk_group = (int)topk_group; p.s = (int)(e / n_group);
+  p.lg_l = 0;
+  while ((n_group << (p.lg_l + 1)) <= 64) ++p.lg_l;   // L lanes per group in the group stage
+  p.magic = (uint32_t)(((1ll << 22) + p.s - 1) / p.s);
+  p.scale = routed_scaling_factor;
+  const int grid = (int)std::min<int64_t>(cdiv(t, 4), (int64_t)chip_cus() * 16);
+  // 16-byte loads and stores where every row of the logits (and of the scores, if asked for) starts on a 16-byte boundary: same layout, same bits, either way
+  const bool vec = (e * elem_bytes) % 16 == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)scores % 16 == 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (elem_bytes == 2) { if (vec) launch_topk_grouped<uint16_t, true>(p, grid, s); else launch_topk_grouped<uint16_t, false>(p, grid, s); }
+  else { if (vec) launch_topk_grouped<float, true>(p, grid, s); else launch_topk_grouped<float, false>(p, grid, s); }
+  return check_launch("moe_topk_grouped_kernel");
+}
+
 // Expert sort.  Up to MOE_SORT_ONE_LAUNCH_MAX slots: one workgroup, one launch.  Beyond: count, scan, scatter -- three launches over caller scratch, workgroups of
 // `spb` consecutive slots (at least 4096 = 8 chunks of 64 per wave, and never more than 256 workgroups: the scratch stays below 1.01 MiB however large n is).
 // The bound is measured (profiles/bench_moe_route_mi355x.txt): one workgroup costs 2.6 + 2.2 us per 1024 slots (E = 8; 2.7 + 3.2 at E = 128),

@@ -547,6 +547,31 @@ void moeTopkSoftmax_(const Tensor& logits, Tensor weights, Tensor ids, bool reno
                                         static_cast<float*>(weights.data_ptr()), static_cast<int32_t*>(ids.data_ptr()), current_stream(logits)));
 }
 
+// moeTopkGrouped_: the grouped router (qutlass_amd_moe_topk_grouped); topk is the outputs' second dimension; an EMPTY bias means "no bias", an EMPTY scores "not asked for"
+void moeTopkGrouped_(const Tensor& logits, const Tensor& bias, Tensor weights, Tensor ids, Tensor scores, int64_t n_group, int64_t topk_group, int64_t scoring,
+                     bool renormalize, double routed_scaling_factor) {
+  const char* op = "moeTopkGrouped_";
+  require_contiguous(op, {{logits, "logits"}, {bias, "bias"}, {weights, "weights"}, {ids, "ids"}, {scores, "scores"}});
+  require_gpu(op, {{logits, "logits"}, {bias, "bias"}, {weights, "weights"}, {ids, "ids"}, {scores, "scores"}});
+  require_same_gpu(op, {{logits, "logits"}, {bias, "bias"}, {weights, "weights"}, {ids, "ids"}, {scores, "scores"}});
+  const bool f32 = has_dtype(logits, ScalarType::Float);
+  STD_TORCH_CHECK(f32 || has_dtype(logits, ScalarType::BFloat16), "logits must be bf16 or float32");
+  STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
+  STD_TORCH_CHECK(has_dtype(ids, ScalarType::Int), "ids must be int32");
+  STD_TORCH_CHECK(logits.dim() == 2, "logits must be 2D (T, E)");
+  STD_TORCH_CHECK(weights.dim() == 2 && ids.dim() == 2 && weights.size(0) == logits.size(0) && ids.size(0) == logits.size(0) && weights.size(1) == ids.size(1),
+                  "weights and ids must both be (T, topk)");
+  const bool use_bias = bias.numel() > 0, want_scores = scores.numel() > 0;
+  STD_TORCH_CHECK(!use_bias || (has_dtype(bias, ScalarType::Float) && bias.dim() == 1 && bias.size(0) == logits.size(1)), "bias must be a float32 tensor of (E,)");
+  STD_TORCH_CHECK(!want_scores || (has_dtype(scores, ScalarType::Float) && scores.dim() == 2 && scores.size(0) == logits.size(0) && scores.size(1) == logits.size(1)),
+                  "scores must be a float32 tensor of (T, E)");
+  const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
+  check_rc(qutlass_amd_moe_topk_grouped(logits.data_ptr(), f32 ? 4 : 2, logits.size(0), logits.size(1), ids.size(1), n_group, topk_group, (int)scoring,
+                                        use_bias ? static_cast<const float*>(bias.data_ptr()) : nullptr, renormalize ? 1 : 0, (float)routed_scaling_factor,
+                                        static_cast<float*>(weights.data_ptr()), static_cast<int32_t*>(ids.data_ptr()),
+                                        want_scores ? static_cast<float*>(scores.data_ptr()) : nullptr, current_stream(logits)));
+}
+
 // moeSort_: the stable sort of the (T, topk) slots by expert (qutlass_amd_moe_sort); an EMPTY expert_map means "no map" (a map has at least one entry); workspace is
 // caller scratch of at least qutlass_amd_moe_sort_workspace_bytes bytes (it may be empty below the one-launch bound)
 void moeSort_(const Tensor& topk_ids, const Tensor& expert_map, int64_t num_experts, Tensor src_row, Tensor offs, Tensor pos, Tensor workspace) {
@@ -718,6 +743,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("fusedGatherQuantizeNv_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method) -> ()");
   m.def("moeCombine_(Tensor Y, Tensor pos, Tensor weights, Tensor(a!) OUT) -> ()");
   m.def("moeTopkSoftmax_(Tensor logits, Tensor(a!) weights, Tensor(b!) ids, bool renormalize) -> ()");
+  m.def("moeTopkGrouped_(Tensor logits, Tensor bias, Tensor(a!) weights, Tensor(b!) ids, Tensor(c!) scores, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor) -> ()");
   m.def("moeSort_(Tensor topk_ids, Tensor expert_map, int num_experts, Tensor(a!) src_row, Tensor(b!) offs, Tensor(c!) pos, Tensor(d!) workspace) -> ()");
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
@@ -764,6 +790,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("fusedGatherQuantizeNv_", TORCH_BOX(&fusedGatherQuantizeNv_));
   m.impl("moeCombine_", TORCH_BOX(&moeCombine_));
   m.impl("moeTopkSoftmax_", TORCH_BOX(&moeTopkSoftmax_));
+  m.impl("moeTopkGrouped_", TORCH_BOX(&moeTopkGrouped_));
   m.impl("moeSort_", TORCH_BOX(&moeSort_));
   m.impl("fusedQuantizeMatmulMxf4", TORCH_BOX(&fusedQuantizeMatmulMxf4));
   m.impl("grouped_matmul_mxf4", TORCH_BOX(&grouped_matmul_mxf4));

@@ -74,7 +74,7 @@ def _register_fakes() -> None:
 
     for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
                  "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
-                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "moeCombine_", "moeTopkSoftmax_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "moeCombine_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -225,6 +225,15 @@ def _define_functional_ops() -> None:
 
     moe_topk_softmax.register_fake(lambda logits, topk, renormalize: _alloc_topk(logits, topk))
 
+    # the grouped router: the third result is the (T, E) scores, or an empty tensor when they are not asked for
+    @custom_op("qutlass_amd::moe_topk_grouped", mutates_args=(),
+               schema="(Tensor logits, Tensor? bias, int topk, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor, bool return_scores) -> (Tensor, Tensor, Tensor)")
+    def moe_topk_grouped(logits, bias, topk, n_group, topk_group, scoring, renormalize, routed_scaling_factor, return_scores):
+        return run_moe_topk_grouped(logits, bias, topk, n_group, topk_group, scoring, renormalize, routed_scaling_factor, return_scores)
+
+    moe_topk_grouped.register_fake(lambda logits, bias, topk, n_group, topk_group, scoring, renormalize, routed_scaling_factor, return_scores:
+                                   _alloc_topk(logits, topk) + (_alloc_scores(logits, return_scores),))
+
     @custom_op("qutlass_amd::moe_sort_fused", mutates_args=(), schema="(Tensor topk_ids, Tensor? expert_map, int num_experts) -> (Tensor, Tensor, Tensor)")
     def moe_sort_fused(topk_ids, expert_map, num_experts):
         return run_moe_sort(topk_ids, expert_map, num_experts)
@@ -299,6 +308,23 @@ def _define_functional_ops() -> None:
 
 def _alloc_topk(logits: torch.Tensor, topk: int):
     return logits.new_empty((logits.size(0), topk), dtype=torch.float32), logits.new_empty((logits.size(0), topk), dtype=torch.int32)
+
+
+def _alloc_scores(logits: torch.Tensor, wanted: bool):
+    return logits.new_empty(tuple(logits.shape) if wanted else (0,), dtype=torch.float32)
+
+
+def run_moe_topk_grouped(logits: torch.Tensor, bias: torch.Tensor | None, topk: int, n_group: int, topk_group: int, scoring: int, renormalize: bool,
+                         routed_scaling_factor: float, return_scores: bool):
+    """Allocate weights, ids and scores (empty when not asked for), then the in-place op; an empty bias is its "no bias"."""
+    if bias is not None and bias.numel() == 0:
+        raise ValueError("bias must have E entries")
+    weights, ids = _alloc_topk(logits, topk)
+    scores = _alloc_scores(logits, return_scores)
+    no_bias = logits.new_empty((0,), dtype=torch.float32)
+    torch.ops.qutlass_amd.moeTopkGrouped_(logits, no_bias if bias is None else bias, weights, ids, scores, n_group, topk_group, scoring, renormalize,
+                                          routed_scaling_factor)
+    return weights, ids, scores
 
 
 def _alloc_sort(topk_ids: torch.Tensor, num_experts: int):
