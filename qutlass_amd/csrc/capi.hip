@@ -394,18 +394,18 @@ inline int grouped_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
   (void)N; (void)cus;
   return (M <= 32 * E && K <= 1024) ? 590 : 593;
 }
-// workgroups of a form: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles
-inline int64_t grouped_grid(int v, int64_t M, int64_t N, int64_t E) {
-  const int TM = v == 590 || v == 591 ? 32 : 64, TN = v == 591 ? 16 : v == 593 ? 64 : 32;
-  return (cdiv(M, TM) + E) * cdiv(N, TN);
+// workgroups of form v of format F (gemm_mx_grouped.hip.h: the tile table and the grid formula)
+inline int64_t grouped_grid(const GroupedFormat& F, int v, int64_t M, int64_t N, int64_t E) {
+  return grouped_workgroups(M, N, E, F.tile[v - F.form0].tm, F.tile[v - F.form0].tn);
 }
-// (EBITS 8: grouped_matmul_mxf8_bf16_tn, AFMT 1: e5m2 A)
-template <int TM, int TN, int EBITS = 4, int AFMT = 0>
+// form F.form0 + I (a wave-owned form) of an MX format; AFMT 1: e5m2 A (grouped_matmul_mxf8_bf16_tn)
+template <const GroupedFormat& F, int I, int AFMT = 0>
 int launch_grouped_os(GroupedParams q, hipStream_t s) {
+  constexpr int TM = F.tile[I].tm, TN = F.tile[I].tn, EBITS = F.ebits;
   q.tiles_m = 1;
   q.tiles_n = (int)cdiv(q.N, TN);
   const int64_t KT = cdiv((int64_t)q.K * EBITS / 8, 128);
-  const dim3 grid((int)((cdiv(q.M, TM) + q.E) * q.tiles_n)), block(256);   // the bound of the real tiles (grouped_tile: the rest return at once)
+  const dim3 grid((int)grouped_workgroups(q.M, q.N, q.E, TM, TN)), block(256);
   constexpr int SMAX = TM == 32 ? 4 : 3;   // slots per wave that fit the LDS (launch_gemm_os)
   if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<1, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
   else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<2, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
@@ -414,12 +414,22 @@ int launch_grouped_os(GroupedParams q, hipStream_t s) {
   else hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, true, true, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
   return check_launch("gemm_mx_os_kernel (grouped)");
 }
-template <class C>
+// form F.form0 + 3 (the ring form) of an MX format
+template <const GroupedFormat& F, class C>
 int launch_grouped_ring(GroupedParams q, hipStream_t s) {
+  static_assert(C::BM == F.tile[3].tm && C::BN == F.tile[3].tn && C::EBITS == F.ebits, "the ring configuration is the format's fourth form");
   q.tiles_m = 1;
   q.tiles_n = (int)cdiv(q.N, C::BN);
-  hipLaunchKernelGGL((gemm_mx_grouped_ring_kernel<C>), dim3((int)((cdiv(q.M, C::BM) + q.E) * q.tiles_n)), dim3(C::THREADS), 0, s, q);
+  hipLaunchKernelGGL((gemm_mx_grouped_ring_kernel<C>), dim3((int)grouped_workgroups(q.M, q.N, q.E, C::BM, C::BN)), dim3(C::THREADS), 0, s, q);
   return check_launch("gemm_mx_grouped_ring_kernel");
+}
+// form v of an MX format: C = its ring configuration
+template <const GroupedFormat& F, class C, int AFMT = 0>
+int launch_grouped_mx(int v, const GroupedParams& q, hipStream_t s) {
+  if (v == F.form0) return launch_grouped_os<F, 0, AFMT>(q, s);
+  if (v == F.form0 + 1) return launch_grouped_os<F, 1, AFMT>(q, s);
+  if (v == F.form0 + 2) return launch_grouped_os<F, 2, AFMT>(q, s);
+  return launch_grouped_ring<F, C>(q, s);
 }
 
 // ---- grouped MXFP8 GEMM: the same two tile bodies on 8-bit elements (a stage is 128 elements, so a row has twice the stages of an MXFP4 row of the same K) ----------
@@ -434,16 +444,42 @@ inline int grouped8_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
   (void)N; (void)cus;
   return (M <= 32 * E && K >= 8192) ? 594 : 597;
 }
-inline int64_t grouped8_grid(int v, int64_t M, int64_t N, int64_t E) {
-  const int TM = v == 594 || v == 595 ? 32 : 64, TN = v == 595 ? 16 : v == 597 ? 64 : 32;
-  return (cdiv(M, TM) + E) * cdiv(N, TN);
+
+// ---- what the three grouped entries share: the argument checks, the choice of a form and the parameter fill ----------------------------------------------------------
+// the grouped ops' argument checks, F the format (gemm_mx_grouped.hip.h): every argument is checked before any HIP call; the grid bound covers every form
+inline int grouped_check(const GroupedFormat& F, const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                         const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E) {
+  if (!A || !B || !A_sf || !B_sf || !alpha || !offs || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (E < 1 || E > GRP_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, GRP_MAX_E, (long long)E);
+  if (n_alpha != 1 && n_alpha != E) return fail(QAMD_ERR_INVALID, "%s: alpha must have 1 or E = %lld elements (got %lld)", name, (long long)E, (long long)n_alpha);
+  if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
+  if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
+  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
+  const char* rowb = F.ebits == 8 ? "K" : "K/2";
+  const int64_t rows_2g = ((1ll << 31) - 1) / F.row_bytes(K) + 1;   // rows of a row's bytes that reach 2 GiB (no product that can overflow)
+  if (N >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * %s bytes, N=%lld K=%lld) must stay below 2 GiB", name, rowb, (long long)N, (long long)K);
+  if (M >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * %s bytes, M=%lld K=%lld) must stay below 2 GiB", name, rowb, (long long)M, (long long)K);
+  if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
+  for (int v = F.form0; F.has(v); ++v)
+    if (grouped_grid(F, v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
+  return QAMD_OK;
 }
-template <int AFMT>
-int launch_grouped8(int v, const GroupedParams& q, hipStream_t s) {
-  if (v == 594) return launch_grouped_os<32, 32, 8, AFMT>(q, s);
-  if (v == 595) return launch_grouped_os<32, 16, 8, AFMT>(q, s);
-  if (v == 596) return launch_grouped_os<64, 32, 8, AFMT>(q, s);
-  return launch_grouped_ring<GroupedRing8Cfg<AFMT>>(q, s);
+// the form of a launch: the lab's gemm_variant option forces one of the format's four, otherwise the op's plan rule on this chip
+using GroupedPlan = int (*)(int64_t M, int64_t N, int64_t K, int64_t E, int cus);
+inline int grouped_form(const GroupedFormat& F, GroupedPlan plan, int64_t M, int64_t N, int64_t K, int64_t E) {
+  const int forced = opt_gemm_variant();
+  return F.has(forced) ? forced : plan(M, N, K, E, chip_cus());
+}
+// the fields GroupedParams and NvGroupedParams share (different bases, the same names)
+template <class P>
+void grouped_fill(P& q, const GroupedFormat& F, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                  const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E) {
+  const int64_t rowbytes = F.row_bytes(K), KB = K / F.sgroup;
+  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
+  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
+  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * rowbytes);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
+  q.sfa_bytes = (uint32_t)(M * KB); q.sfb_bytes = (uint32_t)(N * KB);
+  q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha; q.splits = 1;
 }
 
 // [r4] stream-K form of the two persistent kernels (lab variant 89): one workgroup per CU; p.ws / p.ctr / p.tag / p.sk_tiles set by mx_launch
@@ -1470,83 +1506,32 @@ int qutlass_amd_matmul_ada_mxf4_bf16_tn(const void* A, const void* B, const void
   });
 }
 
-// grouped_matmul_mxf4_bf16_tn: every argument is checked before any HIP call
-static int grouped_check(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
-                         const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E) {
-  if (!A || !B || !A_sf || !B_sf || !alpha || !offs || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (E < 1 || E > GRP_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, GRP_MAX_E, (long long)E);
-  if (n_alpha != 1 && n_alpha != E) return fail(QAMD_ERR_INVALID, "%s: alpha must have 1 or E = %lld elements (got %lld)", name, (long long)E, (long long)n_alpha);
-  if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
-  if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
-  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  if (N * (K / 2) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * K/2 = %lld bytes) must stay below 2 GiB", name, (long long)(N * (K / 2)));
-  if (M * (K / 2) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * K/2 = %lld bytes) must stay below 2 GiB", name, (long long)(M * (K / 2)));
-  if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
-  for (int v = 590; v <= 593; ++v)
-    if (grouped_grid(v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
-  return QAMD_OK;
-}
-
 int qutlass_amd_grouped_matmul_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
                                             const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
-  const char* name = "grouped_matmul_mxf4_bf16_tn";
-  if (int rc = grouped_check(name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  constexpr const GroupedFormat& F = GRP_MXF4;
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
   if (M == 0) return QAMD_OK;
-  const int forced = opt_gemm_variant();   // lab: 590 ... 593 force a form
-  const int v = (forced >= 590 && forced <= 593) ? forced : grouped_plan(M, N, K, E, chip_cus());
-  const int64_t rowbytes = K / 2, KB = K / 32;
   GroupedParams q;
-  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
-  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
-  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * rowbytes);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
-  q.sfa_bytes = (uint32_t)(M * KB); q.sfb_bytes = (uint32_t)(N * KB);
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
   q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
-  q.ws = nullptr; q.splits = 1; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
-  q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha;
-  hipStream_t s = (hipStream_t)stream;
-  if (v == 590) return launch_grouped_os<32, 32>(q, s);
-  if (v == 591) return launch_grouped_os<32, 16>(q, s);
-  if (v == 592) return launch_grouped_os<64, 32>(q, s);
-  return launch_grouped_ring<GroupedRingCfg>(q, s);   // matmul_ada_mxf4_bf16_tn's ring tiles
-}
-
-// grouped_matmul_mxf8_bf16_tn: every argument is checked before any HIP call (grouped_check's checks with one byte per element, plus the A format)
-static int grouped8_check(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
-                          const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E, int a_format) {
-  if (!A || !B || !A_sf || !B_sf || !alpha || !offs || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (E < 1 || E > GRP_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, GRP_MAX_E, (long long)E);
-  if (n_alpha != 1 && n_alpha != E) return fail(QAMD_ERR_INVALID, "%s: alpha must have 1 or E = %lld elements (got %lld)", name, (long long)E, (long long)n_alpha);
-  if (a_format != QAMD_FP8_E4M3 && a_format != QAMD_FP8_E5M2) return fail(QAMD_ERR_INVALID, "%s: invalid a_format %d", name, a_format);
-  if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
-  if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
-  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  const int64_t rows_2g = ((1ll << 31) + K - 1) / K;   // rows of K bytes that reach 2 GiB (no product that can overflow)
-  if (N >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * K bytes, N=%lld K=%lld) must stay below 2 GiB", name, (long long)N, (long long)K);
-  if (M >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * K bytes, M=%lld K=%lld) must stay below 2 GiB", name, (long long)M, (long long)K);
-  if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
-  for (int v = 594; v <= 597; ++v)
-    if (grouped8_grid(v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
-  return QAMD_OK;
+  q.ws = nullptr; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  const int v = grouped_form(F, grouped_plan, M, N, K, E);
+  return launch_grouped_mx<GRP_MXF4, GroupedRingCfg>(v, q, (hipStream_t)stream);   // (the ring form: matmul_ada_mxf4_bf16_tn's ring tiles)
 }
 
 int qutlass_amd_grouped_matmul_mxf8_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
                                             const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, int a_format, void* stream) {
-  const char* name = "grouped_matmul_mxf8_bf16_tn";
-  if (int rc = grouped8_check(name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E, a_format)) return rc;
+  constexpr const GroupedFormat& F = GRP_MXF8;
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if (a_format != QAMD_FP8_E4M3 && a_format != QAMD_FP8_E5M2) return fail(QAMD_ERR_INVALID, "%s: invalid a_format %d", F.name, a_format);
   if (M == 0) return QAMD_OK;
-  const int forced = opt_gemm_variant();   // lab: 594 ... 597 force a form
-  const int v = (forced >= 594 && forced <= 597) ? forced : grouped8_plan(M, N, K, E, chip_cus());
-  const int64_t KB = K / 32;
   GroupedParams q;
-  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
-  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
-  q.a_bytes = (uint32_t)(M * K); q.b_bytes = (uint32_t)(N * K);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
-  q.sfa_bytes = (uint32_t)(M * KB); q.sfb_bytes = (uint32_t)(N * KB);
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
   q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
-  q.ws = nullptr; q.splits = 1; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
-  q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha;
+  q.ws = nullptr; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  const int v = grouped_form(F, grouped8_plan, M, N, K, E);
   hipStream_t s = (hipStream_t)stream;
-  return a_format == QAMD_FP8_E5M2 ? launch_grouped8<1>(v, q, s) : launch_grouped8<0>(v, q, s);
+  return a_format == QAMD_FP8_E5M2 ? launch_grouped_mx<GRP_MXF8, GroupedRing8Cfg<1>, 1>(v, q, s) : launch_grouped_mx<GRP_MXF8, GroupedRing8Cfg<0>, 0>(v, q, s);
 }
 
 // ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
@@ -1564,46 +1549,17 @@ inline int grouped_nv_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) 
   if (M <= 16 * E && K >= 8192) return 598;
   return M <= 48 * E ? 600 : 601;
 }
-inline int64_t grouped_nv_grid(int v, int64_t M, int64_t N, int64_t E) {
-  const int TM = v == 598 ? 32 : v == 601 ? 128 : 64, TN = v == 600 ? 64 : v == 601 ? 128 : 32;
-  return (cdiv(M, TM) + E) * cdiv(N, TN);
-}
-
-// grouped_matmul_nvf4_bf16_tn: every argument is checked before any HIP call (grouped_check's checks; the grid bound covers every form)
-static int grouped_nv_check(const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
-                            const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E) {
-  if (!A || !B || !A_sf || !B_sf || !alpha || !offs || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (E < 1 || E > GRP_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, GRP_MAX_E, (long long)E);
-  if (n_alpha != 1 && n_alpha != E) return fail(QAMD_ERR_INVALID, "%s: alpha must have 1 or E = %lld elements (got %lld)", name, (long long)E, (long long)n_alpha);
-  if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
-  if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
-  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  const int64_t rows_2g = ((1ll << 31) + K / 2 - 1) / (K / 2);   // rows of K/2 bytes that reach 2 GiB (no product that can overflow)
-  if (N >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * K/2 bytes, N=%lld K=%lld) must stay below 2 GiB", name, (long long)N, (long long)K);
-  if (M >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * K/2 bytes, M=%lld K=%lld) must stay below 2 GiB", name, (long long)M, (long long)K);
-  if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
-  for (int v = 598; v <= 601; ++v)
-    if (grouped_nv_grid(v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
-  return QAMD_OK;
-}
 
 int qutlass_amd_grouped_matmul_nvf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
                                             const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
-  const char* name = "grouped_matmul_nvf4_bf16_tn";
-  if (int rc = grouped_nv_check(name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  constexpr const GroupedFormat& F = GRP_NVF4;
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
   if (M == 0) return QAMD_OK;
-  const int forced = opt_gemm_variant();   // lab: 598 ... 601 force a form
-  const int v = (forced >= 598 && forced <= 601) ? forced : grouped_nv_plan(M, N, K, E, chip_cus());
-  const int64_t rowbytes = K / 2, G16 = K / 16;
+  const int v = grouped_form(F, grouped_nv_plan, M, N, K, E);
   qamd::NvGroupedParams q{};
-  q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
-  q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
-  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * rowbytes);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
-  q.sfa_bytes = (uint32_t)(M * G16); q.sfb_bytes = (uint32_t)(N * G16);
-  q.splits = 1;
-  q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha;
-  if (launch_nvf4_grouped_host(q, (hipStream_t)stream, v)) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", name, v);
-  return check_launch("grouped_matmul_nvf4_bf16_tn");
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
+  if (launch_nvf4_grouped_host(q, (hipStream_t)stream, v)) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+  return check_launch(F.name);
 }
 
 int qutlass_amd_matmul_mxf8_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
@@ -2472,35 +2428,26 @@ int qutlass_amd_debug_grouped_decode(const int32_t* offs, int E, int M, int TM, 
   return n;
 }
 
-// debug only: the form grouped_matmul_mxf4_bf16_tn picks (590 = 32x32, 592 = 64x32 tiles of the wave-owned kernel, 593 = the 64x64 ring kernel) on a 256-CU part,
-// after the entry's own argument checks (-1: rejected); out[0] (optional) = the workgroups it launches.  No GPU touched.
+// debug only (not declared in the public header): the form a grouped op's rule picks on a 256-CU part, after the entry's own argument checks (-1: rejected);
+// out[0] (optional) = the workgroups it launches.  No GPU touched.
+static int debug_grouped_plan(const GroupedFormat& F, const char* name, GroupedPlan plan, int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  alignas(16) static char dummy[16];
+  if (grouped_check(F, name, dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E)) return -1;
+  const int v = plan(M, N, K, E, 256);
+  if (out) out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N, E);
+  return v;
+}
+// grouped_matmul_mxf4_bf16_tn: 590 = 32x32, 592 = 64x32 tiles of the wave-owned kernel, 593 = the 64x64 ring kernel
 int qutlass_amd_debug_grouped_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
-  alignas(16) static char dummy[16];
-  if (grouped_check("debug_grouped_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E)) return -1;
-  const int v = grouped_plan(M, N, K, E, 256);
-  if (out) out[0] = M == 0 ? 0 : grouped_grid(v, M, N, E);
-  return v;
+  return debug_grouped_plan(GRP_MXF4, "debug_grouped_plan", grouped_plan, M, N, K, E, out);
 }
-
-// debug only (not declared in the public header): the form grouped_matmul_mxf8_bf16_tn picks (594 = 32x32 tiles of the wave-owned kernel, 597 = the 64x64 ring
-// kernel) on a 256-CU part, after the entry's own argument checks (-1: rejected); out[0] (optional) = the workgroups it launches.  No GPU touched.
+// grouped_matmul_mxf8_bf16_tn: 594 = 32x32 tiles of the wave-owned kernel, 597 = the 64x64 ring kernel
 int qutlass_amd_debug_grouped_mxf8_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
-  alignas(16) static char dummy[16];
-  if (grouped8_check("debug_grouped_mxf8_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E, QAMD_FP8_E4M3)) return -1;
-  const int v = grouped8_plan(M, N, K, E, 256);
-  if (out) out[0] = M == 0 ? 0 : grouped8_grid(v, M, N, E);
-  return v;
+  return debug_grouped_plan(GRP_MXF8, "debug_grouped_mxf8_plan", grouped8_plan, M, N, K, E, out);
 }
-
-// debug only (not declared in the public header): the form grouped_matmul_nvf4_bf16_tn picks (598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 =
-// 64x64 / 128x128 tiles of the tile kernel) on a 256-CU part, after the entry's own argument checks (-1: rejected); out[0] (optional) = the workgroups it launches.
-// No GPU touched.
+// grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel
 int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
-  alignas(16) static char dummy[16];
-  if (grouped_nv_check("debug_grouped_nvf4_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E)) return -1;
-  const int v = grouped_nv_plan(M, N, K, E, 256);
-  if (out) out[0] = M == 0 ? 0 : grouped_nv_grid(v, M, N, E);
-  return v;
+  return debug_grouped_plan(GRP_NVF4, "debug_grouped_nvf4_plan", grouped_nv_plan, M, N, K, E, out);
 }
 
 // debug only (not declared in the public header): what matmul_nvf4_bf16_tn's rule picks for an M x N x K problem (gemm_nvf4.hip.h: nvf4_plan; 256 CUs assumed,

@@ -32,6 +32,26 @@ struct GroupTile {
   int g, row0, rows, nt;   // expert, first row, rows (1 ... TM), column tile
 };
 
+// ---- the grouped ops' formats (host): the ONE place where a form's tile is written -------------------------------------------------------------------------
+// An op has four forms, numbered form0 ... form0 + 3 (the lab's gemm_variant option forces one); form i runs TM x TN = tile[i] tiles.  The argument checks, the
+// debug plan entries and the launchers of both units (capi.hip, gemm_nvf4_os.hip.h) read a tile from here; a launcher whose kernel carries its tile as template
+// arguments takes them from the table or static_asserts against it.
+struct GroupedTileDim { int tm, tn; };
+struct GroupedFormat {
+  const char* name;   // the C entry without its prefix
+  int form0;          // first form number
+  int ebits;          // bits per element
+  int sgroup;         // elements per scale
+  GroupedTileDim tile[4];
+  constexpr bool has(int form) const { return form >= form0 && form < form0 + 4; }
+  constexpr int64_t row_bytes(int64_t K) const { return K / (8 / ebits); }
+};
+constexpr GroupedFormat GRP_MXF4{"grouped_matmul_mxf4_bf16_tn", 590, 4, 32, {{32, 32}, {32, 16}, {64, 32}, {64, 64}}};
+constexpr GroupedFormat GRP_MXF8{"grouped_matmul_mxf8_bf16_tn", 594, 8, 32, {{32, 32}, {32, 16}, {64, 32}, {64, 64}}};
+constexpr GroupedFormat GRP_NVF4{"grouped_matmul_nvf4_bf16_tn", 598, 4, 16, {{32, 32}, {64, 32}, {64, 64}, {128, 128}}};
+// workgroups of a grouped launch: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles (grouped_tile: the rest return at once)
+constexpr int64_t grouped_workgroups(int64_t M, int64_t N, int64_t E, int TM, int TN) { return ((M + TM - 1) / TM + E) * ((N + TN - 1) / TN); }
+
 // ---- the tile decode: ONE function for the device and the host (qutlass_amd_debug_grouped_decode runs it on the CPU) ---------------------------------------
 // Each group's end row is clamped to [0, M] and raised to the largest end before it, so a decreasing (malformed) offset is an empty group and every row range stays
 // inside [0, M) -- for well-formed offs this is exactly rows [offs[g - 1], offs[g]).  Lane l of a wave holds groups l c ... l c + c - 1, c = ceil(E / 64) <= 16, read in

@@ -505,13 +505,19 @@ hipError_t launch_nvf4_os(NvGemmParams p, hipStream_t s, int tn) {
 
 // grouped_matmul_nvf4_bf16_tn's forms (capi.hip grouped_nv_plan): 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles (one shot while the tile's K extent
 // fits the LDS, refilled slots beyond -- launch_nvf4_os's K rule), 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.  The grid is the
-// bound (cdiv(M, TM) + E) tiles_n of the real tiles (grouped_tile: the rest return at once).
+// bound grouped_workgroups of the real tiles; the tile of a form is the format table's (gemm_mx_grouped.hip.h: GRP_NVF4), which the kernels' configurations must match.
 hipError_t launch_nvf4_grouped(NvGroupedParams q, hipStream_t s, int form) {
-  const int TM = form == 598 ? 32 : form == 601 ? 128 : 64, TN = form == 600 ? 64 : form == 601 ? 128 : 32;
+  constexpr const GroupedFormat& F = GRP_NVF4;
+  static_assert(NvOsCfg<1, 32>::TM == F.tile[0].tm && NvOsCfg<2, 32>::TM == F.tile[0].tm && F.tile[0].tn == 32, "form 598");
+  static_assert(NvOsCfg<1, 32, 2>::TM == F.tile[1].tm && F.tile[1].tn == 32, "form 599");
+  static_assert(NvCfg<64, 64, 2, 2>::BM == F.tile[2].tm && NvCfg<64, 64, 2, 2>::BN == F.tile[2].tn, "form 600");
+  static_assert(NvCfg<128, 128, 2, 2>::BM == F.tile[3].tm && NvCfg<128, 128, 2, 2>::BN == F.tile[3].tn, "form 601");
+  if (!F.has(form)) return hipErrorInvalidValue;
+  const GroupedTileDim t = F.tile[form - F.form0];
   q.tiles_m = 1;
-  q.tiles_n = (q.N + TN - 1) / TN;
+  q.tiles_n = (q.N + t.tn - 1) / t.tn;
   const int KT = (q.K / 2 + 127) / 128;
-  const dim3 grid(((q.M + TM - 1) / TM + q.E) * q.tiles_n);
+  const dim3 grid((int)grouped_workgroups(q.M, q.N, q.E, t.tm, t.tn));
   if (form == 598) {
     if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32>, false, true>), grid, dim3(512), 0, s, q);
     else if (KT <= 16) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<2, 32>, false, true>), grid, dim3(512), 0, s, q);
@@ -522,11 +528,9 @@ hipError_t launch_nvf4_grouped(NvGroupedParams q, hipStream_t s, int form) {
   } else if (form == 600) {
     using C = NvCfg<64, 64, 2, 2>;
     hipLaunchKernelGGL((gemm_nvf4_kernel<C, false, false, true>), grid, dim3(C::THREADS), 0, s, q);
-  } else if (form == 601) {
+  } else {
     using C = NvCfg<128, 128, 2, 2>;
     hipLaunchKernelGGL((gemm_nvf4_kernel<C, false, false, true>), grid, dim3(C::THREADS), 0, s, q);
-  } else {
-    return hipErrorInvalidValue;
   }
   return hipSuccess;
 }

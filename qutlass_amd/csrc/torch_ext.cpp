@@ -173,90 +173,56 @@ Tensor matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor
   return out;
 }
 
-// EXTENSION: grouped MXFP4 GEMM for mixture-of-experts layers (qutlass_amd_grouped_matmul_mxf4_bf16_tn).  A (M, K/2) tokens sorted by expert, B (E, N, K/2) stacked
-// expert weights, row-major e8m0 scales, alpha of 1 or E elements, offs int32 (E,) cumulative end rows.  Rows at or past offs[E-1] are not written (left as allocated).
-Tensor grouped_matmul_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
-  const char* op = "grouped_matmul_mxf4";
+// EXTENSION: grouped GEMMs for mixture-of-experts layers (qutlass_amd_grouped_matmul_{mxf4,nvf4,mxf8}_bf16_tn).  A tokens sorted by expert, B (E, N, ...) stacked expert
+// weights, row-major scales, alpha of 1 or E elements, offs int32 (E,) cumulative end rows.  Rows at or past offs[E-1] are not written (left as allocated).
+//   MXF4: A (M, K/2), B (E, N, K/2), e8m0 scales per 32 elements
+//   NVF4: the same operands, e4m3 scales per 16 elements (fusedQuantizeNv's buffer as it is)
+//   MXF8: A (M, K) e4m3 / e5m2 (e5m2 selects the e5m2-A path, as matmul_mxf8_bf16_tn), B (E, N, K) e4m3, e8m0 scales per 32 elements
+enum class Grouped { MXF4, NVF4, MXF8 };
+
+template <Grouped G>
+Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
+  constexpr bool fp8 = G == Grouped::MXF8;
+  const char* op = G == Grouped::MXF4 ? "grouped_matmul_mxf4" : G == Grouped::NVF4 ? "grouped_matmul_nvf4" : "grouped_matmul_mxf8";
   require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
   require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
   require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  STD_TORCH_CHECK(has_dtype(A, ScalarType::Byte) || has_dtype(A, ScalarType::Float4_e2m1fn_x2), "A must be uint8 or float4_e2m1fn_x2");
-  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), "B must be uint8 or float4_e2m1fn_x2");
-  STD_TORCH_CHECK(has_dtype(A_sf, ScalarType::Float8_e8m0fnu), "A_sf must be float8_e8m0fnu");
-  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e8m0fnu), "B_sf must be float8_e8m0fnu");
-  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
+  const ScalarType data_t = fp8 ? ScalarType::Float8_e4m3fn : ScalarType::Byte;                  // either operand
+  const ScalarType a_alt = fp8 ? ScalarType::Float8_e5m2 : ScalarType::Float4_e2m1fn_x2;         // ... or, for A
+  const ScalarType b_alt = fp8 ? ScalarType::Float8_e4m3fn : ScalarType::Float4_e2m1fn_x2;       // ... for B (MXF8: e4m3 only)
+  const ScalarType sf_t = G == Grouped::NVF4 ? ScalarType::Float8_e4m3fn : ScalarType::Float8_e8m0fnu;
+  const char* sf_n = G == Grouped::NVF4 ? "float8_e4m3fn" : "float8_e8m0fnu";
+  STD_TORCH_CHECK(has_dtype(A, data_t) || has_dtype(A, a_alt), "A must be ", fp8 ? "float8_e4m3fn or float8_e5m2" : "uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(B, data_t) || has_dtype(B, b_alt), "B must be ", fp8 ? "float8_e4m3fn" : "uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(A_sf, sf_t), "A_sf must be ", sf_n);
+  STD_TORCH_CHECK(has_dtype(B_sf, sf_t), "B_sf must be ", sf_n);
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, fp8 ? "A must be 2D (M, K) and B 3D (E, N, K)" : "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
   STD_TORCH_CHECK(A.size(1) == B.size(2), "Inner dimensions must match for A @ B[g].T");
-  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * 2;
+  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * (fp8 ? 1 : 2), kb = K / (G == Grouped::NVF4 ? 16 : 32);
   STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
   STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
   STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
-  STD_TORCH_CHECK(A_sf.numel() >= M * (K / 32), "A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * (K / 32));
-  STD_TORCH_CHECK(B_sf.numel() >= E * N * (K / 32), "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * (K / 32));
+  STD_TORCH_CHECK(A_sf.numel() >= M * kb, "A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * kb);
+  STD_TORCH_CHECK(B_sf.numel() >= E * N * kb, "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * kb);
   Tensor out = torch::stable::new_empty(A, {M, N}, ScalarType::BFloat16);
   if (M == 0 || N == 0) return out;   // empty batch: nothing to launch
 
   const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_grouped_matmul_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()),
-                                                   alpha.numel(), static_cast<const int32_t*>(offs.data_ptr()), out.data_ptr(), M, N, K, E, current_stream(A)));
+  const float* al = static_cast<const float*>(alpha.data_ptr());
+  const int32_t* of = static_cast<const int32_t*>(offs.data_ptr());
+  void* s = current_stream(A);
+  int rc;
+  if (G == Grouped::MXF4) rc = qutlass_amd_grouped_matmul_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
+  else if (G == Grouped::NVF4) rc = qutlass_amd_grouped_matmul_nvf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
+  else rc = qutlass_amd_grouped_matmul_mxf8_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E,
+                                                    has_dtype(A, ScalarType::Float8_e5m2) ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3, s);
+  check_rc(rc);
   return out;
 }
 
-// EXTENSION: grouped NVFP4 GEMM for mixture-of-experts layers (qutlass_amd_grouped_matmul_nvf4_bf16_tn).  A (M, K/2) tokens sorted by expert, B (E, N, K/2) stacked
-// expert weights, row-major e4m3 scales per 16 elements (fusedQuantizeNv's buffer as it is); the rest as grouped_matmul_nvf4.
-Tensor grouped_matmul_nvf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
-  const char* op = "grouped_matmul_nvf4";
-  require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  STD_TORCH_CHECK(has_dtype(A, ScalarType::Byte) || has_dtype(A, ScalarType::Float4_e2m1fn_x2), "A must be uint8 or float4_e2m1fn_x2");
-  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), "B must be uint8 or float4_e2m1fn_x2");
-  STD_TORCH_CHECK(has_dtype(A_sf, ScalarType::Float8_e4m3fn), "A_sf must be float8_e4m3fn");
-  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e4m3fn), "B_sf must be float8_e4m3fn");
-  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
-  STD_TORCH_CHECK(A.size(1) == B.size(2), "Inner dimensions must match for A @ B[g].T");
-  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * 2;
-  STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
-  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
-  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
-  STD_TORCH_CHECK(A_sf.numel() >= M * (K / 16), "A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * (K / 16));
-  STD_TORCH_CHECK(B_sf.numel() >= E * N * (K / 16), "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * (K / 16));
-  Tensor out = torch::stable::new_empty(A, {M, N}, ScalarType::BFloat16);
-  if (M == 0 || N == 0) return out;   // empty batch: nothing to launch
-
-  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_grouped_matmul_nvf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()),
-                                                   alpha.numel(), static_cast<const int32_t*>(offs.data_ptr()), out.data_ptr(), M, N, K, E, current_stream(A)));
-  return out;
-}
-
-// EXTENSION: grouped MXFP8 GEMM for mixture-of-experts layers (qutlass_amd_grouped_matmul_mxf8_bf16_tn).  A (M, K) e4m3 / e5m2 tokens sorted by expert (e5m2 selects the
-// e5m2-A path, as matmul_mxf8_bf16_tn), B (E, N, K) e4m3 stacked expert weights; the rest as grouped_matmul_mxf4.
-Tensor grouped_matmul_mxf8(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
-  const char* op = "grouped_matmul_mxf8";
-  require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  STD_TORCH_CHECK(has_dtype(A, ScalarType::Float8_e4m3fn) || has_dtype(A, ScalarType::Float8_e5m2), "A must be float8_e4m3fn or float8_e5m2");
-  STD_TORCH_CHECK(has_dtype(B, ScalarType::Float8_e4m3fn), "B must be float8_e4m3fn");
-  STD_TORCH_CHECK(has_dtype(A_sf, ScalarType::Float8_e8m0fnu), "A_sf must be float8_e8m0fnu");
-  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e8m0fnu), "B_sf must be float8_e8m0fnu");
-  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, "A must be 2D (M, K) and B 3D (E, N, K)");
-  STD_TORCH_CHECK(A.size(1) == B.size(2), "Inner dimensions must match for A @ B[g].T");
-  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1);
-  STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
-  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
-  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
-  STD_TORCH_CHECK(A_sf.numel() >= M * (K / 32), "A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * (K / 32));
-  STD_TORCH_CHECK(B_sf.numel() >= E * N * (K / 32), "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * (K / 32));
-  Tensor out = torch::stable::new_empty(A, {M, N}, ScalarType::BFloat16);
-  if (M == 0 || N == 0) return out;   // empty batch: nothing to launch
-
-  const int a_format = has_dtype(A, ScalarType::Float8_e5m2) ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3;
-  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_grouped_matmul_mxf8_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()),
-                                                   alpha.numel(), static_cast<const int32_t*>(offs.data_ptr()), out.data_ptr(), M, N, K, E, a_format, current_stream(A)));
-  return out;
-}
+Tensor grouped_matmul_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF4>(A, B, A_sf, B_sf, alpha, offs); }
+Tensor grouped_matmul_nvf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::NVF4>(A, B, A_sf, B_sf, alpha, offs); }
+Tensor grouped_matmul_mxf8(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF8>(A, B, A_sf, B_sf, alpha, offs); }
 
 Tensor matmul_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_ada_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::ADA_MXF4>(A, B, A_sf, B_sf, alpha); }

@@ -87,17 +87,11 @@ def _register_fakes() -> None:
         k = X.size(-1)
         return X.new_empty((X.numel() // k if k else 0, B.size(0)), dtype=torch.bfloat16)
 
-    @rf("qutlass_amd::grouped_matmul_mxf4")
-    def _(A, B, A_sf, B_sf, alpha, offs):   # A (M, K/2), B (E, N, K/2)
+    def grouped_tn(A, B, A_sf, B_sf, alpha, offs):   # A (M, K/2 or K), B (E, N, K/2 or K)
         return A.new_empty((A.size(0), B.size(1)), dtype=torch.bfloat16)
 
-    @rf("qutlass_amd::grouped_matmul_mxf8")
-    def _(A, B, A_sf, B_sf, alpha, offs):   # A (M, K), B (E, N, K)
-        return A.new_empty((A.size(0), B.size(1)), dtype=torch.bfloat16)
-
-    @rf("qutlass_amd::grouped_matmul_nvf4")
-    def _(A, B, A_sf, B_sf, alpha, offs):   # A (M, K/2), B (E, N, K/2)
-        return A.new_empty((A.size(0), B.size(1)), dtype=torch.bfloat16)
+    for name in ("grouped_matmul_mxf4", "grouped_matmul_mxf8", "grouped_matmul_nvf4"):
+        rf(f"qutlass_amd::{name}")(grouped_tn)
 
 
 def _define_functional_ops() -> None:
