@@ -143,18 +143,18 @@ def matmul_mxf8_bf16_nn(a: torch.Tensor, b: torch.Tensor, block_scale_a: torch.T
     return qutlass_CUDA.matmul_mxf8_bf16_nn(a, b, block_scale_a, block_scale_b, alpha)
 
 
-def _alloc_mx(a: torch.Tensor, blocked: bool = False):
-    padded_rows, padded_cols = get_padded_shape_mx(a)
-    xh_e2m1 = torch.empty(*a.shape[:-1], a.size(-1) // 2, dtype=torch.uint8, device=a.device)
-    sf_shape = (padded_rows * padded_cols,) if blocked else (padded_rows, padded_cols)
-    return xh_e2m1, torch.empty(*sf_shape, dtype=torch.float8_e8m0fnu, device=a.device)
+def _method_code(method) -> int:
+    if method not in _METHOD_CODE:
+        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
+    return _METHOD_CODE[method]
 
 
-def _alloc_nv(a: torch.Tensor, blocked: bool = False):
-    padded_rows, padded_cols = get_padded_shape_nv(a)
-    xh_e2m1 = torch.empty(*a.shape[:-1], a.size(-1) // 2, dtype=torch.uint8, device=a.device)
-    sf_shape = (padded_rows * padded_cols,) if blocked else (padded_rows, padded_cols)
-    return xh_e2m1, torch.empty(*sf_shape, dtype=torch.float8_e4m3fn, device=a.device)
+def _quantize(op: str, *args):
+    """One op of the rotate + quantize family (a row of ops.QUANT_OPS), args as the functional op ``qutlass_amd::<op>`` takes them.  Eager: allocate, then the in-place
+    twin; under torch.compile: the functional op (see ops.py)."""
+    if torch.compiler.is_compiling():
+        return getattr(_ops_amd, op)(*args)
+    return ops.run_quant(ops.QUANT_OPS[op], *args)
 
 
 def fusedQuantizeMx(a: torch.Tensor, b: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest",
@@ -164,72 +164,36 @@ def fusedQuantizeMx(a: torch.Tensor, b: torch.Tensor, *, method: Literal["quest"
     (first numel/32 bytes) and its padding is left uninitialised.
     (The op calls go through `qutlass_amd::` twins of `_qutlass_C.fusedQuantizeMx*` -- same kernels, same checks: the reference's schemas hide the writes from
     torch.compile.  Eager: the in-place twin on tensors allocated here; under torch.compile: the functional form, see ops.py.)"""
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if return_mask and method != "quest":
+    code = _method_code(method)
+    if not return_mask:
+        return _quantize("quantize_mx", a, b, code)
+    if method != "quest":
         raise ValueError("return_mask is only supported for method 'quest'")
     if torch.compiler.is_compiling():
-        return _ops_amd.quantize_mx_mask(a, b) if return_mask else _ops_amd.quantize_mx(a, b, _METHOD_CODE[method])
-    xh_e2m1, xh_e8m0 = _alloc_mx(a)
-    if return_mask:
-        clip_mask = torch.empty(*a.shape[:-1], a.size(-1) // 8, dtype=torch.uint8, device=a.device)
-        _ops_amd.fusedQuantizeMxMask_(a, b, xh_e2m1, xh_e8m0, clip_mask)
-        return xh_e2m1, xh_e8m0, clip_mask
-    _ops_amd.fusedQuantizeMx_(a, b, xh_e2m1, xh_e8m0, _METHOD_CODE[method])
-    return xh_e2m1, xh_e8m0
+        return _ops_amd.quantize_mx_mask(a, b)
+    xh_e2m1, xh_e8m0 = ops.alloc_quant(ops.QUANT_OPS["quantize_mx"], a)
+    clip_mask = torch.empty(*a.shape[:-1], a.size(-1) // 8, dtype=torch.uint8, device=a.device)
+    _ops_amd.fusedQuantizeMxMask_(a, b, xh_e2m1, xh_e8m0, clip_mask)
+    return xh_e2m1, xh_e8m0, clip_mask
 
 
 def fusedQuantizeNv(a: torch.Tensor, b: torch.Tensor, global_scale: torch.Tensor, *,
                     method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
     """qutlass/__init__.py:183-203."""
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.quantize_nv(a, b, global_scale, _METHOD_CODE[method])
-    xh_e2m1, xh_e4m3 = _alloc_nv(a)
-    _ops_amd.fusedQuantizeNv_(a, b, xh_e2m1, xh_e4m3, global_scale, _METHOD_CODE[method])
-    return xh_e2m1, xh_e4m3
+    return _quantize("quantize_nv", a, b, global_scale, _method_code(method))
 
 
 def fusedQuantizeMxBlocked(a: torch.Tensor, b: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION (no reference counterpart): ``fusedQuantizeMx`` whose scales come out GEMM-ready -- the second tensor is
     byte for byte ``to_blocked(fusedQuantizeMx(a, b, method=method)[1])`` (flat, zero padded), written by the quantizer itself:
     one launch instead of two on the activation path (qutlass/__init__.py:149-180 + qutlass/utils.py:160-193)."""
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.quantize_mx_blocked(a, b, _METHOD_CODE[method])
-    xh_e2m1, xh_e8m0 = _alloc_mx(a, blocked=True)
-    _ops_amd.fusedQuantizeMxBlocked(a, b, xh_e2m1, xh_e8m0, _METHOD_CODE[method])
-    return xh_e2m1, xh_e8m0
+    return _quantize("quantize_mx_blocked", a, b, _method_code(method))
 
 
 def fusedQuantizeNvBlocked(a: torch.Tensor, b: torch.Tensor, global_scale: torch.Tensor, *,
                            method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION: ``fusedQuantizeNv`` with the e4m3 scales written directly in the ``to_blocked`` layout (see fusedQuantizeMxBlocked)."""
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.quantize_nv_blocked(a, b, global_scale, _METHOD_CODE[method])
-    xh_e2m1, xh_e4m3 = _alloc_nv(a, blocked=True)
-    _ops_amd.fusedQuantizeNvBlocked(a, b, xh_e2m1, xh_e4m3, global_scale, _METHOD_CODE[method])
-    return xh_e2m1, xh_e4m3
-
-
-def _act_meta(x: torch.Tensor) -> torch.Tensor:
-    """The (.., I) bf16 activation of a (.., 2 I) gate | up tensor, as a meta tensor: shapes for the allocators, no memory."""
-    if x.size(-1) % 2:
-        raise ValueError(f"the last dimension of x must be 2 * I (got {x.size(-1)})")
-    return torch.empty(*x.shape[:-1], x.size(-1) // 2, dtype=x.dtype, device="meta")
-
-
-def _alloc_gated(x: torch.Tensor, nv: bool, blocked: bool):
-    """The outputs the plain quantizers allocate for a (.., I) tensor (_alloc_mx / _alloc_nv), for x = (.., 2 I)."""
-    act = _act_meta(x)
-    padded_rows, padded_cols = get_padded_shape_nv(act) if nv else get_padded_shape_mx(act)
-    xh_e2m1 = torch.empty(*act.shape[:-1], act.size(-1) // 2, dtype=torch.uint8, device=x.device)
-    sf_shape = (padded_rows * padded_cols,) if blocked else (padded_rows, padded_cols)
-    return xh_e2m1, torch.empty(*sf_shape, dtype=torch.float8_e4m3fn if nv else torch.float8_e8m0fnu, device=x.device)
+    return _quantize("quantize_nv_blocked", a, b, global_scale, _method_code(method))
 
 
 def silu_and_mul(x: torch.Tensor) -> torch.Tensor:
@@ -246,24 +210,10 @@ def silu_and_mul(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _silu_mul_quantize_mx(x, h, method, blocked):
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.silu_mul_quantize_mx(x, h, _METHOD_CODE[method], blocked)
-    xh_e2m1, xh_e8m0 = _alloc_gated(x, False, blocked)
-    _ops_amd.fusedSiluMulQuantizeMx_(x, h, xh_e2m1, xh_e8m0, _METHOD_CODE[method], blocked)
-    return xh_e2m1, xh_e8m0
-
-
-def _silu_mul_quantize_nv(x, h, global_scale, method, blocked):
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.silu_mul_quantize_nv(x, h, global_scale, _METHOD_CODE[method], blocked)
-    xh_e2m1, xh_e4m3 = _alloc_gated(x, True, blocked)
-    _ops_amd.fusedSiluMulQuantizeNv_(x, h, xh_e2m1, xh_e4m3, global_scale, _METHOD_CODE[method], blocked)
-    return xh_e2m1, xh_e4m3
+def _silu_mul_quantize(op: str, x, *args):
+    if not torch.compiler.is_compiling() and x.size(-1) % 2:   # (a traced call leaves this to the op's own check)
+        raise ValueError(f"the last dimension of x must be 2 * I (got {x.size(-1)})")
+    return _quantize(op, x, *args)
 
 
 def fusedSiluMulQuantizeMx(x: torch.Tensor, h: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
@@ -273,26 +223,26 @@ def fusedSiluMulQuantizeMx(x: torch.Tensor, h: torch.Tensor, *, method: Literal[
     fusedQuantizeMx does for a (.., I) tensor (scales flat in the first rows * I / 32 bytes, padding untouched).  x must stay below 2 GiB (the kernel addresses
     it with 32-bit offsets; larger inputs raise -- split them by rows).  Non-finite gate / up values give unspecified bytes in their own groups only.
     Measured faster than the two calls for R <= 32 (1.15-1.45x); at R = 128 it is not: keep silu_and_mul + fusedQuantizeMx there."""
-    return _silu_mul_quantize_mx(x, h, method, False)
+    return _silu_mul_quantize("silu_mul_quantize_mx", x, h, _method_code(method), False)
 
 
 def fusedSiluMulQuantizeMxBlocked(x: torch.Tensor, h: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION: ``fusedQuantizeMxBlocked(silu_and_mul(x), h, method=method)`` in one launch (see fusedSiluMulQuantizeMx): the scales come out flat in the
     ``to_blocked`` layout, zero padded -- what the dense ``matmul_mxf4_bf16_tn`` takes.  x below 2 GiB."""
-    return _silu_mul_quantize_mx(x, h, method, True)
+    return _silu_mul_quantize("silu_mul_quantize_mx", x, h, _method_code(method), True)
 
 
 def fusedSiluMulQuantizeNv(x: torch.Tensor, h: torch.Tensor, global_scale: torch.Tensor, *,
                            method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION: ``fusedQuantizeNv(silu_and_mul(x), h, global_scale, method=method)`` in one launch, byte for byte (see fusedSiluMulQuantizeMx); R may be 16.
     x below 2 GiB."""
-    return _silu_mul_quantize_nv(x, h, global_scale, method, False)
+    return _silu_mul_quantize("silu_mul_quantize_nv", x, h, global_scale, _method_code(method), False)
 
 
 def fusedSiluMulQuantizeNvBlocked(x: torch.Tensor, h: torch.Tensor, global_scale: torch.Tensor, *,
                                   method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION: ``fusedQuantizeNvBlocked(silu_and_mul(x), h, global_scale, method=method)`` in one launch (see fusedSiluMulQuantizeMxBlocked).  x below 2 GiB."""
-    return _silu_mul_quantize_nv(x, h, global_scale, method, True)
+    return _silu_mul_quantize("silu_mul_quantize_nv", x, h, global_scale, _method_code(method), True)
 
 
 def moe_sort(topk_ids: torch.Tensor, num_experts: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -424,14 +374,6 @@ def moe_route_grouped(logits: torch.Tensor, topk: int, num_experts: int | None =
     return (weights, ids) + tuple(moe_sort_fused(ids, logits.size(1) if num_experts is None else num_experts, expert_map=expert_map))
 
 
-def _alloc_gathered(x: torch.Tensor, src_row: torch.Tensor, nv: bool):
-    """The outputs the plain quantizers allocate for x[src_row], an (M, K) tensor (_alloc_mx / _alloc_nv)."""
-    g = torch.empty(src_row.size(0), x.size(-1), dtype=x.dtype, device="meta")
-    padded_rows, padded_cols = get_padded_shape_nv(g) if nv else get_padded_shape_mx(g)
-    xh_e2m1 = torch.empty(g.size(0), g.size(1) // 2, dtype=torch.uint8, device=x.device)
-    return xh_e2m1, torch.empty(padded_rows, padded_cols, dtype=torch.float8_e4m3fn if nv else torch.float8_e8m0fnu, device=x.device)
-
-
 def fusedGatherQuantizeMx(x: torch.Tensor, h: torch.Tensor, src_row: torch.Tensor, *,
                           method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION (no reference counterpart): ``fusedQuantizeMx(x.index_select(0, src_row), h, method=method)`` in ONE launch, byte for byte -- the MoE dispatch: the
@@ -441,26 +383,14 @@ def fusedGatherQuantizeMx(x: torch.Tensor, h: torch.Tensor, src_row: torch.Tenso
     grouped_matmul_mxf4_bf16_tn reads as it is.  The indices are read on the device (no host sync: graph-capturable); an index outside [0, T) -- -1 padding included --
     gives the bytes of an all-zero row and can neither fault nor read another row.  x must stay below 2 GiB (32-bit offsets; larger inputs raise).
     Speed against index_select + fusedQuantizeMx: not measured yet (benchmarks/bench_moe_dispatch_mi355x.py)."""
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.gather_quantize_mx(x, h, src_row, _METHOD_CODE[method])
-    xh_e2m1, xh_e8m0 = _alloc_gathered(x, src_row, False)
-    _ops_amd.fusedGatherQuantizeMx_(x, h, src_row, xh_e2m1, xh_e8m0, _METHOD_CODE[method])
-    return xh_e2m1, xh_e8m0
+    return _quantize("gather_quantize_mx", x, h, src_row, _method_code(method))
 
 
 def fusedGatherQuantizeNv(x: torch.Tensor, h: torch.Tensor, global_scale: torch.Tensor, src_row: torch.Tensor, *,
                           method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
     """EXTENSION: ``fusedQuantizeNv(x.index_select(0, src_row), h, global_scale, method=method)`` in one launch, byte for byte (see fusedGatherQuantizeMx); R may be
     16; e4m3 scales flat in the first M * K / 16 bytes -- what grouped_matmul_nvf4_bf16_tn reads as it is.  x below 2 GiB."""
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.gather_quantize_nv(x, h, src_row, global_scale, _METHOD_CODE[method])
-    xh_e2m1, xh_e4m3 = _alloc_gathered(x, src_row, True)
-    _ops_amd.fusedGatherQuantizeNv_(x, h, src_row, xh_e2m1, xh_e4m3, global_scale, _METHOD_CODE[method])
-    return xh_e2m1, xh_e4m3
+    return _quantize("gather_quantize_nv", x, h, src_row, global_scale, _method_code(method))
 
 
 def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
@@ -500,14 +430,13 @@ def fused_quantize_matmul_mxf4_bf16_tn(x: torch.Tensor, h: torch.Tensor, b: torc
         chosen where it measured faster (``qutlass_amd_activation_path_launches`` in the C library, calibrated on a 256-CU MI355X and scaled
         with the CU count); ``single_launch=True / False`` forces either.
     ``method`` defaults to ``"quest"`` like ``fusedQuantizeMx`` (qutlass/__init__.py:149): swapping the composed calls for this helper keeps the quantizer."""
-    if method not in _METHOD_CODE:
-        raise ValueError(f"invalid method {method!r}, must be 'quest' or 'abs_max'")
+    code = _method_code(method)
     k = x.size(-1)
     m = x.numel() // k if k else 0
     if single_launch is None:
         single_launch = _decode_single_launch_wins(m, b.size(0), k, h.size(0), x.device)
     if single_launch:
-        out = torch.ops.qutlass_amd.fusedQuantizeMatmulMxf4(x, h, b, b_sf, alpha, _METHOD_CODE[method])
+        out = torch.ops.qutlass_amd.fusedQuantizeMatmulMxf4(x, h, b, b_sf, alpha, code)
         return out.view(*x.shape[:-1], b.size(0))
     a_q, a_sf = fusedQuantizeMxBlocked(x, h, method=method)
     return qutlass_CUDA.matmul_mxf4_bf16_tn(a_q.view(-1, k // 2), b, a_sf, b_sf, alpha).view(*x.shape[:-1], b.size(0))

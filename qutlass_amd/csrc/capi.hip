@@ -1250,113 +1250,69 @@ int debug_plan(const char* name, int64_t M, int64_t N, int64_t rowbytes, int gra
 
 #endif   // QAMD_DEF(1)
 
-template <int R, bool NV, int METHOD, bool MASK, bool BLK>
+// One rotation switch for the rotate + quantize family.  KIND picks the __global__ wrapper (quantize.hip.h): the plain quantizer, the gated one (act = silu(gate) * up
+// computed in the tile loads) or the gathering one (the tile loads go through a row index).  BLK: scales written in the to_blocked() layout.
+enum QuantKind { QK_PLAIN, QK_GATED, QK_GATHER };
+
+template <int KIND, int R, bool NV, int METHOD, bool MASK, bool BLK>
 int launch_quant(const QuantParams& p, hipStream_t s, int grid) {
+  if constexpr (KIND == QK_GATED) {
+    hipLaunchKernelGGL((fused_silu_mul_quantize_kernel<R, NV, METHOD, BLK>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_silu_mul_quantize_kernel");
+  } else if constexpr (KIND == QK_GATHER) {
+    hipLaunchKernelGGL((fused_gather_quantize_kernel<R, NV, METHOD>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_gather_quantize_kernel");
+  } else {
 #if QAMD_BENCH
-  if (!opt_hw_fp4()) hipLaunchKernelGGL((fused_quantize_kernel<R, NV, METHOD, MASK, false, BLK>), dim3(grid), dim3(256), 0, s, p);
-  else
+    // lab only, and deliberately on the plain kernels only: the software e2m1 encoder exists to be compared with the hardware convert, and the plain kernels are where
+    // that comparison is made -- the gated and the gathering wrappers are instantiated with the hardware convert alone
+    if (!opt_hw_fp4()) hipLaunchKernelGGL((fused_quantize_kernel<R, NV, METHOD, MASK, false, BLK>), dim3(grid), dim3(256), 0, s, p);
+    else
 #endif
-  hipLaunchKernelGGL((fused_quantize_kernel<R, NV, METHOD, MASK, true, BLK>), dim3(grid), dim3(256), 0, s, p);
-  return check_launch("fused_quantize_kernel");
+    hipLaunchKernelGGL((fused_quantize_kernel<R, NV, METHOD, MASK, true, BLK>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_quantize_kernel");
+  }
 }
 
-// BLK: scales written in the to_blocked() layout (qutlass_amd_fused_quantize_{mx,nv}_blocked)
-template <bool NV, int METHOD, bool MASK, bool BLK = false>
-int dispatch_rot(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
+template <int KIND, bool NV, int METHOD, bool MASK, bool BLK>
+int dispatch_quant(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
+  static_assert(!MASK || (KIND == QK_PLAIN && !NV && METHOD == METHOD_QUEST), "the clip mask exists for the plain MX quest quantizer only");
+  static_assert(!BLK || KIND != QK_GATHER, "the gathering quantizers write flat scales only");
   switch (rot) {
     case 16:
-      if constexpr (NV) return launch_quant<16, NV, METHOD, false, BLK>(p, s, grid);
+      if constexpr (NV) return launch_quant<KIND, 16, NV, METHOD, false, BLK>(p, s, grid);
       break;
-    case 32: return launch_quant<32, NV, METHOD, MASK, BLK>(p, s, grid);
+    case 32: return launch_quant<KIND, 32, NV, METHOD, MASK, BLK>(p, s, grid);
     case 64:
-      if constexpr (!MASK) return launch_quant<64, NV, METHOD, false, BLK>(p, s, grid);
+      if constexpr (!MASK) return launch_quant<KIND, 64, NV, METHOD, false, BLK>(p, s, grid);
       break;
     case 128:
-      if constexpr (!MASK) return launch_quant<128, NV, METHOD, false, BLK>(p, s, grid);
+      if constexpr (!MASK) return launch_quant<KIND, 128, NV, METHOD, false, BLK>(p, s, grid);
       break;
   }
   if (MASK) return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected 32.", name, rot);
   return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, NV ? "16, " : "");
 }
 
+// every instantiation select_quant() can reach, and no other: defined in unit 5 (build.py gives that unit the VGPR-form MFMA flag), declared elsewhere
 #if QAMD_TU != 0
 #if QAMD_TU == 5
-#define QAMD_ROT_INST template
+#define QAMD_QUANT_INST(...) template int dispatch_quant<__VA_ARGS__>(int, const QuantParams&, hipStream_t, int, const char*);
 #else
-#define QAMD_ROT_INST extern template
+#define QAMD_QUANT_INST(...) extern template int dispatch_quant<__VA_ARGS__>(int, const QuantParams&, hipStream_t, int, const char*);
 #endif
-#define QAMD_ROT_BOTH(NV_, M_, K_) \
-  QAMD_ROT_INST int dispatch_rot<NV_, M_, K_, false>(int, const QuantParams&, hipStream_t, int, const char*); \
-  QAMD_ROT_INST int dispatch_rot<NV_, M_, K_, true>(int, const QuantParams&, hipStream_t, int, const char*);
-QAMD_ROT_BOTH(false, METHOD_QUEST, true)
-QAMD_ROT_BOTH(false, METHOD_QUEST, false)
-QAMD_ROT_BOTH(false, METHOD_ABSMAX, false)
-QAMD_ROT_BOTH(true, METHOD_QUEST, false)
-QAMD_ROT_BOTH(true, METHOD_ABSMAX, false)
-#undef QAMD_ROT_BOTH
-#undef QAMD_ROT_INST
-#endif
-
-// the gated quantizers (fused_silu_mul_quantize_kernel: act = silu(gate) * up computed in the tile loads): unit 5 as well
-template <bool NV, int METHOD, bool BLK>
-int dispatch_rot_gated(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
-#define QAMD_GATED_GO(R_) hipLaunchKernelGGL((fused_silu_mul_quantize_kernel<R_, NV, METHOD, BLK>), dim3(grid), dim3(256), 0, s, p); return check_launch("fused_silu_mul_quantize_kernel")
-  switch (rot) {
-    case 16:
-      if constexpr (NV) { QAMD_GATED_GO(16); }
-      break;
-    case 32: QAMD_GATED_GO(32);
-    case 64: QAMD_GATED_GO(64);
-    case 128: QAMD_GATED_GO(128);
-  }
-#undef QAMD_GATED_GO
-  return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, NV ? "16, " : "");
-}
-
-#if QAMD_TU != 0
-#if QAMD_TU == 5
-#define QAMD_ROT_INST template
-#else
-#define QAMD_ROT_INST extern template
-#endif
-#define QAMD_ROT_BOTH(NV_, M_) \
-  QAMD_ROT_INST int dispatch_rot_gated<NV_, M_, false>(int, const QuantParams&, hipStream_t, int, const char*); \
-  QAMD_ROT_INST int dispatch_rot_gated<NV_, M_, true>(int, const QuantParams&, hipStream_t, int, const char*);
-QAMD_ROT_BOTH(false, METHOD_QUEST)
-QAMD_ROT_BOTH(false, METHOD_ABSMAX)
-QAMD_ROT_BOTH(true, METHOD_QUEST)
-QAMD_ROT_BOTH(true, METHOD_ABSMAX)
-#undef QAMD_ROT_BOTH
-#undef QAMD_ROT_INST
-#endif
-
-// the gathering quantizers (fused_gather_quantize_kernel: the tile loads go through a row index): unit 5 as well
-template <bool NV, int METHOD>
-int dispatch_rot_gather(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
-#define QAMD_GATHER_GO(R_) hipLaunchKernelGGL((fused_gather_quantize_kernel<R_, NV, METHOD>), dim3(grid), dim3(256), 0, s, p); return check_launch("fused_gather_quantize_kernel")
-  switch (rot) {
-    case 16:
-      if constexpr (NV) { QAMD_GATHER_GO(16); }
-      break;
-    case 32: QAMD_GATHER_GO(32);
-    case 64: QAMD_GATHER_GO(64);
-    case 128: QAMD_GATHER_GO(128);
-  }
-#undef QAMD_GATHER_GO
-  return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, NV ? "16, " : "");
-}
-
-#if QAMD_TU != 0
-#if QAMD_TU == 5
-#define QAMD_ROT_INST template
-#else
-#define QAMD_ROT_INST extern template
-#endif
-QAMD_ROT_INST int dispatch_rot_gather<false, METHOD_QUEST>(int, const QuantParams&, hipStream_t, int, const char*);
-QAMD_ROT_INST int dispatch_rot_gather<false, METHOD_ABSMAX>(int, const QuantParams&, hipStream_t, int, const char*);
-QAMD_ROT_INST int dispatch_rot_gather<true, METHOD_QUEST>(int, const QuantParams&, hipStream_t, int, const char*);
-QAMD_ROT_INST int dispatch_rot_gather<true, METHOD_ABSMAX>(int, const QuantParams&, hipStream_t, int, const char*);
-#undef QAMD_ROT_INST
+#define QAMD_QUANT_FORMATS(KIND_, BLK_) \
+  QAMD_QUANT_INST(KIND_, false, METHOD_QUEST, false, BLK_) QAMD_QUANT_INST(KIND_, false, METHOD_ABSMAX, false, BLK_) \
+  QAMD_QUANT_INST(KIND_, true, METHOD_QUEST, false, BLK_) QAMD_QUANT_INST(KIND_, true, METHOD_ABSMAX, false, BLK_)
+QAMD_QUANT_FORMATS(QK_PLAIN, false)
+QAMD_QUANT_FORMATS(QK_PLAIN, true)
+QAMD_QUANT_INST(QK_PLAIN, false, METHOD_QUEST, true, false)
+QAMD_QUANT_INST(QK_PLAIN, false, METHOD_QUEST, true, true)
+QAMD_QUANT_FORMATS(QK_GATED, false)
+QAMD_QUANT_FORMATS(QK_GATED, true)
+QAMD_QUANT_FORMATS(QK_GATHER, false)
+#undef QAMD_QUANT_FORMATS
+#undef QAMD_QUANT_INST
 #endif
 
 // backward_t_bf16 / backward_qt_bf16 kernels live in unit 5 with the other rotation quantizers (MFMA results straight in VGPRs: a
@@ -1430,6 +1386,52 @@ int blocked_pad_grid(int grid, int sf_rows, int sf_cols) {
   const int64_t stores = (prow - sf_rows) * cb + (int64_t)sf_rows * (cb * 4 - sf_cols);
   const int64_t want = std::min<int64_t>(cdiv(stores, 256), chip_cus());
   return (int)std::max<int64_t>(grid, want);
+}
+
+// ---- the rotate + quantize family (plain, gated, gathering; MX and NV): every check and the launch set-up written once; each C entry calls them in its own order ----
+inline int quant_check_rot(const char* name, const QuantFormat& f, int rot, bool mask = false) {
+  if (f.has_rot(rot)) return QAMD_OK;   // (a mask with R = 64 / 128 passes here and is refused by dispatch_quant, after the entry's other checks)
+  return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s.", name, rot, mask ? "32" : f.rots);
+}
+
+inline int quant_check_method(const char* name, int method) {
+  if (method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX) return QAMD_OK;
+  return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
+}
+
+// (rot >= 64 stages H with 16-byte vector loads, quantize.hip.h: an offset view of a larger tensor may be 2-byte aligned only -- rejected rather than left to
+//  the device's unaligned-access mode; torch allocations are 256-byte aligned)
+inline int quant_check_h(const char* name, int rot, const void* h) {
+  if (rot < 64 || (uintptr_t)h % 16 == 0) return QAMD_OK;
+  return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 16-byte aligned for rotation sizes >= 64", name);
+}
+
+inline int quant_rp(int rot) { return rot < 32 ? 32 : rot; }   // a tile is 32 rows of max(R, 32) elements: the unit of ntiles and of every row length
+
+// numel elements in rows of k (k is read for blocked scales only); src_row / src_n: the gather index.  Fills ntiles, sf_rows, sf_cols and the index; returns the grid.
+inline int quant_fill(QuantParams& p, const QuantFormat& f, int rot, int64_t numel, int64_t k, bool blocked, const int32_t* src_row = nullptr, int64_t src_n = 0) {
+  p.numel = numel;
+  p.ntiles = (int)cdiv(numel, (int64_t)quant_rp(rot) * 32);
+  p.sf_rows = blocked ? (int)(numel / k) : 0; p.sf_cols = blocked ? (int)(k / f.group) : 0;
+  p.src_row = src_row; p.src_n = (int)src_n;
+  const int grid = quant_grid(p.ntiles, rot);
+  return blocked ? blocked_pad_grid(grid, p.sf_rows, p.sf_cols) : grid;
+}
+
+// runtime (nv, method, mask, blocked) -> the dispatch_quant instantiation; the callers have checked method, and that a mask comes with MX + quest only
+template <int KIND>
+int select_quant(bool nv, int method, bool mask, bool blocked, int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
+  auto go = [&](auto nv_, auto method_, auto mask_) {
+    using NV = decltype(nv_); using M = decltype(method_); using K = decltype(mask_);
+    if constexpr (KIND != QK_GATHER)
+      if (blocked) return dispatch_quant<KIND, NV::value, M::value, K::value, true>(rot, p, s, grid, name);
+    return dispatch_quant<KIND, NV::value, M::value, K::value, false>(rot, p, s, grid, name);
+  };
+  using Quest = std::integral_constant<int, METHOD_QUEST>; using AbsMax = std::integral_constant<int, METHOD_ABSMAX>;
+  if constexpr (KIND == QK_PLAIN)
+    if (mask) return go(std::false_type{}, Quest{}, std::true_type{});
+  if (nv) return method == QAMD_METHOD_QUEST ? go(std::true_type{}, Quest{}, std::false_type{}) : go(std::true_type{}, AbsMax{}, std::false_type{});
+  return method == QAMD_METHOD_QUEST ? go(std::false_type{}, Quest{}, std::false_type{}) : go(std::false_type{}, AbsMax{}, std::false_type{});
 }
 
 #endif   // QAMD_DEF(1)
@@ -1731,87 +1733,50 @@ int qutlass_amd_matmul_nvf4_bf16_tn_ws(const void* A, const void* B, const void*
   return nvf4_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, 0, stream, workspace, workspace_bytes);
 }
 
-// sf_rows / k: logical 2-D shape of x (rows of k elements) for the blocked-scale variants; k == 0: flat scales (the reference's contract)
-static int fused_quantize_mx_impl(const char* name, const void* x, const void* h, int rot, int64_t numel, int64_t k, int method,
-                                  void* out_e2m1, void* out_e8m0, void* out_mask, void* stream) {
-  if (!x || !h || !out_e2m1 || !out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (rot != 32 && rot != 64 && rot != 128)
-    return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s.", name, rot, out_mask ? "32" : "32, 64, or 128");
+// k: logical 2-D shape of x (rows of k elements) for the blocked-scale variants; k == 0: flat scales (the reference's contract).  MX: global_scale null; NV: out_mask null.
+static int fused_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t numel, int64_t k, int method,
+                               const float* global_scale, void* out_e2m1, void* out_sf, void* out_mask, void* stream) {
+  if (!x || !h || !out_e2m1 || !out_sf || (f.nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (int rc = quant_check_rot(name, f, rot, out_mask != nullptr)) return rc;
   if (numel <= 0 || numel % rot) return fail(QAMD_ERR_INVALID, "%s: A must be divisible by %d", name, rot);
   if (numel * 2 >= (1ll << 32)) return fail(QAMD_ERR_INVALID, "%s: more than 2^31 elements is not supported", name);
-  if (method != QAMD_METHOD_QUEST && method != QAMD_METHOD_ABSMAX) return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
+  if (int rc = quant_check_method(name, method)) return rc;
   if (out_mask && method != QAMD_METHOD_QUEST) return fail(QAMD_ERR_INVALID, "%s: the clip mask is only defined for method quest", name);
-  if (k && (k % rot || numel % k)) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of the rotation size %d and divide numel", name, (long long)k, rot);
-  // (rot >= 64 stages H with 16-byte vector loads, quantize.hip.h: an offset view of a larger tensor may be 2-byte aligned only -- rejected rather than left to
-  //  the device's unaligned-access mode; torch allocations are 256-byte aligned)
-  if (rot >= 64 && (uintptr_t)h % 16) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 16-byte aligned for rotation sizes >= 64", name);
+  if (k && (k % quant_rp(rot) || numel % k))
+    return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of %s%d and divide numel", name, (long long)k, f.row_unit, quant_rp(rot));
+  if (int rc = quant_check_h(name, rot, h)) return rc;
   QuantParams p;
-  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_e8m0;
-  p.out_mask = (uint32_t*)out_mask; p.global_scale = nullptr; p.numel = numel;
-  p.ntiles = (int)cdiv(numel, (int64_t)rot * 32);
-  p.sf_rows = k ? (int)(numel / k) : 0; p.sf_cols = k ? (int)(k / 32) : 0;
-  int grid = quant_grid(p.ntiles, rot);
-  if (k) grid = blocked_pad_grid(grid, p.sf_rows, p.sf_cols);
-  hipStream_t s = (hipStream_t)stream;
-  if (k) {
-    if (out_mask) return dispatch_rot<false, METHOD_QUEST, true, true>(rot, p, s, grid, name);
-    if (method == QAMD_METHOD_QUEST) return dispatch_rot<false, METHOD_QUEST, false, true>(rot, p, s, grid, name);
-    return dispatch_rot<false, METHOD_ABSMAX, false, true>(rot, p, s, grid, name);
-  }
-  if (out_mask) return dispatch_rot<false, METHOD_QUEST, true>(rot, p, s, grid, name);
-  if (method == QAMD_METHOD_QUEST) return dispatch_rot<false, METHOD_QUEST, false>(rot, p, s, grid, name);
-  return dispatch_rot<false, METHOD_ABSMAX, false>(rot, p, s, grid, name);
+  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
+  p.out_mask = (uint32_t*)out_mask; p.global_scale = global_scale;
+  const int grid = quant_fill(p, f, rot, numel, k, k != 0);
+  return select_quant<QK_PLAIN>(f.nv, method, out_mask != nullptr, k != 0, rot, p, (hipStream_t)stream, grid, name);
 }
 
 int qutlass_amd_fused_quantize_mx(const void* x, const void* h, int rot, int64_t numel, int method,
                                   void* out_e2m1, void* out_e8m0, void* out_mask, void* stream) {
-  return fused_quantize_mx_impl("fusedQuantizeMx", x, h, rot, numel, 0, method, out_e2m1, out_e8m0, out_mask, stream);
-}
-
-int qutlass_amd_fused_quantize_mx_blocked(const void* x, const void* h, int rot, int64_t rows, int64_t k, int method,
-                                          void* out_e2m1, void* out_e8m0_blocked, void* out_mask, void* stream) {
-  const char* name = "fusedQuantizeMxBlocked";
-  if (rows <= 0 || k <= 0 || rows >= (1ll << 31) || k >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld, %lld)", name, (long long)rows, (long long)k);
-  return fused_quantize_mx_impl(name, x, h, rot, rows * k, k, method, out_e2m1, out_e8m0_blocked, out_mask, stream);
-}
-
-static int fused_quantize_nv_impl(const char* name, const void* x, const void* h, int rot, int64_t numel, int64_t k, int method,
-                                  const float* global_scale, void* out_e2m1, void* out_e4m3, void* stream) {
-  if (!x || !h || !out_e2m1 || !out_e4m3 || !global_scale) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (rot != 16 && rot != 32 && rot != 64 && rot != 128)
-    return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected 16, 32, 64, or 128.", name, rot);
-  if (numel <= 0 || numel % rot) return fail(QAMD_ERR_INVALID, "%s: A must be divisible by %d", name, rot);
-  if (numel * 2 >= (1ll << 32)) return fail(QAMD_ERR_INVALID, "%s: more than 2^31 elements is not supported", name);
-  if (method != QAMD_METHOD_QUEST && method != QAMD_METHOD_ABSMAX) return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
-  const int rp = rot < 32 ? 32 : rot;
-  if (k && (k % rp || numel % k)) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of %d and divide numel", name, (long long)k, rp);
-  if (rot >= 64 && (uintptr_t)h % 16) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 16-byte aligned for rotation sizes >= 64", name);
-  QuantParams p;
-  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_e4m3;
-  p.out_mask = nullptr; p.global_scale = global_scale; p.numel = numel;
-  p.ntiles = (int)cdiv(numel, (int64_t)rp * 32);
-  p.sf_rows = k ? (int)(numel / k) : 0; p.sf_cols = k ? (int)(k / 16) : 0;
-  int grid = quant_grid(p.ntiles, rot);
-  if (k) grid = blocked_pad_grid(grid, p.sf_rows, p.sf_cols);
-  hipStream_t s = (hipStream_t)stream;
-  if (k) {
-    if (method == QAMD_METHOD_QUEST) return dispatch_rot<true, METHOD_QUEST, false, true>(rot, p, s, grid, name);
-    return dispatch_rot<true, METHOD_ABSMAX, false, true>(rot, p, s, grid, name);
-  }
-  if (method == QAMD_METHOD_QUEST) return dispatch_rot<true, METHOD_QUEST, false>(rot, p, s, grid, name);
-  return dispatch_rot<true, METHOD_ABSMAX, false>(rot, p, s, grid, name);
+  return fused_quantize_impl("fusedQuantizeMx", kQuantMx, x, h, rot, numel, 0, method, nullptr, out_e2m1, out_e8m0, out_mask, stream);
 }
 
 int qutlass_amd_fused_quantize_nv(const void* x, const void* h, int rot, int64_t numel, int method,
                                   const float* global_scale, void* out_e2m1, void* out_e4m3, void* stream) {
-  return fused_quantize_nv_impl("fusedQuantizeNv", x, h, rot, numel, 0, method, global_scale, out_e2m1, out_e4m3, stream);
+  return fused_quantize_impl("fusedQuantizeNv", kQuantNv, x, h, rot, numel, 0, method, global_scale, out_e2m1, out_e4m3, nullptr, stream);
+}
+
+static int blocked_shape_check(const char* name, int64_t rows, int64_t k) {
+  if (rows <= 0 || k <= 0 || rows >= (1ll << 31) || k >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld, %lld)", name, (long long)rows, (long long)k);
+  return QAMD_OK;
+}
+
+int qutlass_amd_fused_quantize_mx_blocked(const void* x, const void* h, int rot, int64_t rows, int64_t k, int method,
+                                          void* out_e2m1, void* out_e8m0_blocked, void* out_mask, void* stream) {
+  if (int rc = blocked_shape_check("fusedQuantizeMxBlocked", rows, k)) return rc;
+  return fused_quantize_impl("fusedQuantizeMxBlocked", kQuantMx, x, h, rot, rows * k, k, method, nullptr, out_e2m1, out_e8m0_blocked, out_mask, stream);
 }
 
 int qutlass_amd_fused_quantize_nv_blocked(const void* x, const void* h, int rot, int64_t rows, int64_t k, int method,
                                           const float* global_scale, void* out_e2m1, void* out_e4m3_blocked, void* stream) {
-  const char* name = "fusedQuantizeNvBlocked";
-  if (rows <= 0 || k <= 0 || rows >= (1ll << 31) || k >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld, %lld)", name, (long long)rows, (long long)k);
-  return fused_quantize_nv_impl(name, x, h, rot, rows * k, k, method, global_scale, out_e2m1, out_e4m3_blocked, stream);
+  if (int rc = blocked_shape_check("fusedQuantizeNvBlocked", rows, k)) return rc;
+  return fused_quantize_impl("fusedQuantizeNvBlocked", kQuantNv, x, h, rot, rows * k, k, method, global_scale, out_e2m1, out_e4m3_blocked, nullptr, stream);
 }
 
 // ---- gated MLP: act = silu(gate) * up of x = (rows, 2 * inter) [gate | up], alone or fused into the rotate + quantize ops ----------------------------------
@@ -1837,84 +1802,67 @@ int qutlass_amd_silu_mul_bf16(const void* x, int64_t rows, int64_t inter, void* 
   return check_launch("silu_mul_bf16_kernel");
 }
 
-// nv: 0 = MX (e8m0 per 32), 1 = NV (e4m3 per 16, global_scale)
-static int fused_silu_mul_quantize_impl(const char* name, bool nv, const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
+static int fused_silu_mul_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
                                         const float* global_scale, int blocked, void* out_e2m1, void* out_sf, void* stream) {
-  if (nv ? (rot != 16 && rot != 32 && rot != 64 && rot != 128) : (rot != 32 && rot != 64 && rot != 128))
-    return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, nv ? "16, " : "");
-  if (method != QAMD_METHOD_QUEST && method != QAMD_METHOD_ABSMAX) return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
-  const int rp = rot < 32 ? 32 : rot;
-  if (int rc = gated_common_check(name, x, rows, inter, rp)) return rc;
+  if (int rc = quant_check_rot(name, f, rot)) return rc;
+  if (int rc = quant_check_method(name, method)) return rc;
+  if (int rc = gated_common_check(name, x, rows, inter, quant_rp(rot))) return rc;
   // x is addressed with 32-bit offsets from one buffer descriptor (quantize.hip.h, GATED): no silent wrap beyond it
   if (rows * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: x (rows * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(rows * inter * 4));
   if (rows == 0) return QAMD_OK;
-  if (!x || !h || !out_e2m1 || !out_sf || (nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (rot >= 64 && (uintptr_t)h % 16) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 16-byte aligned for rotation sizes >= 64", name);
+  if (!x || !h || !out_e2m1 || !out_sf || (f.nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (int rc = quant_check_h(name, rot, h)) return rc;
   QuantParams p;
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
-  p.out_mask = nullptr; p.global_scale = global_scale; p.numel = rows * inter; p.inter = (int)inter;
-  p.ntiles = (int)cdiv(p.numel, (int64_t)rp * 32);
-  p.sf_rows = blocked ? (int)rows : 0; p.sf_cols = blocked ? (int)(inter / (nv ? 16 : 32)) : 0;
-  int grid = quant_grid(p.ntiles, rot);
-  if (blocked) grid = blocked_pad_grid(grid, p.sf_rows, p.sf_cols);
-  hipStream_t s = (hipStream_t)stream;
-#define QAMD_GATED_ARM(NV_, M_) (blocked ? dispatch_rot_gated<NV_, M_, true>(rot, p, s, grid, name) : dispatch_rot_gated<NV_, M_, false>(rot, p, s, grid, name))
-  if (nv) return method == QAMD_METHOD_QUEST ? QAMD_GATED_ARM(true, METHOD_QUEST) : QAMD_GATED_ARM(true, METHOD_ABSMAX);
-  return method == QAMD_METHOD_QUEST ? QAMD_GATED_ARM(false, METHOD_QUEST) : QAMD_GATED_ARM(false, METHOD_ABSMAX);
-#undef QAMD_GATED_ARM
+  p.out_mask = nullptr; p.global_scale = global_scale; p.inter = (int)inter;
+  const int grid = quant_fill(p, f, rot, rows * inter, inter, blocked != 0);
+  return select_quant<QK_GATED>(f.nv, method, false, blocked != 0, rot, p, (hipStream_t)stream, grid, name);
 }
 
 int qutlass_amd_fused_silu_mul_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, int blocked, void* out_e2m1,
                                            void* out_e8m0, void* stream) {
-  return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeMxBlocked" : "fusedSiluMulQuantizeMx", false, x, h, rot, rows, inter, method, nullptr, blocked,
+  return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeMxBlocked" : "fusedSiluMulQuantizeMx", kQuantMx, x, h, rot, rows, inter, method, nullptr, blocked,
                                       out_e2m1, out_e8m0, stream);
 }
 
 int qutlass_amd_fused_silu_mul_quantize_nv(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, const float* global_scale, int blocked,
                                            void* out_e2m1, void* out_e4m3, void* stream) {
-  return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", true, x, h, rot, rows, inter, method, global_scale,
+  return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", kQuantNv, x, h, rot, rows, inter, method, global_scale,
                                       blocked, out_e2m1, out_e4m3, stream);
 }
 
 // ---- MoE dispatch and combine: the two ends of a mixture-of-experts MLP around the grouped GEMMs ---------------------------------------------------------
 // Dispatch: fusedQuantize{Mx,Nv}(x.index_select(0, src_row)) in one launch, byte for byte -- the quantizer's tile loads go through the row index (quantize.hip.h,
-// GATHER), so the (M, K) bf16 copy of the routed tokens is never written.  nv: 0 = MX (e8m0 per 32), 1 = NV (e4m3 per 16, global_scale).
-static int fused_gather_quantize_impl(const char* name, bool nv, const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m,
-                                      int method, const float* global_scale, void* out_e2m1, void* out_sf, void* stream) {
-  if (nv ? (rot != 16 && rot != 32 && rot != 64 && rot != 128) : (rot != 32 && rot != 64 && rot != 128))
-    return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected %s32, 64, or 128.", name, rot, nv ? "16, " : "");
-  if (method != QAMD_METHOD_QUEST && method != QAMD_METHOD_ABSMAX) return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
-  const int rp = rot < 32 ? 32 : rot;
+// GATHER), so the (M, K) bf16 copy of the routed tokens is never written.
+static int fused_gather_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row,
+                                      int64_t m, int method, const float* global_scale, void* out_e2m1, void* out_sf, void* stream) {
+  if (int rc = quant_check_rot(name, f, rot)) return rc;
+  if (int rc = quant_check_method(name, method)) return rc;
   if (t < 0 || m < 0 || k <= 0 || t >= (1ll << 31) || m >= (1ll << 31) || k >= (1ll << 31))
     return fail(QAMD_ERR_INVALID, "%s: bad shape (x (%lld, %lld), %lld indices)", name, (long long)t, (long long)k, (long long)m);
-  if (k % rp) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of %d", name, (long long)k, rp);
+  if (k % quant_rp(rot)) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of %d", name, (long long)k, quant_rp(rot));
   if ((uintptr_t)x % 16 || (uintptr_t)src_row % 4) return fail(QAMD_ERR_INVALID, "%s: x must be 16-byte aligned (and src_row 4-byte aligned)", name);
   // x is addressed with 32-bit offsets from one buffer descriptor, and offset 2^31 is the kernel's "zero row" (quantize.hip.h, GATHER): no silent wrap beyond it
   if (t * k >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: x (rows * k * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(t * k * 2));
   if (m * k >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: more than 2^31 elements is not supported", name);
   if (m == 0) return QAMD_OK;
-  if ((!x && t > 0) || !h || !src_row || !out_e2m1 || !out_sf || (nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (rot >= 64 && (uintptr_t)h % 16) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 16-byte aligned for rotation sizes >= 64", name);
+  if ((!x && t > 0) || !h || !src_row || !out_e2m1 || !out_sf || (f.nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (int rc = quant_check_h(name, rot, h)) return rc;
   QuantParams p;
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
-  p.out_mask = nullptr; p.global_scale = global_scale; p.numel = m * k; p.inter = (int)k;
-  p.ntiles = (int)cdiv(p.numel, (int64_t)rp * 32);
-  p.sf_rows = 0; p.sf_cols = 0;
-  p.src_row = src_row; p.src_n = (int)t;
-  const int grid = quant_grid(p.ntiles, rot);
-  hipStream_t s = (hipStream_t)stream;
-  if (nv) return method == QAMD_METHOD_QUEST ? dispatch_rot_gather<true, METHOD_QUEST>(rot, p, s, grid, name) : dispatch_rot_gather<true, METHOD_ABSMAX>(rot, p, s, grid, name);
-  return method == QAMD_METHOD_QUEST ? dispatch_rot_gather<false, METHOD_QUEST>(rot, p, s, grid, name) : dispatch_rot_gather<false, METHOD_ABSMAX>(rot, p, s, grid, name);
+  p.out_mask = nullptr; p.global_scale = global_scale; p.inter = (int)k;
+  const int grid = quant_fill(p, f, rot, m * k, k, false, src_row, t);
+  return select_quant<QK_GATHER>(f.nv, method, false, false, rot, p, (hipStream_t)stream, grid, name);
 }
 
 int qutlass_amd_fused_gather_quantize_mx(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method, void* out_e2m1,
                                          void* out_e8m0, void* stream) {
-  return fused_gather_quantize_impl("fusedGatherQuantizeMx", false, x, h, rot, t, k, src_row, m, method, nullptr, out_e2m1, out_e8m0, stream);
+  return fused_gather_quantize_impl("fusedGatherQuantizeMx", kQuantMx, x, h, rot, t, k, src_row, m, method, nullptr, out_e2m1, out_e8m0, stream);
 }
 
 int qutlass_amd_fused_gather_quantize_nv(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method,
                                          const float* global_scale, void* out_e2m1, void* out_e4m3, void* stream) {
-  return fused_gather_quantize_impl("fusedGatherQuantizeNv", true, x, h, rot, t, k, src_row, m, method, global_scale, out_e2m1, out_e4m3, stream);
+  return fused_gather_quantize_impl("fusedGatherQuantizeNv", kQuantNv, x, h, rot, t, k, src_row, m, method, global_scale, out_e2m1, out_e4m3, stream);
 }
 
 // Combine: out[t] = sum_k w[t][k] * y[pos[t][k]] in the order and with the roundings moe_combine_bf16_kernel states (quantize.hip.h); slots outside [0, m) are skipped.

@@ -44,6 +44,19 @@ struct QuantParams {
   int src_n = 0;
 };
 
+// Host side: what the two formats of the family differ in (capi.hip builds every check and the QuantParams fill from it)
+struct QuantFormat {
+  bool nv;               // the kernels' NV template argument; a global scale is required
+  int group;             // elements per scale: e8m0 per 32 (MX), e4m3 per 16 (NV)
+  int min_rot;           // rotation sizes: min_rot, ..., 64, 128 (powers of two)
+  bool mask;             // a clip mask may be asked for (method quest, R = 32)
+  const char* rots;      // that set as the messages spell it
+  const char* row_unit;  // the blocked row-length message names its unit "the rotation size" for MX (the unit is R) and gives the bare number for NV (max(R, 32))
+  constexpr bool has_rot(int rot) const { return rot >= min_rot && rot <= 128 && (rot & (rot - 1)) == 0; }
+};
+constexpr QuantFormat kQuantMx{false, 32, 32, true, "32, 64, or 128", "the rotation size "};
+constexpr QuantFormat kQuantNv{true, 16, 16, false, "16, 32, 64, or 128", ""};
+
 // byte offset of scale (row, col) in the 128x4-tiled block-scale layout (qutlass/utils.py:60-64, :190-193); CB = ceil(cols / 4)
 __device__ __forceinline__ uint32_t blocked_sf_offset(uint32_t row, uint32_t col, uint32_t CB) {
   return ((row >> 7) * CB + (col >> 2)) * 512u + (row & 31u) * 16u + ((row & 127u) >> 5) * 4u + (col & 3u);

@@ -27,6 +27,7 @@
 #include <initializer_list>
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "../../include/qutlass_amd.h"
 
@@ -43,7 +44,9 @@ struct Named {
 std::string arg_desc(int pos, const char* name) { return "argument #" + std::to_string(pos) + " '" + name + "'"; }
 
 // ---- the three generic checks of include/bindings_utils.h, table-driven ------------------------------------------
-void require_contiguous(const char* op, std::initializer_list<Named> args) {
+// List: a braced list of {tensor, name} (the default: a braced argument deduces nothing), or a std::vector<Named> where the list is put together at run time
+template <class List = std::initializer_list<Named>>
+void require_contiguous(const char* op, const List& args) {
   int pos = 0;
   for (const Named& a : args) {
     STD_TORCH_CHECK(a.t.is_contiguous(), "Expected contiguous tensor, but got non-contiguous tensor for ", arg_desc(pos, a.name),
@@ -52,13 +55,15 @@ void require_contiguous(const char* op, std::initializer_list<Named> args) {
   }
 }
 
-void require_gpu(const char* op, std::initializer_list<Named> args) {
+template <class List = std::initializer_list<Named>>
+void require_gpu(const char* op, const List& args) {
   for (const Named& a : args)
     STD_TORCH_CHECK(a.t.is_cuda(), "Expected tensor to have cuda DeviceType, but got tensor with ", a.t.is_cpu() ? "cpu" : "another",
                     " DeviceType (while checking arguments for ", op, ")");
 }
 
-void require_same_gpu(const char* op, std::initializer_list<Named> args) {
+template <class List = std::initializer_list<Named>>
+void require_same_gpu(const char* op, const List& args) {
   const Named& first = *args.begin();
   int pos = 0;
   for (const Named& a : args) {
@@ -233,80 +238,82 @@ Tensor matmul_mxf8_bf16_nn(const Tensor& A, const Tensor& B, const Tensor& A_sf,
 // ---- fused rotate + quantize ---------------------------------------------------------------------------------------
 int64_t nbytes(const Tensor& t) { return t.numel() * (int64_t)t.element_size(); }
 
-void quant_prologue(const char* op, const Tensor& A, const Tensor& R) {
-  STD_TORCH_CHECK(has_dtype(A, ScalarType::BFloat16), "A must be bf16");
+// The family's checks, written once; every op below calls them in the reference's order: prelude, its own shape derivation, rotation set, its own divisibility
+// check, output sizes.  gscale != nullptr is the NV format (e4m3 scale per 16, rotation 16 allowed, global scale required); nullptr is MX (e8m0 per 32).
+// ts: the op's tensors in argument order, A and the rotation first; global_scale joins the device checks but need not be contiguous (one element).
+// method: checked here for the ops whose schema carries it; the blocked ops leave it to the C ABI.  Returns the rotation size.
+int64_t quant_prelude(const char* op, std::vector<Named> ts, const Tensor* gscale, const int64_t* method = nullptr) {
+  require_contiguous(op, ts);
+  if (gscale) ts.push_back({*gscale, "global_scale"});
+  require_gpu(op, ts);
+  require_same_gpu(op, ts);
+  const Tensor& R = ts[1].t;
+  STD_TORCH_CHECK(has_dtype(ts[0].t, ScalarType::BFloat16), "A must be bf16");
   STD_TORCH_CHECK(has_dtype(R, ScalarType::BFloat16), "B must be bf16");
-  (void)op;
+  if (gscale) {
+    STD_TORCH_CHECK(has_dtype(*gscale, ScalarType::Float), "global_scale must be float");
+    STD_TORCH_CHECK(gscale->dim() == 1 && gscale->size(0) == 1, "global_scale must be a scalar");
+  }
+  if (method) STD_TORCH_CHECK(*method == QAMD_METHOD_QUEST || *method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
+  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
+  return R.size(0);
 }
 
-// mask == nullptr: plain variant (rotation 32 / 64 / 128); mask != nullptr: Quest with clip mask (rotation 32 only)
-void quantize_mx(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, Tensor* OUT_mask, int method) {
-  if (OUT_mask) {
-    require_contiguous(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*OUT_mask, "OUT_mask"}});
-    require_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*OUT_mask, "OUT_mask"}});
-    require_same_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*OUT_mask, "OUT_mask"}});
-  } else {
-    require_contiguous(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-    require_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-    require_same_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  }
-  quant_prologue(op, A, R);
-  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
-  const int64_t rot = R.size(0), numel = A.numel();
-  STD_TORCH_CHECK(numel % rot == 0, "A must be divisible by", rot);
-  if (OUT_mask) {
-    STD_TORCH_CHECK(rot == 32, "Unsupported rotation size ", rot, "; expected 32.");
-  } else {
-    STD_TORCH_CHECK(rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 32, 64, or 128.");
-  }
-  // the C ABI writes numel/2, numel/32 (and numel/8) bytes: the caller's buffers must hold them
+void quant_check_rot(bool nv, int64_t rot, bool mask = false) {
+  const bool ok = mask ? rot == 32 : ((nv && rot == 16) || rot == 32 || rot == 64 || rot == 128);
+  STD_TORCH_CHECK(ok, "Unsupported rotation size ", rot, "; expected ", mask ? "32" : nv ? "16, 32, 64, or 128" : "32, 64, or 128", ".");
+}
+
+int64_t quant_rp(int64_t rot) { return rot < 32 ? 32 : rot; }   // rows are whole tiles of max(rot, 32) elements
+
+// the C ABI writes numel / 2 bytes of codes and one scale byte per group -- flat, or the padded to_blocked() matrix of the (numel / k, k / group) scales
+void quant_check_out(bool nv, const Tensor& OUT, const Tensor& OUT_sf, int64_t numel, int64_t k, bool blocked) {
+  const int64_t group = nv ? 16 : 32;
   STD_TORCH_CHECK(nbytes(OUT) >= numel / 2, "OUT is too small");
-  STD_TORCH_CHECK(nbytes(OUT_sf) >= numel / 32, "OUT_sf is too small");
+  STD_TORCH_CHECK(nbytes(OUT_sf) >= (blocked ? (numel / k + 127) / 128 * 128 * ((k / group + 3) / 4 * 4) : numel / group), "OUT_sf is too small",
+                  blocked ? " for the blocked scale layout" : "");
+}
+
+const float* gscale_ptr(const Tensor* gscale) { return static_cast<const float*>(gscale->data_ptr()); }
+
+// OUT_mask != nullptr (MX only): Quest with clip mask (rotation 32 only)
+void quantize(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, Tensor* OUT_mask, const Tensor* gscale, int method) {
+  std::vector<Named> ts{{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
+  if (OUT_mask) ts.push_back({*OUT_mask, "OUT_mask"});
+  const int64_t rot = quant_prelude(op, ts, gscale), numel = A.numel();
+  STD_TORCH_CHECK(numel % rot == 0, "A must be divisible by", rot);
+  quant_check_rot(gscale, rot, OUT_mask);
+  quant_check_out(gscale, OUT, OUT_sf, numel, 0, false);
   if (OUT_mask) {
     STD_TORCH_CHECK(nbytes(*OUT_mask) >= numel / 8, "OUT_mask is too small");
   }
   const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_fused_quantize_mx(A.data_ptr(), R.data_ptr(), (int)rot, numel, method, OUT.data_ptr(), OUT_sf.data_ptr(),
-                                         OUT_mask ? OUT_mask->data_ptr() : nullptr, current_stream(A)));
+  if (gscale)
+    check_rc(qutlass_amd_fused_quantize_nv(A.data_ptr(), R.data_ptr(), (int)rot, numel, method, gscale_ptr(gscale), OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+  else
+    check_rc(qutlass_amd_fused_quantize_mx(A.data_ptr(), R.data_ptr(), (int)rot, numel, method, OUT.data_ptr(), OUT_sf.data_ptr(),
+                                           OUT_mask ? OUT_mask->data_ptr() : nullptr, current_stream(A)));
 }
 
 std::tuple<Tensor, Tensor> fusedQuantizeMxQuest(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf) {
-  quantize_mx("fusedQuantizeMxQuest", A, R, OUT, OUT_sf, nullptr, QAMD_METHOD_QUEST);
+  quantize("fusedQuantizeMxQuest", A, R, OUT, OUT_sf, nullptr, nullptr, QAMD_METHOD_QUEST);
   return {OUT, OUT_sf};
 }
 std::tuple<Tensor, Tensor> fusedQuantizeMxAbsMax(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf) {
-  quantize_mx("fusedQuantizeMxAbsMax", A, R, OUT, OUT_sf, nullptr, QAMD_METHOD_ABSMAX);
+  quantize("fusedQuantizeMxAbsMax", A, R, OUT, OUT_sf, nullptr, nullptr, QAMD_METHOD_ABSMAX);
   return {OUT, OUT_sf};
 }
 std::tuple<Tensor, Tensor, Tensor> fusedQuantizeMxQuestWithMask(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, Tensor OUT_mask) {
-  quantize_mx("fusedQuantizeMxQuestWithMask", A, R, OUT, OUT_sf, &OUT_mask, QAMD_METHOD_QUEST);
+  quantize("fusedQuantizeMxQuestWithMask", A, R, OUT, OUT_sf, &OUT_mask, nullptr, QAMD_METHOD_QUEST);
   return {OUT, OUT_sf, OUT_mask};
 }
 
-void quantize_nv(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor& gscale, int method) {
-  require_contiguous(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  require_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {gscale, "global_scale"}});
-  require_same_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {gscale, "global_scale"}});
-  quant_prologue(op, A, R);
-  STD_TORCH_CHECK(has_dtype(gscale, ScalarType::Float), "global_scale must be float");
-  STD_TORCH_CHECK(gscale.dim() == 1 && gscale.size(0) == 1, "global_scale must be a scalar");
-  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
-  const int64_t rot = R.size(0), numel = A.numel();
-  STD_TORCH_CHECK(numel % rot == 0, "A must be divisible by", rot);
-  STD_TORCH_CHECK(rot == 16 || rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 16, 32, 64, or 128.");
-  STD_TORCH_CHECK(nbytes(OUT) >= numel / 2, "OUT is too small");
-  STD_TORCH_CHECK(nbytes(OUT_sf) >= numel / 16, "OUT_sf is too small");
-  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_fused_quantize_nv(A.data_ptr(), R.data_ptr(), (int)rot, numel, method, static_cast<const float*>(gscale.data_ptr()),
-                                         OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
-}
-
 std::tuple<Tensor, Tensor> fusedQuantizeNvQuest(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale) {
-  quantize_nv("fusedQuantizeNvQuest", A, R, OUT, OUT_sf, global_scale, QAMD_METHOD_QUEST);
+  quantize("fusedQuantizeNvQuest", A, R, OUT, OUT_sf, nullptr, &global_scale, QAMD_METHOD_QUEST);
   return {OUT, OUT_sf};
 }
 std::tuple<Tensor, Tensor> fusedQuantizeNvAbsMax(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale) {
-  quantize_nv("fusedQuantizeNvAbsMax", A, R, OUT, OUT_sf, global_scale, QAMD_METHOD_ABSMAX);
+  quantize("fusedQuantizeNvAbsMax", A, R, OUT, OUT_sf, nullptr, &global_scale, QAMD_METHOD_ABSMAX);
   return {OUT, OUT_sf};
 }
 
@@ -318,54 +325,36 @@ std::tuple<Tensor, Tensor> fusedQuantizeNvAbsMax(const Tensor& A, const Tensor& 
 // allocated; the `_qutlass_C` ops stay for callers that use them directly (eager), WITHOUT fake kernels, so tracing them fails loudly.
 void fusedQuantizeMx_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, int64_t method) {
   STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
-  quantize_mx(method == QAMD_METHOD_QUEST ? "fusedQuantizeMxQuest" : "fusedQuantizeMxAbsMax", A, R, OUT, OUT_sf, nullptr, (int)method);
+  quantize(method == QAMD_METHOD_QUEST ? "fusedQuantizeMxQuest" : "fusedQuantizeMxAbsMax", A, R, OUT, OUT_sf, nullptr, nullptr, (int)method);
 }
 void fusedQuantizeMxMask_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, Tensor OUT_mask) {
-  quantize_mx("fusedQuantizeMxQuestWithMask", A, R, OUT, OUT_sf, &OUT_mask, QAMD_METHOD_QUEST);
+  quantize("fusedQuantizeMxQuestWithMask", A, R, OUT, OUT_sf, &OUT_mask, nullptr, QAMD_METHOD_QUEST);
 }
 void fusedQuantizeNv_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale, int64_t method) {
   STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
-  quantize_nv(method == QAMD_METHOD_QUEST ? "fusedQuantizeNvQuest" : "fusedQuantizeNvAbsMax", A, R, OUT, OUT_sf, global_scale, (int)method);
+  quantize(method == QAMD_METHOD_QUEST ? "fusedQuantizeNvQuest" : "fusedQuantizeNvAbsMax", A, R, OUT, OUT_sf, nullptr, &global_scale, (int)method);
 }
 
 // ---- EXTENSION: quantizers that emit GEMM-ready (to_blocked-layout) scales: one launch instead of quantize + to_blocked ----------
 // A is (.., K); OUT_sf must hold the padded blocked matrix of the (numel / K, K / gs) scales.  method: 0 quest, 1 abs_max.
-void fusedQuantizeMxBlocked(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, int64_t method) {
-  const char* op = "fusedQuantizeMxBlocked";
-  require_contiguous(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  require_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  require_same_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  quant_prologue(op, A, R);
-  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
+void quantize_blocked(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method) {
+  const int64_t rot = quant_prelude(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, gscale);
   STD_TORCH_CHECK(A.dim() >= 1 && A.numel() > 0, "A must be a non-empty tensor");
-  const int64_t rot = R.size(0), numel = A.numel(), k = A.size(A.dim() - 1), rows = numel / k;
-  STD_TORCH_CHECK(rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 32, 64, or 128.");
-  STD_TORCH_CHECK(k % rot == 0, "the last dimension of A must be divisible by", rot);
-  STD_TORCH_CHECK(nbytes(OUT) >= numel / 2, "OUT is too small");
-  STD_TORCH_CHECK(nbytes(OUT_sf) >= (rows + 127) / 128 * 128 * ((k / 32 + 3) / 4 * 4), "OUT_sf is too small for the blocked scale layout");
+  const int64_t numel = A.numel(), k = A.size(A.dim() - 1), rows = numel / k;
+  quant_check_rot(gscale, rot);
+  STD_TORCH_CHECK(k % quant_rp(rot) == 0, "the last dimension of A must be divisible by", quant_rp(rot));
+  quant_check_out(gscale, OUT, OUT_sf, numel, k, true);
   const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_fused_quantize_mx_blocked(A.data_ptr(), R.data_ptr(), (int)rot, rows, k, (int)method, OUT.data_ptr(), OUT_sf.data_ptr(), nullptr,
-                                                 current_stream(A)));
+  if (gscale)
+    check_rc(qutlass_amd_fused_quantize_nv_blocked(A.data_ptr(), R.data_ptr(), (int)rot, rows, k, (int)method, gscale_ptr(gscale), OUT.data_ptr(), OUT_sf.data_ptr(),
+                                                   current_stream(A)));
+  else
+    check_rc(qutlass_amd_fused_quantize_mx_blocked(A.data_ptr(), R.data_ptr(), (int)rot, rows, k, (int)method, OUT.data_ptr(), OUT_sf.data_ptr(), nullptr,
+                                                   current_stream(A)));
 }
-
+void fusedQuantizeMxBlocked(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, int64_t method) { quantize_blocked("fusedQuantizeMxBlocked", A, R, OUT, OUT_sf, nullptr, method); }
 void fusedQuantizeNvBlocked(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& gscale, int64_t method) {
-  const char* op = "fusedQuantizeNvBlocked";
-  require_contiguous(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  require_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {gscale, "global_scale"}});
-  require_same_gpu(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {gscale, "global_scale"}});
-  quant_prologue(op, A, R);
-  STD_TORCH_CHECK(has_dtype(gscale, ScalarType::Float), "global_scale must be float");
-  STD_TORCH_CHECK(gscale.dim() == 1 && gscale.size(0) == 1, "global_scale must be a scalar");
-  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
-  STD_TORCH_CHECK(A.dim() >= 1 && A.numel() > 0, "A must be a non-empty tensor");
-  const int64_t rot = R.size(0), numel = A.numel(), k = A.size(A.dim() - 1), rows = numel / k;
-  STD_TORCH_CHECK(rot == 16 || rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 16, 32, 64, or 128.");
-  STD_TORCH_CHECK(k % (rot < 32 ? 32 : rot) == 0, "the last dimension of A must be divisible by", rot < 32 ? 32 : rot);
-  STD_TORCH_CHECK(nbytes(OUT) >= numel / 2, "OUT is too small");
-  STD_TORCH_CHECK(nbytes(OUT_sf) >= (rows + 127) / 128 * 128 * ((k / 16 + 3) / 4 * 4), "OUT_sf is too small for the blocked scale layout");
-  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_fused_quantize_nv_blocked(A.data_ptr(), R.data_ptr(), (int)rot, rows, k, (int)method, static_cast<const float*>(gscale.data_ptr()),
-                                                 OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+  quantize_blocked("fusedQuantizeNvBlocked", A, R, OUT, OUT_sf, &gscale, method);
 }
 
 // ---- EXTENSION: the gated-MLP activation act = silu(gate) * up of X = (.., 2 I) [gate | up], alone and fused into the quantizers ----------
@@ -384,94 +373,52 @@ void siluAndMul_(const Tensor& X, Tensor OUT) {
   check_rc(qutlass_amd_silu_mul_bf16(X.data_ptr(), rows, inter, OUT.data_ptr(), current_stream(X)));
 }
 
-void silu_mul_quantize(const char* op, bool nv, const Tensor& X, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method, bool blocked) {
-  require_contiguous(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  if (nv) {
-    require_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
-    require_same_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
-  } else {
-    require_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-    require_same_gpu(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  }
-  quant_prologue(op, X, R);
-  if (nv) {
-    STD_TORCH_CHECK(has_dtype(*gscale, ScalarType::Float), "global_scale must be float");
-    STD_TORCH_CHECK(gscale->dim() == 1 && gscale->size(0) == 1, "global_scale must be a scalar");
-  }
-  STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
-  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
+void silu_mul_quantize(const char* op, const Tensor& X, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method, bool blocked) {
+  const int64_t rot = quant_prelude(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, gscale, &method);
   STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of A must be 2 * I");
-  const int64_t rot = R.size(0), inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter), numel = rows * inter, gs = nv ? 16 : 32;
-  if (nv) {
-    STD_TORCH_CHECK(rot == 16 || rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 16, 32, 64, or 128.");
-  } else {
-    STD_TORCH_CHECK(rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 32, 64, or 128.");
-  }
-  STD_TORCH_CHECK(inter % (rot < 32 ? 32 : rot) == 0, "the gate / up width must be divisible by", rot < 32 ? 32 : rot);
-  STD_TORCH_CHECK(nbytes(OUT) >= numel / 2, "OUT is too small");
-  if (blocked) {
-    STD_TORCH_CHECK(nbytes(OUT_sf) >= (rows + 127) / 128 * 128 * ((inter / gs + 3) / 4 * 4), "OUT_sf is too small for the blocked scale layout");
-  } else {
-    STD_TORCH_CHECK(nbytes(OUT_sf) >= numel / gs, "OUT_sf is too small");
-  }
+  const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
+  quant_check_rot(gscale, rot);
+  STD_TORCH_CHECK(inter % quant_rp(rot) == 0, "the gate / up width must be divisible by", quant_rp(rot));
+  quant_check_out(gscale, OUT, OUT_sf, rows * inter, inter, blocked);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
-  if (nv)
-    check_rc(qutlass_amd_fused_silu_mul_quantize_nv(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, static_cast<const float*>(gscale->data_ptr()),
-                                                    blocked ? 1 : 0, OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
+  if (gscale)
+    check_rc(qutlass_amd_fused_silu_mul_quantize_nv(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, gscale_ptr(gscale), blocked ? 1 : 0, OUT.data_ptr(),
+                                                    OUT_sf.data_ptr(), current_stream(X)));
   else
     check_rc(qutlass_amd_fused_silu_mul_quantize_mx(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, blocked ? 1 : 0, OUT.data_ptr(), OUT_sf.data_ptr(),
                                                     current_stream(X)));
 }
 void fusedSiluMulQuantizeMx_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, int64_t method, bool blocked) {
-  silu_mul_quantize(blocked ? "fusedSiluMulQuantizeMxBlocked" : "fusedSiluMulQuantizeMx", false, A, R, OUT, OUT_sf, nullptr, method, blocked);
+  silu_mul_quantize(blocked ? "fusedSiluMulQuantizeMxBlocked" : "fusedSiluMulQuantizeMx", A, R, OUT, OUT_sf, nullptr, method, blocked);
 }
 void fusedSiluMulQuantizeNv_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale, int64_t method, bool blocked) {
-  silu_mul_quantize(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", true, A, R, OUT, OUT_sf, &global_scale, method, blocked);
+  silu_mul_quantize(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", A, R, OUT, OUT_sf, &global_scale, method, blocked);
 }
 
 // ---- EXTENSION: MoE dispatch and combine around the grouped GEMMs ---------------------------------------------------------------------
 // fusedGatherQuantize{Mx,Nv}_: fusedQuantize{Mx,Nv}_ of A.index_select(0, src_row) in one launch, byte for byte; A (T, K) bf16, src_row (M) int32 read on the device (no
 // host sync).  OUT / OUT_sf are sized as for the plain quantizers on an (M, K) tensor; flat scales.
-void gather_quantize(const char* op, bool nv, const Tensor& X, const Tensor& R, const Tensor& src_row, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method) {
-  require_contiguous(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  if (nv) {
-    require_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
-    require_same_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}, {*gscale, "global_scale"}});
-  } else {
-    require_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-    require_same_gpu(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}});
-  }
-  quant_prologue(op, X, R);
-  if (nv) {
-    STD_TORCH_CHECK(has_dtype(*gscale, ScalarType::Float), "global_scale must be float");
-    STD_TORCH_CHECK(gscale->dim() == 1 && gscale->size(0) == 1, "global_scale must be a scalar");
-  }
-  STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
-  STD_TORCH_CHECK(R.dim() == 2 && R.size(0) == R.size(1), "Rotation matrix must be square");
+void gather_quantize(const char* op, const Tensor& X, const Tensor& R, const Tensor& src_row, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method) {
+  const int64_t rot = quant_prelude(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, gscale, &method);
   STD_TORCH_CHECK(X.dim() == 2 && X.size(1) > 0, "A must be 2D (T, K)");
   STD_TORCH_CHECK(has_dtype(src_row, ScalarType::Int) && src_row.dim() == 1, "src_row must be a 1D int32 tensor");
-  const int64_t rot = R.size(0), T = X.size(0), K = X.size(1), M = src_row.size(0), gs = nv ? 16 : 32;
-  if (nv) {
-    STD_TORCH_CHECK(rot == 16 || rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 16, 32, 64, or 128.");
-  } else {
-    STD_TORCH_CHECK(rot == 32 || rot == 64 || rot == 128, "Unsupported rotation size ", rot, "; expected 32, 64, or 128.");
-  }
-  STD_TORCH_CHECK(K % (rot < 32 ? 32 : rot) == 0, "the last dimension of A must be divisible by", rot < 32 ? 32 : rot);
-  STD_TORCH_CHECK(nbytes(OUT) >= M * K / 2, "OUT is too small");
-  STD_TORCH_CHECK(nbytes(OUT_sf) >= M * K / gs, "OUT_sf is too small");
+  const int64_t T = X.size(0), K = X.size(1), M = src_row.size(0);
+  quant_check_rot(gscale, rot);
+  STD_TORCH_CHECK(K % quant_rp(rot) == 0, "the last dimension of A must be divisible by", quant_rp(rot));
+  quant_check_out(gscale, OUT, OUT_sf, M * K, K, false);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
-  if (nv)
+  if (gscale)
     check_rc(qutlass_amd_fused_gather_quantize_nv(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, (int)method,
-                                                  static_cast<const float*>(gscale->data_ptr()), OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
+                                                  gscale_ptr(gscale), OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
   else
     check_rc(qutlass_amd_fused_gather_quantize_mx(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, (int)method,
                                                   OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
 }
 void fusedGatherQuantizeMx_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf, int64_t method) {
-  gather_quantize("fusedGatherQuantizeMx", false, A, R, src_row, OUT, OUT_sf, nullptr, method);
+  gather_quantize("fusedGatherQuantizeMx", A, R, src_row, OUT, OUT_sf, nullptr, method);
 }
 void fusedGatherQuantizeNv_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale, int64_t method) {
-  gather_quantize("fusedGatherQuantizeNv", true, A, R, src_row, OUT, OUT_sf, &global_scale, method);
+  gather_quantize("fusedGatherQuantizeNv", A, R, src_row, OUT, OUT_sf, &global_scale, method);
 }
 
 // moeCombine_: OUT[t] = sum_k weights[t][k] * Y[pos[t][k]] (the arithmetic is spelled out at qutlass_amd_moe_combine_bf16); slots with pos outside [0, M) are skipped

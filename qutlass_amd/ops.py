@@ -9,11 +9,14 @@ fallback: if the extension is not built, loading it raises.
 """
 from __future__ import annotations
 
+import math
 import os
+from typing import Callable, NamedTuple
 
 import torch
 
 from . import _lib
+from .utils import padded_scale_shape
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # QUTLASS_AMD_OP_LIBRARY: another build of the op library, e.g. the trimmed one (qutlass_amd.build.build_extension(minimal=True), the reference's QUTLASS_MINIMAL_BUILD)
@@ -107,97 +110,19 @@ def _define_functional_ops() -> None:
     amd = torch.ops.qutlass_amd
     have_training_ops = hasattr(amd, "backward_t_bf16_")
 
-    def _mx(a, blocked=False):
-        rows, cols = a.numel() // a.size(-1), a.size(-1) // 32
-        pr, pc = (rows + 127) // 128 * 128, (cols + 3) // 4 * 4
-        return (a.new_empty((*a.shape[:-1], a.size(-1) // 2), dtype=torch.uint8),
-                a.new_empty((pr * pc,) if blocked else (pr, pc), dtype=torch.float8_e8m0fnu))
+    # the rotate + quantize family: one registration per row of QUANT_OPS
+    for name, row in QUANT_OPS.items():
+        op = custom_op(f"qutlass_amd::{name}", mutates_args=(), schema=row.schema)(lambda *args, _row=row: run_quant(_row, *args))
+        op.register_fake(lambda *args, _row=row: alloc_quant(_row, *args))
 
-    def _nv(a, blocked=False):
-        rows, cols = a.numel() // a.size(-1), a.size(-1) // 16
-        pr, pc = (rows + 127) // 128 * 128, (cols + 3) // 4 * 4
-        return (a.new_empty((*a.shape[:-1], a.size(-1) // 2), dtype=torch.uint8),
-                a.new_empty((pr * pc,) if blocked else (pr, pc), dtype=torch.float8_e4m3fn))
-
-    @custom_op("qutlass_amd::quantize_mx", mutates_args=(), schema="(Tensor A, Tensor R, int method) -> (Tensor, Tensor)")
-    def quantize_mx(A, R, method):
-        o = _mx(A)
-        amd.fusedQuantizeMx_(A, R, o[0], o[1], method)
-        return o
-
-    quantize_mx.register_fake(lambda A, R, method: _mx(A))
-
-    @custom_op("qutlass_amd::quantize_nv", mutates_args=(), schema="(Tensor A, Tensor R, Tensor global_scale, int method) -> (Tensor, Tensor)")
-    def quantize_nv(A, R, global_scale, method):
-        o = _nv(A)
-        amd.fusedQuantizeNv_(A, R, o[0], o[1], global_scale, method)
-        return o
-
-    quantize_nv.register_fake(lambda A, R, global_scale, method: _nv(A))
-
-    @custom_op("qutlass_amd::quantize_mx_blocked", mutates_args=(), schema="(Tensor A, Tensor R, int method) -> (Tensor, Tensor)")
-    def quantize_mx_blocked(A, R, method):
-        o = _mx(A, True)
-        amd.fusedQuantizeMxBlocked(A, R, o[0], o[1], method)
-        return o
-
-    quantize_mx_blocked.register_fake(lambda A, R, method: _mx(A, True))
-
-    @custom_op("qutlass_amd::quantize_nv_blocked", mutates_args=(), schema="(Tensor A, Tensor R, Tensor global_scale, int method) -> (Tensor, Tensor)")
-    def quantize_nv_blocked(A, R, global_scale, method):
-        o = _nv(A, True)
-        amd.fusedQuantizeNvBlocked(A, R, o[0], o[1], global_scale, method)
-        return o
-
-    quantize_nv_blocked.register_fake(lambda A, R, global_scale, method: _nv(A, True))
-
-    # gated MLP: X is (.., 2 I) [gate | up]; the results have the shapes of the plain quantizers on a (.., I) tensor
-    def _act(x):
-        return x.new_empty((*x.shape[:-1], x.size(-1) // 2))
-
+    # gated MLP: X is (.., 2 I) [gate | up]
     @custom_op("qutlass_amd::silu_and_mul", mutates_args=(), schema="(Tensor X) -> Tensor")
     def silu_and_mul(X):
-        o = _act(X)
+        o = X.new_empty(_act(X))
         amd.siluAndMul_(X, o)
         return o
 
-    silu_and_mul.register_fake(_act)
-
-    @custom_op("qutlass_amd::silu_mul_quantize_mx", mutates_args=(), schema="(Tensor A, Tensor R, int method, bool blocked) -> (Tensor, Tensor)")
-    def silu_mul_quantize_mx(A, R, method, blocked):
-        o = _mx(_act(A), blocked)
-        amd.fusedSiluMulQuantizeMx_(A, R, o[0], o[1], method, blocked)
-        return o
-
-    silu_mul_quantize_mx.register_fake(lambda A, R, method, blocked: _mx(_act(A), blocked))
-
-    @custom_op("qutlass_amd::silu_mul_quantize_nv", mutates_args=(), schema="(Tensor A, Tensor R, Tensor global_scale, int method, bool blocked) -> (Tensor, Tensor)")
-    def silu_mul_quantize_nv(A, R, global_scale, method, blocked):
-        o = _nv(_act(A), blocked)
-        amd.fusedSiluMulQuantizeNv_(A, R, o[0], o[1], global_scale, method, blocked)
-        return o
-
-    silu_mul_quantize_nv.register_fake(lambda A, R, global_scale, method, blocked: _nv(_act(A), blocked))
-
-    # MoE dispatch / combine: the gathered operand is A[src_row], (M, K) for M indices; the results have the shapes of the plain quantizers on such a tensor
-    def _gathered(A, src_row):
-        return A.new_empty((src_row.size(0), A.size(-1)))
-
-    @custom_op("qutlass_amd::gather_quantize_mx", mutates_args=(), schema="(Tensor A, Tensor R, Tensor src_row, int method) -> (Tensor, Tensor)")
-    def gather_quantize_mx(A, R, src_row, method):
-        o = _mx(_gathered(A, src_row))
-        amd.fusedGatherQuantizeMx_(A, R, src_row, o[0], o[1], method)
-        return o
-
-    gather_quantize_mx.register_fake(lambda A, R, src_row, method: _mx(_gathered(A, src_row)))
-
-    @custom_op("qutlass_amd::gather_quantize_nv", mutates_args=(), schema="(Tensor A, Tensor R, Tensor src_row, Tensor global_scale, int method) -> (Tensor, Tensor)")
-    def gather_quantize_nv(A, R, src_row, global_scale, method):
-        o = _nv(_gathered(A, src_row))
-        amd.fusedGatherQuantizeNv_(A, R, src_row, o[0], o[1], global_scale, method)
-        return o
-
-    gather_quantize_nv.register_fake(lambda A, R, src_row, global_scale, method: _nv(_gathered(A, src_row)))
+    silu_and_mul.register_fake(lambda X: X.new_empty(_act(X)))
 
     def _combined(Y, pos):
         return Y.new_empty((pos.size(0), Y.size(-1)))
@@ -238,7 +163,7 @@ def _define_functional_ops() -> None:
         return
 
     def _mask(a):
-        return _mx(a) + (a.new_empty((*a.shape[:-1], a.size(-1) // 8), dtype=torch.uint8),)
+        return alloc_quant(QUANT_OPS["quantize_mx"], a) + (a.new_empty((*a.shape[:-1], a.size(-1) // 8), dtype=torch.uint8),)
 
     @custom_op("qutlass_amd::quantize_mx_mask", mutates_args=(), schema="(Tensor A, Tensor R) -> (Tensor, Tensor, Tensor)")
     def quantize_mx_mask(A, R):
@@ -298,6 +223,62 @@ def _define_functional_ops() -> None:
         return o
 
     transpose_mxfp8.register_fake(lambda x_fp4, scales: _tr(x_fp4, scales))
+
+
+# ---- the rotate + quantize family: the functional ops `qutlass_amd::<name>`, their fake kernels and the eager wrappers of __init__.py come from this table ----------
+# schema:  of the functional op -- the leading tensors, [global_scale,] method[, blocked]
+# twin:    the in-place op of csrc/torch_ext.cpp: the same arguments with OUT, OUT_sf inserted after the `lead` leading tensors
+# operand: the shape of the tensor that is rotated and quantized, from the leading tensors -- the results are the plain quantizers' for a tensor of that shape
+# fmt:     a key of QUANT_FORMATS;  blocked: scales flat in the to_blocked() layout -- fixed by the op, or None where it is the op's last argument
+class QuantOp(NamedTuple):
+    schema: str
+    twin: str
+    lead: int
+    operand: Callable
+    fmt: str
+    blocked: bool | None
+
+
+def _same(A, R=None):
+    return tuple(A.shape)
+
+
+def _act(X, R=None):   # gated MLP: X is (.., 2 I) [gate | up], the operand (.., I)
+    return (*X.shape[:-1], X.size(-1) // 2)
+
+
+def _gathered(A, R, src_row):   # MoE dispatch: the operand is A[src_row], (M, K) for M indices
+    return (src_row.size(0), A.size(-1))
+
+
+QUANT_FORMATS = {"mx": (32, torch.float8_e8m0fnu), "nv": (16, torch.float8_e4m3fn)}   # elements per scale, scale dtype
+QUANT_OPS = {
+    "quantize_mx": QuantOp("(Tensor A, Tensor R, int method) -> (Tensor, Tensor)", "fusedQuantizeMx_", 2, _same, "mx", False),
+    "quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedQuantizeNv_", 2, _same, "nv", False),
+    "quantize_mx_blocked": QuantOp("(Tensor A, Tensor R, int method) -> (Tensor, Tensor)", "fusedQuantizeMxBlocked", 2, _same, "mx", True),
+    "quantize_nv_blocked": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedQuantizeNvBlocked", 2, _same, "nv", True),
+    "silu_mul_quantize_mx": QuantOp("(Tensor A, Tensor R, int method, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeMx_", 2, _act, "mx", None),
+    "silu_mul_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeNv_", 2, _act, "nv", None),
+    "gather_quantize_mx": QuantOp("(Tensor A, Tensor R, Tensor src_row, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeMx_", 3, _gathered, "mx", False),
+    "gather_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor src_row, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeNv_", 3, _gathered, "nv", False),
+}
+
+
+def alloc_quant(row: QuantOp, *args):
+    """The results of one family op, uninitialised: packed e2m1 (.., K / 2) uint8 and the scales -- (padded_rows, padded_cols), or their product flat when blocked --
+    of the operand (.., K); args as the functional op takes them.  The one allocator of the fake kernels, the functional ops and the eager wrappers."""
+    shape = row.operand(*args[:row.lead])
+    group, sf_dtype = QUANT_FORMATS[row.fmt]
+    pr, pc = padded_scale_shape(math.prod(shape) // shape[-1], shape[-1], group)
+    blocked = args[-1] if row.blocked is None else row.blocked
+    return (args[0].new_empty((*shape[:-1], shape[-1] // 2), dtype=torch.uint8), args[0].new_empty((pr * pc,) if blocked else (pr, pc), dtype=sf_dtype))
+
+
+def run_quant(row: QuantOp, *args):
+    """Allocate, then the in-place twin."""
+    o = alloc_quant(row, *args)
+    getattr(torch.ops.qutlass_amd, row.twin)(*args[:row.lead], o[0], o[1], *args[row.lead:])
+    return o
 
 
 def _alloc_topk(logits: torch.Tensor, topk: int):

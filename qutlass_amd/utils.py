@@ -13,16 +13,19 @@ def ceil_div(a, b):
     return (a + b - 1) // b
 
 
+def padded_scale_shape(rows, k, group):
+    """The (rows, k / group) scale matrix of a (rows, k) operand, padded to whole 128 x 4 tiles: the one place this arithmetic lives."""
+    return ceil_div(rows, 128) * 128, ceil_div(k // group, 4) * 4
+
+
 def get_padded_shape_mx(a: torch.Tensor):
     """qutlass/utils.py:140-147."""
-    rows, cols = a.numel() // a.size(-1), a.size(-1) // 32
-    return ceil_div(rows, 128) * 128, ceil_div(cols, 4) * 4
+    return padded_scale_shape(a.numel() // a.size(-1), a.size(-1), 32)
 
 
 def get_padded_shape_nv(a: torch.Tensor):
     """qutlass/utils.py:150-157."""
-    rows, cols = a.numel() // a.size(-1), a.size(-1) // 16
-    return ceil_div(rows, 128) * 128, ceil_div(cols, 4) * 4
+    return padded_scale_shape(a.numel() // a.size(-1), a.size(-1), 16)
 
 
 def to_blocked(input_matrix: torch.Tensor, use_triton_kernel: bool = False) -> torch.Tensor:
