@@ -306,6 +306,30 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
                                  void* stream);
 
 /*
+ * EXTENSION (no reference counterpart): the two NV quantizers of the MoE chain with ONE GLOBAL SCALE PER EXPERT -- what the per-expert alpha of
+ * qutlass_amd_grouped_matmul_nvf4_bf16_tn (alpha[g] = 1 / (a_gs[g] * w_gs[g])) expects of its A operand, in one graph-capturable launch.
+ *   global_scales  float32 (e), device memory;  offs  int32 (e), device memory, 4-byte aligned: the grouped GEMMs' cumulative END rows (qutlass_amd_moe_sort's offs);
+ *   1 <= e <= 1024.  The expert of operand row r (a sorted row: r < m for the gathering entry, r < rows for the gated one) is
+ *       g(r) = min(e - 1, #{ g : offs[g] <= r })
+ *   -- for non-decreasing offs the group the grouped GEMM puts the row in; rows at or past offs[e - 1] (the dropped slots, which the GEMM never reads) take expert
+ *   e - 1's scale, so every output byte is defined.
+ * The bytes of row r, codes and e4m3 scales, are those of the single-scale entry (qutlass_amd_fused_gather_quantize_nv / qutlass_amd_fused_silu_mul_quantize_nv with
+ * blocked == 0) called with global_scales[g(r)]; everything else is the sibling's, byte for byte: rotation, scale rule, encoder, FLAT row-major scales with the rest
+ * of the caller's buffer untouched (there is no blocked form: the grouped GEMMs read this buffer as it is), the zero-row rule for bad src_row entries, the 2 GiB
+ * limit on x.  method quest never reads a global scale: the result is the sibling's, whatever global_scales and offs hold.
+ * Malformed offs (negative, beyond the row count, decreasing) cannot fault: the kernel reads offs[0, e) and global_scales[0, e) only, every index clamped, and each
+ * row is quantized with the scale of SOME expert in [0, e) -- which one is then unspecified.  No host sync, no workspace.
+ * Checks: the sibling's chain in the sibling's order under the name fusedGatherQuantizeNvGrouped / fusedSiluMulQuantizeNvGrouped -- m == 0 / rows == 0 returns
+ * QAMD_OK where the sibling does, a null offs joins its null-pointer check --, then e outside [1, 1024], then the alignment of offs; all before any HIP call.
+ */
+int qutlass_amd_fused_gather_quantize_nv_grouped(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method,
+                                                 const float* global_scales, const int32_t* offs, int64_t e, void* out_e2m1, void* out_e4m3,
+                                                 void* stream);
+int qutlass_amd_fused_silu_mul_quantize_nv_grouped(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
+                                                   const float* global_scales, const int32_t* offs, int64_t e, void* out_e2m1, void* out_e4m3,
+                                                   void* stream);
+
+/*
  * EXTENSION (no reference counterpart): MoE routing, the step in front of the dispatch above -- router logits to expert ids and weights, and expert ids to the
  * sorted-row metadata the gathering quantizers, the grouped GEMMs and moe_combine read.  Every argument check happens before any HIP call.
  *

@@ -11,6 +11,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
+    fusedGatherQuantizeNvGrouped, fusedSiluMulQuantizeNvGrouped  (extension: the two NVFP4 quantizers of the MoE chain with one global scale per expert)
     moe_topk_softmax, moe_sort_fused, moe_route           (extension: MoE routing in HIP -- router logits to ids, weights and the sorted-row metadata)
     moe_topk_grouped, moe_route_grouped                   (extension: the grouped router of DeepSeek-V2 / V3 and Kimi-K2 -- sigmoid / softmax scores, selection bias, group-limited top-k)
 
@@ -391,6 +392,31 @@ def fusedGatherQuantizeNv(x: torch.Tensor, h: torch.Tensor, global_scale: torch.
     """EXTENSION: ``fusedQuantizeNv(x.index_select(0, src_row), h, global_scale, method=method)`` in one launch, byte for byte (see fusedGatherQuantizeMx); R may be
     16; e4m3 scales flat in the first M * K / 16 bytes -- what grouped_matmul_nvf4_bf16_tn reads as it is.  x below 2 GiB."""
     return _quantize("gather_quantize_nv", x, h, src_row, global_scale, _method_code(method))
+
+
+def fusedGatherQuantizeNvGrouped(x: torch.Tensor, h: torch.Tensor, global_scales: torch.Tensor, src_row: torch.Tensor, offs: torch.Tensor, *,
+                                 method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): ``fusedGatherQuantizeNv`` with ONE GLOBAL SCALE PER EXPERT, in one launch -- the A operand that
+    grouped_matmul_nvf4_bf16_tn's per-expert alpha (alpha[g] = 1 / (a_gs[g] * w_gs[g])) expects, for checkpoints that carry an activation scale per expert.
+
+    global_scales  (E,) float32 on the device;  offs  (E,) int32 on the device: the grouped GEMMs' cumulative END rows (moe_sort's / moe_sort_fused's second result);
+    1 <= E <= 1024.  The expert of sorted row m is g(m) = min(E - 1, #{g : offs[g] <= m}): the group the grouped GEMM puts the row in; rows at or past offs[-1] (the
+    dropped slots, which the GEMM never reads) take expert E - 1's scale, so every byte is defined.
+
+    The bytes of row m, codes and e4m3 scales, are those of ``fusedGatherQuantizeNv(x, h, global_scales[g(m):g(m)+1], src_row, method=method)``; everything else is that
+    function's: flat scales in the first M * K / 16 bytes with the padding untouched, an all-zero row for an index outside [0, T), x below 2 GiB.  method "quest" reads
+    no global scale: the result is fusedGatherQuantizeNv's.  offs is read on the device (no host sync, no workspace: graph-capturable; traces under torch.compile);
+    malformed offs (negative, above M, decreasing) cannot fault -- every row is then quantized with the scale of SOME expert in [0, E), which one is unspecified.
+    Cost against the single-scale op: DESIGN.md section 10."""
+    return _quantize("gather_quantize_nv_grouped", x, h, src_row, global_scales, offs, _method_code(method))
+
+
+def fusedSiluMulQuantizeNvGrouped(x: torch.Tensor, h: torch.Tensor, global_scales: torch.Tensor, offs: torch.Tensor, *,
+                                  method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedSiluMulQuantizeNv`` with one global scale per expert (see fusedGatherQuantizeNvGrouped): row m of act = silu(gate) * up, x = (M, 2 I) the sorted
+    rows a grouped gate/up GEMM returned, is quantized with global_scales[g(m)], g(m) from offs (E,) int32 -- the down projection's A operand.  The bytes of row m are
+    those of ``fusedSiluMulQuantizeNv(x, h, global_scales[g(m):g(m)+1], method=method)``; flat scales only (what grouped_matmul_nvf4_bf16_tn reads as it is); x below 2 GiB."""
+    return _silu_mul_quantize("silu_mul_quantize_nv_grouped", x, h, global_scales, offs, _method_code(method))
 
 
 def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:

@@ -1252,11 +1252,19 @@ int debug_plan(const char* name, int64_t M, int64_t N, int64_t rowbytes, int gra
 
 // One rotation switch for the rotate + quantize family.  KIND picks the __global__ wrapper (quantize.hip.h): the plain quantizer, the gated one (act = silu(gate) * up
 // computed in the tile loads) or the gathering one (the tile loads go through a row index).  BLK: scales written in the to_blocked() layout.
-enum QuantKind { QK_PLAIN, QK_GATED, QK_GATHER };
+// The _GSCALE kinds are the gated and the gathering quantizer with one global scale per expert (quantize.hip.h, GSCALE): NV abs-max with flat scales and nothing else.
+enum QuantKind { QK_PLAIN, QK_GATED, QK_GATHER, QK_GATED_GSCALE, QK_GATHER_GSCALE };
 
 template <int KIND, int R, bool NV, int METHOD, bool MASK, bool BLK>
 int launch_quant(const QuantParams& p, hipStream_t s, int grid) {
-  if constexpr (KIND == QK_GATED) {
+  static_assert((KIND != QK_GATED_GSCALE && KIND != QK_GATHER_GSCALE) || (NV && METHOD == METHOD_ABSMAX && !MASK && !BLK), "per-expert global scales: NV abs-max, flat scales");
+  if constexpr (KIND == QK_GATED_GSCALE) {
+    hipLaunchKernelGGL((fused_silu_mul_quantize_gscale_kernel<R>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_silu_mul_quantize_gscale_kernel");
+  } else if constexpr (KIND == QK_GATHER_GSCALE) {
+    hipLaunchKernelGGL((fused_gather_quantize_gscale_kernel<R>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_gather_quantize_gscale_kernel");
+  } else if constexpr (KIND == QK_GATED) {
     hipLaunchKernelGGL((fused_silu_mul_quantize_kernel<R, NV, METHOD, BLK>), dim3(grid), dim3(256), 0, s, p);
     return check_launch("fused_silu_mul_quantize_kernel");
   } else if constexpr (KIND == QK_GATHER) {
@@ -1277,7 +1285,7 @@ int launch_quant(const QuantParams& p, hipStream_t s, int grid) {
 template <int KIND, bool NV, int METHOD, bool MASK, bool BLK>
 int dispatch_quant(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
   static_assert(!MASK || (KIND == QK_PLAIN && !NV && METHOD == METHOD_QUEST), "the clip mask exists for the plain MX quest quantizer only");
-  static_assert(!BLK || KIND != QK_GATHER, "the gathering quantizers write flat scales only");
+  static_assert(!BLK || (KIND != QK_GATHER && KIND != QK_GATED_GSCALE && KIND != QK_GATHER_GSCALE), "the gathering and the grouped-scale quantizers write flat scales only");
   switch (rot) {
     case 16:
       if constexpr (NV) return launch_quant<KIND, 16, NV, METHOD, false, BLK>(p, s, grid);
@@ -1311,6 +1319,8 @@ QAMD_QUANT_INST(QK_PLAIN, false, METHOD_QUEST, true, true)
 QAMD_QUANT_FORMATS(QK_GATED, false)
 QAMD_QUANT_FORMATS(QK_GATED, true)
 QAMD_QUANT_FORMATS(QK_GATHER, false)
+QAMD_QUANT_INST(QK_GATED_GSCALE, true, METHOD_ABSMAX, false, false)
+QAMD_QUANT_INST(QK_GATHER_GSCALE, true, METHOD_ABSMAX, false, false)
 #undef QAMD_QUANT_FORMATS
 #undef QAMD_QUANT_INST
 #endif
@@ -1418,6 +1428,20 @@ inline int quant_fill(QuantParams& p, const QuantFormat& f, int rot, int64_t num
   return blocked ? blocked_pad_grid(grid, p.sf_rows, p.sf_cols) : grid;
 }
 
+// per-expert global scales (the *_nv_grouped entries): offs (e) = the grouped GEMMs' cumulative END rows, read by the kernel; the entry's global scale then has e floats
+struct QuantGroups {
+  const int32_t* offs;
+  int64_t e;
+};
+static_assert(qamd::QUANT_MAX_E == qamd::GRP_MAX_E, "the quantizers take as many experts as the grouped GEMMs");
+
+// the two checks a grouped entry adds behind its sibling's chain (a null offs joins the sibling's null-pointer check)
+inline int quant_check_groups(const char* name, const QuantGroups& g) {
+  if (g.e < 1 || g.e > qamd::QUANT_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, qamd::QUANT_MAX_E, (long long)g.e);
+  if ((uintptr_t)g.offs % 4) return fail(QAMD_ERR_INVALID, "%s: offs must be 4-byte aligned", name);
+  return QAMD_OK;
+}
+
 // runtime (nv, method, mask, blocked) -> the dispatch_quant instantiation; the callers have checked method, and that a mask comes with MX + quest only
 template <int KIND>
 int select_quant(bool nv, int method, bool mask, bool blocked, int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
@@ -1432,6 +1456,15 @@ int select_quant(bool nv, int method, bool mask, bool blocked, int rot, const Qu
     if (mask) return go(std::false_type{}, Quest{}, std::true_type{});
   if (nv) return method == QAMD_METHOD_QUEST ? go(std::true_type{}, Quest{}, std::false_type{}) : go(std::true_type{}, AbsMax{}, std::false_type{});
   return method == QAMD_METHOD_QUEST ? go(std::false_type{}, Quest{}, std::false_type{}) : go(std::false_type{}, AbsMax{}, std::false_type{});
+}
+
+// the grouped-scale form of KIND (QK_GATED / QK_GATHER), NV with flat scales.  Quest never reads a global scale (quantize.hip.h, the NV Quest arm): it runs the
+// single-scale kernel; abs-max runs the GSCALE kernel over p.offs / p.E.
+template <int KIND>
+int select_quant_grouped(int method, int rot, QuantParams& p, const QuantGroups& g, hipStream_t s, int grid, const char* name) {
+  if (method == QAMD_METHOD_QUEST) return select_quant<KIND>(true, method, false, false, rot, p, s, grid, name);
+  p.offs = g.offs; p.E = (int)g.e;
+  return dispatch_quant<KIND == QK_GATED ? QK_GATED_GSCALE : QK_GATHER_GSCALE, true, METHOD_ABSMAX, false, false>(rot, p, s, grid, name);
 }
 
 #endif   // QAMD_DEF(1)
@@ -1803,19 +1836,21 @@ int qutlass_amd_silu_mul_bf16(const void* x, int64_t rows, int64_t inter, void* 
 }
 
 static int fused_silu_mul_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
-                                        const float* global_scale, int blocked, void* out_e2m1, void* out_sf, void* stream) {
+                                        const float* global_scale, int blocked, void* out_e2m1, void* out_sf, void* stream, const QuantGroups* grp = nullptr) {
   if (int rc = quant_check_rot(name, f, rot)) return rc;
   if (int rc = quant_check_method(name, method)) return rc;
   if (int rc = gated_common_check(name, x, rows, inter, quant_rp(rot))) return rc;
   // x is addressed with 32-bit offsets from one buffer descriptor (quantize.hip.h, GATED): no silent wrap beyond it
   if (rows * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: x (rows * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(rows * inter * 4));
   if (rows == 0) return QAMD_OK;
-  if (!x || !h || !out_e2m1 || !out_sf || (f.nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (!x || !h || !out_e2m1 || !out_sf || (f.nv && !global_scale) || (grp && !grp->offs)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   if (int rc = quant_check_h(name, rot, h)) return rc;
+  if (grp) if (int rc = quant_check_groups(name, *grp)) return rc;
   QuantParams p;
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
   p.out_mask = nullptr; p.global_scale = global_scale; p.inter = (int)inter;
   const int grid = quant_fill(p, f, rot, rows * inter, inter, blocked != 0);
+  if (grp) return select_quant_grouped<QK_GATED>(method, rot, p, *grp, (hipStream_t)stream, grid, name);
   return select_quant<QK_GATED>(f.nv, method, false, blocked != 0, rot, p, (hipStream_t)stream, grid, name);
 }
 
@@ -1835,7 +1870,7 @@ int qutlass_amd_fused_silu_mul_quantize_nv(const void* x, const void* h, int rot
 // Dispatch: fusedQuantize{Mx,Nv}(x.index_select(0, src_row)) in one launch, byte for byte -- the quantizer's tile loads go through the row index (quantize.hip.h,
 // GATHER), so the (M, K) bf16 copy of the routed tokens is never written.
 static int fused_gather_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row,
-                                      int64_t m, int method, const float* global_scale, void* out_e2m1, void* out_sf, void* stream) {
+                                      int64_t m, int method, const float* global_scale, void* out_e2m1, void* out_sf, void* stream, const QuantGroups* grp = nullptr) {
   if (int rc = quant_check_rot(name, f, rot)) return rc;
   if (int rc = quant_check_method(name, method)) return rc;
   if (t < 0 || m < 0 || k <= 0 || t >= (1ll << 31) || m >= (1ll << 31) || k >= (1ll << 31))
@@ -1846,12 +1881,14 @@ static int fused_gather_quantize_impl(const char* name, const QuantFormat& f, co
   if (t * k >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: x (rows * k * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(t * k * 2));
   if (m * k >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: more than 2^31 elements is not supported", name);
   if (m == 0) return QAMD_OK;
-  if ((!x && t > 0) || !h || !src_row || !out_e2m1 || !out_sf || (f.nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if ((!x && t > 0) || !h || !src_row || !out_e2m1 || !out_sf || (f.nv && !global_scale) || (grp && !grp->offs)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   if (int rc = quant_check_h(name, rot, h)) return rc;
+  if (grp) if (int rc = quant_check_groups(name, *grp)) return rc;
   QuantParams p;
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
   p.out_mask = nullptr; p.global_scale = global_scale; p.inter = (int)k;
   const int grid = quant_fill(p, f, rot, m * k, k, false, src_row, t);
+  if (grp) return select_quant_grouped<QK_GATHER>(method, rot, p, *grp, (hipStream_t)stream, grid, name);
   return select_quant<QK_GATHER>(f.nv, method, false, false, rot, p, (hipStream_t)stream, grid, name);
 }
 
@@ -1863,6 +1900,20 @@ int qutlass_amd_fused_gather_quantize_mx(const void* x, const void* h, int rot, 
 int qutlass_amd_fused_gather_quantize_nv(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method,
                                          const float* global_scale, void* out_e2m1, void* out_e4m3, void* stream) {
   return fused_gather_quantize_impl("fusedGatherQuantizeNv", kQuantNv, x, h, rot, t, k, src_row, m, method, global_scale, out_e2m1, out_e4m3, stream);
+}
+
+// The grouped-scale forms of the two NV quantizers of the MoE chain: one global scale per expert, the expert of a row found from offs by the kernel (quantize.hip.h,
+// GSCALE).  Each runs its sibling's chain under its own name (a null offs joins the null-pointer check), then quant_check_groups.
+int qutlass_amd_fused_gather_quantize_nv_grouped(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method,
+                                                 const float* global_scales, const int32_t* offs, int64_t e, void* out_e2m1, void* out_e4m3, void* stream) {
+  const QuantGroups grp{offs, e};
+  return fused_gather_quantize_impl("fusedGatherQuantizeNvGrouped", kQuantNv, x, h, rot, t, k, src_row, m, method, global_scales, out_e2m1, out_e4m3, stream, &grp);
+}
+
+int qutlass_amd_fused_silu_mul_quantize_nv_grouped(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, const float* global_scales,
+                                                   const int32_t* offs, int64_t e, void* out_e2m1, void* out_e4m3, void* stream) {
+  const QuantGroups grp{offs, e};
+  return fused_silu_mul_quantize_impl("fusedSiluMulQuantizeNvGrouped", kQuantNv, x, h, rot, rows, inter, method, global_scales, 0, out_e2m1, out_e4m3, stream, &grp);
 }
 
 // Combine: out[t] = sum_k w[t][k] * y[pos[t][k]] in the order and with the roundings moe_combine_bf16_kernel states (quantize.hip.h); slots outside [0, m) are skipped.
@@ -2374,6 +2425,13 @@ int qutlass_amd_debug_grouped_decode(const int32_t* offs, int E, int M, int TM, 
     }
   }
   return n;
+}
+
+// debug only (not declared in the public header): the expert of operand row m in the grouped-scale quantizers (quantize.hip.h quant_group_of_row, the SAME function
+// the two kernels run) over host offs[0 .. E); -1 when the arguments are rejected.  No GPU touched.
+int qutlass_amd_debug_group_of_row(const int32_t* offs, int E, int m) {
+  if (!offs || E < 1 || E > qamd::QUANT_MAX_E) return -1;
+  return qamd::quant_group_of_row(offs, E, m);
 }
 
 // debug only (not declared in the public header): the form a grouped op's rule picks on a 256-CU part, after the entry's own argument checks (-1: rejected);

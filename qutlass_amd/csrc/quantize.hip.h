@@ -42,7 +42,31 @@ struct QuantParams {
   // inter is the row length K here.  An index outside [0, src_n) stands for an all-zero row.  The plain and the gated kernels never read these.
   const int32_t* src_row = nullptr;
   int src_n = 0;
+  // GSCALE kernels only (fused{Gather,SiluMul}QuantizeNvGrouped): global_scale points at E floats, one per expert, and offs (E) holds the grouped GEMMs' cumulative END
+  // rows -- row m of the operand takes global_scale[quant_group_of_row(offs, E, m)].  No other kernel reads them.  (E sits in the tail padding; offs grows the struct.)
+  int E = 0;
+  const int32_t* offs = nullptr;
 };
+
+// The expert that owns operand row m: g(m) = min(E - 1, #{ g : offs[g] <= m }) for non-decreasing offs -- the group the grouped GEMMs put the row in; rows at or past
+// offs[E - 1] (the dropped slots) belong to expert E - 1.  An upper-bound search over offs[0, E - 1) with a trip count that depends on E alone (uniform over a wave):
+// base + n <= E - 1 holds throughout, so every index read lies in [0, E - 2] and the result in [0, E - 1] WHATEVER offs holds (negative, huge, decreasing: some
+// expert, no fault).  At most 11 reads for E = 1024.  ONE function for the two GSCALE kernels and the host (qutlass_amd_debug_group_of_row runs it on the CPU).
+__host__ __device__ __forceinline__ int quant_group_of_row(const int32_t* offs, int E, int m) {
+  int base = 0, n = E - 1;
+  while (n > 1) {
+    const int half = n >> 1;
+    base = offs[base + half - 1] <= m ? base + half : base;
+    n -= half;
+  }
+  return (n == 1 && offs[base] <= m) ? base + 1 : base;
+}
+constexpr int QUANT_MAX_E = 1024;   // experts per launch of the GSCALE kernels (the grouped GEMMs' GRP_MAX_E): the workgroup's copy of offs is 4 KiB of LDS
+// (a function, so that only the kernels that call it -- the GSCALE ones -- get the allocation)
+__device__ __forceinline__ int32_t* quant_offs_lds() {
+  __shared__ int32_t offs_s[QUANT_MAX_E];
+  return offs_s;
+}
 
 // Host side: what the two formats of the family differ in (capi.hip builds every check and the QuantParams fill from it)
 struct QuantFormat {
@@ -279,11 +303,20 @@ __device__ __forceinline__ v4i silu_mul8(const v4i g, const v4i u) {
 //            run one tile ahead of the MFMAs: gather_loads(t) issues tile t's x loads from the indices fetched a tile earlier, then tile t + nwaves' index load.  The
 //            first tile's index load goes out before H's loads and its x loads before H's LDS writes.  An index is compared with T before any offset is formed from
 //            it; out of range (or an RP-row past the end) the offset is 2^31, off the descriptor (x stays below 2 GiB; the host checks): the load returns zeros.
+//   GSCALE : (NV abs-max, flat scales, on top of GATHER or of GATED) one global scale per EXPERT: logical row m of the operand is quantized with
+//            global_scale[quant_group_of_row(offs, E, m)].  Only `gscale` changes in the epilogue -- from a wave-uniform scalar to the value of the logical row the
+//            lane's RP-row belongs to; the three operations that use it (gscale * (m / 6), rcp(gscale), rcp(sf * ...)) are the same operations in the same order, so
+//            a row's bytes are those of the single-scale kernel called with its expert's scale, by construction.  The lookup stays off the critical path and off the
+//            vector-memory queue: the workgroup copies offs into LDS once (loads issued with the first tile's, written with H), a tile spans at most 32 logical
+//            rows, lane l searches the LDS copy for row (first row of the tile) + (l & 31) and loads that expert's scale (index clamped to [0, E)) -- ONE TILE AHEAD,
+//            right after the next tile's x loads, so the one global load has that tile's wait and this tile's MFMAs and epilogue to land -- and the epilogue lane
+//            picks its own row's value with a cross-lane read (ds_bpermute by (rem + row) / rpr, the split gather_off does).  Two registers: this tile's values and
+//            the next tile's.  There is no METHOD_QUEST instantiation: the NV Quest arm never reads gscale, so the grouped entries launch the single-scale Quest kernel.
 // -------------------------------------------------------------------------------------------------
 // The kernel's body as a device function of (workgroup index, workgroup count): fused_quantize_kernel below is its plain launch; [r6] the one-launch decode layer
 // (gemm_mx_os.hip.h gemm_mx_os16_fq_kernel) runs it on its first few workgroups.  PAD = false: the zero padding of the blocked scale layout is left out (a reader that
 // only looks at the rows it wrote).
-template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false, bool GATHER = false>
+template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false, bool GATHER = false, bool GSCALE = false>
 __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const int bid, const int nblk) {
   constexpr int RP = (R < 32) ? 32 : R;         // rotation padded to one MFMA j-tile (R=16: block-diag)
   constexpr int KC = RP / 16;                   // 16-wide k chunks per row
@@ -310,6 +343,7 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   // x as rows of RP elements (for R = 16 two rotation rows share one 32-element "row")
   const int64_t ngroups = p.numel / (NV ? 16 : 32);
   static_assert(!(GATED && GATHER) && !(GATHER && (BLK || MASK)), "the gathering form: plain operand, flat scales, no clip mask");
+  static_assert(!GSCALE || (NV && METHOD == METHOD_ABSMAX && !BLK && !MASK && (GATED || GATHER)), "per-expert global scales: NV abs-max, flat scales, gathering or gated");
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, GATHER ? (uint32_t)p.src_n * (uint32_t)p.inter * 2u : (uint32_t)(p.numel * (GATED ? 4 : 2)));
 
   const int wave_global = bid * 4 + wave, nwaves = nblk * 4;
@@ -327,6 +361,9 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   // reciprocal multiply and a fix-up of one either way.
   uint32_t g_row = 0, g_rem = 0, g_qstep = 0, g_rstep = 0, g_rpr = 1, g_nrows = 0;
   float g_rc = 1.0f;
+  // GSCALE: a second walk over the same tiles, (s_row, s_rem) = the tile whose scales are looked up next; n_rem = the rem of the tile gs_next belongs to
+  uint32_t s_row = 0, s_rem = 0, n_rem = 0;
+  float gs_next = 1.0f;
   if constexpr (GATED || GATHER) {
     g_rpr = (uint32_t)p.inter / RP;
     g_rc = __builtin_amdgcn_rcpf((float)g_rpr);
@@ -336,6 +373,7 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     g_rem = r0 - g_row * g_rpr;
     g_qstep = step / g_rpr;
     g_rstep = step - g_qstep * g_rpr;
+    if constexpr (GSCALE) { s_row = g_row; s_rem = g_rem; }
   }
   // byte offset of the gate chunk (RP-row lrow of the tile at (g_row, g_rem), byte cb of that RP-row); up sits 2 I bytes further.  RP-rows past the end of act
   // (the last tile's tail, tiles past the end) get an offset off the descriptor: they read 0, as in the plain kernel.
@@ -415,7 +453,16 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
 #pragma unroll
     for (int kc = 0; kc < RP / 16; ++kc) xnext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rx, xoff0 + kc * LSTEP, 0, 0);
   }
-  const float gscale = NV ? *p.global_scale : 1.0f;
+  // GSCALE: this thread's share of offs for the workgroup's LDS copy (entry tid + 256 i; the index is clamped to [0, E)), in flight with the first tile's loads
+  int32_t ov[GSCALE ? QUANT_MAX_E / 256 : 1];
+  if constexpr (GSCALE) {
+#pragma unroll
+    for (int i = 0; i < QUANT_MAX_E / 256; ++i) {
+      const int idx = i * 256 + tid;
+      if (i * 256 < p.E) ov[i] = p.offs[idx < p.E ? idx : p.E - 1];
+    }
+  }
+  const float gscale = (NV && !GSCALE) ? *p.global_scale : 1.0f;
   const uint32_t sfCB = BLK ? ((uint32_t)p.sf_cols + 3u) >> 2 : 0u;
   if (BLK && PAD) {
     // zero padding of the blocked layout (rows up to a multiple of 128, columns up to a multiple of 4), as to_blocked writes it
@@ -482,7 +529,27 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
       }
     }
   }
+  if constexpr (GSCALE) {
+    int32_t* so = quant_offs_lds();
+#pragma unroll
+    for (int i = 0; i < QUANT_MAX_E / 256; ++i)
+      if (i * 256 < p.E) so[i * 256 + tid] = ov[i];
+  }
   __syncthreads();
+  // GSCALE: gs_next = the scale of logical row s_row + (lane & 31) of the tile the second walk stands at, then that walk's step.  The search reads the LDS copy of
+  // offs; its result lies in [0, E) whatever offs holds, and the one global load is clamped to that range once more.
+  auto gscale_lookup = [&]() {
+    if constexpr (GSCALE) {
+      const int g = quant_group_of_row(quant_offs_lds(), p.E, (int)(s_row + (uint32_t)row));
+      gs_next = p.global_scale[g < 0 ? 0 : (g < p.E ? g : p.E - 1)];
+      n_rem = s_rem;
+      s_rem += g_rstep;
+      const uint32_t carry = s_rem >= g_rpr ? 1u : 0u;
+      s_rem -= carry ? g_rpr : 0u;
+      s_row += g_qstep + carry;
+    }
+  };
+  gscale_lookup();   // the first tile's
 
   // BLK: (sf_row, sf_rem) = this lane's RP-element row r_abs = tile * 32 + row as (logical row, RP-row within it); one division
   // here, then a carry-propagating add per tile
@@ -510,6 +577,8 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     // loads of the wave's NEXT tile are issued before this tile is computed (tiles past the end fall off the buffer
     // descriptor and read 0), so the HBM latency of tile i+1 hides behind the MFMAs / epilogue of tile i.
     v8bf xf[KC];
+    const float gs_cur = gs_next;     // GSCALE: this tile's scales (lane l: logical row l & 31 of the tile) and its rem, before the lookup below moves on
+    const uint32_t c_rem = n_rem;
     if constexpr (GATED) {   // gate, up -> the act chunk the plain kernel would have loaded
 #pragma unroll
       for (int i = 0; i < KC; ++i) xnext[i] = silu_mul8(xnext[i], unext[i]);
@@ -538,6 +607,15 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
       const int xoffn = (tile + nwaves < p.ntiles) ? (int)on : 0x7f000000;
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) xnext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rx, xoffn + kc * LSTEP, 0, 0);
+    }
+    gscale_lookup();   // GSCALE: the next tile's, behind its x loads
+    float gs = gscale;   // the global scale of this lane's RP-row
+    if constexpr (GSCALE) {   // the logical row of RP-row `row` within the tile: (c_rem + row) / rpr, as in gather_off
+      const uint32_t x = c_rem + (uint32_t)row;
+      uint32_t q = (uint32_t)((float)x * g_rc);
+      const int32_t r = (int32_t)(x - q * g_rpr);
+      q += r < 0 ? 0xffffffffu : (r >= (int32_t)g_rpr ? 1u : 0u);
+      gs = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), (int)__float_as_uint(gs_cur)));   // q <= row <= 31: the lane that looked that row up
     }
 #pragma unroll
     for (int jt = 0; jt < JT; ++jt) {
@@ -689,10 +767,10 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
             for (int r = 0; r < 8; ++r) m = fmaxf(m, fabsf(v8[r]));
             m = xhalf_max(m);
             nan_risk = m == 0.f || !(m < __builtin_inff());
-            float sf = gscale * (m * (1.0f / 6.0f));
+            float sf = gs * (m * (1.0f / 6.0f));
             sfb = e4m3_encode_pos(sf);
             sf = e4m3_decode_pos(sfb);
-            out_scale = (sf != 0.f) ? __frcp_rn(sf * __frcp_rn(gscale)) : 0.0f;
+            out_scale = (sf != 0.f) ? __frcp_rn(sf * __frcp_rn(gs)) : 0.0f;
           } else {
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -764,6 +842,16 @@ __global__ __launch_bounds__(256) void fused_silu_mul_quantize_kernel(const Quan
 template <int R, bool NV, int METHOD>
 __global__ __launch_bounds__(256) void fused_gather_quantize_kernel(const QuantParams p) {
   fused_quantize_body<R, NV, METHOD, false, true, false, true, false, true>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// the grouped-scale forms (fused{Gather,SiluMul}QuantizeNvGrouped): NV abs-max with one global scale per expert (GSCALE above); method quest runs the kernels above
+template <int R>
+__global__ __launch_bounds__(256) void fused_gather_quantize_gscale_kernel(const QuantParams p) {
+  fused_quantize_body<R, true, METHOD_ABSMAX, false, true, false, true, false, true, true>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+template <int R>
+__global__ __launch_bounds__(256) void fused_silu_mul_quantize_gscale_kernel(const QuantParams p) {
+  fused_quantize_body<R, true, METHOD_ABSMAX, false, true, false, true, true, false, true>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // silu_and_mul: x (rows, 2 I) bf16 -> out (rows, I) bf16, out[r][c] = act(x[r][c], x[r][I + c]) (silu_mul8 above).  Streaming, 4 B in + 2 B out per element: a

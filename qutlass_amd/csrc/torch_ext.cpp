@@ -242,15 +242,21 @@ int64_t nbytes(const Tensor& t) { return t.numel() * (int64_t)t.element_size(); 
 // check, output sizes.  gscale != nullptr is the NV format (e4m3 scale per 16, rotation 16 allowed, global scale required); nullptr is MX (e8m0 per 32).
 // ts: the op's tensors in argument order, A and the rotation first; global_scale joins the device checks but need not be contiguous (one element).
 // method: checked here for the ops whose schema carries it; the blocked ops leave it to the C ABI.  Returns the rotation size.
-int64_t quant_prelude(const char* op, std::vector<Named> ts, const Tensor* gscale, const int64_t* method = nullptr) {
+// offs (the *Grouped_ ops, the last of ts): one global scale per expert -- gscale is then (E,) for offs (E,) int32, and must be contiguous like everything else.
+int64_t quant_prelude(const char* op, std::vector<Named> ts, const Tensor* gscale, const int64_t* method = nullptr, const Tensor* offs = nullptr) {
+  if (offs) ts.push_back({*gscale, "global_scales"});
   require_contiguous(op, ts);
-  if (gscale) ts.push_back({*gscale, "global_scale"});
+  if (gscale && !offs) ts.push_back({*gscale, "global_scale"});
   require_gpu(op, ts);
   require_same_gpu(op, ts);
   const Tensor& R = ts[1].t;
   STD_TORCH_CHECK(has_dtype(ts[0].t, ScalarType::BFloat16), "A must be bf16");
   STD_TORCH_CHECK(has_dtype(R, ScalarType::BFloat16), "B must be bf16");
-  if (gscale) {
+  if (offs) {
+    STD_TORCH_CHECK(has_dtype(*offs, ScalarType::Int) && offs->dim() == 1, "offs must be a 1D int32 tensor");
+    STD_TORCH_CHECK(has_dtype(*gscale, ScalarType::Float), "global_scales must be float");
+    STD_TORCH_CHECK(gscale->dim() == 1 && gscale->size(0) == offs->size(0), "global_scales must have one entry per entry of offs");
+  } else if (gscale) {
     STD_TORCH_CHECK(has_dtype(*gscale, ScalarType::Float), "global_scale must be float");
     STD_TORCH_CHECK(gscale->dim() == 1 && gscale->size(0) == 1, "global_scale must be a scalar");
   }
@@ -373,15 +379,23 @@ void siluAndMul_(const Tensor& X, Tensor OUT) {
   check_rc(qutlass_amd_silu_mul_bf16(X.data_ptr(), rows, inter, OUT.data_ptr(), current_stream(X)));
 }
 
-void silu_mul_quantize(const char* op, const Tensor& X, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method, bool blocked) {
-  const int64_t rot = quant_prelude(op, {{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, gscale, &method);
+// offs != nullptr (NV, flat scales): one global scale per expert, gscale (E,) with the grouped GEMMs' offs (E,) int32
+void silu_mul_quantize(const char* op, const Tensor& X, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method, bool blocked,
+                       const Tensor* offs = nullptr) {
+  std::vector<Named> ts{{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
+  if (offs) ts.push_back({*offs, "offs"});
+  const int64_t rot = quant_prelude(op, ts, gscale, &method, offs);
   STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of A must be 2 * I");
   const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
   quant_check_rot(gscale, rot);
   STD_TORCH_CHECK(inter % quant_rp(rot) == 0, "the gate / up width must be divisible by", quant_rp(rot));
   quant_check_out(gscale, OUT, OUT_sf, rows * inter, inter, blocked);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
-  if (gscale)
+  if (offs)
+    check_rc(qutlass_amd_fused_silu_mul_quantize_nv_grouped(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, gscale_ptr(gscale),
+                                                            static_cast<const int32_t*>(offs->data_ptr()), offs->size(0), OUT.data_ptr(), OUT_sf.data_ptr(),
+                                                            current_stream(X)));
+  else if (gscale)
     check_rc(qutlass_amd_fused_silu_mul_quantize_nv(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, gscale_ptr(gscale), blocked ? 1 : 0, OUT.data_ptr(),
                                                     OUT_sf.data_ptr(), current_stream(X)));
   else
@@ -394,12 +408,18 @@ void fusedSiluMulQuantizeMx_(const Tensor& A, const Tensor& R, Tensor OUT, Tenso
 void fusedSiluMulQuantizeNv_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale, int64_t method, bool blocked) {
   silu_mul_quantize(blocked ? "fusedSiluMulQuantizeNvBlocked" : "fusedSiluMulQuantizeNv", A, R, OUT, OUT_sf, &global_scale, method, blocked);
 }
+void fusedSiluMulQuantizeNvGrouped_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, const Tensor& global_scales, const Tensor& offs, int64_t method) {
+  silu_mul_quantize("fusedSiluMulQuantizeNvGrouped", A, R, OUT, OUT_sf, &global_scales, method, false, &offs);
+}
 
 // ---- EXTENSION: MoE dispatch and combine around the grouped GEMMs ---------------------------------------------------------------------
 // fusedGatherQuantize{Mx,Nv}_: fusedQuantize{Mx,Nv}_ of A.index_select(0, src_row) in one launch, byte for byte; A (T, K) bf16, src_row (M) int32 read on the device (no
 // host sync).  OUT / OUT_sf are sized as for the plain quantizers on an (M, K) tensor; flat scales.
-void gather_quantize(const char* op, const Tensor& X, const Tensor& R, const Tensor& src_row, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method) {
-  const int64_t rot = quant_prelude(op, {{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, gscale, &method);
+void gather_quantize(const char* op, const Tensor& X, const Tensor& R, const Tensor& src_row, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method,
+                     const Tensor* offs = nullptr) {
+  std::vector<Named> ts{{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
+  if (offs) ts.push_back({*offs, "offs"});
+  const int64_t rot = quant_prelude(op, ts, gscale, &method, offs);
   STD_TORCH_CHECK(X.dim() == 2 && X.size(1) > 0, "A must be 2D (T, K)");
   STD_TORCH_CHECK(has_dtype(src_row, ScalarType::Int) && src_row.dim() == 1, "src_row must be a 1D int32 tensor");
   const int64_t T = X.size(0), K = X.size(1), M = src_row.size(0);
@@ -407,7 +427,11 @@ void gather_quantize(const char* op, const Tensor& X, const Tensor& R, const Ten
   STD_TORCH_CHECK(K % quant_rp(rot) == 0, "the last dimension of A must be divisible by", quant_rp(rot));
   quant_check_out(gscale, OUT, OUT_sf, M * K, K, false);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
-  if (gscale)
+  if (offs)
+    check_rc(qutlass_amd_fused_gather_quantize_nv_grouped(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, (int)method,
+                                                          gscale_ptr(gscale), static_cast<const int32_t*>(offs->data_ptr()), offs->size(0), OUT.data_ptr(),
+                                                          OUT_sf.data_ptr(), current_stream(X)));
+  else if (gscale)
     check_rc(qutlass_amd_fused_gather_quantize_nv(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, (int)method,
                                                   gscale_ptr(gscale), OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(X)));
   else
@@ -419,6 +443,10 @@ void fusedGatherQuantizeMx_(const Tensor& A, const Tensor& R, const Tensor& src_
 }
 void fusedGatherQuantizeNv_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf, const Tensor& global_scale, int64_t method) {
   gather_quantize("fusedGatherQuantizeNv", A, R, src_row, OUT, OUT_sf, &global_scale, method);
+}
+void fusedGatherQuantizeNvGrouped_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf, const Tensor& global_scales, const Tensor& offs,
+                                   int64_t method) {
+  gather_quantize("fusedGatherQuantizeNvGrouped", A, R, src_row, OUT, OUT_sf, &global_scales, method, &offs);
 }
 
 // moeCombine_: OUT[t] = sum_k weights[t][k] * Y[pos[t][k]] (the arithmetic is spelled out at qutlass_amd_moe_combine_bf16); slots with pos outside [0, M) are skipped
@@ -654,6 +682,8 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("fusedSiluMulQuantizeNv_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method, bool blocked) -> ()");
   m.def("fusedGatherQuantizeMx_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, int method) -> ()");
   m.def("fusedGatherQuantizeNv_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method) -> ()");
+  m.def("fusedGatherQuantizeNvGrouped_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scales, Tensor offs, int method) -> ()");
+  m.def("fusedSiluMulQuantizeNvGrouped_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scales, Tensor offs, int method) -> ()");
   m.def("moeCombine_(Tensor Y, Tensor pos, Tensor weights, Tensor(a!) OUT) -> ()");
   m.def("moeTopkSoftmax_(Tensor logits, Tensor(a!) weights, Tensor(b!) ids, bool renormalize) -> ()");
   m.def("moeTopkGrouped_(Tensor logits, Tensor bias, Tensor(a!) weights, Tensor(b!) ids, Tensor(c!) scores, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor) -> ()");
@@ -701,6 +731,8 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("fusedSiluMulQuantizeNv_", TORCH_BOX(&fusedSiluMulQuantizeNv_));
   m.impl("fusedGatherQuantizeMx_", TORCH_BOX(&fusedGatherQuantizeMx_));
   m.impl("fusedGatherQuantizeNv_", TORCH_BOX(&fusedGatherQuantizeNv_));
+  m.impl("fusedGatherQuantizeNvGrouped_", TORCH_BOX(&fusedGatherQuantizeNvGrouped_));
+  m.impl("fusedSiluMulQuantizeNvGrouped_", TORCH_BOX(&fusedSiluMulQuantizeNvGrouped_));
   m.impl("moeCombine_", TORCH_BOX(&moeCombine_));
   m.impl("moeTopkSoftmax_", TORCH_BOX(&moeTopkSoftmax_));
   m.impl("moeTopkGrouped_", TORCH_BOX(&moeTopkGrouped_));

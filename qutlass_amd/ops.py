@@ -77,7 +77,7 @@ def _register_fakes() -> None:
 
     for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
                  "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
-                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "moeCombine_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "fusedGatherQuantizeNvGrouped_", "fusedSiluMulQuantizeNvGrouped_", "moeCombine_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -226,7 +226,7 @@ def _define_functional_ops() -> None:
 
 
 # ---- the rotate + quantize family: the functional ops `qutlass_amd::<name>`, their fake kernels and the eager wrappers of __init__.py come from this table ----------
-# schema:  of the functional op -- the leading tensors, [global_scale,] method[, blocked]
+# schema:  of the functional op -- the leading tensors, [global_scale | global_scales, offs,] method[, blocked]
 # twin:    the in-place op of csrc/torch_ext.cpp: the same arguments with OUT, OUT_sf inserted after the `lead` leading tensors
 # operand: the shape of the tensor that is rotated and quantized, from the leading tensors -- the results are the plain quantizers' for a tensor of that shape
 # fmt:     a key of QUANT_FORMATS;  blocked: scales flat in the to_blocked() layout -- fixed by the op, or None where it is the op's last argument
@@ -261,6 +261,11 @@ QUANT_OPS = {
     "silu_mul_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeNv_", 2, _act, "nv", None),
     "gather_quantize_mx": QuantOp("(Tensor A, Tensor R, Tensor src_row, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeMx_", 3, _gathered, "mx", False),
     "gather_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor src_row, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeNv_", 3, _gathered, "nv", False),
+    # one global scale per expert: global_scales (E,) with the grouped GEMMs' offs (E,)
+    "gather_quantize_nv_grouped": QuantOp("(Tensor A, Tensor R, Tensor src_row, Tensor global_scales, Tensor offs, int method) -> (Tensor, Tensor)",
+                                          "fusedGatherQuantizeNvGrouped_", 3, _gathered, "nv", False),
+    "silu_mul_quantize_nv_grouped": QuantOp("(Tensor A, Tensor R, Tensor global_scales, Tensor offs, int method) -> (Tensor, Tensor)", "fusedSiluMulQuantizeNvGrouped_", 2,
+                                            _act, "nv", False),
 }
 
 
