@@ -117,6 +117,56 @@ def test_quantize_nv_vs_reference_oracle(golden_dir):
     assert bad / tot <= 1e-2, (bad, tot)
 
 
+def _rot_cases(golden_dir):
+    g = _load(golden_dir, "quantize_rot.npz")
+    for c in range(int(g["ncases"])):
+        nv, R, quest, general = (int(v) for v in g[f"meta{c}"])
+        h = g[f"h{c}"]
+        assert h.shape == (R, R) and not np.array_equal(h, h.T), c    # the point of this fixture: h is not its own transpose
+        yield g, c, nv, R, quest, h
+
+
+@pytest.mark.parametrize("acc_model", [0, 1])
+def test_quantize_mx_non_symmetric_rotation_vs_reference_oracle(golden_dir, acc_model):
+    """quantize_rot.npz (tests/golden/make_golden_rotations.py): the reference's MX oracle at R = 64 / 128 with a signed, row-permuted Hadamard matrix and with a
+    general random h -- under test_quantize_mx_vs_reference_oracle's comparison.  An oracle that rotated by h.T would miss it by most of the codes (last assert)."""
+    tot = bad = 0
+    for g, c, nv, R, quest, h in _rot_cases(golden_dir):
+        if nv:
+            continue
+        method = oracle.QUEST if quest else oracle.ABS_MAX
+        q, s, m = oracle.fused_quantize_mx(g[f"x{c}"], h, method, with_mask=True, acc_model=acc_model)
+        assert np.array_equal(s, g[f"sf{c}"].reshape(-1)), f"case {c}: e8m0 differs"
+        eq = oracle.codes_equal_mod_zero_sign(q, g[f"e2m1_{c}"])
+        tot += eq.size
+        bad += int((~eq).sum())
+        if quest:
+            assert np.array_equal(m, g[f"mask{c}"].reshape(-1)), f"case {c}: clip mask differs"
+        qt, _, _ = oracle.fused_quantize_mx(g[f"x{c}"], np.ascontiguousarray(h.T), method, acc_model=acc_model)
+        assert (~oracle.codes_equal_mod_zero_sign(qt, g[f"e2m1_{c}"])).mean() > 0.5, f"case {c}: h.T reproduces the fixture"
+    assert tot == 8 * 4 * 512 and bad == 0, (bad, tot)
+
+
+def test_quantize_nv_non_symmetric_rotation_vs_reference_oracle(golden_dir):
+    """The NV half of quantize_rot.npz, R = 16 / 32 / 64 / 128, under test_quantize_nv_vs_reference_oracle's comparison; the transposed rotation misses it."""
+    tot = bad = sbad = 0
+    for g, c, nv, R, quest, h in _rot_cases(golden_dir):
+        if not nv:
+            continue
+        want_s = g[f"sf{c}"].reshape(-1)
+        q, s = oracle.fused_quantize_nv(g[f"x{c}"], h, 6.0, oracle.ABS_MAX)
+        sbad += int((s != want_s).sum())
+        same = s.repeat(16) == want_s.repeat(16)
+        eq = oracle.codes_equal_mod_zero_sign(q, g[f"e2m1_{c}"])
+        tot += eq.size
+        bad += int((~eq & same).sum())
+        qt, st = oracle.fused_quantize_nv(g[f"x{c}"], np.ascontiguousarray(h.T), 6.0, oracle.ABS_MAX)
+        assert (st != want_s).mean() > 0.3 or (~oracle.codes_equal_mod_zero_sign(qt, g[f"e2m1_{c}"])).mean() > 0.3, f"case {c}: h.T reproduces the fixture"
+    assert tot == 8 * 4 * 512
+    assert sbad / (tot / 16) <= 1e-2, (sbad, tot)
+    assert bad / tot <= 1e-2, (bad, tot)
+
+
 def test_gemm_nvfp4_bit_exact(golden_dir):
     g = _load(golden_dir, "gemm_nvfp4.npz")
     for c in range(int(g["ncases"])):
