@@ -330,6 +330,34 @@ int qutlass_amd_fused_silu_mul_quantize_nv_grouped(const void* x, const void* h,
                                                    void* stream);
 
 /*
+ * EXTENSION (no reference counterpart): the rotate + quantize family with 8-BIT codes -- the producers of the A (and B) operands of qutlass_amd_matmul_mxf8_bf16_{tn,nn}
+ * and qutlass_amd_grouped_matmul_mxf8_bf16_tn: MXFP8, one e8m0 scale per 32 elements along the row, e4m3fn or e5m2 codes.
+ *   fmt   QAMD_FP8_E4M3 (0) or QAMD_FP8_E5M2 (1), the GEMMs' _fmt convention; the gated entry takes QAMD_FP8_E4M3 only (a forward activation has no use for e5m2).
+ *   y = x_g . h exactly as qutlass_amd_fused_quantize_mx computes it (x viewed as (numel / rot, rot), h a runtime rot x rot bf16 matrix, bf16 MFMA, fp32 sums;
+ *   the identity gives a plain quantizer); rot in {32, 64, 128} (no 16: the scale group is 32).  Then for every 32 consecutive y:
+ *       amax = max |y|  (NaNs ignored)          E = the biased exponent field of the FP32 amax          SH = 7 (e4m3) / 14 (e5m2)
+ *       e8   = 127 if amax == 0, else clamp(E - SH, 0, 254)                                              -- the scale byte, 2^(e8 - 127)
+ *       q    = RNE(y * 2^(127 - e8)) to e4m3fn / e5m2; the scaling is exact, -0 keeps its sign          -- the code byte
+ *   The scaled maximum lies in [128, 256) / [2^14, 2^15): no finite input saturates.  Abs-max is the only method (Quest's constant is an FP4 constant); no clip
+ *   mask, no global scale.  A NaN input gives NaN codes throughout its own rotation block; the bytes of a block that holds +-inf are unspecified; no other
+ *   block is affected.
+ *   out_fp8: numel bytes, element order.  Scales: as the MX sibling -- flat in the first numel / 32 bytes with the rest of the caller's buffer untouched
+ *   (what the grouped GEMM reads as it is), or, for the _blocked entry and blocked != 0, the to_blocked() layout of the (rows, k / 32) scale matrix, padding zero-filled
+ *   (what the dense GEMMs read).
+ * qutlass_amd_fused_silu_mul_quantize_mxf8 = the plain entries on act = silu(gate) * up, qutlass_amd_fused_gather_quantize_mxf8 = the plain entry on x[src_row] (an
+ * index outside [0, t) gives a zero row: codes 0, scale 127), byte for byte, with the siblings' limits: x below 2 GiB, numel < 2^31.
+ * Checks: each entry runs its MX sibling's chain in the sibling's order under the name fusedQuantizeMxf8 / fusedQuantizeMxf8Blocked / fusedSiluMulQuantizeMxf8[Blocked]
+ * / fusedGatherQuantizeMxf8, with "invalid fmt" where the sibling has "invalid method"; all before any HIP call.
+ */
+int qutlass_amd_fused_quantize_mxf8(const void* x, const void* h, int rot, int64_t numel, int fmt, void* out_fp8, void* out_e8m0, void* stream);
+int qutlass_amd_fused_quantize_mxf8_blocked(const void* x, const void* h, int rot, int64_t rows, int64_t k, int fmt, void* out_fp8, void* out_e8m0_blocked,
+                                            void* stream);
+int qutlass_amd_fused_silu_mul_quantize_mxf8(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int fmt, int blocked, void* out_fp8,
+                                             void* out_e8m0, void* stream);
+int qutlass_amd_fused_gather_quantize_mxf8(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int fmt, void* out_fp8,
+                                           void* out_e8m0, void* stream);
+
+/*
  * EXTENSION (no reference counterpart): MoE routing, the step in front of the dispatch above -- router logits to expert ids and weights, and expert ids to the
  * sorted-row metadata the gathering quantizers, the grouped GEMMs and moe_combine read.  Every argument check happens before any HIP call.
  *

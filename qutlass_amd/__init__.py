@@ -12,6 +12,7 @@ meaning, defaults and Python-level error behaviour):
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
     fusedGatherQuantizeNvGrouped, fusedSiluMulQuantizeNvGrouped  (extension: the two NVFP4 quantizers of the MoE chain with one global scale per expert)
+    fusedQuantizeMxf8 [Blocked], fusedGatherQuantizeMxf8, fusedSiluMulQuantizeMxf8 [Blocked]  (extension: the MXFP8 quantizers -- the operands of the three MXFP8 GEMMs)
     moe_topk_softmax, moe_sort_fused, moe_route           (extension: MoE routing in HIP -- router logits to ids, weights and the sorted-row metadata)
     moe_topk_grouped, moe_route_grouped                   (extension: the grouped router of DeepSeek-V2 / V3 and Kimi-K2 -- sigmoid / softmax scores, selection bias, group-limited top-k)
 
@@ -417,6 +418,50 @@ def fusedSiluMulQuantizeNvGrouped(x: torch.Tensor, h: torch.Tensor, global_scale
     rows a grouped gate/up GEMM returned, is quantized with global_scales[g(m)], g(m) from offs (E,) int32 -- the down projection's A operand.  The bytes of row m are
     those of ``fusedSiluMulQuantizeNv(x, h, global_scales[g(m):g(m)+1], method=method)``; flat scales only (what grouped_matmul_nvf4_bf16_tn reads as it is); x below 2 GiB."""
     return _silu_mul_quantize("silu_mul_quantize_nv_grouped", x, h, global_scales, offs, _method_code(method))
+
+
+def fusedQuantizeMxf8(a: torch.Tensor, h: torch.Tensor, *, dtype: torch.dtype = torch.float8_e4m3fn) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): rotate and quantize to MXFP8 -- the operand the three MXFP8 GEMMs take, made on the device.  a is (.., K) bf16, h a
+    runtime R x R bf16 matrix, R in {32, 64, 128} (no 16: the scale group is 32); K % R == 0.  y = a_group @ h exactly as fusedQuantizeMx computes it (the
+    identity matrix gives a plain quantizer); then for every 32 consecutive y
+
+        amax = max |y| (NaNs ignored);  E = the biased exponent field of the fp32 amax;  SH = 7 for float8_e4m3fn, 14 for float8_e5m2
+        scale byte  e8 = 127 if amax == 0 else clamp(E - SH, 0, 254)       (the scaled maximum lies in [128, 256) / [2^14, 2^15): no finite input saturates)
+        code        q = RNE(y * 2^(127 - e8)) in dtype                      (the scaling is exact; -0 keeps its sign)
+
+    -- the rule of the reference's e8m0_shift7 and of oracle.pseudoquant_mxfp8 (without the latter's bf16-log2 rounding of the exponent).  Abs-max only (Quest's
+    constant is an FP4 constant); no clip mask, no global scale.  Returns codes, a's shape in dtype, and float8_e8m0fnu scales allocated (padded_rows, padded_cols) and
+    written flat in the first numel / 32 bytes, padding untouched, exactly as fusedQuantizeMx's: what grouped_matmul_mxf8_bf16_tn reads as it is.  A NaN input
+    gives NaN codes throughout its own rotation block, the bytes of a block that holds +-inf are unspecified; no other block is affected.  Fewer than 2^31 elements."""
+    return _quantize("quantize_mxf8", a, h, ops.mxf8_dtype(dtype))
+
+
+def fusedQuantizeMxf8Blocked(a: torch.Tensor, h: torch.Tensor, *, dtype: torch.dtype = torch.float8_e4m3fn) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMxf8`` whose scales come out GEMM-ready -- the second tensor is byte for byte ``to_blocked(fusedQuantizeMxf8(a, h, dtype=dtype)[1])``
+    (flat, zero padded), written by the quantizer itself: what the dense ``matmul_mxf8_bf16_tn`` takes.  K % R == 0 for the last dimension K."""
+    return _quantize("quantize_mxf8_blocked", a, h, ops.mxf8_dtype(dtype))
+
+
+def fusedGatherQuantizeMxf8(x: torch.Tensor, h: torch.Tensor, src_row: torch.Tensor, *, dtype: torch.dtype = torch.float8_e4m3fn) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMxf8(x.index_select(0, src_row), h, dtype=dtype)`` in ONE launch, byte for byte -- the MXFP8 MoE dispatch (float8_e5m2: the dgrad token
+    path of grouped_matmul_mxf8_bf16_tn).  x is (T, K) bf16, contiguous, src_row (M,) int32 on the device, K % R == 0; codes (M, K), flat scales.  An index outside
+    [0, T) gives a zero row (codes 0, scale 127) and can neither fault nor read another row; the indices are read on the device (graph-capturable).  x below 2 GiB.
+    Measured 1.2-2.4x faster than index_select + fusedQuantizeMxf8 at every shape taken."""
+    return _quantize("gather_quantize_mxf8", x, h, src_row, ops.mxf8_dtype(dtype))
+
+
+def fusedSiluMulQuantizeMxf8(x: torch.Tensor, h: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMxf8(silu_and_mul(x), h)`` in ONE launch, byte for byte (see fusedSiluMulQuantizeMx): x is (.., 2 I) bf16 [gate | up], I % R == 0;
+    float8_e4m3fn codes (.., I) and flat scales -- the down projection's A operand for grouped_matmul_mxf8_bf16_tn.  e4m3 only: a forward activation has no use for
+    e5m2.  x below 2 GiB.  Measured faster than the two calls at R = 32 (1.17-1.46x); at R = 128 it is NOT -- 0.50-0.72x at decode shapes, 0.94-1.08x at prefill
+    (as for fusedSiluMulQuantizeMx): keep silu_and_mul + fusedQuantizeMxf8 there."""
+    return _silu_mul_quantize("silu_mul_quantize_mxf8", x, h, torch.float8_e4m3fn, False)
+
+
+def fusedSiluMulQuantizeMxf8Blocked(x: torch.Tensor, h: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMxf8Blocked(silu_and_mul(x), h)`` in one launch (see fusedSiluMulQuantizeMxf8): the scales come out flat in the ``to_blocked`` layout,
+    zero padded -- what the dense ``matmul_mxf8_bf16_tn`` takes.  x below 2 GiB.  Slower than its two-launch composition at R = 128, like the flat form."""
+    return _silu_mul_quantize("silu_mul_quantize_mxf8", x, h, torch.float8_e4m3fn, True)
 
 
 def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:

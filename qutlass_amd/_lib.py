@@ -47,6 +47,10 @@ SYMBOLS = {
     "qutlass_amd_fused_gather_quantize_nv": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "qutlass_amd_fused_gather_quantize_nv_grouped": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "qutlass_amd_fused_silu_mul_quantize_nv_grouped": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "qutlass_amd_fused_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "qutlass_amd_fused_quantize_mxf8_blocked": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "qutlass_amd_fused_silu_mul_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "qutlass_amd_fused_gather_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "qutlass_amd_moe_combine_bf16": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "qutlass_amd_moe_topk_softmax": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "qutlass_amd_moe_topk_grouped": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, ctypes.c_float, _vp, _vp, _vp, _vp]),

@@ -1255,10 +1255,21 @@ int debug_plan(const char* name, int64_t M, int64_t N, int64_t rowbytes, int gra
 // The _GSCALE kinds are the gated and the gathering quantizer with one global scale per expert (quantize.hip.h, GSCALE): NV abs-max with flat scales and nothing else.
 enum QuantKind { QK_PLAIN, QK_GATED, QK_GATHER, QK_GATED_GSCALE, QK_GATHER_GSCALE };
 
-template <int KIND, int R, bool NV, int METHOD, bool MASK, bool BLK>
+// FMT: QF_E2M1, or QF_E4M3 / QF_E5M2 for the MXFP8 quantizers (MX abs-max; plain, gated or gathering) -- their own three __global__ wrappers.
+template <int KIND, int R, bool NV, int METHOD, bool MASK, bool BLK, int FMT = QF_E2M1>
 int launch_quant(const QuantParams& p, hipStream_t s, int grid) {
   static_assert((KIND != QK_GATED_GSCALE && KIND != QK_GATHER_GSCALE) || (NV && METHOD == METHOD_ABSMAX && !MASK && !BLK), "per-expert global scales: NV abs-max, flat scales");
-  if constexpr (KIND == QK_GATED_GSCALE) {
+  static_assert(FMT == QF_E2M1 || (KIND == QK_PLAIN || KIND == QK_GATED || KIND == QK_GATHER), "MXFP8: plain, gated or gathering");
+  if constexpr (FMT != QF_E2M1 && KIND == QK_GATED) {
+    hipLaunchKernelGGL((fused_silu_mul_quantize_mxf8_kernel<R, FMT, BLK>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_silu_mul_quantize_mxf8_kernel");
+  } else if constexpr (FMT != QF_E2M1 && KIND == QK_GATHER) {
+    hipLaunchKernelGGL((fused_gather_quantize_mxf8_kernel<R, FMT>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_gather_quantize_mxf8_kernel");
+  } else if constexpr (FMT != QF_E2M1) {
+    hipLaunchKernelGGL((fused_quantize_mxf8_kernel<R, FMT, BLK>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_quantize_mxf8_kernel");
+  } else if constexpr (KIND == QK_GATED_GSCALE) {
     hipLaunchKernelGGL((fused_silu_mul_quantize_gscale_kernel<R>), dim3(grid), dim3(256), 0, s, p);
     return check_launch("fused_silu_mul_quantize_gscale_kernel");
   } else if constexpr (KIND == QK_GATHER_GSCALE) {
@@ -1282,20 +1293,21 @@ int launch_quant(const QuantParams& p, hipStream_t s, int grid) {
   }
 }
 
-template <int KIND, bool NV, int METHOD, bool MASK, bool BLK>
+template <int KIND, bool NV, int METHOD, bool MASK, bool BLK, int FMT = QF_E2M1>
 int dispatch_quant(int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
   static_assert(!MASK || (KIND == QK_PLAIN && !NV && METHOD == METHOD_QUEST), "the clip mask exists for the plain MX quest quantizer only");
+  static_assert(FMT == QF_E2M1 || (!NV && METHOD == METHOD_ABSMAX && !MASK), "MXFP8: MX scales, abs-max, no clip mask");
   static_assert(!BLK || (KIND != QK_GATHER && KIND != QK_GATED_GSCALE && KIND != QK_GATHER_GSCALE), "the gathering and the grouped-scale quantizers write flat scales only");
   switch (rot) {
     case 16:
       if constexpr (NV) return launch_quant<KIND, 16, NV, METHOD, false, BLK>(p, s, grid);
       break;
-    case 32: return launch_quant<KIND, 32, NV, METHOD, MASK, BLK>(p, s, grid);
+    case 32: return launch_quant<KIND, 32, NV, METHOD, MASK, BLK, FMT>(p, s, grid);
     case 64:
-      if constexpr (!MASK) return launch_quant<KIND, 64, NV, METHOD, false, BLK>(p, s, grid);
+      if constexpr (!MASK) return launch_quant<KIND, 64, NV, METHOD, false, BLK, FMT>(p, s, grid);
       break;
     case 128:
-      if constexpr (!MASK) return launch_quant<KIND, 128, NV, METHOD, false, BLK>(p, s, grid);
+      if constexpr (!MASK) return launch_quant<KIND, 128, NV, METHOD, false, BLK, FMT>(p, s, grid);
       break;
   }
   if (MASK) return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected 32.", name, rot);
@@ -1321,6 +1333,11 @@ QAMD_QUANT_FORMATS(QK_GATED, true)
 QAMD_QUANT_FORMATS(QK_GATHER, false)
 QAMD_QUANT_INST(QK_GATED_GSCALE, true, METHOD_ABSMAX, false, false)
 QAMD_QUANT_INST(QK_GATHER_GSCALE, true, METHOD_ABSMAX, false, false)
+// MXFP8 (x R = 32, 64, 128 each): plain flat and blocked x e4m3, e5m2; gathering x e4m3, e5m2; gated flat and blocked x e4m3 (a forward activation has no use for e5m2)
+QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, false, QF_E4M3) QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, false, QF_E5M2)
+QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, true, QF_E4M3) QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, true, QF_E5M2)
+QAMD_QUANT_INST(QK_GATHER, false, METHOD_ABSMAX, false, false, QF_E4M3) QAMD_QUANT_INST(QK_GATHER, false, METHOD_ABSMAX, false, false, QF_E5M2)
+QAMD_QUANT_INST(QK_GATED, false, METHOD_ABSMAX, false, false, QF_E4M3) QAMD_QUANT_INST(QK_GATED, false, METHOD_ABSMAX, false, true, QF_E4M3)
 #undef QAMD_QUANT_FORMATS
 #undef QAMD_QUANT_INST
 #endif
@@ -1409,6 +1426,14 @@ inline int quant_check_method(const char* name, int method) {
   return fail(QAMD_ERR_INVALID, "%s: invalid method %d", name, method);
 }
 
+// the MXFP8 entries have no method (abs-max is the only one): the code format stands in its place in every chain.  fmt is the C ABI's (the GEMMs' _fmt convention);
+// the kernels' FMT is fmt + 1.  e4m3_only: the gated form.
+inline int quant_check_how(const char* name, const QuantFormat& f, int method, int fmt, bool e4m3_only = false) {
+  if (!f.fp8) return quant_check_method(name, method);
+  if (fmt == QAMD_FP8_E4M3 || (fmt == QAMD_FP8_E5M2 && !e4m3_only)) return QAMD_OK;
+  return fail(QAMD_ERR_INVALID, "%s: invalid fmt %d; expected %s", name, fmt, e4m3_only ? "0 (e4m3)" : "0 (e4m3) or 1 (e5m2)");
+}
+
 // (rot >= 64 stages H with 16-byte vector loads, quantize.hip.h: an offset view of a larger tensor may be 2-byte aligned only -- rejected rather than left to
 //  the device's unaligned-access mode; torch allocations are 256-byte aligned)
 inline int quant_check_h(const char* name, int rot, const void* h) {
@@ -1443,8 +1468,20 @@ inline int quant_check_groups(const char* name, const QuantGroups& g) {
 }
 
 // runtime (nv, method, mask, blocked) -> the dispatch_quant instantiation; the callers have checked method, and that a mask comes with MX + quest only
+// fmt8: -1, or the C ABI's fmt of an MXFP8 entry (checked by quant_check_how): MX abs-max with e4m3 / e5m2 codes
 template <int KIND>
-int select_quant(bool nv, int method, bool mask, bool blocked, int rot, const QuantParams& p, hipStream_t s, int grid, const char* name) {
+int select_quant(bool nv, int method, bool mask, bool blocked, int rot, const QuantParams& p, hipStream_t s, int grid, const char* name, int fmt8 = -1) {
+  if (fmt8 >= 0) {
+    auto go8 = [&](auto fmt_) {
+      using F = decltype(fmt_);
+      if constexpr (KIND != QK_GATHER)
+        if (blocked) return dispatch_quant<KIND, false, METHOD_ABSMAX, false, true, F::value>(rot, p, s, grid, name);
+      return dispatch_quant<KIND, false, METHOD_ABSMAX, false, false, F::value>(rot, p, s, grid, name);
+    };
+    if constexpr (KIND != QK_GATED)
+      if (fmt8 == QAMD_FP8_E5M2) return go8(std::integral_constant<int, QF_E5M2>{});
+    return go8(std::integral_constant<int, QF_E4M3>{});
+  }
   auto go = [&](auto nv_, auto method_, auto mask_) {
     using NV = decltype(nv_); using M = decltype(method_); using K = decltype(mask_);
     if constexpr (KIND != QK_GATHER)
@@ -1767,13 +1804,14 @@ int qutlass_amd_matmul_nvf4_bf16_tn_ws(const void* A, const void* B, const void*
 }
 
 // k: logical 2-D shape of x (rows of k elements) for the blocked-scale variants; k == 0: flat scales (the reference's contract).  MX: global_scale null; NV: out_mask null.
+// MXFP8 (f.fp8): out_e2m1 takes numel code bytes, fmt8 is the entry's fmt and method is not read.
 static int fused_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t numel, int64_t k, int method,
-                               const float* global_scale, void* out_e2m1, void* out_sf, void* out_mask, void* stream) {
+                               const float* global_scale, void* out_e2m1, void* out_sf, void* out_mask, void* stream, int fmt8 = -1) {
   if (!x || !h || !out_e2m1 || !out_sf || (f.nv && !global_scale)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   if (int rc = quant_check_rot(name, f, rot, out_mask != nullptr)) return rc;
   if (numel <= 0 || numel % rot) return fail(QAMD_ERR_INVALID, "%s: A must be divisible by %d", name, rot);
   if (numel * 2 >= (1ll << 32)) return fail(QAMD_ERR_INVALID, "%s: more than 2^31 elements is not supported", name);
-  if (int rc = quant_check_method(name, method)) return rc;
+  if (int rc = quant_check_how(name, f, method, fmt8)) return rc;
   if (out_mask && method != QAMD_METHOD_QUEST) return fail(QAMD_ERR_INVALID, "%s: the clip mask is only defined for method quest", name);
   if (k && (k % quant_rp(rot) || numel % k))
     return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of %s%d and divide numel", name, (long long)k, f.row_unit, quant_rp(rot));
@@ -1782,7 +1820,7 @@ static int fused_quantize_impl(const char* name, const QuantFormat& f, const voi
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_sf;
   p.out_mask = (uint32_t*)out_mask; p.global_scale = global_scale;
   const int grid = quant_fill(p, f, rot, numel, k, k != 0);
-  return select_quant<QK_PLAIN>(f.nv, method, out_mask != nullptr, k != 0, rot, p, (hipStream_t)stream, grid, name);
+  return select_quant<QK_PLAIN>(f.nv, method, out_mask != nullptr, k != 0, rot, p, (hipStream_t)stream, grid, name, f.fp8 ? fmt8 : -1);
 }
 
 int qutlass_amd_fused_quantize_mx(const void* x, const void* h, int rot, int64_t numel, int method,
@@ -1836,9 +1874,10 @@ int qutlass_amd_silu_mul_bf16(const void* x, int64_t rows, int64_t inter, void* 
 }
 
 static int fused_silu_mul_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method,
-                                        const float* global_scale, int blocked, void* out_e2m1, void* out_sf, void* stream, const QuantGroups* grp = nullptr) {
+                                        const float* global_scale, int blocked, void* out_e2m1, void* out_sf, void* stream, const QuantGroups* grp = nullptr,
+                                        int fmt8 = -1) {
   if (int rc = quant_check_rot(name, f, rot)) return rc;
-  if (int rc = quant_check_method(name, method)) return rc;
+  if (int rc = quant_check_how(name, f, method, fmt8, true)) return rc;
   if (int rc = gated_common_check(name, x, rows, inter, quant_rp(rot))) return rc;
   // x is addressed with 32-bit offsets from one buffer descriptor (quantize.hip.h, GATED): no silent wrap beyond it
   if (rows * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: x (rows * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(rows * inter * 4));
@@ -1851,7 +1890,7 @@ static int fused_silu_mul_quantize_impl(const char* name, const QuantFormat& f, 
   p.out_mask = nullptr; p.global_scale = global_scale; p.inter = (int)inter;
   const int grid = quant_fill(p, f, rot, rows * inter, inter, blocked != 0);
   if (grp) return select_quant_grouped<QK_GATED>(method, rot, p, *grp, (hipStream_t)stream, grid, name);
-  return select_quant<QK_GATED>(f.nv, method, false, blocked != 0, rot, p, (hipStream_t)stream, grid, name);
+  return select_quant<QK_GATED>(f.nv, method, false, blocked != 0, rot, p, (hipStream_t)stream, grid, name, f.fp8 ? fmt8 : -1);
 }
 
 int qutlass_amd_fused_silu_mul_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, int blocked, void* out_e2m1,
@@ -1870,9 +1909,10 @@ int qutlass_amd_fused_silu_mul_quantize_nv(const void* x, const void* h, int rot
 // Dispatch: fusedQuantize{Mx,Nv}(x.index_select(0, src_row)) in one launch, byte for byte -- the quantizer's tile loads go through the row index (quantize.hip.h,
 // GATHER), so the (M, K) bf16 copy of the routed tokens is never written.
 static int fused_gather_quantize_impl(const char* name, const QuantFormat& f, const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row,
-                                      int64_t m, int method, const float* global_scale, void* out_e2m1, void* out_sf, void* stream, const QuantGroups* grp = nullptr) {
+                                      int64_t m, int method, const float* global_scale, void* out_e2m1, void* out_sf, void* stream, const QuantGroups* grp = nullptr,
+                                      int fmt8 = -1) {
   if (int rc = quant_check_rot(name, f, rot)) return rc;
-  if (int rc = quant_check_method(name, method)) return rc;
+  if (int rc = quant_check_how(name, f, method, fmt8)) return rc;
   if (t < 0 || m < 0 || k <= 0 || t >= (1ll << 31) || m >= (1ll << 31) || k >= (1ll << 31))
     return fail(QAMD_ERR_INVALID, "%s: bad shape (x (%lld, %lld), %lld indices)", name, (long long)t, (long long)k, (long long)m);
   if (k % quant_rp(rot)) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of %d", name, (long long)k, quant_rp(rot));
@@ -1889,7 +1929,7 @@ static int fused_gather_quantize_impl(const char* name, const QuantFormat& f, co
   p.out_mask = nullptr; p.global_scale = global_scale; p.inter = (int)k;
   const int grid = quant_fill(p, f, rot, m * k, k, false, src_row, t);
   if (grp) return select_quant_grouped<QK_GATHER>(method, rot, p, *grp, (hipStream_t)stream, grid, name);
-  return select_quant<QK_GATHER>(f.nv, method, false, false, rot, p, (hipStream_t)stream, grid, name);
+  return select_quant<QK_GATHER>(f.nv, method, false, false, rot, p, (hipStream_t)stream, grid, name, f.fp8 ? fmt8 : -1);
 }
 
 int qutlass_amd_fused_gather_quantize_mx(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int method, void* out_e2m1,
@@ -1914,6 +1954,30 @@ int qutlass_amd_fused_silu_mul_quantize_nv_grouped(const void* x, const void* h,
                                                    const int32_t* offs, int64_t e, void* out_e2m1, void* out_e4m3, void* stream) {
   const QuantGroups grp{offs, e};
   return fused_silu_mul_quantize_impl("fusedSiluMulQuantizeNvGrouped", kQuantNv, x, h, rot, rows, inter, method, global_scales, 0, out_e2m1, out_e4m3, stream, &grp);
+}
+
+// ---- MXFP8: the same three forms with e4m3 / e5m2 codes (quantize.hip.h, the FP8 arm): the A operands of matmul_mxf8_bf16_tn and grouped_matmul_mxf8_bf16_tn.
+// Each entry runs its MX sibling's chain under its own name, with the fmt check where the sibling checks the method (abs-max is the only method).
+int qutlass_amd_fused_quantize_mxf8(const void* x, const void* h, int rot, int64_t numel, int fmt, void* out_fp8, void* out_e8m0, void* stream) {
+  return fused_quantize_impl("fusedQuantizeMxf8", kQuantMxf8, x, h, rot, numel, 0, QAMD_METHOD_ABSMAX, nullptr, out_fp8, out_e8m0, nullptr, stream, fmt);
+}
+
+int qutlass_amd_fused_quantize_mxf8_blocked(const void* x, const void* h, int rot, int64_t rows, int64_t k, int fmt, void* out_fp8, void* out_e8m0_blocked,
+                                            void* stream) {
+  if (int rc = blocked_shape_check("fusedQuantizeMxf8Blocked", rows, k)) return rc;
+  return fused_quantize_impl("fusedQuantizeMxf8Blocked", kQuantMxf8, x, h, rot, rows * k, k, QAMD_METHOD_ABSMAX, nullptr, out_fp8, out_e8m0_blocked, nullptr, stream, fmt);
+}
+
+int qutlass_amd_fused_silu_mul_quantize_mxf8(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int fmt, int blocked, void* out_fp8, void* out_e8m0,
+                                             void* stream) {
+  return fused_silu_mul_quantize_impl(blocked ? "fusedSiluMulQuantizeMxf8Blocked" : "fusedSiluMulQuantizeMxf8", kQuantMxf8, x, h, rot, rows, inter, QAMD_METHOD_ABSMAX,
+                                      nullptr, blocked, out_fp8, out_e8m0, stream, nullptr, fmt);
+}
+
+int qutlass_amd_fused_gather_quantize_mxf8(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int fmt, void* out_fp8,
+                                           void* out_e8m0, void* stream) {
+  return fused_gather_quantize_impl("fusedGatherQuantizeMxf8", kQuantMxf8, x, h, rot, t, k, src_row, m, QAMD_METHOD_ABSMAX, nullptr, out_fp8, out_e8m0, stream, nullptr,
+                                    fmt);
 }
 
 // Combine: out[t] = sum_k w[t][k] * y[pos[t][k]] in the order and with the roundings moe_combine_bf16_kernel states (quantize.hip.h); slots outside [0, m) are skipped.

@@ -1,4 +1,4 @@
-// Fused rotate + quantize kernels for gfx950 (HBM-bound; 2 B/elem in, ~0.53-0.66 B/elem out).
+// Fused rotate + quantize kernels for gfx950 (HBM-bound; 2 B/elem in, ~0.53-0.66 B/elem out; 1.03 B/elem out for the MXFP8 arm).
 //
 //   fusedQuantizeMx : y = x_g . h (bf16 x bf16 -> fp32, x viewed as (numel/R, R), h a RUNTIME RxR
 //                     matrix), then per 32 values an e8m0 scale (abs-max or Quest) + 32 e2m1 codes
@@ -7,6 +7,8 @@
 //                     cutlass_extensions/epilogue/threadblock/epilogue_quant.h:460-812, :1087-1230.
 //   fusedQuantizeNv : same rotation, per 16 values an e4m3 scale relative to a global scale.
 //                     Replaces fused_quantize_nv.cu:109-252 / epilogue_quant.h:1560-2128.
+//   fusedQuantizeMxf8: same rotation, per 32 values an e8m0 scale (abs-max) + 32 e4m3 or e5m2 codes: the A operand of the MXFP8 GEMMs.  No reference counterpart
+//                     as a kernel; the scale rule is e8m0_shift7's (the FP8 arm of the epilogue below).
 //
 // CDNA4 mapping.  The rotation is computed TRANSPOSED on the bf16 MFMA:
 //   D^T (32 j x 32 rows) = H^T (32 j x 16 k) . X^T (16 k x 32 rows)   [v_mfma_f32_32x32x16_bf16]
@@ -22,11 +24,12 @@
 namespace qamd {
 
 enum { METHOD_QUEST = 0, METHOD_ABSMAX = 1 };
+enum { QF_E2M1 = 0, QF_E4M3 = 1, QF_E5M2 = 2 };   // output code format of the kernels (FMT): 4-bit (MX / NV) or one of the two 8-bit MX formats
 
 struct QuantParams {
   const uint16_t* x;   // bf16, numel
   const uint16_t* h;   // bf16, R x R row-major
-  uint8_t* out;        // packed e2m1, numel/2
+  uint8_t* out;        // packed e2m1, numel/2 (FMT e4m3 / e5m2: one byte per element, numel)
   uint8_t* out_sf;     // e8m0 (MX, numel/32) or e4m3 (NV, numel/16), flat group order
   uint32_t* out_mask;  // MX quest-with-mask: one u32 per 32-group (may be null)
   const float* global_scale;  // NV only
@@ -76,10 +79,12 @@ struct QuantFormat {
   bool mask;             // a clip mask may be asked for (method quest, R = 32)
   const char* rots;      // that set as the messages spell it
   const char* row_unit;  // the blocked row-length message names its unit "the rotation size" for MX (the unit is R) and gives the bare number for NV (max(R, 32))
+  bool fp8 = false;      // MXFP8: one code byte per element (e4m3 or e5m2, the entry's fmt), abs-max only, no clip mask; scales as MX
   constexpr bool has_rot(int rot) const { return rot >= min_rot && rot <= 128 && (rot & (rot - 1)) == 0; }
 };
 constexpr QuantFormat kQuantMx{false, 32, 32, true, "32, 64, or 128", "the rotation size "};
 constexpr QuantFormat kQuantNv{true, 16, 16, false, "16, 32, 64, or 128", ""};
+constexpr QuantFormat kQuantMxf8{false, 32, 32, false, "32, 64, or 128", "the rotation size ", true};
 
 // byte offset of scale (row, col) in the 128x4-tiled block-scale layout (qutlass/utils.py:60-64, :190-193); CB = ceil(cols / 4)
 __device__ __forceinline__ uint32_t blocked_sf_offset(uint32_t row, uint32_t col, uint32_t CB) {
@@ -148,6 +153,22 @@ __device__ __forceinline__ uint32_t e2m1_pack8(const float* t, float scale = 1.0
     for (int i = 0; i < 8; ++i) r |= e2m1_encode_sw(t[i]) << (4 * i);
     return r;
   }
+}
+
+// Four fp32 -> four e4m3fn (FMT = QF_E4M3) or e5m2 (QF_E5M2) bytes, t[0] in the low byte: v_cvt_scalef32_pk_{fp8,bf8}_f32, round-to-nearest-even, NaN stays NaN.
+// The converter's scale operand is left at 1.0 -- see the FP8 arm of the epilogue for why the block scale is applied by a multiply instead.
+template <int FMT>
+__device__ __forceinline__ uint32_t fp8_pack4(const float* t) {
+  typedef short v2s_ __attribute__((ext_vector_type(2)));
+  v2s_ w = {0, 0};
+  if constexpr (FMT == QF_E4M3) {
+    w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, t[0], t[1], 1.0f, false);
+    w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, t[2], t[3], 1.0f, true);
+  } else {
+    w = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(w, t[0], t[1], 1.0f, false);
+    w = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(w, t[2], t[3], 1.0f, true);
+  }
+  return __builtin_bit_cast(uint32_t, w);
 }
 
 // t[0..N) = a[0..N) * s as N/2 v_pk_mul_f32 (4 cycles per wave for two products, the same issue cost as one v_mul_f32:
@@ -312,11 +333,14 @@ __device__ __forceinline__ v4i silu_mul8(const v4i g, const v4i u) {
 //            right after the next tile's x loads, so the one global load has that tile's wait and this tile's MFMAs and epilogue to land -- and the epilogue lane
 //            picks its own row's value with a cross-lane read (ds_bpermute by (rem + row) / rpr, the split gather_off does).  Two registers: this tile's values and
 //            the next tile's.  There is no METHOD_QUEST instantiation: the NV Quest arm never reads gscale, so the grouped entries launch the single-scale Quest kernel.
+//   FMT    : QF_E2M1 (the default: everything above) or QF_E4M3 / QF_E5M2 -- the MXFP8 quantizers (MX abs-max without a clip mask; plain, BLK, GATED or GATHER):
+//            everything up to and including the MFMAs is the MX kernel, the epilogue is the FP8 arm below (one byte per element, a 32-byte run per group).
 // -------------------------------------------------------------------------------------------------
 // The kernel's body as a device function of (workgroup index, workgroup count): fused_quantize_kernel below is its plain launch; [r6] the one-launch decode layer
 // (gemm_mx_os.hip.h gemm_mx_os16_fq_kernel) runs it on its first few workgroups.  PAD = false: the zero padding of the blocked scale layout is left out (a reader that
 // only looks at the rows it wrote).
-template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false, bool GATHER = false, bool GSCALE = false>
+template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false, bool GATHER = false, bool GSCALE = false,
+          int FMT = QF_E2M1>
 __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const int bid, const int nblk) {
   constexpr int RP = (R < 32) ? 32 : R;         // rotation padded to one MFMA j-tile (R=16: block-diag)
   constexpr int KC = RP / 16;                   // 16-wide k chunks per row
@@ -343,6 +367,8 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   // x as rows of RP elements (for R = 16 two rotation rows share one 32-element "row")
   const int64_t ngroups = p.numel / (NV ? 16 : 32);
   static_assert(!(GATED && GATHER) && !(GATHER && (BLK || MASK)), "the gathering form: plain operand, flat scales, no clip mask");
+  static_assert(FMT == QF_E2M1 || ((FMT == QF_E4M3 || FMT == QF_E5M2) && !NV && METHOD == METHOD_ABSMAX && !MASK && !GSCALE && R >= 32),
+                "the MXFP8 arm: MX scales (so no R = 16), abs-max, no clip mask");
   static_assert(!GSCALE || (NV && METHOD == METHOD_ABSMAX && !BLK && !MASK && (GATED || GATHER)), "per-expert global scales: NV abs-max, flat scales, gathering or gated");
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, GATHER ? (uint32_t)p.src_n * (uint32_t)p.inter * 2u : (uint32_t)(p.numel * (GATED ? 4 : 2)));
 
@@ -651,7 +677,42 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
       // acc[4q+e] = y[r_abs][32 jt + 8q + 4 half + e]
       const int64_t grp32 = r_abs * JT + jt;   // 32-element group index in the flat output
 
-      if (!NV) {
+      if constexpr (FMT != QF_E2M1) {
+        // ------------------------------ MXFP8: e8m0 per 32, e4m3 / e5m2 codes ------------------
+        // amax = max |y| over the group (v_max_f32 drops NaNs: a group that is all NaN has amax 0), E = the exponent field of the FP32 amax, and
+        //   e8 = 127 if amax == 0, else clamp(E - SH, 0, 254),  SH = 7 (e4m3) / 14 (e5m2)
+        // -- the scaled maximum lies in [128, 256) / [2^14, 2^15), below the formats' largest finite values 448 / 57344: no finite input saturates, whatever
+        // the converter does on overflow.  Integer arithmetic on the exponent field; E <= 255 makes the upper clamp vacuous (e8 <= 248).
+        float m = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m = fmaxf(m, fabsf(acc[r]));
+        m = xhalf_max(m);
+        constexpr int SH = FMT == QF_E4M3 ? 7 : 14;
+        const int ex = (int)(__float_as_uint(m) >> 23) - SH;   // m >= +0: no sign bit above the exponent field
+        const uint32_t e8 = m == 0.f ? 127u : (uint32_t)(ex < 0 ? 0 : ex);
+        // q = RNE(y * 2^(127 - e8)).  The scaling is an fp32 MULTIPLY in front of a unit-scale convert, not the converter's scale operand: that operand would be
+        // 2^(e8 - 127), which for e8 = 0 (a group whose maximum is below 2^-120 / 2^-113) is 2^-127, an fp32 DENORMAL -- and what the converter makes of a
+        // denormal scale is not pinned by anything in this tree (tests/native/cvt_scale_probe.hip covers the fp4 converter with normal scales only).  The
+        // multiplier 2^(127 - e8) is a normal number for every e8 the rule can give (e8 in [0, 248]: 2^127 ... 2^-121), so the product is exact unless it
+        // falls below 2^-126 -- far under half the formats' smallest subnormals (2^-10, 2^-17), where it rounds to (signed) zero either way.  -0 keeps its sign.
+        float t[16];
+        scale_pk<16>(acc, 0, __uint_as_float((254u - e8) << 23), t);
+        // acc[4 q + e] = element 8 q + 4 half + e of the group: dword 2 q + half of its 32 bytes.  Half 0 keeps its dwords 0 and 2 and takes 1 and 3 from the
+        // partner lane, half 1 keeps 5 and 7 and takes 4 and 6: 8 of a lane's 16 bytes change hands, 4 per v_permlane32_swap each way -- two swaps (the e2m1 arm
+        // moves 4 of 8 bytes and needs one), then one 16-byte store per lane: the group is one 32-byte run.
+        const uint32_t w0 = fp8_pack4<FMT>(t), w1 = fp8_pack4<FMT>(t + 4), w2 = fp8_pack4<FMT>(t + 8), w3 = fp8_pack4<FMT>(t + 12);
+        auto s0 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);   // half 0: {own w0 = D0, partner w0 = D1}; half 1: {partner w2 = D4, own w2 = D5}
+        auto s1 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);   // half 0: {D2, D3}; half 1: {D6, D7}
+        v4i o;
+        o[0] = (int)s0[0];
+        o[1] = (int)s0[1];
+        o[2] = (int)s1[0];
+        o[3] = (int)s1[1];
+        if (grp32 < ngroups) {
+          *(v4i*)(p.out + grp32 * 32 + half * 16) = o;
+          if (half == 0) p.out_sf[BLK ? (int64_t)blocked_sf_offset(sf_row, sf_col0 + jt, sfCB) : grp32] = (uint8_t)e8;
+        }
+      } else if (!NV) {
         // ------------------------------ MX: e8m0 per 32 ----------------------------------------
         float scale;
         // nan_risk: the group may hold NaNs.  A NaN activation makes ALL outputs of its rotation NaN (0 x NaN included), an inf makes them +-inf or NaN: the
@@ -852,6 +913,20 @@ __global__ __launch_bounds__(256) void fused_gather_quantize_gscale_kernel(const
 template <int R>
 __global__ __launch_bounds__(256) void fused_silu_mul_quantize_gscale_kernel(const QuantParams p) {
   fused_quantize_body<R, true, METHOD_ABSMAX, false, true, false, true, true, false, true>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// the MXFP8 quantizers (fusedQuantizeMxf8[Blocked], fusedSiluMulQuantizeMxf8[Blocked], fusedGatherQuantizeMxf8): FMT = QF_E4M3 / QF_E5M2, abs-max
+template <int R, int FMT, bool BLK>
+__global__ __launch_bounds__(256) void fused_quantize_mxf8_kernel(const QuantParams p) {
+  fused_quantize_body<R, false, METHOD_ABSMAX, false, true, BLK, true, false, false, false, FMT>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+template <int R, int FMT, bool BLK>
+__global__ __launch_bounds__(256) void fused_silu_mul_quantize_mxf8_kernel(const QuantParams p) {
+  fused_quantize_body<R, false, METHOD_ABSMAX, false, true, BLK, true, true, false, false, FMT>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+template <int R, int FMT>
+__global__ __launch_bounds__(256) void fused_gather_quantize_mxf8_kernel(const QuantParams p) {
+  fused_quantize_body<R, false, METHOD_ABSMAX, false, true, false, true, false, true, false, FMT>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // silu_and_mul: x (rows, 2 I) bf16 -> out (rows, I) bf16, out[r][c] = act(x[r][c], x[r][I + c]) (silu_mul8 above).  Streaming, 4 B in + 2 B out per element: a

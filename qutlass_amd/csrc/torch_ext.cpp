@@ -273,28 +273,43 @@ void quant_check_rot(bool nv, int64_t rot, bool mask = false) {
 int64_t quant_rp(int64_t rot) { return rot < 32 ? 32 : rot; }   // rows are whole tiles of max(rot, 32) elements
 
 // the C ABI writes numel / 2 bytes of codes and one scale byte per group -- flat, or the padded to_blocked() matrix of the (numel / k, k / group) scales
-void quant_check_out(bool nv, const Tensor& OUT, const Tensor& OUT_sf, int64_t numel, int64_t k, bool blocked) {
+// (fp8: the MXFP8 ops -- one code byte per element)
+void quant_check_out(bool nv, const Tensor& OUT, const Tensor& OUT_sf, int64_t numel, int64_t k, bool blocked, bool fp8 = false) {
   const int64_t group = nv ? 16 : 32;
-  STD_TORCH_CHECK(nbytes(OUT) >= numel / 2, "OUT is too small");
+  STD_TORCH_CHECK(nbytes(OUT) >= (fp8 ? numel : numel / 2), "OUT is too small");
   STD_TORCH_CHECK(nbytes(OUT_sf) >= (blocked ? (numel / k + 127) / 128 * 128 * ((k / group + 3) / 4 * 4) : numel / group), "OUT_sf is too small",
                   blocked ? " for the blocked scale layout" : "");
 }
 
 const float* gscale_ptr(const Tensor* gscale) { return static_cast<const float*>(gscale->data_ptr()); }
 
-// OUT_mask != nullptr (MX only): Quest with clip mask (rotation 32 only)
-void quantize(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, Tensor* OUT_mask, const Tensor* gscale, int method) {
+// The MXFP8 ops (fusedQuantizeMxf8_ ...): OUT's dtype selects the code format -- the C ABI's fmt; the scales are e8m0 (or plain bytes).  e4m3_only: the gated op.
+int mxf8_fmt(const Tensor& OUT, const Tensor& OUT_sf, bool e4m3_only = false) {
+  const bool e4m3 = has_dtype(OUT, ScalarType::Float8_e4m3fn), e5m2 = has_dtype(OUT, ScalarType::Float8_e5m2);
+  if (e4m3_only) {
+    STD_TORCH_CHECK(e4m3, "OUT must be float8_e4m3fn");
+  } else {
+    STD_TORCH_CHECK(e4m3 || e5m2, "OUT must be float8_e4m3fn or float8_e5m2");
+  }
+  STD_TORCH_CHECK(has_dtype(OUT_sf, ScalarType::Float8_e8m0fnu) || has_dtype(OUT_sf, ScalarType::Byte), "OUT_sf must be float8_e8m0fnu or uint8");
+  return e5m2 ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3;
+}
+
+// OUT_mask != nullptr (MX only): Quest with clip mask (rotation 32 only).  fmt8 >= 0 (MX only): the MXFP8 op, method is not read.
+void quantize(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, Tensor* OUT_mask, const Tensor* gscale, int method, int fmt8 = -1) {
   std::vector<Named> ts{{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
   if (OUT_mask) ts.push_back({*OUT_mask, "OUT_mask"});
   const int64_t rot = quant_prelude(op, ts, gscale), numel = A.numel();
   STD_TORCH_CHECK(numel % rot == 0, "A must be divisible by", rot);
   quant_check_rot(gscale, rot, OUT_mask);
-  quant_check_out(gscale, OUT, OUT_sf, numel, 0, false);
+  quant_check_out(gscale, OUT, OUT_sf, numel, 0, false, fmt8 >= 0);
   if (OUT_mask) {
     STD_TORCH_CHECK(nbytes(*OUT_mask) >= numel / 8, "OUT_mask is too small");
   }
   const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  if (gscale)
+  if (fmt8 >= 0)
+    check_rc(qutlass_amd_fused_quantize_mxf8(A.data_ptr(), R.data_ptr(), (int)rot, numel, fmt8, OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+  else if (gscale)
     check_rc(qutlass_amd_fused_quantize_nv(A.data_ptr(), R.data_ptr(), (int)rot, numel, method, gscale_ptr(gscale), OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
   else
     check_rc(qutlass_amd_fused_quantize_mx(A.data_ptr(), R.data_ptr(), (int)rot, numel, method, OUT.data_ptr(), OUT_sf.data_ptr(),
@@ -343,15 +358,17 @@ void fusedQuantizeNv_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_s
 
 // ---- EXTENSION: quantizers that emit GEMM-ready (to_blocked-layout) scales: one launch instead of quantize + to_blocked ----------
 // A is (.., K); OUT_sf must hold the padded blocked matrix of the (numel / K, K / gs) scales.  method: 0 quest, 1 abs_max.
-void quantize_blocked(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method) {
+void quantize_blocked(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method, int fmt8 = -1) {
   const int64_t rot = quant_prelude(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, gscale);
   STD_TORCH_CHECK(A.dim() >= 1 && A.numel() > 0, "A must be a non-empty tensor");
   const int64_t numel = A.numel(), k = A.size(A.dim() - 1), rows = numel / k;
   quant_check_rot(gscale, rot);
   STD_TORCH_CHECK(k % quant_rp(rot) == 0, "the last dimension of A must be divisible by", quant_rp(rot));
-  quant_check_out(gscale, OUT, OUT_sf, numel, k, true);
+  quant_check_out(gscale, OUT, OUT_sf, numel, k, true, fmt8 >= 0);
   const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  if (gscale)
+  if (fmt8 >= 0)
+    check_rc(qutlass_amd_fused_quantize_mxf8_blocked(A.data_ptr(), R.data_ptr(), (int)rot, rows, k, fmt8, OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+  else if (gscale)
     check_rc(qutlass_amd_fused_quantize_nv_blocked(A.data_ptr(), R.data_ptr(), (int)rot, rows, k, (int)method, gscale_ptr(gscale), OUT.data_ptr(), OUT_sf.data_ptr(),
                                                    current_stream(A)));
   else
@@ -381,7 +398,7 @@ void siluAndMul_(const Tensor& X, Tensor OUT) {
 
 // offs != nullptr (NV, flat scales): one global scale per expert, gscale (E,) with the grouped GEMMs' offs (E,) int32
 void silu_mul_quantize(const char* op, const Tensor& X, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method, bool blocked,
-                       const Tensor* offs = nullptr) {
+                       const Tensor* offs = nullptr, int fmt8 = -1) {
   std::vector<Named> ts{{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
   if (offs) ts.push_back({*offs, "offs"});
   const int64_t rot = quant_prelude(op, ts, gscale, &method, offs);
@@ -389,9 +406,12 @@ void silu_mul_quantize(const char* op, const Tensor& X, const Tensor& R, Tensor&
   const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
   quant_check_rot(gscale, rot);
   STD_TORCH_CHECK(inter % quant_rp(rot) == 0, "the gate / up width must be divisible by", quant_rp(rot));
-  quant_check_out(gscale, OUT, OUT_sf, rows * inter, inter, blocked);
+  quant_check_out(gscale, OUT, OUT_sf, rows * inter, inter, blocked, fmt8 >= 0);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
-  if (offs)
+  if (fmt8 >= 0)
+    check_rc(qutlass_amd_fused_silu_mul_quantize_mxf8(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, fmt8, blocked ? 1 : 0, OUT.data_ptr(), OUT_sf.data_ptr(),
+                                                      current_stream(X)));
+  else if (offs)
     check_rc(qutlass_amd_fused_silu_mul_quantize_nv_grouped(X.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, gscale_ptr(gscale),
                                                             static_cast<const int32_t*>(offs->data_ptr()), offs->size(0), OUT.data_ptr(), OUT_sf.data_ptr(),
                                                             current_stream(X)));
@@ -416,7 +436,7 @@ void fusedSiluMulQuantizeNvGrouped_(const Tensor& A, const Tensor& R, Tensor OUT
 // fusedGatherQuantize{Mx,Nv}_: fusedQuantize{Mx,Nv}_ of A.index_select(0, src_row) in one launch, byte for byte; A (T, K) bf16, src_row (M) int32 read on the device (no
 // host sync).  OUT / OUT_sf are sized as for the plain quantizers on an (M, K) tensor; flat scales.
 void gather_quantize(const char* op, const Tensor& X, const Tensor& R, const Tensor& src_row, Tensor& OUT, Tensor& OUT_sf, const Tensor* gscale, int64_t method,
-                     const Tensor* offs = nullptr) {
+                     const Tensor* offs = nullptr, int fmt8 = -1) {
   std::vector<Named> ts{{X, "A"}, {R, "B"}, {src_row, "src_row"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
   if (offs) ts.push_back({*offs, "offs"});
   const int64_t rot = quant_prelude(op, ts, gscale, &method, offs);
@@ -425,9 +445,12 @@ void gather_quantize(const char* op, const Tensor& X, const Tensor& R, const Ten
   const int64_t T = X.size(0), K = X.size(1), M = src_row.size(0);
   quant_check_rot(gscale, rot);
   STD_TORCH_CHECK(K % quant_rp(rot) == 0, "the last dimension of A must be divisible by", quant_rp(rot));
-  quant_check_out(gscale, OUT, OUT_sf, M * K, K, false);
+  quant_check_out(gscale, OUT, OUT_sf, M * K, K, false, fmt8 >= 0);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
-  if (offs)
+  if (fmt8 >= 0)
+    check_rc(qutlass_amd_fused_gather_quantize_mxf8(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, fmt8, OUT.data_ptr(),
+                                                    OUT_sf.data_ptr(), current_stream(X)));
+  else if (offs)
     check_rc(qutlass_amd_fused_gather_quantize_nv_grouped(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, (int)method,
                                                           gscale_ptr(gscale), static_cast<const int32_t*>(offs->data_ptr()), offs->size(0), OUT.data_ptr(),
                                                           OUT_sf.data_ptr(), current_stream(X)));
@@ -447,6 +470,22 @@ void fusedGatherQuantizeNv_(const Tensor& A, const Tensor& R, const Tensor& src_
 void fusedGatherQuantizeNvGrouped_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf, const Tensor& global_scales, const Tensor& offs,
                                    int64_t method) {
   gather_quantize("fusedGatherQuantizeNvGrouped", A, R, src_row, OUT, OUT_sf, &global_scales, method, &offs);
+}
+
+// ---- EXTENSION: the MXFP8 quantizers -- e4m3 / e5m2 codes with one e8m0 scale per 32 elements, abs-max; the same four forms through the same four functions ------
+// OUT is (.., K) float8_e4m3fn or float8_e5m2 (the dtype selects the format; the gated op takes e4m3 only), OUT_sf as for the MX ops.
+void fusedQuantizeMxf8_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf) {
+  quantize("fusedQuantizeMxf8", A, R, OUT, OUT_sf, nullptr, nullptr, QAMD_METHOD_ABSMAX, mxf8_fmt(OUT, OUT_sf));
+}
+void fusedQuantizeMxf8Blocked_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf) {
+  quantize_blocked("fusedQuantizeMxf8Blocked", A, R, OUT, OUT_sf, nullptr, QAMD_METHOD_ABSMAX, mxf8_fmt(OUT, OUT_sf));
+}
+void fusedSiluMulQuantizeMxf8_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, bool blocked) {
+  silu_mul_quantize(blocked ? "fusedSiluMulQuantizeMxf8Blocked" : "fusedSiluMulQuantizeMxf8", A, R, OUT, OUT_sf, nullptr, QAMD_METHOD_ABSMAX, blocked, nullptr,
+                    mxf8_fmt(OUT, OUT_sf, true));
+}
+void fusedGatherQuantizeMxf8_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf) {
+  gather_quantize("fusedGatherQuantizeMxf8", A, R, src_row, OUT, OUT_sf, nullptr, QAMD_METHOD_ABSMAX, nullptr, mxf8_fmt(OUT, OUT_sf));
 }
 
 // moeCombine_: OUT[t] = sum_k weights[t][k] * Y[pos[t][k]] (the arithmetic is spelled out at qutlass_amd_moe_combine_bf16); slots with pos outside [0, M) are skipped
@@ -684,6 +723,10 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("fusedGatherQuantizeNv_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scale, int method) -> ()");
   m.def("fusedGatherQuantizeNvGrouped_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scales, Tensor offs, int method) -> ()");
   m.def("fusedSiluMulQuantizeNvGrouped_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, Tensor global_scales, Tensor offs, int method) -> ()");
+  m.def("fusedQuantizeMxf8_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf) -> ()");   // OUT's dtype (float8_e4m3fn / float8_e5m2) selects the code format
+  m.def("fusedQuantizeMxf8Blocked_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf) -> ()");
+  m.def("fusedSiluMulQuantizeMxf8_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, bool blocked) -> ()");
+  m.def("fusedGatherQuantizeMxf8_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf) -> ()");
   m.def("moeCombine_(Tensor Y, Tensor pos, Tensor weights, Tensor(a!) OUT) -> ()");
   m.def("moeTopkSoftmax_(Tensor logits, Tensor(a!) weights, Tensor(b!) ids, bool renormalize) -> ()");
   m.def("moeTopkGrouped_(Tensor logits, Tensor bias, Tensor(a!) weights, Tensor(b!) ids, Tensor(c!) scores, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor) -> ()");
@@ -733,6 +776,10 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("fusedGatherQuantizeNv_", TORCH_BOX(&fusedGatherQuantizeNv_));
   m.impl("fusedGatherQuantizeNvGrouped_", TORCH_BOX(&fusedGatherQuantizeNvGrouped_));
   m.impl("fusedSiluMulQuantizeNvGrouped_", TORCH_BOX(&fusedSiluMulQuantizeNvGrouped_));
+  m.impl("fusedQuantizeMxf8_", TORCH_BOX(&fusedQuantizeMxf8_));
+  m.impl("fusedQuantizeMxf8Blocked_", TORCH_BOX(&fusedQuantizeMxf8Blocked_));
+  m.impl("fusedSiluMulQuantizeMxf8_", TORCH_BOX(&fusedSiluMulQuantizeMxf8_));
+  m.impl("fusedGatherQuantizeMxf8_", TORCH_BOX(&fusedGatherQuantizeMxf8_));
   m.impl("moeCombine_", TORCH_BOX(&moeCombine_));
   m.impl("moeTopkSoftmax_", TORCH_BOX(&moeTopkSoftmax_));
   m.impl("moeTopkGrouped_", TORCH_BOX(&moeTopkGrouped_));

@@ -77,7 +77,8 @@ def _register_fakes() -> None:
 
     for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
                  "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
-                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "fusedGatherQuantizeNvGrouped_", "fusedSiluMulQuantizeNvGrouped_", "moeCombine_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "fusedGatherQuantizeNvGrouped_", "fusedSiluMulQuantizeNvGrouped_",
+                 "fusedQuantizeMxf8_", "fusedQuantizeMxf8Blocked_", "fusedSiluMulQuantizeMxf8_", "fusedGatherQuantizeMxf8_", "moeCombine_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -230,6 +231,8 @@ def _define_functional_ops() -> None:
 # twin:    the in-place op of csrc/torch_ext.cpp: the same arguments with OUT, OUT_sf inserted after the `lead` leading tensors
 # operand: the shape of the tensor that is rotated and quantized, from the leading tensors -- the results are the plain quantizers' for a tensor of that shape
 # fmt:     a key of QUANT_FORMATS;  blocked: scales flat in the to_blocked() layout -- fixed by the op, or None where it is the op's last argument
+# The "mxf8" ops have no method: the argument behind the leading tensors is the code dtype (float8_e4m3fn / float8_e5m2).  It decides what is allocated and is not
+# passed on to the twin, which reads the format off OUT's dtype.
 class QuantOp(NamedTuple):
     schema: str
     twin: str
@@ -251,7 +254,8 @@ def _gathered(A, R, src_row):   # MoE dispatch: the operand is A[src_row], (M, K
     return (src_row.size(0), A.size(-1))
 
 
-QUANT_FORMATS = {"mx": (32, torch.float8_e8m0fnu), "nv": (16, torch.float8_e4m3fn)}   # elements per scale, scale dtype
+QUANT_FORMATS = {"mx": (32, torch.float8_e8m0fnu), "nv": (16, torch.float8_e4m3fn), "mxf8": (32, torch.float8_e8m0fnu)}   # elements per scale, scale dtype
+MXF8_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2)   # code dtypes of the "mxf8" ops; "mx" and "nv" pack two e2m1 codes per uint8
 QUANT_OPS = {
     "quantize_mx": QuantOp("(Tensor A, Tensor R, int method) -> (Tensor, Tensor)", "fusedQuantizeMx_", 2, _same, "mx", False),
     "quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedQuantizeNv_", 2, _same, "nv", False),
@@ -266,23 +270,36 @@ QUANT_OPS = {
                                           "fusedGatherQuantizeNvGrouped_", 3, _gathered, "nv", False),
     "silu_mul_quantize_nv_grouped": QuantOp("(Tensor A, Tensor R, Tensor global_scales, Tensor offs, int method) -> (Tensor, Tensor)", "fusedSiluMulQuantizeNvGrouped_", 2,
                                             _act, "nv", False),
+    # MXFP8: e4m3 / e5m2 codes, one e8m0 scale per 32 elements, abs-max (the gated op: e4m3 only)
+    "quantize_mxf8": QuantOp("(Tensor A, Tensor R, ScalarType dtype) -> (Tensor, Tensor)", "fusedQuantizeMxf8_", 2, _same, "mxf8", False),
+    "quantize_mxf8_blocked": QuantOp("(Tensor A, Tensor R, ScalarType dtype) -> (Tensor, Tensor)", "fusedQuantizeMxf8Blocked_", 2, _same, "mxf8", True),
+    "silu_mul_quantize_mxf8": QuantOp("(Tensor A, Tensor R, ScalarType dtype, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeMxf8_", 2, _act, "mxf8", None),
+    "gather_quantize_mxf8": QuantOp("(Tensor A, Tensor R, Tensor src_row, ScalarType dtype) -> (Tensor, Tensor)", "fusedGatherQuantizeMxf8_", 3, _gathered, "mxf8", False),
 }
 
 
+def mxf8_dtype(dtype) -> torch.dtype:
+    if dtype not in MXF8_DTYPES:
+        raise ValueError(f"invalid dtype {dtype!r}, must be torch.float8_e4m3fn or torch.float8_e5m2")
+    return dtype
+
+
 def alloc_quant(row: QuantOp, *args):
-    """The results of one family op, uninitialised: packed e2m1 (.., K / 2) uint8 and the scales -- (padded_rows, padded_cols), or their product flat when blocked --
-    of the operand (.., K); args as the functional op takes them.  The one allocator of the fake kernels, the functional ops and the eager wrappers."""
+    """The results of one family op, uninitialised: packed e2m1 (.., K / 2) uint8 -- "mxf8": (.., K) codes in the dtype asked for -- and the scales -- (padded_rows,
+    padded_cols), or their product flat when blocked -- of the operand (.., K); args as the functional op takes them.  The one allocator of the fake kernels, the
+    functional ops and the eager wrappers."""
     shape = row.operand(*args[:row.lead])
     group, sf_dtype = QUANT_FORMATS[row.fmt]
     pr, pc = padded_scale_shape(math.prod(shape) // shape[-1], shape[-1], group)
     blocked = args[-1] if row.blocked is None else row.blocked
-    return (args[0].new_empty((*shape[:-1], shape[-1] // 2), dtype=torch.uint8), args[0].new_empty((pr * pc,) if blocked else (pr, pc), dtype=sf_dtype))
+    codes = args[0].new_empty(shape, dtype=mxf8_dtype(args[row.lead])) if row.fmt == "mxf8" else args[0].new_empty((*shape[:-1], shape[-1] // 2), dtype=torch.uint8)
+    return codes, args[0].new_empty((pr * pc,) if blocked else (pr, pc), dtype=sf_dtype)
 
 
 def run_quant(row: QuantOp, *args):
     """Allocate, then the in-place twin."""
     o = alloc_quant(row, *args)
-    getattr(torch.ops.qutlass_amd, row.twin)(*args[:row.lead], o[0], o[1], *args[row.lead:])
+    getattr(torch.ops.qutlass_amd, row.twin)(*args[:row.lead], o[0], o[1], *args[row.lead + (row.fmt == "mxf8"):])
     return o
 
 
