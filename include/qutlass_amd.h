@@ -306,6 +306,46 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
                                  void* stream);
 
 /*
+ * EXTENSION (no reference counterpart): what a gpt-oss mixture-of-experts layer needs around the grouped GEMMs -- the clamped SwiGLU with the gate/up bias of the
+ * row's expert, alone and fused into the MXFP4 quantizer, and moe_combine with the down projection's bias.  The reference model adds each bias to the bf16 GEMM result
+ * in bf16; so do these, in the op that reads the GEMM's output.
+ *   x      bf16 (rows, 2 * inter), contiguous, 16-byte aligned, [gate | up] halves as above (gpt-oss stores the columns interleaved: de-interleave the weight, its
+ *          scales and its bias once at load time)
+ *   alpha  fp32, finite, > 0 (gpt-oss: 1.702);  limit  > 0, finite and exactly representable in bf16 (gpt-oss: 7) -- QAMD_ERR_INVALID otherwise
+ *   bias   null, or bf16 (e, 2 * inter) in the same halves, 16-byte aligned; 1 <= e <= 1024.  With a bias x is (rows, 2 * inter) SORTED rows and row r takes
+ *          bias[g(r)], g(r) = min(e - 1, #{ g : offs[g] <= r }) -- the lookup of the *_nv_grouped entries above; rows at or past offs[e - 1] take expert e - 1's
+ *   offs   int32 (e), device memory, 4-byte aligned: the grouped GEMMs' cumulative END rows.  Required for e > 1; never read (may be null) for e == 1.  Malformed
+ *          offs select SOME expert in [0, e) and cannot address outside bias.  Without a bias, offs and e are not read.
+ * Per element, g, u, bg, bu bf16:
+ *     g1 = bias ? bf16_rne(fadd(float(g), float(bg))) : g       u1 = bias ? bf16_rne(fadd(float(u), float(bu))) : u        (what a bf16 tensor add computes)
+ *     gc = min(g1, limit)                                       uc = min(max(u1, -limit), limit)                           (exact)
+ *     s   = bf16 of the REAL number gc / (1 + exp(-alpha * gc)), correctly rounded (alpha the fp32 value, the product not rounded): fp32 arithmetic with
+ *           alpha * log2 e split into a 16-bit part and a remainder, redone in fp64 within 16 fp32 ulp of a bf16 tie and for |alpha * gc| > 16
+ *     act = bf16_rne(fmul(float(s), fadd(float(uc), 1.0f)))     (one fp32 add, one fp32 multiply, no fma, then RNE)
+ * Fewer roundings than the model's bf16 op chain, on purpose.  For |gc| < 2^-120 the true s lies within 2^-130 (relative) of a tie between bf16 subnormals: s is
+ * then within one bf16 step, and no more is promised.  NaN / +-inf in gate, up or bias give unspecified bytes for their own element (fused: their own rotation
+ * group).  A zero gate, up and bias give +0: zero-padded columns (gpt-oss: 2880 -> 2944 with zero weight rows and zero bias) stay zero.
+ * qutlass_amd_swiglu_oai_mul_bf16 writes act, bf16 (rows, inter); inter % 8 == 0; rows, inter < 2^31 (64-bit addressing).
+ * qutlass_amd_fused_swiglu_oai_quantize_mx: qutlass_amd_fused_quantize_mx applied to act viewed as (rows, inter), byte for byte, in one launch: flat scales in the
+ * first rows * inter / 32 bytes, the rest of the caller's buffer untouched; rot 32 or 64 (128: QAMD_ERR_INVALID, the message names the two-call composition);
+ * inter % rot == 0; both methods; hardware e2m1 convert, no clip mask, no blocked form.  LIMIT: x, and bias, below 2 GiB (rows * inter, e * inter < 2^29).
+ * qutlass_amd_moe_combine_bias_bf16: qutlass_amd_moe_combine_bf16 with bias bf16 (e, hdim), 16-byte aligned, and offs as above (required for e > 1):
+ *     acc = +0.0f
+ *     for k = 0 .. topk - 1, in this order:  p = pos[t][k];  if 0 <= p < m:
+ *         v   = bf16_rne(fadd(float(y[p][c]), float(bias[g(p)][c])))
+ *         acc = fadd_rn(acc, fmul_rn(weights[t][k], float(v)))
+ *     out[t][c] = bf16_rne(acc)
+ * g(p) is the group the grouped GEMM computed row p in.  Skipped slots stay skipped: nothing read of y or bias for them reaches out.  Limits as the plain entry.
+ * Checks: all before any HIP call; rows == 0 / t == 0 returns QAMD_OK without a launch.
+ */
+int qutlass_amd_swiglu_oai_mul_bf16(const void* x, int64_t rows, int64_t inter, float alpha, float limit, const void* bias, const int32_t* offs, int64_t e,
+                                    void* out, void* stream);
+int qutlass_amd_fused_swiglu_oai_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, float alpha, float limit,
+                                             const void* bias, const int32_t* offs, int64_t e, void* out_e2m1, void* out_e8m0, void* stream);
+int qutlass_amd_moe_combine_bias_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk,
+                                      const void* bias, const int32_t* offs, int64_t e, void* out, void* stream);
+
+/*
  * EXTENSION (no reference counterpart): the two NV quantizers of the MoE chain with ONE GLOBAL SCALE PER EXPERT -- what the per-expert alpha of
  * qutlass_amd_grouped_matmul_nvf4_bf16_tn (alpha[g] = 1 / (a_gs[g] * w_gs[g])) expects of its A operand, in one graph-capturable launch.
  *   global_scales  float32 (e), device memory;  offs  int32 (e), device memory, 4-byte aligned: the grouped GEMMs' cumulative END rows (qutlass_amd_moe_sort's offs);

@@ -15,6 +15,8 @@ meaning, defaults and Python-level error behaviour):
     fusedQuantizeMxf8 [Blocked], fusedGatherQuantizeMxf8, fusedSiluMulQuantizeMxf8 [Blocked]  (extension: the MXFP8 quantizers -- the operands of the three MXFP8 GEMMs)
     moe_topk_softmax, moe_sort_fused, moe_route           (extension: MoE routing in HIP -- router logits to ids, weights and the sorted-row metadata)
     moe_topk_grouped, moe_route_grouped                   (extension: the grouped router of DeepSeek-V2 / V3 and Kimi-K2 -- sigmoid / softmax scores, selection bias, group-limited top-k)
+    swiglu_oai_and_mul, fusedSwigluOaiQuantizeMx, moe_combine(bias=, offs=)  (extension: gpt-oss -- the clamped SwiGLU and the per-expert biases of both projections,
+                                                          applied by the ops that read the grouped GEMMs' outputs; utils.split_interleaved_gate_up for the checkpoint layout)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -156,7 +158,7 @@ def _quantize(op: str, *args):
     twin; under torch.compile: the functional op (see ops.py)."""
     if torch.compiler.is_compiling():
         return getattr(_ops_amd, op)(*args)
-    return ops.run_quant(ops.QUANT_OPS[op], *args)
+    return ops.run_quant_op(ops.QUANT_OPS[op], *args)
 
 
 def fusedQuantizeMx(a: torch.Tensor, b: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest",
@@ -464,7 +466,98 @@ def fusedSiluMulQuantizeMxf8Blocked(x: torch.Tensor, h: torch.Tensor) -> tuple[t
     return _silu_mul_quantize("silu_mul_quantize_mxf8", x, h, torch.float8_e4m3fn, True)
 
 
-def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+def _bf16_exact(v: float) -> bool:
+    import struct
+
+    try:
+        return struct.unpack("<I", struct.pack("<f", v))[0] & 0xffff == 0
+    except OverflowError:
+        return False
+
+
+def _check_swiglu_oai(x, alpha, limit, bias, offs, rot=None):
+    """The Python-level checks of the two clamped-SwiGLU ops (a traced call leaves the shapes to the op's own checks)."""
+    import math
+
+    if torch.compiler.is_compiling():   # (the C entry repeats the value checks)
+        return float(alpha), float(limit)
+    alpha, limit = float(alpha), float(limit)
+    if not (math.isfinite(alpha) and alpha > 0):
+        raise ValueError(f"alpha must be finite and > 0 (got {alpha})")
+    if not (math.isfinite(limit) and limit > 0 and _bf16_exact(limit)):
+        raise ValueError(f"limit must be > 0, finite and exactly representable in bf16 (got {limit})")
+    if rot == 128:
+        raise ValueError("rotation size 128 is not supported by fusedSwigluOaiQuantizeMx (R = 32 or 64): use swiglu_oai_and_mul followed by fusedQuantizeMx")
+    if x.size(-1) % 2:
+        raise ValueError(f"the last dimension of x must be 2 * I (got {x.size(-1)})")
+    if bias is None:
+        if offs is not None:
+            raise ValueError("offs without a bias")
+    else:
+        if bias.dim() != 2 or bias.size(1) != x.size(-1):
+            raise ValueError(f"bias must be (E, 2 * I) = (E, {x.size(-1)}) (got {tuple(bias.shape)})")
+        _check_bias_offs(bias, offs)
+    return alpha, limit
+
+
+def _check_bias_offs(bias, offs):
+    E = bias.size(0)
+    if not 1 <= E <= 1024:
+        raise ValueError(f"the number of experts must be in [1, 1024] (got {E})")
+    if offs is None:
+        if E > 1:
+            raise ValueError(f"a bias of E = {E} experts needs offs")
+    elif offs.dim() != 1 or offs.size(0) != E or offs.dtype != torch.int32:
+        raise ValueError(f"offs must be an int32 tensor of (E,) = ({E},) (got {offs.dtype} {tuple(offs.shape)})")
+
+
+def swiglu_oai_and_mul(x: torch.Tensor, *, alpha: float = 1.702, limit: float = 7.0, bias: torch.Tensor | None = None,
+                       offs: torch.Tensor | None = None) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): the activation of a gpt-oss expert, the clamped SwiGLU, as one streaming HIP kernel -- with the gate/up bias of the row's
+    expert added on the way in.  x is (.., 2 I) bf16, contiguous, with gate = x[..., :I] and up = x[..., I:] (gpt-oss stores the columns interleaved:
+    utils.split_interleaved_gate_up, once at load time); the result is (.., I) bf16.  Per element, g, u, bg, bu bf16:
+
+        g1 = bf16(float(g) + float(bg)),  u1 = bf16(float(u) + float(bu))     with a bias (one fp32 add, then RNE: torch's bf16 add); else g1 = g, u1 = u
+        gc = min(g1, limit);   uc = min(max(u1, -limit), limit)                (exact)
+        s  = bf16 of the REAL number gc / (1 + exp(-alpha * gc)), CORRECTLY rounded (alpha the fp32 value, the product not rounded: fp32 arithmetic, fp64 near a
+             bf16 tie and for |alpha * gc| > 16)
+        act = bf16(float(s) * (float(uc) + 1.0f))                              (one fp32 add, one fp32 multiply, no fma, then RNE)
+
+    Deliberately NOT bit-equal to the reference model's bf16 op chain (which rounds alpha * gate, the sigmoid, up + 1 and both products separately): fewer
+    roundings, closer to the exact function.  For gates with |gc| < 2^-120 the true s lies within 2^-130 (relative) of a tie between bf16 subnormals; s is then
+    within one bf16 step, and no more is promised.  NaN / +-inf in gate, up or bias give unspecified bytes for their own element.  A zero gate, up and bias give +0,
+    so zero-padded columns are harmless: gpt-oss's H = I = 2880 is no multiple of 128 -- pad K to 2944 with zero weight rows and zero bias.
+
+    bias (E, 2 I) bf16 in the same [gate | up] halves, 1 <= E <= 1024; offs (E,) int32 on the device, the grouped GEMMs' cumulative END rows -- required for E > 1,
+    optional for E == 1.  With a bias x is read as (rows, 2 I) SORTED rows: row r takes bias[g(r)], g(r) = min(E - 1, #{g : offs[g] <= r}), the group the grouped GEMM
+    put the row in; rows at or past offs[-1] take expert E - 1's bias.  Malformed offs select SOME expert in [0, E) and cannot address outside bias.  offs is read
+    on the device (no host sync: graph-capturable).  I % 8 == 0; alpha finite and > 0; limit > 0, finite and a bf16 value -- ValueError otherwise.
+    Measured 4.5-5.4x faster (with fusedQuantizeMx behind it) than the torch composition of bias add, clamp, sigmoid and multiply (README;
+    profiles/bench_swiglu_oai_mi355x.txt)."""
+    alpha, limit = _check_swiglu_oai(x, alpha, limit, bias, offs)
+    if torch.compiler.is_compiling():
+        return _ops_amd.swiglu_oai_and_mul(x, alpha, limit, bias, offs)
+    return ops.run_swiglu_oai(x, alpha, limit, bias, offs)
+
+
+def fusedSwigluOaiQuantizeMx(x: torch.Tensor, h: torch.Tensor, *, alpha: float = 1.702, limit: float = 7.0, bias: torch.Tensor | None = None,
+                             offs: torch.Tensor | None = None, method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMx(swiglu_oai_and_mul(x, alpha=alpha, limit=limit, bias=bias, offs=offs), h, method=method)`` in ONE launch, byte for byte -- the
+    down projection's A operand of a gpt-oss layer: the quantizer reads gate, up and the two bias chunks of the row's expert itself and applies the activation in
+    registers (see swiglu_oai_and_mul for the arithmetic and fusedSiluMulQuantizeMx for the form).  Returns e2m1 (.., I/2) and e8m0 (padded_rows, padded_cols) as
+    fusedQuantizeMx does for a (.., I) tensor: scales flat in the first rows * I / 32 bytes, padding untouched -- what grouped_matmul_mxf4_bf16_tn reads as it is.
+    R in {32, 64} for the R x R rotation h (I = 2880 admits no 128, and the gated kernels at R = 128 are slower than their two launches: R = 128 raises -- use
+    swiglu_oai_and_mul followed by fusedQuantizeMx); I % R == 0; both methods; no clip mask, no blocked form.  x, and bias, below 2 GiB.  Non-finite gate / up /
+    bias values give unspecified bytes in their own rotation groups only.
+    Measured against the two calls (gpt-oss shapes, I = 2944, with bias; profiles/bench_swiglu_oai_mi355x.txt): R = 32 wins from 128 tokens x top-4 on (1.14-1.23x)
+    and is level to SLOWER at 16 tokens (0.95-1.01x); at R = 64 it is SLOWER up to 128 tokens (0.67-0.69x at 16, 0.94-0.96x at 128) and wins only at prefill sizes
+    (1.12-1.13x at 4096 tokens): keep swiglu_oai_and_mul + fusedQuantizeMx for R = 64 at decode sizes.  4.6-6.6x (R = 32) faster than the torch composition."""
+    code = _method_code(method)
+    alpha, limit = _check_swiglu_oai(x, alpha, limit, bias, offs, h.size(0) if h.dim() == 2 else None)
+    return _quantize("swiglu_oai_quantize_mx", x, h, alpha, limit, bias, offs, code)
+
+
+def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor, *, bias: torch.Tensor | None = None, offs: torch.Tensor | None = None) -> torch.Tensor:
     """EXTENSION (no reference counterpart): the weighted sum that ends a mixture-of-experts layer, one streaming HIP kernel.  y is (M, H) bf16 (the down projection's
     sorted rows), pos (T, topk) int32 (moe_sort's third result), weights (T, topk) float32; the result is (T, H) bf16 with, for every column c,
 
@@ -472,7 +565,25 @@ def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> to
 
     every product and every sum rounded to fp32 on its own (no fma: numpy.float32 reproduces it bit for bit), bf16 by round-to-nearest-even.  A slot with pos outside
     [0, M) is SKIPPED, not multiplied by zero: the unspecified rows a grouped GEMM leaves past offs[-1] (NaN, inf, garbage) never reach the result, and a token
-    whose slots are all dropped gives +0.  A gather without atomics: deterministic.  H % 8 == 0, 1 <= topk <= 32; no size limit below 2^31 rows / columns."""
+    whose slots are all dropped gives +0.  A gather without atomics: deterministic.  H % 8 == 0, 1 <= topk <= 32; no size limit below 2^31 rows / columns.
+
+    bias (E, H) bf16 with offs (E,) int32 (the grouped GEMMs' cumulative END rows; optional for E == 1): the down projection's per-expert bias of gpt-oss, added to
+    every gathered row in bf16 as the reference model adds it to the GEMM result -- a kernel of its own; without a bias the call is the op above, unchanged:
+
+        acc = +0.0f;  for k in slot order:  p = pos[t, k];  if 0 <= p < M:  v = bf16(float(y[p, c]) + float(bias[g(p), c]));  acc = acc + weights[t, k] * float(v)
+
+    g(p) = min(E - 1, #{g : offs[g] <= p}) is the group the grouped GEMM computed row p in, so an expert_map needs no special case.  Skipped slots stay skipped:
+    nothing of y or bias read for them reaches out.  1 <= E <= 1024; malformed offs select some expert in [0, E).  Measured 2.5-4.5x faster than torch's bias add
+    followed by the op; the bias costs 1.4-4.1 us over the op without one (profiles/bench_swiglu_oai_mi355x.txt)."""
+    if bias is not None:
+        if not torch.compiler.is_compiling():
+            if bias.dim() != 2 or bias.size(1) != y.size(-1):
+                raise ValueError(f"bias must be (E, H) = (E, {y.size(-1)}) (got {tuple(bias.shape)})")
+            _check_bias_offs(bias, offs)
+            return ops.run_moe_combine_bias(y, pos, weights, bias, offs)
+        return _ops_amd.moe_combine_bias(y, pos, weights, bias, offs)
+    if offs is not None:
+        raise ValueError("offs without a bias")
     if torch.compiler.is_compiling():
         return _ops_amd.moe_combine(y, pos, weights)
     out = torch.empty(pos.size(0), y.size(-1), dtype=y.dtype, device=y.device)

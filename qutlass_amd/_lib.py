@@ -15,7 +15,7 @@ QAMD_OK, QAMD_ERR_INVALID, QAMD_ERR_HIP = 0, 1, 2
 METHOD_QUEST, METHOD_ABSMAX = 0, 1
 MOE_SCORING = {"sigmoid": 0, "softmax": 1}   # QAMD_MOE_SCORING_*
 
-_vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+_vp, _i64, _i32, _f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 _GEMM_ARGS = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]
 
 SYMBOLS = {
@@ -52,6 +52,9 @@ SYMBOLS = {
     "qutlass_amd_fused_silu_mul_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "qutlass_amd_fused_gather_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "qutlass_amd_moe_combine_bf16": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "qutlass_amd_swiglu_oai_mul_bf16": (_i32, [_vp, _i64, _i64, _f32, _f32, _vp, _vp, _i64, _vp, _vp]),
+    "qutlass_amd_fused_swiglu_oai_quantize_mx": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "qutlass_amd_moe_combine_bias_bf16": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "qutlass_amd_moe_topk_softmax": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "qutlass_amd_moe_topk_grouped": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "qutlass_amd_moe_sort_workspace_bytes": (_i64, [_i64, _i64]),

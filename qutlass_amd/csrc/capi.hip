@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -1393,6 +1394,35 @@ int launch_bwd_quant(const BwdTParams& p, bool qt, int which, bool hw, int grid,
 }
 #endif
 
+// The clamped-SwiGLU kernels and moe_combine's bias form (quantize.hip.h) live in unit 5 with the other quantizers: the fused arm for R = 32 / 64 x method x
+// bias, the streaming activation with and without a bias, the combine.  The C entries (unit 1) have checked everything; these only pick the instantiation.
+int launch_swiglu_oai_quant(int rot, int method, bool bias, const QuantParams& p, hipStream_t s, int grid);
+int launch_swiglu_oai_stream(const SwigluOaiParams& p, int grid, hipStream_t s);
+int launch_moe_combine_bias(const MoeCombineBiasParams& p, int grid, hipStream_t s);
+#if QAMD_DEF(5)
+int launch_swiglu_oai_quant(int rot, int method, bool bias, const QuantParams& p, hipStream_t s, int grid) {
+  auto go = [&](auto r_, auto m_) {
+    using RT = decltype(r_); using M = decltype(m_);
+    if (bias) hipLaunchKernelGGL((fused_swiglu_oai_quantize_kernel<RT::value, M::value, true>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((fused_swiglu_oai_quantize_kernel<RT::value, M::value, false>), dim3(grid), dim3(256), 0, s, p);
+  };
+  using Quest = std::integral_constant<int, METHOD_QUEST>; using AbsMax = std::integral_constant<int, METHOD_ABSMAX>;
+  using R32 = std::integral_constant<int, 32>; using R64 = std::integral_constant<int, 64>;
+  if (rot == 32) { if (method == QAMD_METHOD_QUEST) go(R32{}, Quest{}); else go(R32{}, AbsMax{}); }
+  else { if (method == QAMD_METHOD_QUEST) go(R64{}, Quest{}); else go(R64{}, AbsMax{}); }
+  return check_launch("fused_swiglu_oai_quantize_kernel");
+}
+int launch_swiglu_oai_stream(const SwigluOaiParams& p, int grid, hipStream_t s) {
+  if (p.bias) hipLaunchKernelGGL(swiglu_oai_mul_bf16_kernel<true>, dim3(grid), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(swiglu_oai_mul_bf16_kernel<false>, dim3(grid), dim3(256), 0, s, p);
+  return check_launch("swiglu_oai_mul_bf16_kernel");
+}
+int launch_moe_combine_bias(const MoeCombineBiasParams& p, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(moe_combine_bias_bf16_kernel<0>, dim3(grid), dim3(256), 0, s, p);
+  return check_launch("moe_combine_bias_bf16_kernel");
+}
+#endif
+
 #if QAMD_DEF(1)
 int quant_grid(int ntiles, int rot) {
   // 4 waves per workgroup, one 32-row tile per wave per trip.  Small rotations are pure streaming: as many waves as
@@ -2000,6 +2030,101 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
   const int grid = (int)std::min<int64_t>(cdiv(p.chunks, 256), (int64_t)chip_cus() * 8);
   hipLaunchKernelGGL(moe_combine_bf16_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   return check_launch("moe_combine_bf16_kernel");
+}
+
+// ---- gpt-oss: the clamped SwiGLU with per-expert biases (quantize.hip.h, swiglu_oai_mul8), alone and fused into the MXFP4 quantizer; moe_combine with the down bias ----
+// alpha and limit -> the kernels' constants (SwigluOaiAct).  alpha * log2 e = c_hi + c_lo in fp64, c_hi rounded to 16 significant bits: with the gate's 8 the
+// product c_hi * gate is exact in fp32.  Outside [2^-100, 2^100] -- where c_hi or ln 2 * c_lo would leave fp32's normal range -- every element takes the fp64 path.
+static int swiglu_oai_act(const char* name, float alpha, float limit, SwigluOaiAct& a) {
+  if (!(alpha > 0.f) || !std::isfinite(alpha)) return fail(QAMD_ERR_INVALID, "%s: alpha must be finite and > 0 (got %g)", name, (double)alpha);
+  uint32_t lb;
+  memcpy(&lb, &limit, 4);
+  if (!(limit > 0.f) || !std::isfinite(limit) || (lb & 0xffffu))
+    return fail(QAMD_ERR_INVALID, "%s: limit must be > 0, finite and exactly representable in bf16 (got %.9g)", name, (double)limit);
+  const double c = (double)alpha * 1.4426950408889634;
+  int ex;
+  (void)frexp(c, &ex);
+  const double q = ldexp(1.0, ex - 16), chi = nearbyint(c / q) * q;
+  const bool fast = c >= ldexp(1.0, -100) && c <= ldexp(1.0, 100);
+  a.nch = fast ? (float)-chi : 0.f;
+  a.klo = fast ? (float)(-0.6931471805599453 * (c - chi)) : 0.f;
+  a.alpha = alpha; a.tmax = fast ? 16.0f : -1.0f; a.limit = limit;
+  return QAMD_OK;
+}
+
+// the checks a per-expert bias adds: e, the alignments, offs where more than one expert could own a row
+static int swiglu_oai_check_bias(const char* name, const void* bias, const int32_t* offs, int64_t e) {
+  if (e < 1 || e > qamd::QUANT_MAX_E) return fail(QAMD_ERR_INVALID, "%s: E must be in [1, %d] (got %lld)", name, qamd::QUANT_MAX_E, (long long)e);
+  if ((uintptr_t)bias % 16) return fail(QAMD_ERR_INVALID, "%s: bias must be 16-byte aligned", name);
+  if (!offs && e > 1) return fail(QAMD_ERR_INVALID, "%s: a bias of E = %lld experts needs offs", name, (long long)e);
+  if ((uintptr_t)offs % 4) return fail(QAMD_ERR_INVALID, "%s: offs must be 4-byte aligned", name);
+  return QAMD_OK;
+}
+
+int qutlass_amd_swiglu_oai_mul_bf16(const void* x, int64_t rows, int64_t inter, float alpha, float limit, const void* bias, const int32_t* offs, int64_t e, void* out,
+                                    void* stream) {
+  const char* name = "swiglu_oai_and_mul";
+  SwigluOaiParams p;
+  if (int rc = gated_common_check(name, x, rows, inter, 8)) return rc;
+  if ((uintptr_t)out % 16) return fail(QAMD_ERR_INVALID, "%s: out must be 16-byte aligned", name);
+  if (int rc = swiglu_oai_act(name, alpha, limit, p.act)) return rc;
+  if (bias) if (int rc = swiglu_oai_check_bias(name, bias, offs, e)) return rc;
+  if (rows == 0) return QAMD_OK;
+  if (!x || !out) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  p.x = (const uint16_t*)x; p.out = (uint16_t*)out; p.bias = (const uint16_t*)bias; p.offs = offs; p.E = bias ? (int)e : 0;
+  p.chunks = rows * (inter / 8); p.cpr = (uint32_t)(inter / 8);
+  const int grid = (int)std::min<int64_t>(cdiv(p.chunks, 256), (int64_t)chip_cus() * 8);
+  return launch_swiglu_oai_stream(p, grid, (hipStream_t)stream);
+}
+
+// fusedQuantizeMx(swiglu_oai_and_mul(x, ...), h) in one launch, byte for byte: the gated quantizer's chain with the activation's checks; flat scales only
+int qutlass_amd_fused_swiglu_oai_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, float alpha, float limit, const void* bias,
+                                             const int32_t* offs, int64_t e, void* out_e2m1, void* out_e8m0, void* stream) {
+  const char* name = "fusedSwigluOaiQuantizeMx";
+  QuantParams p;
+  if (rot == 128)
+    return fail(QAMD_ERR_INVALID, "%s: rotation size 128 is not supported; expected 32 or 64 (use swiglu_oai_and_mul followed by fusedQuantizeMx)", name);
+  if (rot != 32 && rot != 64) return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected 32 or 64.", name, rot);
+  if (int rc = quant_check_method(name, method)) return rc;
+  if (int rc = gated_common_check(name, x, rows, inter, rot)) return rc;
+  if (rows * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: x (rows * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(rows * inter * 4));
+  if (int rc = swiglu_oai_act(name, alpha, limit, p.oai)) return rc;
+  if (bias) {
+    if (int rc = swiglu_oai_check_bias(name, bias, offs, e)) return rc;
+    if (e * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: bias (E * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(e * inter * 4));
+  }
+  if (rows == 0) return QAMD_OK;
+  if (!x || !h || !out_e2m1 || !out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (int rc = quant_check_h(name, rot, h)) return rc;
+  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_e8m0;
+  p.out_mask = nullptr; p.global_scale = nullptr; p.inter = (int)inter;
+  p.bias = (const uint16_t*)bias; p.offs = offs; p.E = bias ? (int)e : 0;
+  const int grid = quant_fill(p, kQuantMx, rot, rows * inter, inter, false);
+  return launch_swiglu_oai_quant(rot, method, bias != nullptr, p, (hipStream_t)stream, grid);
+}
+
+// moe_combine with the down projection's per-expert bias added to every gathered row in bf16 (moe_combine_bias_bf16_kernel, quantize.hip.h)
+int qutlass_amd_moe_combine_bias_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, const void* bias,
+                                      const int32_t* offs, int64_t e, void* out, void* stream) {
+  const char* name = "moe_combine";
+  if (m < 0 || t < 0 || hdim <= 0 || m >= (1ll << 31) || t >= (1ll << 31) || hdim >= (1ll << 31))
+    return fail(QAMD_ERR_INVALID, "%s: bad shape (y (%lld, %lld), %lld tokens)", name, (long long)m, (long long)hdim, (long long)t);
+  if (hdim % 8) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of 8", name, (long long)hdim);
+  if (topk < 1 || topk > 32) return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, 32] (got %lld)", name, (long long)topk);
+  if (((uintptr_t)y | (uintptr_t)out) % 16) return fail(QAMD_ERR_INVALID, "%s: y and out must be 16-byte aligned", name);
+  if (int rc = swiglu_oai_check_bias(name, bias, offs, e)) return rc;
+  if (t == 0) return QAMD_OK;
+  if ((!y && m > 0) || !pos || !weights || !out || !bias) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (m == 0) {   // no row to name: every slot is skipped and every sum is its start, +0
+    if (hipMemsetAsync(out, 0, (size_t)(t * hdim * 2), (hipStream_t)stream) != hipSuccess) return fail(QAMD_ERR_HIP, "%s: hipMemsetAsync failed", name);
+    return QAMD_OK;
+  }
+  MoeCombineBiasParams p;
+  p.c.y = (const uint16_t*)y; p.c.pos = pos; p.c.w = weights; p.c.out = (uint16_t*)out;
+  p.c.chunks = t * (hdim / 8); p.c.cpr = (uint32_t)(hdim / 8); p.c.m = (uint32_t)m; p.c.topk = (int)topk;
+  p.bias = (const uint16_t*)bias; p.offs = offs; p.E = (int)e;
+  const int grid = (int)std::min<int64_t>(cdiv(p.c.chunks, 256), (int64_t)chip_cus() * 8);
+  return launch_moe_combine_bias(p, grid, (hipStream_t)stream);
 }
 
 // ---- MoE routing: the front of the chain (moe_route.hip.h) ---------------------------------------------------------------------------------------------------

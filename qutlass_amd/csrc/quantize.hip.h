@@ -26,6 +26,13 @@ namespace qamd {
 enum { METHOD_QUEST = 0, METHOD_ABSMAX = 1 };
 enum { QF_E2M1 = 0, QF_E4M3 = 1, QF_E5M2 = 2 };   // output code format of the kernels (FMT): 4-bit (MX / NV) or one of the two 8-bit MX formats
 
+// The constants of the clamped SwiGLU (swiglu_oai_mul8 below), made by the host from the caller's alpha and limit (swiglu_oai_act in capi.hip):
+//   alpha * log2 e = c_hi + c_lo in fp64, c_hi of 16 significant bits;  nch = -c_hi,  klo = -ln 2 * c_lo,  tmax = 16 (or -1: every element through fp64)
+struct SwigluOaiAct {
+  float nch, klo, alpha, tmax, limit;
+};
+enum { ACT_SILU = 0, ACT_OAI = 1, ACT_OAI_BIAS = 2 };   // activation of the GATED kernels (ACT)
+
 struct QuantParams {
   const uint16_t* x;   // bf16, numel
   const uint16_t* h;   // bf16, R x R row-major
@@ -49,6 +56,10 @@ struct QuantParams {
   // rows -- row m of the operand takes global_scale[quant_group_of_row(offs, E, m)].  No other kernel reads them.  (E sits in the tail padding; offs grows the struct.)
   int E = 0;
   const int32_t* offs = nullptr;
+  // OAI kernels only (fusedSwigluOaiQuantizeMx): the gated layout, with act = swiglu_oai(gate, up) (swiglu_oai_mul8 below) in place of silu(gate) * up.  With a bias
+  // (ACT == ACT_OAI_BIAS): bias (E, 2 * inter) bf16 in the same [gate | up] halves, row m of x takes bias[quant_group_of_row(offs, E, m)]; E == 1 never reads offs.
+  const uint16_t* bias = nullptr;
+  SwigluOaiAct oai = {};
 };
 
 // The expert that owns operand row m: g(m) = min(E - 1, #{ g : offs[g] <= m }) for non-decreasing offs -- the group the grouped GEMMs put the row in; rows at or past
@@ -306,6 +317,80 @@ __device__ __forceinline__ v4i silu_mul8(const v4i g, const v4i u) {
   return r;
 }
 
+// --- clamped SwiGLU (gpt-oss) ------------------------------------------------------------------------
+// Per element, g, u, bg, bu bf16, alpha an fp32 value > 0, limit a bf16 value > 0:
+//   g1 = bias ? bf16_rne(float(g) + float(bg)) : g,  u1 likewise          (one fp32 add, then RNE: a bf16 tensor add)
+//   gc = min(g1, limit),  uc = min(max(u1, -limit), limit)                 (exact)
+//   s  = the CORRECTLY rounded bf16 of the real number gc / (1 + exp(-alpha * gc))   (the product alpha * gc not rounded)
+//   act = bf16_rne(float(s) * (float(uc) + 1.0f))                          (one fp32 add, one fp32 multiply, no fma, then RNE)
+// s by silu's mechanism, the error analysis redone for a runtime alpha.  With T = alpha * log2 e * gc:
+//   fast path  |fl(alpha * gc)| <= 16, i.e. |T| <= 23.1 -- silu's own domain.  The host splits alpha * log2 e = c_hi + c_lo in fp64 with c_hi of 16 significant
+//              bits: gc has 8, so c_hi * gc is an exact fp32 product whatever alpha is, and |c_lo| <= 2^-16 c.  exp(-alpha gc) = 2^(-c_hi gc) * exp(-x),
+//              x = ln 2 c_lo gc, |x| <= ln 2 * 2^-16 * 23.1 = 2^-12.  Relative errors: v_exp_f32 2^-23; exp(-x) against 1 - x at most x^2 / 2 = 2^-25 (silu's
+//              fixed 15-bit c_hi happens to leave 2^-27); the rounding of klo and of gc * klo 2^-35; the fma 2^-24: e within 2^-22.19.  1 + e: that times
+//              e / (1 + e) <= 1, plus its rounding 2^-24: 2^-21.85.  v_rcp_f32 2^-23, the last product 2^-24: s within 3.72 * 2^-23 = 2^-21.1 of the true
+//              value, at most 7.5 fp32 ulp (silu: 7).  The tie window is widened from silu's 12 to 16 fp32 ulp either side.
+//   slow path  results within 16 fp32 ulp of a bf16 tie (2^-11 of the values), and |fl(alpha * gc)| > 16 or NaN -- the large-negative threshold is -16 / alpha,
+//              and the positive side joins it because limit and alpha are the caller's (gc * klo must not overflow against e0 = 0): fp64,
+//              gd / (1 + exp(-(double)alpha * gd)) with the product exact, rounded to bf16 once.  tmax = -1 (the host: alpha * log2 e outside
+//              [2^-100, 2^100], where c_hi or klo would leave fp32's normal range) sends every element here.
+// For |gc| < 2^-120 the true value lies within 2^-130 (relative) of a tie between bf16 subnormals, which fp64 does not resolve either: s is then within one
+// bf16 step.  A zero gate gives s = gate (signed), so zero gate, up and bias give +0 * 1 = +0.  NaN / inf: unspecified bytes for their own element.
+__device__ __forceinline__ float swiglu_oai_f32(float g, const SwigluOaiAct& a) {
+  const float e0 = __builtin_amdgcn_exp2f(g * a.nch);   // exact product
+  const float e = fmaf(e0, g * a.klo, e0);
+  return g * __builtin_amdgcn_rcpf(1.0f + e);
+}
+__device__ __forceinline__ bool swiglu_oai_needs_fp64(float g, float s, const SwigluOaiAct& a) {
+  return ((__float_as_uint(s) & 0xffffu) - (0x8000u - 16u) <= 32u) || !(fabsf(g * a.alpha) <= a.tmax);
+}
+// 8 gate + 8 up bf16 (one 16-byte load each) [+ 8 + 8 bias bf16 of the row's expert] -> 8 packed act bf16.  The ONE definition of the activation, as silu_mul8 is:
+// swiglu_oai_mul_bf16_kernel stores its result, the OAI arm of the quantizer feeds it to the rotation MFMA.
+template <bool BIAS>
+__device__ __forceinline__ v4i swiglu_oai_mul8(const v4i g, const v4i u, const v4i bg, const v4i bu, const SwigluOaiAct& a) {
+#pragma clang fp contract(off)
+  uint32_t gc[4], sw[4], need = 0;
+  float up1[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint32_t gw = (uint32_t)g[i], uw = (uint32_t)u[i];
+    if constexpr (BIAS) {
+      const uint32_t bgw = (uint32_t)bg[i], buw = (uint32_t)bu[i];
+      gw = pack_bf16x2(__uint_as_float(gw << 16) + __uint_as_float(bgw << 16), __uint_as_float(gw & 0xffff0000u) + __uint_as_float(bgw & 0xffff0000u));
+      uw = pack_bf16x2(__uint_as_float(uw << 16) + __uint_as_float(buw << 16), __uint_as_float(uw & 0xffff0000u) + __uint_as_float(buw & 0xffff0000u));
+    }
+    // the clamps as compare + select: the values stay the bf16 values they were, subnormals included
+    const float gl = __uint_as_float(gw << 16), gh = __uint_as_float(gw & 0xffff0000u), ul = __uint_as_float(uw << 16), uh = __uint_as_float(uw & 0xffff0000u);
+    const float g0 = gl > a.limit ? a.limit : gl, g1 = gh > a.limit ? a.limit : gh;
+    gc[i] = (__float_as_uint(g0) >> 16) | (__float_as_uint(g1) & 0xffff0000u);
+    up1[2 * i] = (ul < -a.limit ? -a.limit : (ul > a.limit ? a.limit : ul)) + 1.0f;
+    up1[2 * i + 1] = (uh < -a.limit ? -a.limit : (uh > a.limit ? a.limit : uh)) + 1.0f;
+    const float s0 = swiglu_oai_f32(g0, a), s1 = swiglu_oai_f32(g1, a);
+    sw[i] = pack_bf16x2(s0, s1);
+    need |= (swiglu_oai_needs_fp64(g0, s0, a) ? 1u : 0u) << (2 * i) | (swiglu_oai_needs_fp64(g1, s1, a) ? 1u : 0u) << (2 * i + 1);
+  }
+  if (__builtin_expect(need != 0, 0)) {
+    // one copy of the fp64 code: a loop over the eight positions, taken by the lanes that flagged that position (as in silu_mul8)
+#pragma nounroll
+    for (int i = 0; i < 8; ++i) {
+      if (need & (1u << i)) {
+        const int w = i >> 1;
+        const uint32_t gw = w == 0 ? gc[0] : w == 1 ? gc[1] : w == 2 ? gc[2] : gc[3];
+        const double gd = (double)__uint_as_float((i & 1) ? (gw & 0xffff0000u) : (gw << 16));
+        const uint32_t r = f64_to_bf16_bits(gd / (1.0 + exp(-(double)a.alpha * gd)));
+        const uint32_t keep = (i & 1) ? 0x0000ffffu : 0xffff0000u, val = (i & 1) ? (r << 16) : r;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sw[k] = (k == w) ? ((sw[k] & keep) | val) : sw[k];
+      }
+    }
+  }
+  v4i r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    r[i] = (int)pack_bf16x2(__uint_as_float(sw[i] << 16) * up1[2 * i], __uint_as_float(sw[i] & 0xffff0000u) * up1[2 * i + 1]);
+  return r;
+}
+
 // -------------------------------------------------------------------------------------------------
 // Kernel.  One wave owns one 32-row tile at a time (grid-stride over tiles).
 //   R      : rotation size (MX: 32/64/128, NV: 16/32/64/128)
@@ -333,6 +418,15 @@ __device__ __forceinline__ v4i silu_mul8(const v4i g, const v4i u) {
 //            right after the next tile's x loads, so the one global load has that tile's wait and this tile's MFMAs and epilogue to land -- and the epilogue lane
 //            picks its own row's value with a cross-lane read (ds_bpermute by (rem + row) / rpr, the split gather_off does).  Two registers: this tile's values and
 //            the next tile's.  There is no METHOD_QUEST instantiation: the NV Quest arm never reads gscale, so the grouped entries launch the single-scale Quest kernel.
+//   ACT    : (GATED, MX e2m1, flat scales) ACT_OAI / ACT_OAI_BIAS: the activation is the clamped SwiGLU, swiglu_oai_mul8, in place of silu_mul8 -- nothing else changes.
+//            ACT_OAI_BIAS adds the gate/up bias of the row's expert: a tile's loads fetch, next to gate and up, the two bias chunks at the same columns of row
+//            quant_group_of_row(offs, E, logical row) of bias = (E, 2 I), through a descriptor of their own (bias stays below 2 GiB; the host checks; the expert is
+//            clamped to [0, E), so malformed offs cannot address outside it).  The lookup is GSCALE's: offs in LDS, lane l searches for logical row (first row of
+//            the tile) + (l & 31), a chunk load picks its row's expert with a cross-lane read -- and it runs AHEAD of the loads that depend on it, as GATHER's indices
+//            do: the experts of tile t + nwaves are looked up right after the bias loads of tile t went out (the first tile's after the barrier that publishes
+//            offs).  The bias loads themselves go out at the top of the tile that uses them, behind that tile's gate / up loads, which have been in flight for a
+//            whole tile: they are L2 hits (every row of an expert shares them), and holding a tile's bias chunks in registers across a tile as well (24-34 more
+//            VGPRs, a wave per SIMD) measured 2-6 % slower.
 //   FMT    : QF_E2M1 (the default: everything above) or QF_E4M3 / QF_E5M2 -- the MXFP8 quantizers (MX abs-max without a clip mask; plain, BLK, GATED or GATHER):
 //            everything up to and including the MFMAs is the MX kernel, the epilogue is the FP8 arm below (one byte per element, a 32-byte run per group).
 // -------------------------------------------------------------------------------------------------
@@ -340,7 +434,7 @@ __device__ __forceinline__ v4i silu_mul8(const v4i g, const v4i u) {
 // (gemm_mx_os.hip.h gemm_mx_os16_fq_kernel) runs it on its first few workgroups.  PAD = false: the zero padding of the blocked scale layout is left out (a reader that
 // only looks at the rows it wrote).
 template <int R, bool NV, int METHOD, bool MASK, bool HWCVT, bool BLK = false, bool PAD = true, bool GATED = false, bool GATHER = false, bool GSCALE = false,
-          int FMT = QF_E2M1>
+          int FMT = QF_E2M1, int ACT = ACT_SILU>
 __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const int bid, const int nblk) {
   constexpr int RP = (R < 32) ? 32 : R;         // rotation padded to one MFMA j-tile (R=16: block-diag)
   constexpr int KC = RP / 16;                   // 16-wide k chunks per row
@@ -370,11 +464,14 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   static_assert(FMT == QF_E2M1 || ((FMT == QF_E4M3 || FMT == QF_E5M2) && !NV && METHOD == METHOD_ABSMAX && !MASK && !GSCALE && R >= 32),
                 "the MXFP8 arm: MX scales (so no R = 16), abs-max, no clip mask");
   static_assert(!GSCALE || (NV && METHOD == METHOD_ABSMAX && !BLK && !MASK && (GATED || GATHER)), "per-expert global scales: NV abs-max, flat scales, gathering or gated");
+  static_assert(ACT == ACT_SILU || (GATED && !NV && !BLK && !MASK && !GSCALE && FMT == QF_E2M1 && R >= 32 && R <= 64), "the clamped SwiGLU: gated MX e2m1, flat scales, R = 32 / 64");
+  constexpr bool OAIB = ACT == ACT_OAI_BIAS;
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, GATHER ? (uint32_t)p.src_n * (uint32_t)p.inter * 2u : (uint32_t)(p.numel * (GATED ? 4 : 2)));
 
   const int wave_global = bid * 4 + wave, nwaves = nblk * 4;
   v4i xnext[RP / 16];
   v4i unext[GATED ? RP / 16 : 1];   // GATED: xnext holds the gate chunks, unext the up chunks of the same elements
+  v4i bgnext[OAIB ? RP / 16 : 1], bunext[OAIB ? RP / 16 : 1];   // ACT_OAI_BIAS: the bias chunks that go with them (loaded at the top of the tile that uses them)
   // per-lane byte offset inside a tile and the step between a lane's loads: MFMA layout (row, half; 32 bytes apart) or,
   // staged, chunk lane + 64 i of the tile's contiguous 32 * RP * 2 bytes
   const int lane_off = STAGED ? lane * 16 : row * RP * 2 + half * 16;
@@ -388,8 +485,10 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   uint32_t g_row = 0, g_rem = 0, g_qstep = 0, g_rstep = 0, g_rpr = 1, g_nrows = 0;
   float g_rc = 1.0f;
   // GSCALE: a second walk over the same tiles, (s_row, s_rem) = the tile whose scales are looked up next; n_rem = the rem of the tile gs_next belongs to
+  // (ACT_OAI_BIAS: the same walk for the experts, e_next = the expert of logical row (first row of that tile) + (lane & 31))
   uint32_t s_row = 0, s_rem = 0, n_rem = 0;
   float gs_next = 1.0f;
+  int e_next = 0;
   if constexpr (GATED || GATHER) {
     g_rpr = (uint32_t)p.inter / RP;
     g_rc = __builtin_amdgcn_rcpf((float)g_rpr);
@@ -399,7 +498,7 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     g_rem = r0 - g_row * g_rpr;
     g_qstep = step / g_rpr;
     g_rstep = step - g_qstep * g_rpr;
-    if constexpr (GSCALE) { s_row = g_row; s_rem = g_rem; }
+    if constexpr (GSCALE || OAIB) { s_row = g_row; s_rem = g_rem; }
   }
   // byte offset of the gate chunk (RP-row lrow of the tile at (g_row, g_rem), byte cb of that RP-row); up sits 2 I bytes further.  RP-rows past the end of act
   // (the last tile's tail, tiles past the end) get an offset off the descriptor: they read 0, as in the plain kernel.
@@ -480,12 +579,19 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     for (int kc = 0; kc < RP / 16; ++kc) xnext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rx, xoff0 + kc * LSTEP, 0, 0);
   }
   // GSCALE: this thread's share of offs for the workgroup's LDS copy (entry tid + 256 i; the index is clamped to [0, E)), in flight with the first tile's loads
-  int32_t ov[GSCALE ? QUANT_MAX_E / 256 : 1];
+  int32_t ov[(GSCALE || OAIB) ? QUANT_MAX_E / 256 : 1];
   if constexpr (GSCALE) {
 #pragma unroll
     for (int i = 0; i < QUANT_MAX_E / 256; ++i) {
       const int idx = i * 256 + tid;
       if (i * 256 < p.E) ov[i] = p.offs[idx < p.E ? idx : p.E - 1];
+    }
+  }
+  if constexpr (OAIB) {   // (one expert: the search reads nothing, and offs may be null)
+#pragma unroll
+    for (int i = 0; i < QUANT_MAX_E / 256; ++i) {
+      const int idx = i * 256 + tid;
+      if (i * 256 < p.E && p.E > 1) ov[i] = p.offs[idx < p.E ? idx : p.E - 1];
     }
   }
   const float gscale = (NV && !GSCALE) ? *p.global_scale : 1.0f;
@@ -561,6 +667,12 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     for (int i = 0; i < QUANT_MAX_E / 256; ++i)
       if (i * 256 < p.E) so[i * 256 + tid] = ov[i];
   }
+  if constexpr (OAIB) {
+    int32_t* so = quant_offs_lds();
+#pragma unroll
+    for (int i = 0; i < QUANT_MAX_E / 256; ++i)
+      if (i * 256 < p.E && p.E > 1) so[i * 256 + tid] = ov[i];
+  }
   __syncthreads();
   // GSCALE: gs_next = the scale of logical row s_row + (lane & 31) of the tile the second walk stands at, then that walk's step.  The search reads the LDS copy of
   // offs; its result lies in [0, E) whatever offs holds, and the one global load is clamped to that range once more.
@@ -576,6 +688,53 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     }
   };
   gscale_lookup();   // the first tile's
+  // ACT_OAI_BIAS: oai_lookup() = e_next for the tile the second walk stands at (its rem in n_rem), then that walk's step; oai_bias_loads() = the bias loads of the tile
+  // e_next belongs to (issued at the top of that tile): the chunk mapping of gated_loads, the row's expert picked across lanes as GSCALE picks its scale, then the
+  // lookup for this wave's next tile.
+  const __amdgpu_buffer_rsrc_t rb = make_rsrc(OAIB ? (const void*)p.bias : (const void*)p.x, OAIB ? (uint32_t)p.E * (uint32_t)p.inter * 4u : 0u);
+  auto oai_lookup = [&]() {
+    if constexpr (OAIB) {
+      const int g = quant_group_of_row(quant_offs_lds(), p.E, (int)(s_row + (uint32_t)row));
+      e_next = g < 0 ? 0 : (g < p.E ? g : p.E - 1);
+      n_rem = s_rem;
+      s_rem += g_rstep;
+      const uint32_t carry = s_rem >= g_rpr ? 1u : 0u;
+      s_rem -= carry ? g_rpr : 0u;
+      s_row += g_qstep + carry;
+    }
+  };
+  auto oai_bias_off = [&](const uint32_t lrow, const uint32_t cb) -> int {
+    const uint32_t x = n_rem + lrow;
+    uint32_t q = (uint32_t)((float)x * g_rc);
+    int32_t r = (int32_t)(x - q * g_rpr);
+    if (r < 0) { q -= 1; r += (int32_t)g_rpr; }
+    if (r >= (int32_t)g_rpr) { q += 1; r -= (int32_t)g_rpr; }
+    const uint32_t e = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q * 4u), e_next);   // q <= lrow <= 31: the lane that looked that row up; e in [0, E)
+    return (int)(e * ((uint32_t)p.inter * 4u) + (uint32_t)r * (RP * 2u) + cb);
+  };
+  auto oai_bias_loads = [&]() {
+    if constexpr (OAIB) {
+      if constexpr (STAGED) {
+        constexpr int CPR = RP / 8;
+#pragma unroll
+        for (int i = 0; i < RP / 16; ++i) {
+          const int q = i * 64 + lane;
+          const int off = oai_bias_off((uint32_t)(q / CPR), (uint32_t)(q % CPR) * 16u);
+          bgnext[i] = __builtin_amdgcn_raw_buffer_load_b128(rb, off, 0, 0);
+          bunext[i] = __builtin_amdgcn_raw_buffer_load_b128(rb, off, p.inter * 2, 0);
+        }
+      } else {
+        const int off = oai_bias_off((uint32_t)row, (uint32_t)half * 16u);
+#pragma unroll
+        for (int kc = 0; kc < RP / 16; ++kc) {
+          bgnext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rb, off + kc * 32, 0, 0);
+          bunext[kc] = __builtin_amdgcn_raw_buffer_load_b128(rb, off + kc * 32, p.inter * 2, 0);
+        }
+      }
+      oai_lookup();
+    }
+  };
+  oai_lookup();   // the first tile's experts
 
   // BLK: (sf_row, sf_rem) = this lane's RP-element row r_abs = tile * 32 + row as (logical row, RP-row within it); one division
   // here, then a carry-propagating add per tile
@@ -606,8 +765,13 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
     const float gs_cur = gs_next;     // GSCALE: this tile's scales (lane l: logical row l & 31 of the tile) and its rem, before the lookup below moves on
     const uint32_t c_rem = n_rem;
     if constexpr (GATED) {   // gate, up -> the act chunk the plain kernel would have loaded
+      oai_bias_loads();   // ACT_OAI_BIAS: this tile's bias chunks (its experts were looked up a tile ago), then the lookup for the next tile
 #pragma unroll
-      for (int i = 0; i < KC; ++i) xnext[i] = silu_mul8(xnext[i], unext[i]);
+      for (int i = 0; i < KC; ++i) {
+        if constexpr (ACT == ACT_SILU) xnext[i] = silu_mul8(xnext[i], unext[i]);
+        else if constexpr (OAIB) xnext[i] = swiglu_oai_mul8<true>(xnext[i], unext[i], bgnext[i], bunext[i], p.oai);
+        else xnext[i] = swiglu_oai_mul8<false>(xnext[i], unext[i], xnext[i], unext[i], p.oai);   // (no bias: the last two are not read)
+      }
     }
     if (STAGED) {
       constexpr int CPR = RP / 8;                // 16-byte chunks per row
@@ -899,6 +1063,12 @@ __global__ __launch_bounds__(256) void fused_silu_mul_quantize_kernel(const Quan
   fused_quantize_body<R, NV, METHOD, false, true, BLK, true, true>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// the clamped-SwiGLU quantizer (fusedSwigluOaiQuantizeMx): MX e2m1 with flat scales, R = 32 / 64, with or without the per-expert gate/up bias
+template <int R, int METHOD, bool BIAS>
+__global__ __launch_bounds__(256) void fused_swiglu_oai_quantize_kernel(const QuantParams p) {
+  fused_quantize_body<R, false, METHOD, false, true, false, true, true, false, false, QF_E2M1, BIAS ? ACT_OAI_BIAS : ACT_OAI>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
 // the gathering quantizers (fusedGatherQuantize{Mx,Nv}): the hardware e2m1 convert only, flat scales, no clip mask
 template <int R, bool NV, int METHOD>
 __global__ __launch_bounds__(256) void fused_gather_quantize_kernel(const QuantParams p) {
@@ -954,6 +1124,54 @@ __global__ __launch_bounds__(256) void silu_mul_bf16_kernel(const SiluMulParams 
   }
 }
 
+// swiglu_oai_and_mul: silu_mul_bf16_kernel with the clamped SwiGLU (swiglu_oai_mul8 above), out[r][c] = act(x[r][c], x[r][I + c] [, bias[g(r)][c], bias[g(r)][I + c]]).
+// BIAS: bias is (E, 2 I) bf16 in the same halves and g(r) = quant_group_of_row(offs, E, r) -- the workgroup copies offs into LDS once (E > 1; one expert reads no
+// offs), a thread searches the copy once per chunk it visits (at most 11 LDS reads) and fetches the two bias chunks, which every row of the expert shares, from L2.
+// The expert is clamped to [0, E): malformed offs cannot address outside bias.  64-bit addresses throughout.
+struct SwigluOaiParams {
+  const uint16_t* x;
+  uint16_t* out;
+  const uint16_t* bias;   // (E, 2 I) bf16 or null
+  const int32_t* offs;    // (E) or null (E == 1)
+  int64_t chunks;         // rows * I / 8
+  uint32_t cpr;           // chunks per row, I / 8
+  int E;
+  SwigluOaiAct act;
+};
+// the workgroup's LDS copy of offs for the streaming kernels (E > 1), published by a barrier
+__device__ __forceinline__ const int32_t* stream_offs_lds(const int32_t* offs, int E) {
+  int32_t* so = quant_offs_lds();
+  if (E > 1)
+    for (int i = threadIdx.x; i < E; i += 256) so[i] = offs[i];
+  __syncthreads();
+  return so;
+}
+template <bool BIAS>
+__global__ __launch_bounds__(256) void swiglu_oai_mul_bf16_kernel(const SwigluOaiParams p) {
+  const int32_t* so = nullptr;
+  if constexpr (BIAS) so = stream_offs_lds(p.offs, p.E);
+  const uint32_t first = blockIdx.x * 256u + threadIdx.x, step = gridDim.x * 256u;
+  uint32_t row = first / p.cpr, cc = first - row * p.cpr;
+  const uint32_t qstep = step / p.cpr, rstep = step - qstep * p.cpr;
+  for (int64_t c = first; c < p.chunks; c += step) {
+    const uint16_t* g = p.x + ((int64_t)row * 2 * p.cpr + cc) * 8;
+    const v4i gv = *(const v4i*)g, uv = *(const v4i*)(g + (int64_t)p.cpr * 8);
+    if constexpr (BIAS) {
+      int e = quant_group_of_row(so, p.E, (int)row);
+      e = e < 0 ? 0 : (e < p.E ? e : p.E - 1);
+      const uint16_t* b = p.bias + ((int64_t)e * 2 * p.cpr + cc) * 8;
+      const v4i bg = *(const v4i*)b, bu = *(const v4i*)(b + (int64_t)p.cpr * 8);
+      *(v4i*)(p.out + c * 8) = swiglu_oai_mul8<true>(gv, uv, bg, bu, p.act);
+    } else {
+      *(v4i*)(p.out + c * 8) = swiglu_oai_mul8<false>(gv, uv, gv, uv, p.act);
+    }
+    cc += rstep;
+    const uint32_t carry = cc >= p.cpr ? 1u : 0u;
+    cc -= carry ? p.cpr : 0u;
+    row += qstep + carry;
+  }
+}
+
 // moe_combine: out[t][c] = bf16_rne(sum over k = 0 .. topk - 1, in that order, of w[t][k] * float(y[pos[t][k]][c])), the sum starting from +0 and every product and every
 // sum rounded to fp32 on its own (no fma: numpy.float32 reproduces it bit for bit).  A slot whose pos lies outside [0, M) is SKIPPED -- its load goes to row 0 and the
 // loaded value is dropped by a select, never multiplied -- so a NaN in a row that no slot names cannot reach out.  Written as a gather: no atomics, the result does
@@ -998,6 +1216,68 @@ __global__ __launch_bounds__(256) void moe_combine_bf16_kernel(const MoeCombineP
         for (int e = 0; e < 4; ++e) {
           const uint32_t yw = (uint32_t)v[j][e];
           const float lo = w[j] * __uint_as_float(yw << 16), hi = w[j] * __uint_as_float(yw & 0xffff0000u);
+          const float slo = acc[2 * e] + lo, shi = acc[2 * e + 1] + hi;
+          acc[2 * e] = ok[j] ? slo : acc[2 * e];
+          acc[2 * e + 1] = ok[j] ? shi : acc[2 * e + 1];
+        }
+      }
+    }
+    v4i o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
+    *(v4i*)(p.out + c * 8) = o;
+    cc += rstep;
+    const uint32_t carry = cc >= p.cpr ? 1u : 0u;
+    cc -= carry ? p.cpr : 0u;
+    row += qstep + carry;
+  }
+}
+
+// moe_combine with the down projection's bias: moe_combine_bf16_kernel with v = bf16_rne(float(y[p][c]) + float(bias[g(p)][c])) (one fp32 add, then RNE: a bf16
+// tensor add) in place of y[p][c], g(p) = quant_group_of_row(offs, E, p) from the workgroup's LDS copy of offs -- the group the grouped GEMM computed row p in.  A
+// skipped slot reads row 0 of y and the bias row of row 0's expert, and both are dropped by the same select.  bias is (E, H) bf16; the expert is clamped to [0, E).
+struct MoeCombineBiasParams {
+  MoeCombineParams c;
+  const uint16_t* bias;
+  const int32_t* offs;
+  int E;
+};
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void moe_combine_bias_bf16_kernel(const MoeCombineBiasParams pb) {
+#pragma clang fp contract(off)
+  const MoeCombineParams& p = pb.c;
+  const int32_t* so = stream_offs_lds(pb.offs, pb.E);
+  const uint32_t first = blockIdx.x * 256u + threadIdx.x, step = gridDim.x * 256u;
+  uint32_t row = first / p.cpr, cc = first - row * p.cpr;
+  const uint32_t qstep = step / p.cpr, rstep = step - qstep * p.cpr;
+  for (int64_t c = first; c < p.chunks; c += step) {
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    const int64_t slot0 = (int64_t)row * p.topk;
+    for (int k0 = 0; k0 < p.topk; k0 += 4) {
+      float w[4];
+      bool ok[4];
+      v4i v[4], b[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = k0 + j < p.topk ? k0 + j : p.topk - 1;   // (past the last slot: a second read of it, dropped below)
+        const uint32_t ps = (uint32_t)p.pos[slot0 + k];
+        w[j] = p.w[slot0 + k];
+        ok[j] = k0 + j < p.topk && ps < p.m;
+        const uint32_t r = ok[j] ? ps : 0u;
+        int g = quant_group_of_row(so, pb.E, (int)r);
+        g = g < 0 ? 0 : (g < pb.E ? g : pb.E - 1);
+        v[j] = *(const v4i*)(p.y + ((int64_t)r * p.cpr + cc) * 8);
+        b[j] = *(const v4i*)(pb.bias + ((int64_t)g * p.cpr + cc) * 8);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t yw = (uint32_t)v[j][e], bw = (uint32_t)b[j][e];
+          const uint32_t vw = pack_bf16x2(__uint_as_float(yw << 16) + __uint_as_float(bw << 16), __uint_as_float(yw & 0xffff0000u) + __uint_as_float(bw & 0xffff0000u));
+          const float lo = w[j] * __uint_as_float(vw << 16), hi = w[j] * __uint_as_float(vw & 0xffff0000u);
           const float slo = acc[2 * e] + lo, shi = acc[2 * e + 1] + hi;
           acc[2 * e] = ok[j] ? slo : acc[2 * e];
           acc[2 * e + 1] = ok[j] ? shi : acc[2 * e + 1];

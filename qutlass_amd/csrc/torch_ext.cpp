@@ -508,6 +508,93 @@ void moeCombine_(const Tensor& Y, const Tensor& pos, const Tensor& weights, Tens
                                         OUT.data_ptr(), current_stream(Y)));
 }
 
+// ---- EXTENSION: gpt-oss -- the clamped SwiGLU with per-expert gate/up biases, alone and fused into the MXFP4 quantizer, and moe_combine with the down bias ------
+// bias: (E, 2 I) bf16, or an EMPTY tensor for "no bias"; offs: (E,) int32, or an empty tensor where there is no bias or E == 1.  The arithmetic is spelled out at
+// qutlass_amd_swiglu_oai_mul_bf16 (include/qutlass_amd.h).
+struct OaiBias {
+  const void* bias = nullptr;
+  const int32_t* offs = nullptr;
+  int64_t e = 0;
+};
+OaiBias oai_bias(const char* op, const Tensor& X, const Tensor& bias, const Tensor& offs, int64_t width) {
+  OaiBias b;
+  if (bias.numel() == 0) {
+    STD_TORCH_CHECK(offs.numel() == 0, "offs without a bias");
+    return b;
+  }
+  require_contiguous(op, {{bias, "bias"}});
+  require_gpu(op, {{bias, "bias"}});
+  require_same_gpu(op, {{X, "X"}, {bias, "bias"}});
+  STD_TORCH_CHECK(has_dtype(bias, ScalarType::BFloat16), "bias must be bf16");
+  STD_TORCH_CHECK(bias.dim() == 2 && bias.size(1) == width, "bias must be (E, ", width, ")");
+  b.bias = bias.data_ptr();
+  b.e = bias.size(0);
+  STD_TORCH_CHECK(b.e >= 1 && b.e <= 1024, "the number of experts must be in [1, 1024] (got ", b.e, ")");
+  if (offs.numel() == 0) {
+    STD_TORCH_CHECK(b.e == 1, "a bias of E = ", b.e, " experts needs offs");
+    return b;
+  }
+  require_contiguous(op, {{offs, "offs"}});
+  require_gpu(op, {{offs, "offs"}});
+  require_same_gpu(op, {{X, "X"}, {offs, "offs"}});
+  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.dim() == 1 && offs.size(0) == b.e, "offs must be an int32 tensor of E = ", b.e, " elements");
+  b.offs = static_cast<const int32_t*>(offs.data_ptr());
+  return b;
+}
+
+void swigluOaiAndMul_(const Tensor& X, Tensor OUT, double alpha, double limit, const Tensor& bias, const Tensor& offs) {
+  const char* op = "swigluOaiAndMul_";
+  require_contiguous(op, {{X, "X"}, {OUT, "OUT"}});
+  require_gpu(op, {{X, "X"}, {OUT, "OUT"}});
+  require_same_gpu(op, {{X, "X"}, {OUT, "OUT"}});
+  STD_TORCH_CHECK(has_dtype(X, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "X and OUT must be bf16");
+  STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of X must be 2 * I");
+  const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
+  STD_TORCH_CHECK(inter % 8 == 0, "the gate / up width must be divisible by", 8);
+  STD_TORCH_CHECK(OUT.numel() >= rows * inter, "OUT is too small");
+  const OaiBias b = oai_bias(op, X, bias, offs, 2 * inter);
+  const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
+  check_rc(qutlass_amd_swiglu_oai_mul_bf16(X.data_ptr(), rows, inter, (float)alpha, (float)limit, b.bias, b.offs, b.e, OUT.data_ptr(), current_stream(X)));
+}
+
+void fusedSwigluOaiQuantizeMx_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, double alpha, double limit, const Tensor& bias, const Tensor& offs,
+                               int64_t method) {
+  const char* op = "fusedSwigluOaiQuantizeMx";
+  const int64_t rot = quant_prelude(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, nullptr, &method);
+  STD_TORCH_CHECK(A.dim() >= 1 && A.size(A.dim() - 1) > 0 && A.size(A.dim() - 1) % 2 == 0, "the last dimension of A must be 2 * I");
+  const int64_t inter = A.size(A.dim() - 1) / 2, rows = A.numel() / (2 * inter);
+  STD_TORCH_CHECK(rot != 128, "rotation size 128 is not supported; expected 32 or 64 (use swiglu_oai_and_mul followed by fusedQuantizeMx)");
+  STD_TORCH_CHECK(rot == 32 || rot == 64, "Unsupported rotation size ", rot, "; expected 32 or 64.");
+  STD_TORCH_CHECK(inter % rot == 0, "the gate / up width must be divisible by", rot);
+  quant_check_out(false, OUT, OUT_sf, rows * inter, inter, false);
+  const OaiBias b = oai_bias(op, A, bias, offs, 2 * inter);
+  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
+  check_rc(qutlass_amd_fused_swiglu_oai_quantize_mx(A.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, (float)alpha, (float)limit, b.bias, b.offs, b.e,
+                                                    OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+}
+
+// moeCombineBias_: moeCombine_ with bias (E, H) bf16 added to every gathered row in bf16; offs (E,) int32, or empty for E == 1
+void moeCombineBias_(const Tensor& Y, const Tensor& pos, const Tensor& weights, const Tensor& bias, const Tensor& offs, Tensor OUT) {
+  const char* op = "moeCombineBias_";
+  require_contiguous(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
+  require_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
+  require_same_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
+  STD_TORCH_CHECK(has_dtype(Y, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "Y and OUT must be bf16");
+  STD_TORCH_CHECK(has_dtype(pos, ScalarType::Int), "pos must be int32");
+  STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
+  STD_TORCH_CHECK(Y.dim() == 2 && Y.size(1) > 0, "Y must be 2D (M, H)");
+  STD_TORCH_CHECK(pos.dim() == 2 && weights.dim() == 2 && pos.size(0) == weights.size(0) && pos.size(1) == weights.size(1), "pos and weights must both be (T, topk)");
+  const int64_t M = Y.size(0), H = Y.size(1), T = pos.size(0), topk = pos.size(1);
+  STD_TORCH_CHECK(H % 8 == 0, "the row length of Y must be divisible by", 8);
+  STD_TORCH_CHECK(topk >= 1 && topk <= 32, "topk must be in [1, 32] (got ", topk, ")");
+  STD_TORCH_CHECK(OUT.numel() >= T * H, "OUT is too small");
+  STD_TORCH_CHECK(bias.numel() > 0, "bias must be (E, ", H, ")");
+  const OaiBias b = oai_bias(op, Y, bias, offs, H);
+  const torch::stable::accelerator::DeviceGuard guard(Y.get_device_index());
+  check_rc(qutlass_amd_moe_combine_bias_bf16(Y.data_ptr(), M, H, static_cast<const int32_t*>(pos.data_ptr()), static_cast<const float*>(weights.data_ptr()), T, topk,
+                                             b.bias, b.offs, b.e, OUT.data_ptr(), current_stream(Y)));
+}
+
 // ---- EXTENSION: MoE routing in front of the dispatch ---------------------------------------------------------------------------------------------
 // moeTopkSoftmax_: router logits (T, E) bf16 / float32 -> weights (T, topk) float32 and ids (T, topk) int32; topk is the outputs' second dimension
 void moeTopkSoftmax_(const Tensor& logits, Tensor weights, Tensor ids, bool renormalize) {
@@ -728,6 +815,9 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("fusedSiluMulQuantizeMxf8_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, bool blocked) -> ()");
   m.def("fusedGatherQuantizeMxf8_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf) -> ()");
   m.def("moeCombine_(Tensor Y, Tensor pos, Tensor weights, Tensor(a!) OUT) -> ()");
+  m.def("swigluOaiAndMul_(Tensor X, Tensor(a!) OUT, float alpha, float limit, Tensor bias, Tensor offs) -> ()");
+  m.def("fusedSwigluOaiQuantizeMx_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, float alpha, float limit, Tensor bias, Tensor offs, int method) -> ()");
+  m.def("moeCombineBias_(Tensor Y, Tensor pos, Tensor weights, Tensor bias, Tensor offs, Tensor(a!) OUT) -> ()");
   m.def("moeTopkSoftmax_(Tensor logits, Tensor(a!) weights, Tensor(b!) ids, bool renormalize) -> ()");
   m.def("moeTopkGrouped_(Tensor logits, Tensor bias, Tensor(a!) weights, Tensor(b!) ids, Tensor(c!) scores, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor) -> ()");
   m.def("moeSort_(Tensor topk_ids, Tensor expert_map, int num_experts, Tensor(a!) src_row, Tensor(b!) offs, Tensor(c!) pos, Tensor(d!) workspace) -> ()");
@@ -781,6 +871,9 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("fusedSiluMulQuantizeMxf8_", TORCH_BOX(&fusedSiluMulQuantizeMxf8_));
   m.impl("fusedGatherQuantizeMxf8_", TORCH_BOX(&fusedGatherQuantizeMxf8_));
   m.impl("moeCombine_", TORCH_BOX(&moeCombine_));
+  m.impl("swigluOaiAndMul_", TORCH_BOX(&swigluOaiAndMul_));
+  m.impl("fusedSwigluOaiQuantizeMx_", TORCH_BOX(&fusedSwigluOaiQuantizeMx_));
+  m.impl("moeCombineBias_", TORCH_BOX(&moeCombineBias_));
   m.impl("moeTopkSoftmax_", TORCH_BOX(&moeTopkSoftmax_));
   m.impl("moeTopkGrouped_", TORCH_BOX(&moeTopkGrouped_));
   m.impl("moeSort_", TORCH_BOX(&moeSort_));

@@ -78,7 +78,8 @@ def _register_fakes() -> None:
     for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
                  "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
                  "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "fusedGatherQuantizeNvGrouped_", "fusedSiluMulQuantizeNvGrouped_",
-                 "fusedQuantizeMxf8_", "fusedQuantizeMxf8Blocked_", "fusedSiluMulQuantizeMxf8_", "fusedGatherQuantizeMxf8_", "moeCombine_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "fusedQuantizeMxf8_", "fusedQuantizeMxf8Blocked_", "fusedSiluMulQuantizeMxf8_", "fusedGatherQuantizeMxf8_", "moeCombine_",
+                 "swigluOaiAndMul_", "fusedSwigluOaiQuantizeMx_", "moeCombineBias_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -113,7 +114,7 @@ def _define_functional_ops() -> None:
 
     # the rotate + quantize family: one registration per row of QUANT_OPS
     for name, row in QUANT_OPS.items():
-        op = custom_op(f"qutlass_amd::{name}", mutates_args=(), schema=row.schema)(lambda *args, _row=row: run_quant(_row, *args))
+        op = custom_op(f"qutlass_amd::{name}", mutates_args=(), schema=row.schema)(lambda *args, _row=row: run_quant_op(_row, *args))
         op.register_fake(lambda *args, _row=row: alloc_quant(_row, *args))
 
     # gated MLP: X is (.., 2 I) [gate | up]
@@ -135,6 +136,19 @@ def _define_functional_ops() -> None:
         return o
 
     moe_combine.register_fake(lambda Y, pos, weights: _combined(Y, pos))
+
+    # gpt-oss: the clamped SwiGLU with an optional per-expert bias (E, 2 I) and the grouped GEMMs' offs (E,); moe_combine with the down bias (E, H)
+    @custom_op("qutlass_amd::swiglu_oai_and_mul", mutates_args=(), schema="(Tensor X, float alpha, float limit, Tensor? bias, Tensor? offs) -> Tensor")
+    def swiglu_oai_and_mul(X, alpha, limit, bias, offs):
+        return run_swiglu_oai(X, alpha, limit, bias, offs)
+
+    swiglu_oai_and_mul.register_fake(lambda X, alpha, limit, bias, offs: X.new_empty(_act(X)))
+
+    @custom_op("qutlass_amd::moe_combine_bias", mutates_args=(), schema="(Tensor Y, Tensor pos, Tensor weights, Tensor bias, Tensor? offs) -> Tensor")
+    def moe_combine_bias(Y, pos, weights, bias, offs):
+        return run_moe_combine_bias(Y, pos, weights, bias, offs)
+
+    moe_combine_bias.register_fake(lambda Y, pos, weights, bias, offs: _combined(Y, pos))
 
     # MoE routing: (T, E) logits -> (T, topk) weights and ids; (T, topk) ids -> src_row (T * topk), offs (num_experts), pos (T, topk)
     @custom_op("qutlass_amd::moe_topk_softmax", mutates_args=(), schema="(Tensor logits, int topk, bool renormalize) -> (Tensor, Tensor)")
@@ -263,6 +277,9 @@ QUANT_OPS = {
     "quantize_nv_blocked": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedQuantizeNvBlocked", 2, _same, "nv", True),
     "silu_mul_quantize_mx": QuantOp("(Tensor A, Tensor R, int method, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeMx_", 2, _act, "mx", None),
     "silu_mul_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeNv_", 2, _act, "nv", None),
+    # gpt-oss: the clamped SwiGLU in place of silu * up, with the gate/up bias of the row's expert (None: no bias; offs None: one expert); flat scales
+    "swiglu_oai_quantize_mx": QuantOp("(Tensor A, Tensor R, float alpha, float limit, Tensor? bias, Tensor? offs, int method) -> (Tensor, Tensor)",
+                                      "fusedSwigluOaiQuantizeMx_", 2, _act, "mx", False),
     "gather_quantize_mx": QuantOp("(Tensor A, Tensor R, Tensor src_row, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeMx_", 3, _gathered, "mx", False),
     "gather_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor src_row, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeNv_", 3, _gathered, "nv", False),
     # one global scale per expert: global_scales (E,) with the grouped GEMMs' offs (E,)
@@ -300,6 +317,35 @@ def run_quant(row: QuantOp, *args):
     """Allocate, then the in-place twin."""
     o = alloc_quant(row, *args)
     getattr(torch.ops.qutlass_amd, row.twin)(*args[:row.lead], o[0], o[1], *args[row.lead + (row.fmt == "mxf8"):])
+    return o
+
+
+def run_quant_op(row: QuantOp, *args):
+    """run_quant -- or, for the one row whose op takes optional tensors, its own runner (the in-place twins take no None)."""
+    return (run_swiglu_oai_quant if row.twin == "fusedSwigluOaiQuantizeMx_" else run_quant)(row, *args)
+
+
+def _optional(x: torch.Tensor, t: torch.Tensor | None, dtype: torch.dtype) -> torch.Tensor:
+    """The in-place ops' "no tensor": an empty one."""
+    return x.new_empty((0,), dtype=dtype) if t is None else t
+
+
+def run_swiglu_oai_quant(row: QuantOp, A, R, alpha, limit, bias, offs, method):
+    """run_quant for the one op of the table with optional tensors."""
+    o = alloc_quant(row, A, R)
+    torch.ops.qutlass_amd.fusedSwigluOaiQuantizeMx_(A, R, o[0], o[1], alpha, limit, _optional(A, bias, A.dtype), _optional(A, offs, torch.int32), method)
+    return o
+
+
+def run_swiglu_oai(X, alpha, limit, bias, offs):
+    o = X.new_empty(_act(X))
+    torch.ops.qutlass_amd.swigluOaiAndMul_(X, o, alpha, limit, _optional(X, bias, X.dtype), _optional(X, offs, torch.int32))
+    return o
+
+
+def run_moe_combine_bias(Y, pos, weights, bias, offs):
+    o = Y.new_empty((pos.size(0), Y.size(-1)))
+    torch.ops.qutlass_amd.moeCombineBias_(Y, pos, weights, bias, _optional(Y, offs, torch.int32), o)
     return o
 
 

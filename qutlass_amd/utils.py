@@ -47,3 +47,13 @@ def pad_to_block(tensor, dims, blocksize):
     out = tensor.new_zeros(shape)
     out[tuple(slice(0, n) for n in tensor.shape)] = tensor
     return out
+
+
+def split_interleaved_gate_up(t: torch.Tensor, dim: int) -> torch.Tensor:
+    """gpt-oss stores the gate and up projections interleaved along their 2 I axis (even = gate, odd = up); every gated op here takes [gate | up] halves.  Returns
+    ``cat(t[0::2], t[1::2])`` along `dim`.  Apply it once at load time to the gate/up weight, its scales and its bias.  Plain torch: works on CPU tensors."""
+    if t.size(dim) % 2:
+        raise ValueError(f"dimension {dim} must have an even length (got {t.size(dim)})")
+    n = t.size(dim)
+    idx = torch.arange(n, device=t.device)
+    return torch.cat([t.index_select(dim, idx[0::2]), t.index_select(dim, idx[1::2])], dim=dim)
