@@ -200,6 +200,22 @@ int qutlass_amd_grouped_matmul_mxf8_bf16_tn(const void* A, const void* B, const 
                                             int64_t M, int64_t N, int64_t K, int64_t E, int a_format, void* stream);
 
 /*
+ * EXTENSION (no counterpart in the reference): grouped W4A8 GEMM for mixture-of-experts layers -- MXFP8 tokens against MXFP4
+ * expert weights as they are stored (gpt-oss checkpoints, fusedQuantizeMx's output), one launch over E experts.
+ * A: (M, K) e4m3 tokens sorted by expert, A_sf: row-major (M, K/32) e8m0 (fusedQuantizeMxf8 / fusedGatherQuantizeMxf8 write both).
+ * B: (E, N, K/2) packed e2m1 stacked expert weights, B_sf: row-major (E, N, K/32) e8m0 (the operands of
+ * qutlass_amd_grouped_matmul_mxf4_bf16_tn).  alpha, offs, D, the clamping of the offsets and the rows that are not written: as
+ * qutlass_amd_grouped_matmul_mxf8_bf16_tn.  D[r] = alpha[g] * (A_r . SFA_r) (B_g . SFB_g)^T with fp32 accumulation, one fp32
+ * multiply by alpha and one rounding to bf16.  Scale byte 255 and the e4m3 NaN code give NaN outputs as they do there.
+ * K % 128 == 0, N % 8 == 0, 1 <= E <= 1024, M * K and N * K/2 (one expert) below 2 GiB; the stack may exceed 2 GiB.
+ * M == 0 returns QAMD_OK without a launch.  Wave-owned 32x32 / 32x16 / 64x32 tiles only: there is no 64x64 ring form, so
+ * prefill-sized groups run on the decode tiles.
+ */
+int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
+                                                 const float* alpha, int64_t n_alpha, const int32_t* offs, void* D,
+                                                 int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
+
+/*
  * EXTENSION (no counterpart in the reference): grouped NVFP4 GEMM for mixture-of-experts layers, one launch over E experts.
  * A: (M, K/2) packed e2m1 tokens sorted by expert, A_sf: ROW-MAJOR (M, K/16) e4m3 (the quantizer's buffer as it is, no to_blocked).
  * B: (E, N, K/2) stacked expert weights, B_sf: row-major (E, N, K/16).  alpha: device fp32[n_alpha], n_alpha = 1 (shared)

@@ -9,6 +9,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_mxf4_bf16_tn                      (extension: mixture-of-experts layers, one launch over all experts)
     grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
+    grouped_matmul_mxf8_mxf4_bf16_tn, matmul_mxf8_mxf4_bf16_tn  (extension: W4A8 -- MXFP8 tokens against MXFP4 expert weights as stored; the dense form is E = 1)
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
     fusedGatherQuantizeNvGrouped, fusedSiluMulQuantizeNvGrouped  (extension: the two NVFP4 quantizers of the MoE chain with one global scale per expert)
@@ -102,6 +103,58 @@ def grouped_matmul_mxf8_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Te
     K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; the token matrix and one expert's weight below 2 GiB (the stack may exceed it).  M == 0 returns an
     empty output."""
     return _ops_amd.grouped_matmul_mxf8(a, b, a_sf, b_sf, alpha, offs)
+
+
+def _check_w4a8_operands(op: str, a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, b_dim: int) -> None:
+    """the rejections of the W4A8 ops that need no device: raised before the op is dispatched (shapes and dtypes only, so tracing goes through them)"""
+    if a.dtype == torch.float8_e5m2:
+        raise ValueError(f"{op}: a must be float8_e4m3fn, float8_e5m2 tokens are not supported (grouped_matmul_mxf8_bf16_tn takes them, against e4m3 weights)")
+    if a.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{op}: a must be float8_e4m3fn (got {a.dtype})")
+    if b.dtype not in (torch.uint8, torch.float4_e2m1fn_x2):
+        raise ValueError(f"{op}: b must be uint8 or float4_e2m1fn_x2 packed e2m1 (got {b.dtype})")
+    if a.dim() != 2 or b.dim() != b_dim:
+        raise ValueError(f"{op}: a must be 2D (M, K) and b {b_dim}D ({'E, ' if b_dim == 3 else ''}N, K/2)")
+    if a.size(1) != 2 * b.size(-1):
+        raise ValueError(f"{op}: inner dimensions must match, a is (M, K = {a.size(1)}) and b (.., K/2 = {b.size(-1)})")
+    for name, sf, rows in (("a_sf", a_sf, a.size(0)), ("b_sf", b_sf, b.numel() // max(b.size(-1), 1))):
+        if sf.dtype != torch.float8_e8m0fnu:
+            raise ValueError(f"{op}: {name} must be float8_e8m0fnu (got {sf.dtype})")
+        if sf.numel() < rows * (a.size(1) // 32):
+            raise ValueError(f"{op}: {name} has {sf.numel()} elements, the row-major scale layout needs {rows * (a.size(1) // 32)}")
+
+
+def grouped_matmul_mxf8_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,
+                                     alpha: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): grouped W4A8 GEMM for mixture-of-experts layers -- MXFP8 tokens against MXFP4 expert weights as a checkpoint stores
+    them (gpt-oss; every weight fusedQuantizeMx writes), one launch over all experts.
+
+    a      (M, K) float8_e4m3fn -- the tokens, sorted by expert: what fusedQuantizeMxf8 / fusedGatherQuantizeMxf8 / fusedSiluMulQuantizeMxf8 write (e5m2 is rejected)
+    b      (E, N, K/2) uint8 / float4_e2m1fn_x2 -- the stacked expert weights: what fusedQuantizeMx writes and grouped_matmul_mxf4_bf16_tn reads
+    a_sf   float8_e8m0fnu, >= M*K/32 elements, read as row-major (M, K/32): the quantizer's flat scale buffer as it is (no to_blocked)
+    b_sf   float8_e8m0fnu, >= E*N*K/32 elements, read as row-major (E, N, K/32)
+    alpha  float32, 1 element (shared) or E elements (per expert)
+    offs   int32 (E,): the cumulative END rows of the groups (torch._grouped_mm's convention) -- group g is rows [offs[g-1], offs[g]), offs[-1] := 0
+
+    Returns out (M, N) bf16 with out[r] = alpha[g] * (A_r . SFA_r) (B_g . SFB_g)^T for every row r of group g: fp32 accumulation, one fp32 multiply by alpha, one
+    rounding to bf16.  Empty groups are allowed; rows at or past offs[E-1] are not written.  The offsets are read on the device, so the call needs no host sync and
+    works under graph capture and torch.compile; each offset is clamped to [0, M] and a decreasing one is an empty group.  Scale byte 255 and the e4m3 NaN code give
+    NaN outputs as in grouped_matmul_mxf8_bf16_tn.  K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; the token matrix and one expert's weight below 2 GiB (the stack may
+    exceed it).  M == 0 returns an empty output.
+
+    The op runs wave-owned 32x32 / 32x16 / 64x32 tiles only -- it has no 64x64 ring form, so prefill-sized groups run on the decode tiles (README, DESIGN.md
+    section 8 for what that costs against grouped_matmul_mxf8_bf16_tn on weights upcast to e4m3)."""
+    _check_w4a8_operands("grouped_matmul_mxf8_mxf4_bf16_tn", a, b, a_sf, b_sf, 3)
+    return _ops_amd.grouped_matmul_mxf8_mxf4(a, b, a_sf, b_sf, alpha, offs)
+
+
+def matmul_mxf8_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): the dense form of grouped_matmul_mxf8_mxf4_bf16_tn -- a (M, K) float8_e4m3fn against ONE MXFP4 weight b (N, K/2)
+    uint8 / float4_e2m1fn_x2, flat row-major e8m0 scales (M, K/32) and (N, K/32) like matmul_ada_mxf4_bf16_tn's, alpha float32 with one element.  Returns (M, N)
+    bf16.  The grouped op with E = 1: its offs is a one-element device tensor filled with M, so there is no host sync and no kernel of its own."""
+    _check_w4a8_operands("matmul_mxf8_mxf4_bf16_tn", a, b, a_sf, b_sf, 2)
+    offs = torch.full((1,), a.size(0), dtype=torch.int32, device=a.device)
+    return _ops_amd.grouped_matmul_mxf8_mxf4(a, b.unsqueeze(0), a_sf, b_sf, alpha, offs)
 
 
 def grouped_matmul_nvf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,

@@ -19,6 +19,7 @@
 #include "gemm_mx_skinny.hip.h"
 #include "gemm_mx_ks.hip.h"
 #include "gemm_mx_os.hip.h"
+#include "gemm_mx_os_w4a8.hip.h"
 #include "gemm_mx_fusedq.hip.h"
 #include "gemm_nvf4.hip.h"
 #include "gemm_nvf4_pk.hip.h"
@@ -446,7 +447,54 @@ inline int grouped8_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
   return (M <= 32 * E && K >= 8192) ? 594 : 597;
 }
 
-// ---- what the three grouped entries share: the argument checks, the choice of a form and the parameter fill ----------------------------------------------------------
+// ---- grouped W4A8 GEMM (gemm_mx_os_w4a8.hip.h): MXFP8 tokens against MXFP4 expert weights ------------------------------------------------------------------------------
+// Forms: 602 = 32x32 tiles of the mixed-width wave-owned kernel, 603 = 32x16, 604 = 64x32 (one shot while a tile's K extent fits the LDS, wave-owned rings beyond).  There
+// is no 64x64 ring form: GemmCtx, which every product GEMM shares, has one row width for both operands -- so prefill-sized groups run on the decode tiles.
+// Measured on the decode and prefill shapes of Qwen3-30B-A3B, Mixtral-8x7B and gpt-oss-20b / 120b and on a sweep of 16 ... 128 rows per expert at K = 768 ... 2944
+// (profiles/calib_grouped_w4a8.txt): 603 never leads.  Up to K = 1536 -- the 32-row tile's stages of a wave fit three slots, two workgroups share a CU -- 602 leads
+// at every row count (K = 1536, 128 rows per expert: 358.0 us against 449.1 for 604; K = 768, Qwen3 down prefill: 369.2 against 594.6).  From K = 2048 on 604 leads as
+// soon as the groups fill its 64 rows halfway (K = 2048: 32 rows 224.5 against 249.1, 128 rows 574.0 against 728.4; Mixtral gate/up prefill 4072.6 against 6415.6):
+// it fetches each weight row once for two m-tiles; at 16 rows and below 602 leads at every K (K = 2944: 202.3 against 237.2; Mixtral down decode, K = 14336: 60.8
+// against 66.6).  So: mean rows per group M / E >= 32 and K > 1536 -> 604, otherwise 602.  N and the CU count are arguments so that a rule re-taken from more
+// measurements can use them.
+inline int grouped_w4a8_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M >= 32 * E && K > 1536) ? 604 : 602;
+}
+// form GRP_MXF8_MXF4.form0 + I: the one-shot ladder up to 4 SMAX stages, wave-owned rings of SMAX slots beyond.  The smaller stage moves SMAX: 6 slots per wave for
+// the 32-row tiles (one shot up to K = 3072), 3 for the 64-row tile (K = 1536)
+template <int I>
+int launch_grouped_w4a8_os(GroupedParams q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_MXF8_MXF4;
+  constexpr int TM = F.tile[I].tm, TN = F.tile[I].tn, SMAX = os_w4a8_smax(TM);
+  q.tiles_m = 1;
+  q.tiles_n = (int)cdiv(q.N, TN);
+  const int64_t KT = q.K / 128;
+  const dim3 grid((int)grouped_workgroups(q.M, q.N, q.E, TM, TN)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_w4a8_kernel<OsW4A8Cfg<1, TN, TM>, false>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_w4a8_kernel<OsW4A8Cfg<2, TN, TM>, false>), grid, block, 0, s, q);
+  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_w4a8_kernel<OsW4A8Cfg<3, TN, TM>, false>), grid, block, 0, s, q);
+  else if (SMAX > 4 && KT <= 16) hipLaunchKernelGGL((gemm_mx_os_w4a8_kernel<OsW4A8Cfg<(SMAX > 4 ? 4 : SMAX), TN, TM>, false>), grid, block, 0, s, q);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_w4a8_kernel<OsW4A8Cfg<SMAX, TN, TM>, false>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_w4a8_kernel<OsW4A8Cfg<SMAX, TN, TM>, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  return check_launch("gemm_mx_os_w4a8_kernel");
+}
+// form v of the W4A8 op; its kernels ride in the persistent NVFP4 kernel's unit, the shortest of the parallel build
+int launch_grouped_w4a8(int v, const GroupedParams& q, hipStream_t s)
+#if QAMD_DEF(8)
+{
+  constexpr const GroupedFormat& F = GRP_MXF8_MXF4;
+  static_assert(F.nforms == 3 && F.ebits == 8 && F.ebits_b == 4, "the three wave-owned forms of the mixed-width kernel");
+  if (v == F.form0) return launch_grouped_w4a8_os<0>(q, s);
+  if (v == F.form0 + 1) return launch_grouped_w4a8_os<1>(q, s);
+  if (v == F.form0 + 2) return launch_grouped_w4a8_os<2>(q, s);
+  return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+}
+#else
+;
+#endif
+
+// ---- what the grouped entries share: the argument checks, the choice of a form and the parameter fill ----------------------------------------------------------
 // the grouped ops' argument checks, F the format (gemm_mx_grouped.hip.h): every argument is checked before any HIP call; the grid bound covers every form
 inline int grouped_check(const GroupedFormat& F, const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
                          const int32_t* offs, const void* D, int64_t M, int64_t N, int64_t K, int64_t E) {
@@ -456,10 +504,12 @@ inline int grouped_check(const GroupedFormat& F, const char* name, const void* A
   if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
   if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
   if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  const char* rowb = F.ebits == 8 ? "K" : "K/2";
+  const char* rowa = F.row_bytes(K) == K ? "K" : "K/2";
+  const char* rowb = F.row_bytes_b(K) == K ? "K" : "K/2";
   const int64_t rows_2g = ((1ll << 31) - 1) / F.row_bytes(K) + 1;   // rows of a row's bytes that reach 2 GiB (no product that can overflow)
-  if (N >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * %s bytes, N=%lld K=%lld) must stay below 2 GiB", name, rowb, (long long)N, (long long)K);
-  if (M >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * %s bytes, M=%lld K=%lld) must stay below 2 GiB", name, rowb, (long long)M, (long long)K);
+  const int64_t rows_2g_b = ((1ll << 31) - 1) / F.row_bytes_b(K) + 1;
+  if (N >= rows_2g_b) return fail(QAMD_ERR_INVALID, "%s: one expert's weight (N * %s bytes, N=%lld K=%lld) must stay below 2 GiB", name, rowb, (long long)N, (long long)K);
+  if (M >= rows_2g) return fail(QAMD_ERR_INVALID, "%s: the token matrix (M * %s bytes, M=%lld K=%lld) must stay below 2 GiB", name, rowa, (long long)M, (long long)K);
   if (M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
   for (int v = F.form0; F.has(v); ++v)
     if (grouped_grid(F, v, M, N, E) >= (1ll << 24)) return fail(QAMD_ERR_INVALID, "%s: %lld x %lld over %lld experts needs more than 2^24 workgroups", name, (long long)M, (long long)N, (long long)E);
@@ -478,7 +528,7 @@ void grouped_fill(P& q, const GroupedFormat& F, const void* A, const void* B, co
   const int64_t rowbytes = F.row_bytes(K), KB = K / F.sgroup;
   q.A = (const uint8_t*)A; q.B = (const uint8_t*)B; q.SFA = (const uint8_t*)A_sf; q.SFB = (const uint8_t*)B_sf;
   q.alpha = alpha; q.D = (uint16_t*)D; q.M = (int)M; q.N = (int)N; q.K = (int)K; q.ldd = (int)N;
-  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * rowbytes);     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
+  q.a_bytes = (uint32_t)(M * rowbytes); q.b_bytes = (uint32_t)(N * F.row_bytes_b(K));     // b_bytes / sfb_bytes: ONE expert's (the kernel rebases per expert)
   q.sfa_bytes = (uint32_t)(M * KB); q.sfb_bytes = (uint32_t)(N * KB);
   q.offs = offs; q.E = (int)E; q.n_alpha = (int)n_alpha; q.splits = 1;
 }
@@ -1636,6 +1686,18 @@ int qutlass_amd_grouped_matmul_mxf8_bf16_tn(const void* A, const void* B, const 
   return a_format == QAMD_FP8_E5M2 ? launch_grouped_mx<GRP_MXF8, GroupedRing8Cfg<1>, 1>(v, q, s) : launch_grouped_mx<GRP_MXF8, GroupedRing8Cfg<0>, 0>(v, q, s);
 }
 
+int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                                 const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_MXF8_MXF4;
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if (M == 0) return QAMD_OK;
+  GroupedParams q;
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
+  q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
+  q.ws = nullptr; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  return launch_grouped_w4a8(grouped_form(F, grouped_w4a8_plan, M, N, K, E), q, (hipStream_t)stream);
+}
+
 // ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
 // Forms: 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles, 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.
 // Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B and on token counts between them (profiles/calib_grouped_nvf4_r7.txt; these are not the MX
@@ -2639,6 +2701,10 @@ int qutlass_amd_debug_grouped_plan(int64_t M, int64_t N, int64_t K, int64_t E, i
 // grouped_matmul_mxf8_bf16_tn: 594 = 32x32 tiles of the wave-owned kernel, 597 = the 64x64 ring kernel
 int qutlass_amd_debug_grouped_mxf8_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
   return debug_grouped_plan(GRP_MXF8, "debug_grouped_mxf8_plan", grouped8_plan, M, N, K, E, out);
+}
+// grouped_matmul_mxf8_mxf4_bf16_tn: 602 = 32x32, 604 = 64x32 tiles of the mixed-width wave-owned kernel
+int qutlass_amd_debug_grouped_mxf8_mxf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  return debug_grouped_plan(GRP_MXF8_MXF4, "debug_grouped_mxf8_mxf4_plan", grouped_w4a8_plan, M, N, K, E, out);
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel
 int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {

@@ -33,7 +33,7 @@ struct GroupTile {
 };
 
 // ---- the grouped ops' formats (host): the ONE place where a form's tile is written -------------------------------------------------------------------------
-// An op has four forms, numbered form0 ... form0 + 3 (the lab's gemm_variant option forces one); form i runs TM x TN = tile[i] tiles.  The argument checks, the
+// An op has up to four forms (nforms), numbered form0 ... form0 + nforms - 1 (the lab's gemm_variant option forces one); form i runs TM x TN = tile[i] tiles.  The argument checks, the
 // debug plan entries and the launchers of both units (capi.hip, gemm_nvf4_os.hip.h) read a tile from here; a launcher whose kernel carries its tile as template
 // arguments takes them from the table or static_asserts against it.
 struct GroupedTileDim { int tm, tn; };
@@ -43,12 +43,17 @@ struct GroupedFormat {
   int ebits;          // bits per element
   int sgroup;         // elements per scale
   GroupedTileDim tile[4];
-  constexpr bool has(int form) const { return form >= form0 && form < form0 + 4; }
-  constexpr int64_t row_bytes(int64_t K) const { return K / (8 / ebits); }
+  int nforms = 4;     // forms the op has (tile[0 .. nforms))
+  int ebits_b = 0;    // bits per element of B where they differ from A's (0: ebits)
+  constexpr bool has(int form) const { return form >= form0 && form < form0 + nforms; }
+  constexpr int64_t row_bytes(int64_t K) const { return K / (8 / ebits); }                             // of an A row
+  constexpr int64_t row_bytes_b(int64_t K) const { return K / (8 / (ebits_b ? ebits_b : ebits)); }     // of a B row
 };
 constexpr GroupedFormat GRP_MXF4{"grouped_matmul_mxf4_bf16_tn", 590, 4, 32, {{32, 32}, {32, 16}, {64, 32}, {64, 64}}};
 constexpr GroupedFormat GRP_MXF8{"grouped_matmul_mxf8_bf16_tn", 594, 8, 32, {{32, 32}, {32, 16}, {64, 32}, {64, 64}}};
 constexpr GroupedFormat GRP_NVF4{"grouped_matmul_nvf4_bf16_tn", 598, 4, 16, {{32, 32}, {64, 32}, {64, 64}, {128, 128}}};
+// W4A8: e4m3 tokens against e2m1 weights (gemm_mx_os_w4a8.hip.h) -- the three wave-owned forms, no ring form
+constexpr GroupedFormat GRP_MXF8_MXF4{"grouped_matmul_mxf8_mxf4_bf16_tn", 602, 8, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
 // workgroups of a grouped launch: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles (grouped_tile: the rest return at once)
 constexpr int64_t grouped_workgroups(int64_t M, int64_t N, int64_t E, int TM, int TN) { return ((M + TM - 1) / TM + E) * ((N + TN - 1) / TN); }
 

@@ -183,12 +183,14 @@ Tensor matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor
 //   MXF4: A (M, K/2), B (E, N, K/2), e8m0 scales per 32 elements
 //   NVF4: the same operands, e4m3 scales per 16 elements (fusedQuantizeNv's buffer as it is)
 //   MXF8: A (M, K) e4m3 / e5m2 (e5m2 selects the e5m2-A path, as matmul_mxf8_bf16_tn), B (E, N, K) e4m3, e8m0 scales per 32 elements
-enum class Grouped { MXF4, NVF4, MXF8 };
+//   MXF8_MXF4 (W4A8): A (M, K) e4m3 as MXF8's, B (E, N, K/2) packed e2m1 as MXF4's, e8m0 scales per 32 elements
+enum class Grouped { MXF4, NVF4, MXF8, MXF8_MXF4 };
 
 template <Grouped G>
 Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
+  constexpr bool w4a8 = G == Grouped::MXF8_MXF4;
   constexpr bool fp8 = G == Grouped::MXF8;
-  const char* op = G == Grouped::MXF4 ? "grouped_matmul_mxf4" : G == Grouped::NVF4 ? "grouped_matmul_nvf4" : "grouped_matmul_mxf8";
+  const char* op = G == Grouped::MXF4 ? "grouped_matmul_mxf4" : G == Grouped::NVF4 ? "grouped_matmul_nvf4" : w4a8 ? "grouped_matmul_mxf8_mxf4" : "grouped_matmul_mxf8";
   require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
   require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
   require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
@@ -197,13 +199,19 @@ Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, cons
   const ScalarType b_alt = fp8 ? ScalarType::Float8_e4m3fn : ScalarType::Float4_e2m1fn_x2;       // ... for B (MXF8: e4m3 only)
   const ScalarType sf_t = G == Grouped::NVF4 ? ScalarType::Float8_e4m3fn : ScalarType::Float8_e8m0fnu;
   const char* sf_n = G == Grouped::NVF4 ? "float8_e4m3fn" : "float8_e8m0fnu";
-  STD_TORCH_CHECK(has_dtype(A, data_t) || has_dtype(A, a_alt), "A must be ", fp8 ? "float8_e4m3fn or float8_e5m2" : "uint8 or float4_e2m1fn_x2");
-  STD_TORCH_CHECK(has_dtype(B, data_t) || has_dtype(B, b_alt), "B must be ", fp8 ? "float8_e4m3fn" : "uint8 or float4_e2m1fn_x2");
+  if (w4a8) {   // e4m3 tokens only (e5m2 tokens have no W4A8 kernel), the weights as MXF4's
+    STD_TORCH_CHECK(!has_dtype(A, ScalarType::Float8_e5m2), op, ": A must be float8_e4m3fn, float8_e5m2 tokens are not supported");
+    STD_TORCH_CHECK(has_dtype(A, ScalarType::Float8_e4m3fn), op, ": A must be float8_e4m3fn");
+    STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), op, ": B must be uint8 or float4_e2m1fn_x2");
+  } else {
+    STD_TORCH_CHECK(has_dtype(A, data_t) || has_dtype(A, a_alt), "A must be ", fp8 ? "float8_e4m3fn or float8_e5m2" : "uint8 or float4_e2m1fn_x2");
+    STD_TORCH_CHECK(has_dtype(B, data_t) || has_dtype(B, b_alt), "B must be ", fp8 ? "float8_e4m3fn" : "uint8 or float4_e2m1fn_x2");
+  }
   STD_TORCH_CHECK(has_dtype(A_sf, sf_t), "A_sf must be ", sf_n);
   STD_TORCH_CHECK(has_dtype(B_sf, sf_t), "B_sf must be ", sf_n);
-  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, fp8 ? "A must be 2D (M, K) and B 3D (E, N, K)" : "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
-  STD_TORCH_CHECK(A.size(1) == B.size(2), "Inner dimensions must match for A @ B[g].T");
-  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * (fp8 ? 1 : 2), kb = K / (G == Grouped::NVF4 ? 16 : 32);
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, w4a8 ? "A must be 2D (M, K) and B 3D (E, N, K/2)" : fp8 ? "A must be 2D (M, K) and B 3D (E, N, K)" : "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
+  STD_TORCH_CHECK(A.size(1) == B.size(2) * (w4a8 ? 2 : 1), "Inner dimensions must match for A @ B[g].T");
+  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * (fp8 || w4a8 ? 1 : 2), kb = K / (G == Grouped::NVF4 ? 16 : 32);
   STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
   STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
   STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
@@ -219,6 +227,7 @@ Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, cons
   int rc;
   if (G == Grouped::MXF4) rc = qutlass_amd_grouped_matmul_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
   else if (G == Grouped::NVF4) rc = qutlass_amd_grouped_matmul_nvf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
+  else if (w4a8) rc = qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
   else rc = qutlass_amd_grouped_matmul_mxf8_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E,
                                                     has_dtype(A, ScalarType::Float8_e5m2) ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3, s);
   check_rc(rc);
@@ -228,6 +237,7 @@ Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, cons
 Tensor grouped_matmul_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF4>(A, B, A_sf, B_sf, alpha, offs); }
 Tensor grouped_matmul_nvf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::NVF4>(A, B, A_sf, B_sf, alpha, offs); }
 Tensor grouped_matmul_mxf8(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF8>(A, B, A_sf, B_sf, alpha, offs); }
+Tensor grouped_matmul_mxf8_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF8_MXF4>(A, B, A_sf, B_sf, alpha, offs); }
 
 Tensor matmul_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_ada_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::ADA_MXF4>(A, B, A_sf, B_sf, alpha); }
@@ -824,6 +834,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
+  m.def("grouped_matmul_mxf8_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // W4A8, inference op: in the minimal library too
   m.def("grouped_matmul_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
 }
 
@@ -880,6 +891,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("fusedQuantizeMatmulMxf4", TORCH_BOX(&fusedQuantizeMatmulMxf4));
   m.impl("grouped_matmul_mxf4", TORCH_BOX(&grouped_matmul_mxf4));
   m.impl("grouped_matmul_mxf8", TORCH_BOX(&grouped_matmul_mxf8));
+  m.impl("grouped_matmul_mxf8_mxf4", TORCH_BOX(&grouped_matmul_mxf8_mxf4));
   m.impl("grouped_matmul_nvf4", TORCH_BOX(&grouped_matmul_nvf4));
 }
 

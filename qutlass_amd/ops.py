@@ -95,7 +95,7 @@ def _register_fakes() -> None:
     def grouped_tn(A, B, A_sf, B_sf, alpha, offs):   # A (M, K/2 or K), B (E, N, K/2 or K)
         return A.new_empty((A.size(0), B.size(1)), dtype=torch.bfloat16)
 
-    for name in ("grouped_matmul_mxf4", "grouped_matmul_mxf8", "grouped_matmul_nvf4"):
+    for name in ("grouped_matmul_mxf4", "grouped_matmul_mxf8", "grouped_matmul_nvf4", "grouped_matmul_mxf8_mxf4"):
         rf(f"qutlass_amd::{name}")(grouped_tn)
 
 
