@@ -874,7 +874,7 @@ extern template int launch_gemm<GemmCfg<256, 256, 2, 2, 8, true>, 6>(GemmParams,
 // NVFP4 launches live in their own unit
 #if QAMD_DEF(4)
 int launch_nvf4_host(const NvGemmParams& p, hipStream_t s, int variant, int* splits_out) {
-  return launch_nvf4_gemm(p, s, variant, chip_cus(), splits_out) == hipSuccess ? 0 : 1;
+  return launch_nvf4_gemm(p, s, variant, chip_cus(), splits_out, opt_deepp_grid()) == hipSuccess ? 0 : 1;   // (the lab's "deepp_grid": the forced persistent kernel, variant 42)
 }
 int launch_nvf4_grouped_host(const NvGroupedParams& q, hipStream_t s, int form) { return launch_nvf4_grouped(q, s, form) == hipSuccess ? 0 : 1; }
 #else

@@ -992,7 +992,9 @@ inline NvPlan nvf4_plan(int64_t M, int64_t N, int64_t K, int cus, bool may_split
 // Returns hipErrorInvalidValue for a variant this build does not know (the product library knows only 0 = auto).
 // cus: compute units of the device (capi.hip chip_cus): every occupancy threshold below derives from it
 // *splits_out (when given): the number of K ranges the launch wrote to p.ws -- the caller then runs splitk_reduce_kernel; 1 = D is final
-inline hipError_t launch_nvf4_gemm(NvGemmParams p, hipStream_t s, int variant = 0, int cus = 256, int* splits_out = nullptr) {
+// pk_grid (lab, variant 42 only; 0 = nvpk_plan's): workgroups of the forced persistent kernel, so that a small shape gives each of them several tiles
+inline hipError_t launch_nvf4_gemm(NvGemmParams p, hipStream_t s, int variant = 0, int cus = 256, int* splits_out = nullptr, int pk_grid = 0) {
+  (void)pk_grid;
   const int64_t want = cus * 3 / 4;
   if (splits_out) *splits_out = 1;
   int force_split = 0;
@@ -1085,7 +1087,11 @@ inline hipError_t launch_nvf4_gemm(NvGemmParams p, hipStream_t s, int variant = 
 #else
       const bool may_sk = false;
 #endif
-      const NvPkPlan pl = nvpk_plan(p.M, p.N, p.K, cus, may_sk);
+      NvPkPlan pl = nvpk_plan(p.M, p.N, p.K, cus, may_sk);
+#if QAMD_BENCH
+      if (pk_forced && !pk_sk && !pk_trace && pk_grid > 0)   // (whole tiles w, w + grid, ...: the walk takes any grid)
+        pl.grid = (int)std::min<int64_t>(pk_grid, (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256));
+#endif
       p.sk_tiles = pl.sk_tiles;
       p.sk_ws = (float*)scratch;
       p.sk_flags = (unsigned long long*)((char*)scratch + (int64_t)pl.grid * NVPK_PART_BYTES);

@@ -2,9 +2,10 @@
 
 A CASE is one kernel form of one MX GEMM op at one shape: (op, a5, variant, lab options, m, n, k).
   op       "mxf4" matmul_mxf4_bf16_tn (_ws entry) | "mxf8" matmul_mxf8_bf16_tn (_fmt entry) | "ada" matmul_ada_mxf4_bf16_tn (row-major scales) |
-           "nn" matmul_mxf8_bf16_nn (_fmt entry; A stored (K, M)) | "g4" / "g8" grouped_matmul_mxf{4,8}_bf16_tn (m = token rows over GROUPED_E experts, offs[-1] == m)
+           "nn" matmul_mxf8_bf16_nn (_fmt entry; A stored (K, M)) | "g4" / "g8" grouped_matmul_mxf{4,8}_bf16_tn (m = token rows over GROUPED_E experts, offs[-1] == m) |
+           "g48" grouped_matmul_mxf8_mxf4_bf16_tn (W4A8: e4m3 tokens against e2m1 weights; its reference is tests/_w4a8_model.py, the oracle has no mixed kind)
   a5       MXFP8 only: A in e5m2
-  variant  the lab library's "gemm_variant" (capi.hip dispatch_variant's numbering; 62 / 63: the two operand paths of the NN op; 590 ... 597: the grouped forms)
+  variant  the lab library's "gemm_variant" (capi.hip dispatch_variant's numbering; 62 / 63: the two operand paths of the NN op; 590 ... 597, 602 ... 604: the grouped forms)
   options  further lab options: deepp_grid (persistent workgroups, so that each walks several tiles), splitk_force (K ranges of a forced ring tile: the _ws entry with scratch)
 
 Shapes are the smallest at which a form can still go wrong: two tiles plus a ragged remainder in M (not a multiple of 16) and in N (a multiple of 8, not of the tile), a K
@@ -46,7 +47,11 @@ class Case(NamedTuple):
 
     @property
     def fp8(self):
-        return self.op in ("mxf8", "nn", "g8")
+        return self.op in ("mxf8", "nn", "g8", "g48")      # (the A operand: "g48" has e2m1 weights)
+
+    @property
+    def grouped(self):
+        return self.op in ("g4", "g8", "g48")
 
 
 T256, T128, T64, T32, T64N = (531, 552), (275, 296), (147, 168), (83, 200), (147, 200)
@@ -77,6 +82,7 @@ _MXF4_ONLY = [(60, (), T32, (2432,)), (561, (), T32, (2432, 6528)), (562, (), T3
 _ADA = [60, 70] + list(range(568, 576))
 _GROUPED4 = [(590, (1408, 4352)), (591, (1408, 4352)), (592, (1408, 3328)), (593, (2432,))]
 _GROUPED8 = [(594, (640, 2176)), (595, (640, 2176)), (596, (640, 1664)), (597, (1152,))]            # (the grouped ops take K % 128 == 0 only)
+_GROUPED48 = [(602, (3072, 3200)), (603, (3072, 3200)), (604, (1536, 1664))]   # a stage is 128 elements: one shot up to 6 slots per wave (604: up to K = 1536), rings beyond (tests/test_gpu_grouped_w4a8.py)
 
 
 def _build_cases():
@@ -99,6 +105,8 @@ def _build_cases():
         out += [Case("g4", False, v, (), 300, 200, k) for k in ks]
     for v, ks in _GROUPED8:
         out += [Case("g8", a5, v, (), 300, 200, k) for a5 in (False, True) for k in ks]
+    for v, ks in _GROUPED48:
+        out += [Case("g48", False, v, (), 300, 200, k) for k in ks]
     return out
 
 
@@ -122,8 +130,8 @@ def isnan_bf16(bits):
     return (np.asarray(bits) & 0x7FFF) > 0x7F80
 
 
-def _codes(c: Case, rows, rng, e5m2):
-    if not c.fp8:
+def _codes(c: Case, rows, rng, e5m2, weights=False):
+    if not c.fp8 or (weights and c.op == "g48"):
         return rng.integers(0, 256, size=(rows, c.k // 2), dtype=np.uint8)
     import torch
 
@@ -158,7 +166,13 @@ class Data(NamedTuple):
 
 def _reference(c: Case, a, b, sa, sb, alpha):
     kind = oracle.KIND_MXFP4 if not c.fp8 else oracle.KIND_MXFP8_TN_A5 if c.a5 else oracle.KIND_MXFP8_TN
-    if c.op not in ("g4", "g8"):
+    if c.op == "g48":   # fp64 dequantise, matmul, one rounding
+        import _w4a8_model as W
+
+        kb = c.k // 32
+        p = W.W4A8(a, b.reshape(GROUPED_E, c.n, c.k // 2), sa, sb.reshape(GROUPED_E, c.n, kb))
+        return W.to_bf16_bits(W.reference_f64(p, group_counts(c), alpha)).numpy().view(np.uint16)
+    if not c.grouped:
         return oracle.gemm_blockscaled(kind, a, b, oracle.to_blocked(sa[:c.m]), oracle.to_blocked(sb[:c.n]), alpha, c.m, c.n, c.k)
     ref = np.empty((c.m, c.n), np.uint16)
     r0 = 0
@@ -180,12 +194,12 @@ def nan_pattern(c: Case):
 def _dataset(key: Case, part: str) -> Data:
     """key: a case with variant 0 and no options -- forms that share (op, a5, shape) share the operands and the reference"""
     c = key
-    grouped = c.op in ("g4", "g8")
+    grouped = c.grouped
     rng = np.random.default_rng(zlib.crc32(repr((c.op, c.a5, c.m, c.n, c.k, part)).encode()))
     kb = c.k // 32
     rows_a, rows_b = (c.m, GROUPED_E * c.n) if grouped else (pad128(c.m), pad128(c.n))
     nb = rows_b if grouped else c.n
-    a, b = _codes(c, c.m, rng, c.a5), _codes(c, nb, rng, False)
+    a, b = _codes(c, c.m, rng, c.a5), _codes(c, nb, rng, False, weights=True)
     ra, rb = np.arange(rows_a)[:, None], np.arange(rows_b)[:, None]
     alpha = 0.5
     if part in ("sweep", "extremes"):
@@ -206,7 +220,8 @@ def _dataset(key: Case, part: str) -> Data:
         assert c.fp8 and c.m >= 80 and c.k >= 640
         nanp, nanm = (0x7D, 0xFE) if c.a5 else (0x7F, 0xFF)
         a[2, 5], a[c.m - 1, c.k - 1] = nanp, nanm                     # NaN of both signs in A: first tile, the ragged last row and the last K byte
-        b[(2 * c.n if grouped else 0) + 3, 40], b[nb - 1, c.k - 2] = 0x7F, 0xFF   # ... and in B (grouped: the third and the last expert)
+        if c.op != "g48":                                             # (e2m1 weights have no NaN code)
+            b[(2 * c.n if grouped else 0) + 3, 40], b[nb - 1, c.k - 2] = 0x7F, 0xFF   # ... and in B (grouped: the third and the last expert)
         if c.a5:
             a[c.m - 2, 7], a[c.m - 2, 300] = 0x7E, 0x7F               # the other two e5m2 NaN codes
             col = np.arange(nb) % c.n
@@ -229,26 +244,31 @@ def f32_to_bf16_bits(x):
 
 
 def sums_in_fp32(c: Case, d: Data, reverse: bool):
-    """sampled outputs with the K groups' block sums added one by one in fp32, forward or reversed: equal bits for both orders = the exact regime"""
-    assert c.op in ("mxf4", "mxf8")
-    rows = np.unique(np.r_[0:8, c.m - 8:c.m])
+    """sampled outputs with the K groups' block sums added one by one in fp32, forward or reversed: equal bits for both orders = the exact regime
+    ("g48": the first and last rows of every expert, each against its own expert's weights)"""
+    assert c.op in ("mxf4", "mxf8", "g48")
+    bounds = np.r_[0, np.cumsum(group_counts(c))] if c.grouped else np.array([0, c.m])
+    segs = [(e, int(r0), int(r1)) for e, (r0, r1) in enumerate(zip(bounds[:-1], bounds[1:])) if r1 > r0]
+    rows = np.unique(np.concatenate([np.r_[r0:min(r0 + 8, r1), max(r1 - 8, r0):r1] for _, r0, r1 in segs]))
     cols = np.unique(np.r_[0:16, c.n - 16:c.n])
     kb = c.k // 32
     dec = np.array([oracle.lib().orc_e2m1_decode(i) for i in range(16)], np.float64)
-    if c.fp8:
-        dec8 = np.array([oracle.lib().orc_e4m3_decode(i) for i in range(256)], np.float64)
-        dec5 = np.array([oracle.lib().orc_e5m2_decode(i) for i in range(256)], np.float64)
-        av, bv = (dec5 if c.a5 else dec8)[d.a[rows]], dec8[d.b[cols]]
-    else:
-        unpack = lambda x: np.stack([dec[x & 15], dec[x >> 4]], -1).reshape(x.shape[0], -1)
-        av, bv = unpack(d.a[rows]), unpack(d.b[cols])
-    blk = np.einsum("rgi,cgi->rcg", av.reshape(len(rows), kb, 32), bv.reshape(len(cols), kb, 32))          # exact: small integers / 4
-    e = d.sa[rows].astype(np.int64)[:, None, :] + d.sb[cols].astype(np.int64)[None, :, :] - 254
-    terms = np.ldexp(blk, e).astype(np.float32)
-    assert np.array_equal(terms.astype(np.float64), np.ldexp(blk, e))
-    acc = np.zeros(terms.shape[:2], np.float32)
-    for g in (range(kb - 1, -1, -1) if reverse else range(kb)):
-        acc = (acc + terms[:, :, g]).astype(np.float32)
+    dec8 = np.array([oracle.lib().orc_e4m3_decode(i) for i in range(256)], np.float64)
+    dec5 = np.array([oracle.lib().orc_e5m2_decode(i) for i in range(256)], np.float64)
+    unpack = lambda x: np.stack([dec[x & 15], dec[x >> 4]], -1).reshape(x.shape[0], -1)
+    av = (dec5 if c.a5 else dec8)[d.a[rows]] if c.fp8 else unpack(d.a[rows])
+    acc = np.zeros((len(rows), len(cols)), np.float32)
+    for ex, r0, r1 in segs:
+        sel, bsel = (rows >= r0) & (rows < r1), ex * c.n + cols
+        bv = unpack(d.b[bsel]) if c.op in ("mxf4", "g48") else dec8[d.b[bsel]]
+        blk = np.einsum("rgi,cgi->rcg", av[sel].reshape(-1, kb, 32), bv.reshape(len(cols), kb, 32))          # exact: small integers / 4
+        e = d.sa[rows[sel]].astype(np.int64)[:, None, :] + d.sb[bsel].astype(np.int64)[None, :, :] - 254
+        terms = np.ldexp(blk, e).astype(np.float32)
+        assert np.array_equal(terms.astype(np.float64), np.ldexp(blk, e))
+        part = np.zeros(terms.shape[:2], np.float32)
+        for g in (range(kb - 1, -1, -1) if reverse else range(kb)):
+            part = (part + terms[:, :, g]).astype(np.float32)
+        acc[sel] = part
     return rows, cols, acc
 
 
@@ -271,7 +291,7 @@ def operands(c: Case, d: Data, past_k=None):
     """the byte images the op reads: (A, B, A_sf, B_sf).  past_k: an rng -- the scale columns past K of the blocked images get random FINITE bytes instead of zeros"""
     kb = c.k // 32
     a = np.ascontiguousarray(d.a.T) if c.op == "nn" else d.a
-    if c.op in ("ada", "g4", "g8"):
+    if c.op == "ada" or c.grouped:
         return a, d.b, np.ascontiguousarray(d.sa[:c.m]), np.ascontiguousarray(d.sb[:GROUPED_E * c.n if c.op != "ada" else c.n])
 
     def img(s):
@@ -326,7 +346,7 @@ def run(c: Case, d: Data, fill: int = 0xFF, past_k=None, dev="cuda:0") -> Result
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     a, b, sfa, sfb = operands(c, d, past_k)
     rowbytes = c.k if c.fp8 else c.k // 2
-    ea, eb = Embedded(a, fill, 256 * rowbytes, dev), Embedded(b, fill, 256 * rowbytes, dev)
+    ea, eb = Embedded(a, fill, 256 * rowbytes, dev), Embedded(b, fill, 256 * (c.k // 2 if c.op == "g48" else rowbytes), dev)
     esa, esb = Embedded(sfa, fill, 1 << 16, dev), Embedded(sfb, fill, 1 << 16, dev)
     alpha = torch.tensor([d.alpha], device=dev)
     dbuf = torch.full((c.m + 2 * GUARD_ROWS, c.n), SENTINEL, dtype=torch.int16, device=dev)
@@ -354,7 +374,8 @@ def run(c: Case, d: Data, fill: int = 0xFF, past_k=None, dev="cuda:0") -> Result
         else:
             offs = torch.tensor(np.cumsum(group_counts(c)), dtype=torch.int32, device=dev)
             tail = [i64] * 4 + ([i32] if c.op == "g8" else []) + [vp]
-            f = _entry(lib, f"qutlass_amd_grouped_matmul_mxf{4 if c.op == 'g4' else 8}_bf16_tn", [vp] * 5 + [i64, vp, vp] + tail)
+            kind = {"g4": "mxf4", "g8": "mxf8", "g48": "mxf8_mxf4"}[c.op]
+            f = _entry(lib, f"qutlass_amd_grouped_matmul_{kind}_bf16_tn", [vp] * 5 + [i64, vp, vp] + tail)
             fmt = (int(c.a5),) if c.op == "g8" else ()
             rc = f(*head, 1, offs.data_ptr(), dptr, c.m, c.n, c.k, GROUPED_E, *fmt, stream)
         assert rc == 0, lib.qutlass_amd_last_error().decode()

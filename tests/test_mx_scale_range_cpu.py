@@ -14,7 +14,8 @@ import pytest
 import _mx_cases as mc
 
 DENSE = [c for c in mc.CASES if c.op in ("mxf4", "mxf8")]
-KEYS = sorted({c._replace(variant=0, opts=()) for c in DENSE}, key=lambda c: c.id)
+W4A8 = sorted({c._replace(variant=0, opts=()) for c in mc.CASES if c.op == "g48"}, key=lambda c: c.id)      # (their reference is numpy's fp64 matmul: no size cut)
+KEYS = sorted({c._replace(variant=0, opts=()) for c in DENSE}, key=lambda c: c.id) + W4A8
 SMALL_KEYS = [c for c in KEYS if c.m * c.n * c.k <= 83 * 200 * 4352]          # (CPU time: the large tiles' shapes run on the GPU side against the same builder)
 
 
@@ -22,7 +23,7 @@ SMALL_KEYS = [c for c in KEYS if c.m * c.n * c.k <= 83 * 200 * 4352]          # 
 @pytest.mark.parametrize("c", KEYS, ids=lambda c: c.id)
 def test_whole_range_layouts_are_in_the_exact_regime(c, layout):
     d = mc.dataset(c, layout)
-    for s, rows in ((d.sa, c.m), (d.sb, c.n)):
+    for s, rows in ((d.sa, c.m), (d.sb, c.n * (mc.GROUPED_E if c.grouped else 1))):
         seen = set(np.unique(s[:rows]).tolist())
         if layout == "extremes":
             assert {0, 1, 127, 253, 254} <= seen
@@ -38,12 +39,12 @@ def test_whole_range_layouts_are_in_the_exact_regime(c, layout):
     assert not mc.isnan_bf16(d.ref).any() and len(np.unique(d.ref)) > 100
 
 
-@pytest.mark.parametrize("c", [k for k in {c._replace(variant=0, opts=()) for c in mc.CASES} if k.m * k.n * k.k <= 83 * 200 * 4352], ids=lambda c: c.id)
+@pytest.mark.parametrize("c", [k for k in {c._replace(variant=0, opts=()) for c in mc.CASES} if k.m * k.n * k.k <= 83 * 200 * 4352 or k in W4A8], ids=lambda c: c.id)
 def test_oracle_nan_pattern_of_the_tracer_data_is_the_predicted_one(c):
     d = mc.dataset(c, "nan")
     want = mc.nan_pattern(c)
     assert np.array_equal(mc.isnan_bf16(d.ref), want)
-    assert 0.4 < want.mean() < 0.6 and (d.sa[c.m:] == 255).any() == (mc.pad128(c.m) > c.m and c.op not in ("g4", "g8"))
+    assert 0.4 < want.mean() < 0.6 and (d.sa[c.m:] == 255).any() == (mc.pad128(c.m) > c.m and not c.grouped)
 
 
 @pytest.mark.parametrize("c", [k for k in {c._replace(variant=0, opts=()) for c in mc.FP8_CASES} if k.m * k.n * k.k <= 300 * 200 * 1184], ids=lambda c: c.id)
@@ -125,7 +126,7 @@ def test_every_form_the_ada_and_grouped_plans_return_is_run_on_the_gpu(lib):
                     seen |= {out[3 * i] for i in range(cnt)}
     assert len(seen) >= 6 and seen <= mc.covered("ada"), sorted(seen - mc.covered("ada"))
     o3 = (ctypes.c_int64 * 8)()
-    for name, op in (("qutlass_amd_debug_grouped_plan", "g4"), ("qutlass_amd_debug_grouped_mxf8_plan", "g8")):
+    for name, op in (("qutlass_amd_debug_grouped_plan", "g4"), ("qutlass_amd_debug_grouped_mxf8_plan", "g8"), ("qutlass_amd_debug_grouped_mxf8_mxf4_plan", "g48")):
         g = getattr(lib, name)
         g.restype = ctypes.c_int
         g.argtypes = [ctypes.c_int64] * 4 + [ctypes.POINTER(ctypes.c_int64)]
