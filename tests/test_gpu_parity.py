@@ -159,9 +159,22 @@ def test_fused_quantize_mx_ragged_shapes_and_exact_inputs(q, shape):
 
 def test_fused_quantize_mx_leaves_scale_padding_untouched(q):
     # reference contract: only the first numel/32 bytes of the (padded_rows, padded_cols) buffer are written
-    x = torch.randn(3, 96, dtype=torch.bfloat16, device=DEV)
-    _, s = q.fusedQuantizeMx(x, _hadamard(32), method="abs_max")
+    # (exact-regime input, tests/_rotations.py: the oracle's scale bytes hold to the bit)
+    import _rotations as rot
+
+    x, h = rot.exact_input((3, 96), seed=3), _hadamard(32)
+    codes, s = q.ops.alloc_quant(q.ops.QUANT_OPS["quantize_mx"], x.to(DEV), h, 1)
     assert s.shape == (128, 4)
+    n = x.numel() // 32
+    rq, rs, _ = oracle.fused_quantize_mx(_np(x), _np(h), oracle.ABS_MAX, acc_model=1)
+    for fill in (0x5A, 0xA5):
+        s.view(torch.uint8).fill_(fill)
+        codes.fill_(fill)
+        torch.ops.qutlass_amd.fusedQuantizeMx_(x.to(DEV), h, codes, s, 1)
+        flat = _np(s).reshape(-1)
+        assert (flat[n:] == fill).all(), (hex(fill), int((flat[n:] != fill).sum()), int(np.flatnonzero(flat[n:] != fill)[0]) + n)
+        assert np.array_equal(flat[:n], rs), (hex(fill), flat[:n], rs)
+        assert oracle.codes_equal_mod_zero_sign(_np(codes).reshape(-1), rq).all()
 
 
 # ------------------------------------------------------------------------------------------------
