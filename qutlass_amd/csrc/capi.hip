@@ -873,12 +873,10 @@ extern template int launch_gemm<GemmCfg<256, 256, 2, 2, 8, true>, 6>(GemmParams,
 
 // NVFP4 launches live in their own unit
 #if QAMD_DEF(4)
-int launch_nvf4_host(const NvGemmParams& p, hipStream_t s, int variant, int* splits_out) {
-  return launch_nvf4_gemm(p, s, variant, chip_cus(), splits_out, opt_deepp_grid()) == hipSuccess ? 0 : 1;   // (the lab's "deepp_grid": the forced persistent kernel, variant 42)
-}
+int launch_nvf4_host(const NvLaunch& l, const NvGemmParams& p, hipStream_t s) { return launch_nvf4_gemm(l, p, s) == hipSuccess ? 0 : 1; }
 int launch_nvf4_grouped_host(const NvGroupedParams& q, hipStream_t s, int form) { return launch_nvf4_grouped(q, s, form) == hipSuccess ? 0 : 1; }
 #else
-int launch_nvf4_host(const NvGemmParams& p, hipStream_t s, int variant, int* splits_out);
+int launch_nvf4_host(const NvLaunch& l, const NvGemmParams& p, hipStream_t s);
 int launch_nvf4_grouped_host(const NvGroupedParams& q, hipStream_t s, int form);
 #endif
 
@@ -1177,20 +1175,32 @@ inline int ada_plan(int64_t M, int64_t N, int64_t K, int cus) {
 
 // ---- the executor.  The operands of one MX GEMM: scales in the to_blocked layout (128-row blocks of ceil(K / 128) 512-byte pieces: the TN and NN ops) or row-major (rows, K / 32)
 // (rm: matmul_ada_mxf4_bf16_tn); ldd: row stride of D in elements
-struct MxArgs { const void *A, *B, *A_sf, *B_sf; const float* alpha; void* D; int64_t K, ldd; int ebits; bool rm; };
-// the GemmParams of rows [r0, r0 + m) x columns [c0, c0 + n) of the output (with blocked scales r0 and c0 are multiples of 128)
-inline GemmParams mx_params(const MxArgs& x, int64_t r0, int64_t c0, int64_t m, int64_t n) {
-  const int64_t rowbytes = x.K * x.ebits / 8, KB = x.K / 32, CB = cdiv(KB, 4);
+// group: K elements per scale (32: the MX formats, 16: NVFP4)
+struct MxArgs { const void *A, *B, *A_sf, *B_sf; const float* alpha; void* D; int64_t K, ldd; int ebits; bool rm; int group = 32; };
+// the operand, scale and output fields of rows [r0, r0 + m) x columns [c0, c0 + n) of the output (with blocked scales r0 and c0 are multiples of 128); P: GemmParams / NvGemmParams
+template <class P>
+inline P operand_params(const MxArgs& x, int64_t r0, int64_t c0, int64_t m, int64_t n) {
+  const int64_t rowbytes = x.K * x.ebits / 8, KB = x.K / x.group, CB = cdiv(KB, 4);
   auto sf_offset = [&](int64_t row) { return x.rm ? row * KB : (row / 128) * CB * 512; };
   auto sf_bytes = [&](int64_t rows) { return (uint32_t)(x.rm ? rows * KB : cdiv(rows, 128) * CB * 512); };
-  GemmParams p{};
+  P p{};
   p.A = (const uint8_t*)x.A + r0 * rowbytes; p.B = (const uint8_t*)x.B + c0 * rowbytes;
   p.SFA = (const uint8_t*)x.A_sf + sf_offset(r0); p.SFB = (const uint8_t*)x.B_sf + sf_offset(c0);
   p.alpha = x.alpha; p.D = (uint16_t*)x.D + r0 * x.ldd + c0; p.M = (int)m; p.N = (int)n; p.K = (int)x.K; p.ldd = (int)x.ldd;
   p.a_bytes = (uint32_t)(m * rowbytes); p.b_bytes = (uint32_t)(n * rowbytes);
   p.sfa_bytes = sf_bytes(m); p.sfb_bytes = sf_bytes(n);
-  p.pp_shift = opt_pp_shift(); p.pp_flags = opt_pp_flags(); p.dbg = opt_dbg();
+  p.dbg = opt_dbg();
   p.splits = 1;
+  return p;
+}
+inline GemmParams mx_params(const MxArgs& x, int64_t r0, int64_t c0, int64_t m, int64_t n) {
+  GemmParams p = operand_params<GemmParams>(x, r0, c0, m, n);
+  p.pp_shift = opt_pp_shift(); p.pp_flags = opt_pp_flags();
+  return p;
+}
+inline NvGemmParams nv_params(const MxArgs& x, int64_t r0, int64_t c0, int64_t m, int64_t n) {
+  NvGemmParams p = operand_params<NvGemmParams>(x, r0, c0, m, n);
+  p.sk_tag = next_launch_tag();
   return p;
 }
 inline SkinnyParams skinny_params(const GemmParams& p) {
@@ -1198,6 +1208,19 @@ inline SkinnyParams skinny_params(const GemmParams& p) {
   q.A = p.A; q.B = p.B; q.SFA = p.SFA; q.SFB = p.SFB; q.alpha = p.alpha; q.D = p.D; q.M = p.M; q.N = p.N; q.K = p.K;
   q.a_bytes = p.a_bytes; q.b_bytes = p.b_bytes; q.sfa_bytes = p.sfa_bytes; q.sfb_bytes = p.sfb_bytes; q.ldd = p.ldd;
   return q;
+}
+
+// the second launch of a split: sum the `splits` K ranges of fp32 partials in ws in fixed z order, alpha, bf16 (deterministic; gemm_mx.hip.h)
+inline int splitk_reduce(const char* name, int splits, const void* ws, uint16_t* D, const float* alpha, int M, int N, int ldd, hipStream_t s) {
+  const int64_t quads = (int64_t)M * (N / 4);
+  const int grid = (int)std::min<int64_t>(cdiv(quads, 256), 2048);
+  switch (splits) {
+#define QAMD_RED(S_) case S_: hipLaunchKernelGGL(splitk_reduce_kernel<S_>, dim3(grid), dim3(256), 0, s, (const float*)ws, D, alpha, M, N, ldd); break;
+    QAMD_RED(2) QAMD_RED(3) QAMD_RED(4) QAMD_RED(5) QAMD_RED(6) QAMD_RED(7) QAMD_RED(8)
+#undef QAMD_RED
+    default: return fail(QAMD_ERR_INVALID, "%s: unsupported split count %d", name, splits);
+  }
+  return check_launch("splitk_reduce_kernel");
 }
 
 // one planned launch of matmul_mx{f4,f8}_bf16_tn, then the reduce pass of a split
@@ -1244,32 +1267,37 @@ int mx_launch(const char* name, const MxLaunch& l, GemmParams p, void* ws, int a
     return dispatch(l.variant);
   }
 #endif
-  // second launch: sum the partials in fixed z order, alpha, bf16 (deterministic)
   if (int rc = dispatch(l.variant)) return rc;
-  const int64_t quads = (int64_t)p.M * (p.N / 4);
-  const int grid = (int)std::min<int64_t>(cdiv(quads, 256), 2048);
-  switch (l.splits) {
-#define QAMD_RED(S_) case S_: hipLaunchKernelGGL(splitk_reduce_kernel<S_>, dim3(grid), dim3(256), 0, s, (const float*)ws, p.D, p.alpha, p.M, p.N, p.ldd); break;
-    QAMD_RED(2) QAMD_RED(3) QAMD_RED(4) QAMD_RED(5) QAMD_RED(6) QAMD_RED(7) QAMD_RED(8)
-#undef QAMD_RED
-    default: return fail(QAMD_ERR_INVALID, "%s: unsupported split count %d", name, l.splits);
-  }
-  return check_launch("splitk_reduce_kernel");
+  return splitk_reduce(name, l.splits, ws, p.D, p.alpha, p.M, p.N, p.ldd, s);
 }
 
-// the argument checks of matmul_mx{f4,f8}_bf16_tn (EBITS 4 / 8)
-inline int mx_check(const char* name, int ebits, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, const void* D,
-                    int64_t M, int64_t N, int64_t K) {
+// the argument checks of the plain TN GEMMs: K >= kmin and a multiple of kalign; mn_got: the M / N message names the values (the MX ops)
+inline int gemm_check(const char* name, int kmin, int kalign, bool mn_got, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha,
+                      const void* D, int64_t M, int64_t N, int64_t K) {
   if (!A || !B || !A_sf || !B_sf || !alpha || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   // [r5] operands are fetched as 16-byte LDS-DMA pieces and the output leaves as 16-byte stores (the reference's CUTLASS kernels ask for 128-bit alignment as well, via TMA)
   if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)A_sf | (uintptr_t)B_sf | (uintptr_t)D) % 16)
     return fail(QAMD_ERR_INVALID, "%s: A, B, the scale operands and D must be 16-byte aligned", name);
-  if (M <= 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M and N must be positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
-  const int kalign = (ebits == 4) ? 128 : 32;
-  if (K < 32 || K % kalign) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of %d (got %lld)", name, kalign, (long long)K);
+  if (M <= 0 || N <= 0)
+    return mn_got ? fail(QAMD_ERR_INVALID, "%s: M and N must be positive (got M=%lld N=%lld)", name, (long long)M, (long long)N)
+                  : fail(QAMD_ERR_INVALID, "%s: M and N must be positive", name);
+  if (K < kmin || K % kalign) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of %d (got %lld)", name, kalign, (long long)K);
   if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
   if (M * N >= (1ll << 40) || M >= (1ll << 31) || N >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
   return QAMD_OK;
+}
+// ... of matmul_mx{f4,f8}_bf16_tn (ebits 4 / 8)
+inline int mx_check(const char* name, int ebits, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, const void* D,
+                    int64_t M, int64_t N, int64_t K) {
+  return gemm_check(name, 32, ebits == 4 ? 128 : 32, true, A, B, A_sf, B_sf, alpha, D, M, N, K);
+}
+
+// matmul_nvf4_bf16_tn: f(r0, c0, m, n, launch) for the planned launch of every range.  A ranged call runs without scratch (avail: bytes of the caller's scratch, 0: none).
+template <class F>
+int nv_for_each_launch(const char* name, int64_t M, int64_t N, int64_t K, int64_t avail, int cus, F&& f) {
+  return for_each_range(name, M, N, K / 2, 256, [&](int64_t r0, int64_t c0, int64_t m, int64_t n) -> int {
+    return f(r0, c0, m, n, qamd::nvf4_launch_plan(opt_nvf4_variant(), m, n, K, cus, (m == M && n == N) ? avail : 0, opt_deepp_grid()));   // (the lab's "deepp_grid": the forced persistent kernel, variant 42)
+  });
 }
 
 // EBITS: 4 = MXFP4, 8 = MXFP8 (TN); a_fmt (MXFP8 only): QAMD_FP8_E4M3 / QAMD_FP8_E5M2 element format of A
@@ -1807,92 +1835,44 @@ int qutlass_amd_matmul_mxf8_bf16_nn_fmt(const void* A, const void* B, const void
   return mxf8_nn_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, a_format, workspace, workspace_bytes, stream);
 }
 
-// ldd: row stride of D in elements when the call covers a column range of a wider output (0 = N)
-// [r3] split-K scratch of matmul_nvf4_bf16_tn: bytes for the fp32 partials ws[splits][M][N] of the planned split, 0 when the shape does not split
-static int64_t nvf4_ws_bytes(int64_t M, int64_t N, int64_t K) {
+// matmul_nvf4_bf16_tn: the plan of each range (gemm_nvf4.hip.h nvf4_launch_plan; operands of >= 2 GiB: ranges of whole 256-row / 256-column tiles, as gemm_mx), its
+// launch, then the reduce pass of a split.  ws: caller scratch (null: none)
+static int nvf4_impl(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, void* D, int64_t M, int64_t N,
+                     int64_t K, void* stream, void* ws = nullptr, int64_t ws_bytes = 0) {
+  const char* name = "matmul_nvf4_bf16_tn";
+  if (int rc = gemm_check(name, 16, 32, false, A, B, A_sf, B_sf, alpha, D, M, N, K)) return rc;
+  const MxArgs x{A, B, A_sf, B_sf, alpha, D, K, N, 4, false, 16};
+  const hipStream_t s = (hipStream_t)stream;
+  return nv_for_each_launch(name, M, N, K, ws ? ws_bytes : 0, chip_cus(), [&](int64_t r0, int64_t c0, int64_t m, int64_t n, const qamd::NvLaunch& l) -> int {
+    NvGemmParams p = nv_params(x, r0, c0, m, n);
+    if (l.ws > 0) p.ws = (float*)ws;
+    if (launch_nvf4_host(l, p, s)) return fail(QAMD_ERR_INVALID, "%s: unknown nvf4_variant %d", name, opt_nvf4_variant());
+    if (int rc = check_launch(name)) return rc;
+    return l.splits > 1 ? splitk_reduce(name, l.splits, ws, p.D, alpha, p.M, p.N, p.ldd, s) : QAMD_OK;
+  });
+}
+
+int qutlass_amd_matmul_nvf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
+                                    const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream) {
+  return nvf4_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, stream);
+}
+
+// [r3] the scratch of the plan with unlimited scratch: bytes for the fp32 partials ws[splits][M][N] of the planned split, 0 when the shape does not split
+// (256x256 tiles run the persistent kernel in balanced whole-tile rounds: no scratch; its stream-K form is lab-only, gemm_nvf4_pk.hip.h)
+int64_t qutlass_amd_nvf4_splitk_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K < 32 || N % 4 || N * (K / 2) >= (1ll << 31) || M * (K / 2) >= (1ll << 31)) return 0;
 #if QAMD_BENCH
   if (opt_nvf4_variant() >= 100) return 8 * M * N * 4;   // lab: room for any forced split
   if (opt_nvf4_variant() >= 42 && opt_nvf4_variant() <= 45) return qamd::nvpk_ws_bytes(chip_cus());   // lab: forced persistent kernel
 #endif
-  const qamd::NvPlan pl = qamd::nvf4_plan(M, N, K, chip_cus(), true);
-  if (pl.splits > 1) return (int64_t)pl.splits * M * N * 4;
-  return 0;   // (256x256 tiles run the persistent kernel in balanced whole-tile rounds: no scratch; its stream-K form is lab-only, gemm_nvf4_pk.hip.h)
+  return qamd::nvf4_launch_plan(0, M, N, K, chip_cus(), INT64_MAX).ws;
 }
-
-static int nvf4_impl(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, void* D, int64_t M, int64_t N,
-                     int64_t K, int64_t ldd, void* stream, void* ws = nullptr, int64_t ws_bytes = 0) {
-  const char* name = "matmul_nvf4_bf16_tn";
-  if (!A || !B || !A_sf || !B_sf || !alpha || !D) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)A_sf | (uintptr_t)B_sf | (uintptr_t)D) % 16)   // [r5] as in mx_check
-    return fail(QAMD_ERR_INVALID, "%s: A, B, the scale operands and D must be 16-byte aligned", name);
-  if (M <= 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M and N must be positive", name);
-  if (K < 16 || K % 32) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 32 (got %lld)", name, (long long)K);
-  if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  if (M >= (1ll << 31) || N >= (1ll << 31) || M * N >= (1ll << 40)) return fail(QAMD_ERR_INVALID, "%s: an output of 2^40 elements is not supported", name);
-  if (ldd == 0) ldd = N;
-  const int64_t rowbytes = K / 2, CB = cdiv(K / 16, 4);
-  // The kernels address an operand through 32-bit buffer-descriptor offsets (< 2 GiB); the reference hands 64-bit strides to CUTLASS
-  // (qutlass/csrc/gemm.cu:90-143).  A larger operand runs as ranges of whole 256-row tiles with rebased operand / scale / D pointers
-  // (gemm_mx does the same): every output element is computed by exactly one launch, in the same K order.
-  if (N * rowbytes >= (1ll << 31)) {
-    const int64_t cols = ((1ll << 31) - 1) / rowbytes / 256 * 256;
-    if (cols < 256) return fail(QAMD_ERR_INVALID, "%s: K too large for a 256-column range of B to stay below 2 GiB", name);
-    for (int64_t c0 = 0; c0 < N; c0 += cols)
-      if (int rc = nvf4_impl(A, (const uint8_t*)B + c0 * rowbytes, A_sf, (const uint8_t*)B_sf + (c0 / 128) * CB * 512, alpha, (uint16_t*)D + c0, M,
-                             std::min(cols, N - c0), K, ldd, stream))
-        return rc;
-    return QAMD_OK;
-  }
-  if (M * rowbytes >= (1ll << 31)) {
-    const int64_t rows = ((1ll << 31) - 1) / rowbytes / 256 * 256;
-    if (rows < 256) return fail(QAMD_ERR_INVALID, "%s: K too large for a 256-row range of A to stay below 2 GiB", name);
-    for (int64_t r0 = 0; r0 < M; r0 += rows)
-      if (int rc = nvf4_impl((const uint8_t*)A + r0 * rowbytes, B, (const uint8_t*)A_sf + (r0 / 128) * CB * 512, B_sf, alpha, (uint16_t*)D + r0 * ldd,
-                             std::min(rows, M - r0), N, K, ldd, stream))
-        return rc;
-    return QAMD_OK;
-  }
-  NvGemmParams p;
-  p.A = (const uint8_t*)A; p.B = (const uint8_t*)B; p.SFA = (const uint8_t*)A_sf; p.SFB = (const uint8_t*)B_sf;
-  p.alpha = alpha; p.D = (uint16_t*)D; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.ldd = (int)ldd;
-  p.a_bytes = (uint32_t)(M * rowbytes); p.b_bytes = (uint32_t)(N * rowbytes);
-  p.sfa_bytes = (uint32_t)(cdiv(M, 128) * CB * 512); p.sfb_bytes = (uint32_t)(cdiv(N, 128) * CB * 512);
-  p.dbg = opt_dbg();
-  // split-K only with caller scratch of the size nvf4_ws_bytes reports for this very shape (a smaller or absent workspace runs the single pass)
-  const int64_t need = ws ? nvf4_ws_bytes(M, N, K) : 0;
-  p.ws = (need > 0 && ws_bytes >= need && ldd == N) ? (float*)ws : nullptr;
-  p.splits = 1; p.kt_per = 0;
-  p.sk_tiles = 0; p.sk_ws = nullptr; p.sk_flags = nullptr; p.sk_tag = next_launch_tag();
-  int splits = 1;
-  if (launch_nvf4_host(p, (hipStream_t)stream, opt_nvf4_variant(), &splits)) return fail(QAMD_ERR_INVALID, "%s: unknown nvf4_variant %d", name, opt_nvf4_variant());
-  if (int rc = check_launch(name)) return rc;
-  if (splits <= 1) return QAMD_OK;
-  if ((int64_t)splits * M * N * 4 > ws_bytes) return fail(QAMD_ERR_INVALID, "%s: internal: split count %d exceeds the workspace", name, splits);
-  // second launch: sum the K ranges in fixed z order, alpha, bf16 (deterministic; gemm_mx.hip.h)
-  const int64_t quads = M * (N / 4);
-  const int grid = (int)std::min<int64_t>(cdiv(quads, 256), 2048);
-  switch (splits) {
-#define QAMD_RED(S_) case S_: hipLaunchKernelGGL(splitk_reduce_kernel<S_>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)ws, (uint16_t*)D, alpha, (int)M, (int)N, (int)ldd); break;
-    QAMD_RED(2) QAMD_RED(3) QAMD_RED(4) QAMD_RED(5) QAMD_RED(6) QAMD_RED(7) QAMD_RED(8)
-#undef QAMD_RED
-    default: return fail(QAMD_ERR_INVALID, "%s: unsupported split count %d", name, splits);
-  }
-  return check_launch("splitk_reduce_kernel");
-}
-
-int qutlass_amd_matmul_nvf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
-                                    const float* alpha, void* D, int64_t M, int64_t N, int64_t K, void* stream) {
-  return nvf4_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, 0, stream);
-}
-
-int64_t qutlass_amd_nvf4_splitk_workspace_bytes(int64_t M, int64_t N, int64_t K) { return nvf4_ws_bytes(M, N, K); }
 
 int qutlass_amd_matmul_nvf4_bf16_tn_ws(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, void* D, int64_t M,
                                        int64_t N, int64_t K, void* workspace, int64_t workspace_bytes, void* stream) {
   if (workspace_bytes < 0 || (workspace_bytes > 0 && !workspace)) return fail(QAMD_ERR_INVALID, "matmul_nvf4_bf16_tn: invalid workspace");
   if ((uintptr_t)workspace % 16) return fail(QAMD_ERR_INVALID, "matmul_nvf4_bf16_tn: the workspace must be 16-byte aligned");
-  return nvf4_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, 0, stream, workspace, workspace_bytes);
+  return nvf4_impl(A, B, A_sf, B_sf, alpha, D, M, N, K, stream, workspace, workspace_bytes);
 }
 
 // k: logical 2-D shape of x (rows of k elements) for the blocked-scale variants; k == 0: flat scales (the reference's contract).  MX: global_scale null; NV: out_mask null.
@@ -2718,6 +2698,25 @@ int qutlass_amd_debug_nvf4_plan(int64_t M, int64_t N, int64_t K, int may_split) 
   if (M <= 0 || N <= 0 || K <= 0) return -2;
   const qamd::NvPlan pl = qamd::nvf4_plan(M, N, K, 256, may_split != 0);
   return pl.splits > 1 ? pl.cfg + 256 * pl.splits : pl.cfg;
+}
+
+// debug only (not declared in the public header): which kernels would matmul_nvf4_bf16_tn(_ws) launch for this shape on a 256-CU part?
+// out[6 * i + {0 ... 5}] = {form (gemm_nvf4.hip.h NvForm), columns, rows, K ranges, stages per range, workgroups} of launch i (the first min(cap, 8)); returns the
+// number of launches (the reduce pass is implied by K ranges > 1), or -1 when the arguments are rejected.  No GPU is touched.
+int qutlass_amd_debug_nvf4_launch_plan(int64_t M, int64_t N, int64_t K, int64_t workspace_bytes, int* out, int cap) {
+  alignas(16) static char dummy[16];
+  const char* name = "debug_nvf4_launch_plan";
+  if (gemm_check(name, 16, 32, false, dummy, dummy, dummy, dummy, (const float*)dummy, dummy, M, N, K)) return -1;
+  int cnt = 0;
+  const int rc = nv_for_each_launch(name, M, N, K, std::max<int64_t>(workspace_bytes, 0), 256, [&](int64_t, int64_t, int64_t m, int64_t n, const qamd::NvLaunch& l) {
+    if (cnt < 8 && cnt < cap) {
+      const int v[6] = {l.form, (int)n, (int)m, l.splits, l.kt_per, (int)l.grid};
+      std::copy(v, v + 6, out + 6 * cnt);
+    }
+    ++cnt;
+    return QAMD_OK;
+  });
+  return rc == QAMD_OK ? cnt : -1;
 }
 
 // [r4] the persistent NVFP4 kernel's plan on a 256-CU part: out[0] = workgroups, out[1] = tiles in the stream-K region (0: whole tiles only),

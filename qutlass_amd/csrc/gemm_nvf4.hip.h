@@ -891,44 +891,78 @@ inline int nvf4_big_cfg(int64_t M, int64_t N, int64_t K, int cus, double* t_us =
 // Against the calibration the chosen candidates sum to 10 353 us (best measured candidate per shape: 10 288; the occupancy thresholds this replaces:
 // 11 057), e.g. 256 x 4096 x 14336 54.7 -> 39.2 us (128x128 tiles, 4 K ranges), 128 x 8192 x 28672 107 -> 67, 64 x 28672 x 4096 36.7 -> 26.6 (64x64 tiles
 // instead of the skinny kernel), 512 x 5120 x 5120 47.0 -> 41.1 (160 tiles of 128x128 instead of 320 of 128x64, which put two on 64 CUs).
-struct NvPlan { int cfg, splits, kt_per; };   // cfg as above (-1 skinny, [r6] -2 / -3 wave-owned small-batch kernel with 32 / 16 columns per workgroup, -4 / -5 its 16x16 / 32x16 decode form, -6 ... -9 the decode form with 32 / 48 / 56 / 56 (8 A rows) columns per workgroup, -10 / -11 the 32x32-MFMA kernel on 64x32 / 96x32 tiles); splits = K ranges actually launched (none empty), kt_per = stages per range (even)
-// [r6] Does the wave-owned small-batch kernel (gemm_nvf4_os.hip.h) take the shape?  0 (no) or 32 (columns per workgroup; 16 is lab-only: the kernel is bound by its
+// The ONE list of matmul_nvf4_bf16_tn's kernel forms.  The values are what qutlass_amd_debug_nvf4_plan reports (the CPU tests assert them); nv_os_plan, nvf4_plan,
+// nvf4_launch_plan, launch_nvf4_os and launch_nvf4_gemm all speak this numbering.  5 ... 10 exist in the lab build only.
+enum NvForm : int {
+  NV_NONE = -100,                                        // no form: nv_os_plan passes the shape on / a variant this build does not know
+  NV_OS96 = -11, NV_OS64 = -10,                          // the 32x32-MFMA wave-owned kernel with three / two m-tiles per workgroup (96x32 / 64x32 tiles)
+  NV_D56A8 = -9, NV_D56 = -8, NV_D48 = -7, NV_D32 = -6,  // the decode form with 56 (A rows 0 ... 7 only) / 56 / 48 / 32 columns per workgroup
+  NV_D32x16 = -5, NV_D16 = -4,                           // the decode form on 32x16 / 16x16 tiles
+  NV_OS16 = -3, NV_OS32 = -2,                            // the wave-owned small-batch kernel with 16 (lab only) / 32 columns per workgroup
+  NV_SKINNY = -1,                                        // the split-K skinny kernel
+  NV_T256 = 0,                                           // 256x256 tiles: the persistent kernel (K % 256 == 0, K >= 512: nvpk_shape_ok), else the per-tile kernel
+  NV_T128 = 1, NV_T128x64 = 2, NV_T64 = 3, NV_T256x128 = 4,
+  NV_LAB_T256_W8 = 5, NV_LAB_LDS128 = 6, NV_LAB_LDS256 = 7, NV_LAB_T128_1x2 = 8, NV_LAB_T128_2x1 = 9, NV_LAB_ABL = 10,
+};
+enum NvFamily { NVF_OS, NVF_DECODE, NVF_OS_ROWS, NVF_SKINNY, NVF_TILE, NVF_PK, NVF_LAB };   // wave-owned 32-row, 16-row decode, 64 / 96-row, skinny, tile kernel, persistent
+struct NvFormRow { int form, tm, tn, family, variant; };   // tile rows x columns of a workgroup; variant: the lab's "nvf4_variant" that forces the form
+constexpr NvFormRow NV_FORMS[] = {
+    {NV_OS96, 96, 32, NVF_OS_ROWS, 55}, {NV_OS64, 64, 32, NVF_OS_ROWS, 54},
+    {NV_D56A8, 16, 56, NVF_DECODE, 53}, {NV_D56, 16, 56, NVF_DECODE, 52}, {NV_D48, 16, 48, NVF_DECODE, 51}, {NV_D32, 16, 32, NVF_DECODE, 50},
+    {NV_D32x16, 32, 16, NVF_DECODE, 49}, {NV_D16, 16, 16, NVF_DECODE, 48},
+    {NV_OS16, 32, 16, NVF_OS, 47}, {NV_OS32, 32, 32, NVF_OS, 46},
+    {NV_SKINNY, 32, 32, NVF_SKINNY, 3},
+    {NV_T256, 256, 256, NVF_PK, 42},
+    {NV_T128, 128, 128, NVF_TILE, 5}, {NV_T128x64, 128, 64, NVF_TILE, 6}, {NV_T64, 64, 64, NVF_TILE, 7}, {NV_T256x128, 256, 128, NVF_TILE, 40},
+    // lab only: 256x256 on 8 waves of 128x64 (variant 1 on a large output), the v2 kernel that dequantises once into f16 LDS tiles (variant 2: 128x128 for a small output),
+    // 128x128 on two waves of 128x64 / 64x128, the v2 kernel's ablations (variant 10 + b, launch_nvf4_ablation)
+    {NV_LAB_T256_W8, 256, 256, NVF_TILE, 1}, {NV_LAB_LDS128, 128, 128, NVF_LAB, 2}, {NV_LAB_LDS256, 256, 256, NVF_LAB, 2},
+    {NV_LAB_T128_1x2, 128, 128, NVF_TILE, 8}, {NV_LAB_T128_2x1, 128, 128, NVF_TILE, 9}, {NV_LAB_ABL, 256, 256, NVF_LAB, 10},
+};
+constexpr const NvFormRow* nv_form(int form) {
+  for (const NvFormRow& f : NV_FORMS)
+    if (f.form == form) return &f;
+  return nullptr;
+}
+struct NvPlan { int cfg, splits, kt_per; };   // cfg: an NvForm (NV_OS96 ... NV_T256x128); splits = K ranges actually launched (none empty), kt_per = stages per range (even)
+// [r6] Does the wave-owned small-batch kernel (gemm_nvf4_os.hip.h) take the shape?  NV_NONE (no) or its form (32 columns per workgroup; 16 is lab-only: the kernel is bound by its
 // dequantisation instructions -- ~16 per MFMA -- not by bytes, so spreading the weight over twice the workgroups buys nothing: profiles/calib_nvos_r6u.txt).
 // Measured against the plan before it (skinny / tile kernels / split-K with scratch), M = 1 ... 128:
 //   K <= 4096 (one shot): up to THREE rounds of 32x32 tiles (N = 4096, M = 128: 11.5 -> 9.7 us; 6144 x 4096, M = 128 = 768 tiles: 16.8 -> 13.8; four rounds lose)
 //   longer K (wave-owned rings, <= 64 stages): one tile per CU at most (4096 x 14336, M <= 64: 14.4-20.0 -> 13.4-15.5 us), two rounds up to 32 stages
 //   (4096 x 8192, M = 128: 21.6 -> 18.0), and never fewer than a quarter of the CUs busy (a long K on few tiles stays with the split plans)
-// [r6, third session] 1616 = its decode form, 16x16 tiles on v_mfma_f32_16x16x32_f16 (gemm_nvf4_os16_kernel): the same dequantisation instructions per weight element spread
+// [r6, third session] NV_D16 = its decode form, 16x16 tiles on v_mfma_f32_16x16x32_f16 (gemm_nvf4_os16_kernel): the same dequantisation instructions per weight element spread
 // over twice the workgroups.  Whenever the 16x16 tiles fit one per CU it wins at every K and every workgroup count measured (K = 2048 ... 28672, 32 ... 256 workgroups:
 // N = K = 4096, M <= 16: 5.3 -> 3.7-3.9 us; 4096 x 14336: 13.6 -> 9.1-9.7; 1024 x 14336, M = 32: 18.6 -> 8.8; x 28672, M = 16: 30.0 -> 16.4 -- also against the split-K
 // plans); two per CU (N = 6144 / 8192, M <= 16) still 4-8 % ahead at K = 4096 and behind from K = 8192 on.  profiles/calib_nv16_r7.txt
 inline int nv_os_plan(int64_t M, int64_t N, int64_t K, int cus) {
   const int64_t T32 = ((M + 31) / 32) * ((N + 31) / 32), KT = (K / 2 + 127) / 128;
-  if (M > 128) return 0;
+  if (M > 128) return NV_NONE;
   const int64_t G16 = ((M + 15) / 16) * ((N + 15) / 16);
-  if (G16 <= cus && KT <= 128) return 1616;
+  if (G16 <= cus && KT <= 128) return NV_D16;
   // M <= 16 against a weight too wide for 16-column workgroups: the decode form with 32 / 48 / 56 columns per workgroup, the A dword dequantised once for 2 / 3 / 4 n-tiles
-  // (1632 / 1648 / 1656; 856 = 56 columns with only A rows 0 ... 7 fetched, M <= 8: its 16 stages fit the LDS).  N = 11008 / 12288 x K = 4096: 9.2-10.8 -> 5.8-5.9 us (the
+  // (NV_D32 / NV_D48 / NV_D56; NV_D56A8 = 56 columns with only A rows 0 ... 7 fetched, M <= 8: its 16 stages fit the LDS).  N = 11008 / 12288 x K = 4096: 9.2-10.8 -> 5.8-5.9 us (the
   // 32x32 kernel ran two rounds of tiles); 12288 x 5120 13.6-14.1 -> 8.7-9.2; 14336 x 4096 9.5-9.8 -> 7.6-7.7 (M <= 8) / 8.0-8.3; x 8192 19.2 -> 15.0; N = 6144 / 8192:
   // -5 % at K = 4096, -12 % at K = 8192; 5120^2 -12 ... -15 %.  profiles/calib_nv16w_r7.txt
   if (M <= 16 && KT <= 32) {
     for (int tn : {32, 48, 56})
-      if ((N + tn - 1) / tn <= cus) return tn == 56 ? ((M <= 8 && KT <= 16) ? 856 : 1656) : 1600 + tn;
+      if ((N + tn - 1) / tn <= cus) return tn == 32 ? NV_D32 : tn == 48 ? NV_D48 : (M <= 8 && KT <= 16) ? NV_D56A8 : NV_D56;
     // wider still (the fused up / gate projections, N = 24576 / 28672): 48 columns per workgroup in two or three rounds, K <= 4096 (24576 x 4096: 14.9-15.4 -> 13.2 us,
     // 28672 x 4096, M = 16: 20.6 -> 17.6; 16384: a tie, left alone)
-    if (KT <= 16 && N >= 20480 && (N + 47) / 48 <= 3 * (int64_t)cus) return 1648;
+    if (KT <= 16 && N >= 20480 && (N + 47) / 48 <= 3 * (int64_t)cus) return NV_D48;
   }
-  // 3216 = the same with two m-tiles per workgroup (a B dword dequantised once for both): where 32x16 tiles fit one per CU (N = 4096, M = 17 ... 32: K = 4096 5.35 -> 4.75 us,
+  // NV_D32x16 = the same with two m-tiles per workgroup (a B dword dequantised once for both): where 32x16 tiles fit one per CU (N = 4096, M = 17 ... 32: K = 4096 5.35 -> 4.75 us,
   // K = 14336 14.1 -> 11.7, K = 28672 30-36 -> 20)
-  if (((M + 31) / 32) * ((N + 15) / 16) <= cus && KT <= 128) return 3216;
+  if (((M + 31) / 32) * ((N + 15) / 16) <= cus && KT <= 128) return NV_D32x16;
   // one round of 32x32 tiles: here; [r6, third session] several rounds (and the 64x32 form) are priced in nvf4_plan against the fitted models of the other kernels
-  if (T32 <= cus && (KT <= 16 || (KT <= 64 && 4 * T32 >= cus))) return 32;
-  return 0;
+  if (T32 <= cus && (KT <= 16 || (KT <= 64 && 4 * T32 >= cus))) return NV_OS32;
+  return NV_NONE;
 }
-hipError_t launch_nvf4_os(NvGemmParams p, hipStream_t s, int tn);   // capi.hip (the NVFP4 unit)
+struct NvLaunch;
+hipError_t launch_nvf4_os(const NvLaunch& l, NvGemmParams p, hipStream_t s);   // capi.hip (the NVFP4 unit; gemm_nvf4_os.hip.h): the NVF_OS / NVF_DECODE / NVF_OS_ROWS forms
 hipError_t launch_nvf4_grouped(NvGroupedParams q, hipStream_t s, int form);   // capi.hip (the NVFP4 unit; gemm_nvf4_os.hip.h): form 598 ... 601
 inline NvPlan nvf4_plan(int64_t M, int64_t N, int64_t K, int cus, bool may_split) {
-  if (const int tn = nv_os_plan(M, N, K, cus)) return {tn == 856 ? -9 : tn == 1656 ? -8 : tn == 1648 ? -7 : tn == 1632 ? -6 : tn == 3216 ? -5 : tn == 1616 ? -4 : tn == 16 ? -3 : -2, 1, 0};
+  if (const int f = nv_os_plan(M, N, K, cus); f != NV_NONE) return {f, 1, 0};
   if (M <= 32) {   // one m-tile: the wave-owned 32x32 kernel in up to four rounds of tiles (1.75 + 4.05 us per round and 16 stages, K <= 8192) or the split-K kernel (2.53 + 4.66)
     const int64_t KT0 = (K / 2 + 127) / 128, R0 = (((N + 31) / 32) + cus - 1) / cus;
     return {(KT0 <= 32 && R0 <= 4) ? -2 : -1, 1, 0};
@@ -988,183 +1022,146 @@ inline NvPlan nvf4_plan(int64_t M, int64_t N, int64_t K, int cus, bool may_split
   return best;
 }
 
-#if QAMD_TU == 0 || QAMD_TU == 4
-// Returns hipErrorInvalidValue for a variant this build does not know (the product library knows only 0 = auto).
-// cus: compute units of the device (capi.hip chip_cus): every occupancy threshold below derives from it
-// *splits_out (when given): the number of K ranges the launch wrote to p.ws -- the caller then runs splitk_reduce_kernel; 1 = D is final
+// ---- the launch plan: a pure function of the lab variant, the shape, the CU count and the caller's scratch (no pointers, no GPU touched), read by the launcher, by
+// qutlass_amd_nvf4_splitk_workspace_bytes and by the debug entries (capi.hip)
+struct NvLaunch {
+  int form = NV_NONE;         // NvForm; NV_NONE: a variant this build does not know (the product library knows only 0 = auto)
+  int splits = 1, kt_per = 0; // K ranges of the launch (> 1: fp32 partials in the caller's scratch, then splitk_reduce_kernel) of kt_per stages each (even, none empty)
+  int64_t grid = 0;           // workgroups
+  bool pk = false;            // NV_T256 on the persistent kernel (gemm_nvf4_pk.hip.h), whole tiles in balanced rounds
+  bool fenced = false, trace = false;   // lab: fixed MFMA / dequantisation order of the 128x128 tile; stage trace of the persistent kernel
+  int abl = 0;                // lab: the variant of NV_LAB_ABL
+  int64_t ws = 0;             // bytes of the caller's scratch the launch uses: the K ranges' partials (0: none)
+};
+// variant: the lab's "nvf4_variant" -- 0 auto (nvf4_plan); 1 the round-1 choice (256x256 on 8 waves for a large output); 2 the v2 kernel; 4 tiles by occupancy alone;
+//   the `variant` column of NV_FORMS; 41 = NV_T256 on the per-tile kernel only, 43 = 42, 44 / 45 = 42 + stage trace; 100 + 10 cfg + S = tile cfg (1 128x128, 2 128x64, 3 64x64) with S K ranges (tools/calib_nv_small.py);
+//   150 + S = 128x128 tiles, S K ranges (1 = none), fixed MFMA / dequantisation order; 160 + S = 128x128 tiles on two waves of 128x64, S K ranges; >= 10: NV_LAB_ABL
+// cus: compute units of the device (capi.hip chip_cus): every occupancy threshold derives from it
+// avail: bytes of the caller's scratch (0: none).  A split is planned only into scratch that holds it; a smaller or absent workspace runs the single pass.
 // pk_grid (lab, variant 42 only; 0 = nvpk_plan's): workgroups of the forced persistent kernel, so that a small shape gives each of them several tiles
-inline hipError_t launch_nvf4_gemm(NvGemmParams p, hipStream_t s, int variant = 0, int cus = 256, int* splits_out = nullptr, int pk_grid = 0) {
-  (void)pk_grid;
-  const int64_t want = cus * 3 / 4;
-  if (splits_out) *splits_out = 1;
-  int force_split = 0;
+inline NvLaunch nvf4_launch_plan(int variant, int64_t M, int64_t N, int64_t K, int cus, int64_t avail, int pk_grid = 0) {
+  NvLaunch r;
+  bool may_pk = true, pk_grid_ok = false;   // NV_T256: may it run the persistent kernel; lab: on pk_grid workgroups (variant 42)
 #if QAMD_BENCH
-  bool fenced = false;
-  if (variant >= 160 && variant < 170) {   // lab: 160 + S = 128x128 tiles on TWO waves of 128x64 (6 fragment dequantisations per 8 MFMAs), S K ranges
+  int force_split = 0;
+  if (variant >= 160 && variant < 170) {
     force_split = variant - 160;
     variant = 8;
-    if (force_split < 1) return hipErrorInvalidValue;
+    if (force_split < 1) return r;
   }
-  if (variant >= 150 && variant < 160) { fenced = true; variant -= 40; }   // lab: 150 + S = 128x128 tiles, S K ranges (1 = none), fixed MFMA / dequantisation order
-  if (variant >= 100 && variant < 140) {   // lab: 100 + 10 cfg + S = tile cfg (1 128x128, 2 128x64, 3 64x64) with S K ranges (tools/calib_nv_small.py)
+  if (variant >= 150 && variant < 160) { r.fenced = true; variant -= 40; }
+  if (variant >= 100 && variant < 140) {
     force_split = variant % 10;
-    variant = 4 + (variant - 100) / 10;    // 5 / 6 / 7 force the tile below
-    if ((force_split < 2 && !fenced) || force_split < 1 || variant < 5 || variant > 7) return hipErrorInvalidValue;
+    variant = 4 + (variant - 100) / 10;    // 5 / 6 / 7: the tile's row of NV_FORMS
+    if ((force_split < 2 && !r.fenced) || force_split < 1 || variant < 5) return r;
   }
-#endif
-#if !QAMD_BENCH
-  if (variant != 0) return hipErrorInvalidValue;
-#endif
+  if (variant >= 41 && variant <= 45) {
+    may_pk = variant != 41;
+    pk_grid_ok = variant == 42;
+    r.trace = variant >= 44;
+    variant = 42;
+  }
   // 128x128 tiles when a dimension is small OR when 256x256 tiles would leave most CUs without work
-  const bool small = p.M <= 128 || p.N <= 128 || (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256) < want;
-  // small batch: split-K kernel for M <= 64, and up to M = 128 while even 64x64 tiles would leave CUs idle (measured,
-  // M = 128, K = 4096: N = 4096 11.8 us vs 17.3 us for 64x64 tiles; N = 14336 35.6 us vs 25.2 us for 128x64 tiles)
-  const NvPlan plan = nvf4_plan(p.M, p.N, p.K, cus, p.ws != nullptr);
-#if QAMD_BENCH
-  if (variant == 46 || variant == 47) return launch_nvf4_os(p, s, variant == 47 ? 16 : 32);   // lab: force the wave-owned small-batch kernel (any K: rings beyond 4096)
-  if (variant == 48) return launch_nvf4_os(p, s, 1616);                                       // lab: ... its 16x16 decode form (any M: rows in tiles of 16)
-  if (variant == 49) return launch_nvf4_os(p, s, 3216);                                       // lab: ... with two m-tiles per workgroup (32x16)
-  if (variant == 55) return launch_nvf4_os(p, s, 9632);                                       // lab: ... with three m-tiles per workgroup (96x32 tiles)
-  if (variant == 54) return launch_nvf4_os(p, s, 6432);                                       // lab: the 32x32-MFMA kernel with two m-tiles per workgroup (64x32 tiles)
-  if (variant >= 50 && variant <= 53) return launch_nvf4_os(p, s, variant == 50 ? 1632 : variant == 51 ? 1648 : variant == 52 ? 1656 : 856);   // lab: ... with 32 / 48 / 56 columns per workgroup (53: 56 columns, A rows 0 ... 7 only)
+  const bool small = M <= 128 || N <= 128 || ((M + 255) / 256) * ((N + 255) / 256) < cus * 3 / 4;
+  if (variant < 0) return r;
+#else
+  if (variant != 0) return r;
 #endif
-  if (variant == 0 && plan.cfg <= -2) return launch_nvf4_os(p, s, plan.cfg == -11 ? 9632 : plan.cfg == -10 ? 6432 : plan.cfg == -9 ? 856 : plan.cfg == -8 ? 1656 : plan.cfg == -7 ? 1648 : plan.cfg == -6 ? 1632 : plan.cfg == -5 ? 3216 : plan.cfg == -4 ? 1616 : plan.cfg == -3 ? 16 : 32);
-  if (variant == 3 || (variant == 0 && plan.cfg < 0)) {
-    hipLaunchKernelGGL((gemm_nvf4_skinny_kernel<8>), dim3((p.N + 31) / 32, (p.M + 31) / 32), dim3(512), 0, s, p);
-    return hipSuccess;
+  if (variant <= 1) {   // the auto rule; K ranges only into scratch that holds them
+    NvPlan pl = nvf4_plan(M, N, K, cus, avail > 0);
+    if (avail > 0 && !(pl.splits > 1 && avail >= (int64_t)pl.splits * M * N * 4)) pl = nvf4_plan(M, N, K, cus, false);
+    r.form = pl.cfg;
+    if (variant == 0) { r.splits = pl.splits; r.kt_per = pl.kt_per; }
   }
 #if QAMD_BENCH
-  if (variant == 1 && !small) {   // lab: the round-1 choice for 256x256 tiles, 8 waves of 128x64 (each A chunk dequantised by 4 waves, each B chunk by 2)
-    using C = NvCfg<256, 256, 2, 4>;
-    p.tiles_m = (p.M + C::BM - 1) / C::BM;
-    p.tiles_n = (p.N + C::BN - 1) / C::BN;
-    p.raster_magic = raster_magic(p.tiles_n);
-    hipLaunchKernelGGL((gemm_nvf4_kernel<C>), dim3(p.tiles_m * p.tiles_n), dim3(C::THREADS), 0, s, p);
-    return hipSuccess;
+  if (variant == 1) {
+    r.form = !small ? NV_LAB_T256_W8 : r.form >= 0 ? r.form : NV_T128;
+  } else if (variant == 2) {
+    r.form = small ? NV_LAB_LDS128 : NV_LAB_LDS256;
+  } else if (variant == 4) {
+    r.form = small ? NV_T128 : NV_T256;
+    may_pk = false;
+  } else if (variant != 0) {
+    for (const NvFormRow& f : NV_FORMS)
+      if (f.variant == variant) r.form = f.form;
+    if (r.form == NV_NONE && variant >= 10) { r.form = NV_LAB_ABL; r.abl = variant; }
+    if (force_split > 1 && N % 4 == 0) {   // K ranges of an even number of 256-element stages, none empty
+      const int KT = (int)((K / 2 + 127) / 128), kt = 2 * ((KT + 2 * force_split - 1) / (2 * force_split)), S = (KT + kt - 1) / kt;
+      if (S > 1 && avail >= (int64_t)S * M * N * 4) { r.splits = S; r.kt_per = kt; }
+    }
   }
 #endif
+  if (r.splits > 1) r.ws = (int64_t)r.splits * M * N * 4;
+  const NvFormRow& f = *nv_form(r.form);
+  r.grid = ((M + f.tm - 1) / f.tm) * ((N + f.tn - 1) / f.tn) * r.splits;
+  // [r4] 256x256 tiles: the persistent kernel in balanced whole-tile rounds, no scratch.  (Its stream-K form over parked tiles -- nvpk_plan's may_sk, the lab's variants
+  // 43 / 45 -- was measured equal to balanced rounds for this power-bound kernel; the launcher has never handed it scratch, and no plan asks for it.)
+  if (r.form == NV_T256 && may_pk && nvpk_shape_ok(M, N, K)) {
+    r.pk = true;
+    r.grid = nvpk_plan(M, N, K, cus, false).grid;
+    if (pk_grid_ok && pk_grid > 0) r.grid = std::min<int64_t>(pk_grid, ((M + 255) / 256) * ((N + 255) / 256));   // (whole tiles w, w + grid, ...: the walk takes any grid)
+  }
+  return r;
+}
+
+#if QAMD_TU == 0 || QAMD_TU == 4
+// one launch of gemm_nvf4_kernel on C's tiles (l.splits K ranges when SPLIT)
+template <class C, bool SPLIT = false, bool FENCED = false>
+hipError_t launch_nvf4_tiles(const NvLaunch& l, NvGemmParams p, hipStream_t s) {
+  p.tiles_m = (p.M + C::BM - 1) / C::BM;
+  p.tiles_n = (p.N + C::BN - 1) / C::BN;
+  p.raster_magic = raster_magic(p.tiles_n);
+  hipLaunchKernelGGL((gemm_nvf4_kernel<C, SPLIT, FENCED>), dim3((unsigned)l.grid), dim3(C::THREADS), 0, s, p);
+  return hipSuccess;
+}
+template <class C>
+hipError_t launch_nvf4_tiles_maybe_split(const NvLaunch& l, const NvGemmParams& p, hipStream_t s) {
+  return l.splits > 1 ? launch_nvf4_tiles<C, true>(l, p, s) : launch_nvf4_tiles<C>(l, p, s);
+}
 #if QAMD_BENCH
-  // lab: 42 = the persistent 256x256 kernel, whole tiles in balanced rounds; 43 = with stream-K over the last round (needs scratch); 44 / 45 = 42 / 43 + stage trace
-  const bool pk_forced = variant >= 42 && variant <= 45;
-  const bool pk_sk = variant == 43 || variant == 45, pk_trace = variant == 44 || variant == 45;
-  if (pk_forced) variant = 41;
-#else
-  constexpr bool pk_forced = false, pk_trace = false;
+template <class C>
+hipError_t launch_nvf4_lds(const NvLaunch& l, NvGemmParams p, hipStream_t s) {
+  p.tiles_m = (p.M + C::BM - 1) / C::BM;
+  p.tiles_n = (p.N + C::BN - 1) / C::BN;
+  p.raster_magic = raster_magic(p.tiles_n);
+  hipLaunchKernelGGL((gemm_nvf4_lds_kernel<C>), dim3((unsigned)l.grid), dim3(C::THREADS), 0, s, p);
+  return hipSuccess;
+}
 #endif
-  if (variant <= 1 || variant == 4 || (variant >= 5 && variant <= 9) || variant == 40 || variant == 41) {
-    // tile choice by occupancy (as for the MX kernels): the largest tile that gives >= 192 workgroups
-    auto tiles = [&](int bm, int bn) { return (int64_t)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-    int cfg = small ? 1 : 0;                                  // 0: 256x256, 1: 128x128, 2: 128x64, 3: 64x64
-    if (variant == 0 || variant == 1) {
-      // the pricing of nvf4_plan above ([r2] wave quantisation of the 256x256 grid, [r3] the 256x128 four-wave tile and the cost model)
-      if (plan.cfg >= 0) cfg = plan.cfg;
-    }
-    if (variant == 5) cfg = 1;
-    if (variant == 6) cfg = 2;
-    if (variant == 7) cfg = 3;
-#if QAMD_BENCH
-    if (variant == 40) cfg = 4;   // lab: force the 256x128 tile on four waves of 128x64
-    if (variant == 41) cfg = 0;   //      force the 256x256 tile (tools/calib_tiles.py)
-    if (variant == 8) cfg = 8;    // lab: 128x128 tile on 2 waves of 128x64 (A dequantised by 2 waves, B by 1)
-    if (variant == 9) cfg = 9;    //      128x128 tile on 2 waves of 64x128
-#endif
-    // [r3] split-K (caller scratch in p.ws, capi.hip checks its size against nvf4_plan): K ranges of an even number of 256-element stages, none empty
-    int splits = 1;
-    if (p.ws && p.N % 4 == 0) {
-      splits = force_split ? force_split : (variant == 0 ? plan.splits : 1);
-      const int KT = (p.K / 2 + 127) / 128;
-      p.kt_per = 2 * ((KT + 2 * splits - 1) / (2 * splits));
-      splits = (KT + p.kt_per - 1) / p.kt_per;
-    }
-    p.splits = splits;
-    if (splits <= 1) p.ws = nullptr;
-    if (splits_out) *splits_out = splits;
-    // [r4] 256x256 tiles: the persistent kernel (lab: variant 41 keeps the per-tile kernel for A/B runs)
-    if (cfg == 0 && nvpk_shape_ok(p.M, p.N, p.K) && (variant <= 1 || pk_forced)) {
-      void* scratch = p.ws;   // (splits == 1 for this configuration: the caller's scratch is free for parked tiles; capi.hip checked its size)
-#if QAMD_BENCH
-      const bool may_sk = scratch != nullptr && pk_sk;   // stream-K: lab only (variants 43 / 45); measured equal to balanced rounds for this power-bound kernel
-#else
-      const bool may_sk = false;
-#endif
-      NvPkPlan pl = nvpk_plan(p.M, p.N, p.K, cus, may_sk);
-#if QAMD_BENCH
-      if (pk_forced && !pk_sk && !pk_trace && pk_grid > 0)   // (whole tiles w, w + grid, ...: the walk takes any grid)
-        pl.grid = (int)std::min<int64_t>(pk_grid, (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256));
-#endif
-      p.sk_tiles = pl.sk_tiles;
-      p.sk_ws = (float*)scratch;
-      p.sk_flags = (unsigned long long*)((char*)scratch + (int64_t)pl.grid * NVPK_PART_BYTES);
-      p.ws = nullptr;
-      return launch_nvf4_pk(p, s, pl.grid, pk_trace);
-    }
-    if (cfg == 0) p.ws = nullptr;
-#define QAMD_NV_LAUNCH_SPLIT(BM_, BN_, WM_, WN_)                                                               \
-    if (splits > 1) {                                                                                          \
-      using C = NvCfg<BM_, BN_, WM_, WN_>;                                                                     \
-      p.tiles_m = (p.M + C::BM - 1) / C::BM;                                                                   \
-      p.tiles_n = (p.N + C::BN - 1) / C::BN;                                                                   \
-      p.raster_magic = raster_magic(p.tiles_n);          \
-      hipLaunchKernelGGL((gemm_nvf4_kernel<C, true>), dim3(p.tiles_m * p.tiles_n * splits), dim3(C::THREADS), 0, s, p); \
-      return hipSuccess;                                                                                       \
-    }
-#define QAMD_NV_LAUNCH(BM_, BN_, WM_, WN_)                                                                     \
-    {                                                                                                          \
-      using C = NvCfg<BM_, BN_, WM_, WN_>;                                                                     \
-      p.tiles_m = (p.M + C::BM - 1) / C::BM;                                                                   \
-      p.tiles_n = (p.N + C::BN - 1) / C::BN;                                                                   \
-      p.raster_magic = raster_magic(p.tiles_n);          \
-      hipLaunchKernelGGL((gemm_nvf4_kernel<C>), dim3(p.tiles_m * p.tiles_n), dim3(C::THREADS), 0, s, p);       \
-      return hipSuccess;                                                                                       \
-    }
+
+// Launches what nvf4_launch_plan planned.  p.ws: the caller's scratch when l.ws > 0 (the K ranges' partials).
+// Returns hipErrorInvalidValue for NV_NONE.
+inline hipError_t launch_nvf4_gemm(const NvLaunch& l, NvGemmParams p, hipStream_t s) {
+  p.splits = l.splits;
+  p.kt_per = l.kt_per;
+  if (l.splits <= 1) p.ws = nullptr;
+  switch (l.form) {
+    case NV_SKINNY:
+      hipLaunchKernelGGL((gemm_nvf4_skinny_kernel<8>), dim3((p.N + 31) / 32, (p.M + 31) / 32), dim3(512), 0, s, p);
+      return hipSuccess;
     // [r2] 256x256 tiles: 4 waves of 128x128 -- every operand chunk is dequantised by 2 waves (8 waves of 128x64: A by 4, B by 2),
     // 64 converts / multiplies per 16 MFMAs instead of 48 per 8: +1.7 % (4096^3) .. +3.3 % (8192^3) in the steady state
     // (profiles/native_r2_nvsteady.log)
-    if (cfg == 0) QAMD_NV_LAUNCH(256, 256, 2, 2)
+    case NV_T256: return l.pk ? launch_nvf4_pk(p, s, (int)l.grid, l.trace) : launch_nvf4_tiles<NvCfg<256, 256, 2, 2>>(l, p, s);
     // [r3] 256x128 on four waves of 128x64: 6 fragment dequantisations per 8 MFMAs (0.75 per MFMA) against 4 per 4 for the 64x64 wave tiles of the 128x128 tile
-    if (cfg == 4) QAMD_NV_LAUNCH(256, 128, 2, 2)
+    case NV_T256x128: return launch_nvf4_tiles<NvCfg<256, 128, 2, 2>>(l, p, s);
+    case NV_T128:
 #if QAMD_BENCH
-    if (cfg == 8) { QAMD_NV_LAUNCH_SPLIT(128, 128, 1, 2) QAMD_NV_LAUNCH(128, 128, 1, 2) }
-    if (cfg == 9) QAMD_NV_LAUNCH(128, 128, 2, 1)
+      if (l.fenced) return l.splits > 1 ? launch_nvf4_tiles<NvCfg<128, 128, 2, 2>, true, true>(l, p, s) : launch_nvf4_tiles<NvCfg<128, 128, 2, 2>, false, true>(l, p, s);
 #endif
+      return launch_nvf4_tiles_maybe_split<NvCfg<128, 128, 2, 2>>(l, p, s);
+    case NV_T128x64: return launch_nvf4_tiles_maybe_split<NvCfg<128, 64, 2, 2>>(l, p, s);
+    case NV_T64: return launch_nvf4_tiles_maybe_split<NvCfg<64, 64, 2, 2>>(l, p, s);
 #if QAMD_BENCH
-    if (cfg == 1 && fenced) {
-      using C = NvCfg<128, 128, 2, 2>;
-      p.tiles_m = (p.M + C::BM - 1) / C::BM;
-      p.tiles_n = (p.N + C::BN - 1) / C::BN;
-      p.raster_magic = raster_magic(p.tiles_n);
-      if (splits > 1) hipLaunchKernelGGL((gemm_nvf4_kernel<C, true, true>), dim3(p.tiles_m * p.tiles_n * splits), dim3(C::THREADS), 0, s, p);
-      else hipLaunchKernelGGL((gemm_nvf4_kernel<C, false, true>), dim3(p.tiles_m * p.tiles_n), dim3(C::THREADS), 0, s, p);
-      return hipSuccess;
-    }
+    case NV_LAB_T256_W8: return launch_nvf4_tiles<NvCfg<256, 256, 2, 4>>(l, p, s);   // each A chunk dequantised by 4 waves, each B chunk by 2
+    case NV_LAB_T128_1x2: return launch_nvf4_tiles_maybe_split<NvCfg<128, 128, 1, 2>>(l, p, s);   // A dequantised by 2 waves, B by 1
+    case NV_LAB_T128_2x1: return launch_nvf4_tiles<NvCfg<128, 128, 2, 1>>(l, p, s);
+    case NV_LAB_LDS128: return launch_nvf4_lds<NvLdsCfg<128, 128, 2, 2>>(l, p, s);
+    case NV_LAB_LDS256: return launch_nvf4_lds<NvLdsCfg<256, 256, 2, 4>>(l, p, s);
+    case NV_LAB_ABL: return launch_nvf4_ablation(p, s, l.abl) ? hipSuccess : hipErrorInvalidValue;
 #endif
-    if (cfg == 1) { QAMD_NV_LAUNCH_SPLIT(128, 128, 2, 2) QAMD_NV_LAUNCH(128, 128, 2, 2) }
-    if (cfg == 2) { QAMD_NV_LAUNCH_SPLIT(128, 64, 2, 2) QAMD_NV_LAUNCH(128, 64, 2, 2) }
-    QAMD_NV_LAUNCH_SPLIT(64, 64, 2, 2)
-    QAMD_NV_LAUNCH(64, 64, 2, 2)
-#undef QAMD_NV_LAUNCH
-#undef QAMD_NV_LAUNCH_SPLIT
+    default: return l.form >= NV_OS96 && l.form <= NV_OS32 ? launch_nvf4_os(l, p, s) : hipErrorInvalidValue;
   }
-#if QAMD_BENCH
-  if (variant >= 10 && launch_nvf4_ablation(p, s, variant)) return hipSuccess;
-  if (variant != 2) return hipErrorInvalidValue;
-  if (small) {
-    using C = NvLdsCfg<128, 128, 2, 2>;
-    p.tiles_m = (p.M + C::BM - 1) / C::BM;
-    p.tiles_n = (p.N + C::BN - 1) / C::BN;
-    p.raster_magic = raster_magic(p.tiles_n);
-    hipLaunchKernelGGL((gemm_nvf4_lds_kernel<C>), dim3(p.tiles_m * p.tiles_n), dim3(C::THREADS), 0, s, p);
-  } else {
-    using C = NvLdsCfg<256, 256, 2, 4>;
-    p.tiles_m = (p.M + C::BM - 1) / C::BM;
-    p.tiles_n = (p.N + C::BN - 1) / C::BN;
-    p.raster_magic = raster_magic(p.tiles_n);
-    hipLaunchKernelGGL((gemm_nvf4_lds_kernel<C>), dim3(p.tiles_m * p.tiles_n), dim3(C::THREADS), 0, s, p);
-  }
-  return hipSuccess;
-#else
-  return hipErrorInvalidValue;
-#endif
 }
 #endif   // QAMD_TU == 0 || QAMD_TU == 4
 

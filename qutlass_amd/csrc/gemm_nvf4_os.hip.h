@@ -429,77 +429,52 @@ __global__ __launch_bounds__(512) void gemm_nvf4_os16_kernel(const NvGemmParams 
 
 #if QAMD_TU == 0 || QAMD_TU == 4
 // (not inline: the NVFP4 unit of capi.hip emits it; declared in gemm_nvf4.hip.h for launch_nvf4_gemm)
-// [r6] the wave-owned small-batch kernel (gemm_nvf4_os.hip.h): K <= 2048 one stage per wave, K <= 4096 two, longer K two refilled slots per wave
-hipError_t launch_nvf4_os(NvGemmParams p, hipStream_t s, int tn) {
-  if (tn == 1616 || tn == 3216) {   // [r6] the decode form: 16x16 (3216: 32x16) tiles on the 16x16x32 MFMA -- one shot while the tile's K extent fits the LDS (K <= 8192 / 4096), refilled slots beyond
-    const bool two = tn == 3216;
-    p.tiles_m = two ? (p.M + 31) / 32 : (p.M + 15) / 16;
-    p.tiles_n = (p.N + 15) / 16;
-    const int KT = (p.K / 2 + 127) / 128;
-    const dim3 grid(p.tiles_m * p.tiles_n), block(512);
-    if (two) {
-      if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<1, 2>>), grid, block, 0, s, p);
-      else if (KT <= 16) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<2, 2>>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<2, 2>, true>), grid, block, 0, s, p);
-      return hipSuccess;
-    }
-    if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<1>>), grid, block, 0, s, p);
-    else if (KT <= 16) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<2>>), grid, block, 0, s, p);
-    else if (KT <= 24) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<3>>), grid, block, 0, s, p);
-    else if (KT <= 32) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<4>>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<4>, true>), grid, block, 0, s, p);
-    return hipSuccess;
-  }
-  if (tn == 1632 || tn == 1648 || tn == 1656 || tn == 856) {   // [r6] 16 rows x 32 / 48 / 56 columns per workgroup (856: only A rows 0 ... 7 fetched, M <= 8); K <= 4096 one shot, two refilled slots per wave beyond
-    const int cols = tn == 1632 ? 32 : tn == 1648 ? 48 : 56;
-    p.tiles_m = (p.M + 15) / 16;
-    p.tiles_n = (p.N + cols - 1) / cols;
-    const int KT = (p.K / 2 + 127) / 128;
-    const dim3 grid(p.tiles_m * p.tiles_n), block(512);
-#define QAMD_NVW(TN_, NPA_)                                                                                                         \
-    do {                                                                                                                            \
-      if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, TN_, NPA_>>), grid, block, 0, s, p);                    \
-      else if (KT <= 16) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, TN_, NPA_>>), grid, block, 0, s, p);              \
-      else hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, TN_, NPA_>, true>), grid, block, 0, s, p);                      \
-    } while (0)
-    if (tn == 1632) QAMD_NVW(32, 2);
-    else if (tn == 1648) QAMD_NVW(48, 2);
-    else if (tn == 856) QAMD_NVW(56, 1);
-    else {   // 56 columns with all 16 A rows: 16 stages do not fit the LDS (164 KiB) -- one shot up to 8 stages, refilled slots beyond
-      if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, 56, 2>>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, 56, 2>, true>), grid, block, 0, s, p);
-    }
-#undef QAMD_NVW
-    return hipSuccess;
-  }
-  if (tn == 6432 || tn == 9632) {   // [r6] two / three m-tiles per workgroup (64x32 / 96x32 tiles): one slot per wave -- one shot up to K = 2048, refilled beyond
-    const int tm = tn == 9632 ? 96 : 64;
-    p.tiles_m = (p.M + tm - 1) / tm;
-    p.tiles_n = (p.N + 31) / 32;
-    const int KT = (p.K / 2 + 127) / 128;
-    const dim3 grid(p.tiles_m * p.tiles_n), block(512);
-    if (tm == 96) {
-      if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32, 3>, false>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32, 3>, true>), grid, block, 0, s, p);
-      return hipSuccess;
-    }
-    if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32, 2>, false>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<1, 32, 2>, true>), grid, block, 0, s, p);
-    return hipSuccess;
-  }
-  p.tiles_m = (p.M + 31) / 32;
-  p.tiles_n = (p.N + tn - 1) / tn;
+// [r6] the wave-owned small-batch forms (NV_FORMS: families NVF_OS, NVF_DECODE, NVF_OS_ROWS).  The form gives the tile; the K stages pick the instantiation: one shot while
+// the tile's K extent fits the LDS (one, two ... stages per wave), refilled slots per wave beyond.
+hipError_t launch_nvf4_os(const NvLaunch& l, NvGemmParams p, hipStream_t s) {
+  const NvFormRow& f = *nv_form(l.form);
+  p.tiles_m = (p.M + f.tm - 1) / f.tm;
+  p.tiles_n = (p.N + f.tn - 1) / f.tn;
   const int KT = (p.K / 2 + 127) / 128;
-  const dim3 grid(p.tiles_m * p.tiles_n), block(512);
-#define QAMD_NVOS(SPW_, RING_)                                                                                                      \
-  do {                                                                                                                              \
-    if (tn == 16) hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<SPW_, 16>, RING_>), grid, block, 0, s, p);                           \
-    else hipLaunchKernelGGL((gemm_nvf4_os_kernel<NvOsCfg<SPW_, 32>, RING_>), grid, block, 0, s, p);                                     \
-  } while (0)
-  if (KT <= 8) QAMD_NVOS(1, false);
-  else if (KT <= 16) QAMD_NVOS(2, false);
-  else QAMD_NVOS(2, true);
-#undef QAMD_NVOS
+  void (*k)(NvGemmParams) = nullptr;
+  switch (l.form) {
+    case NV_OS32:   // K <= 2048 one stage per wave, K <= 4096 two, longer K two refilled slots per wave
+      k = KT <= 8 ? gemm_nvf4_os_kernel<NvOsCfg<1, 32>, false> : KT <= 16 ? gemm_nvf4_os_kernel<NvOsCfg<2, 32>, false> : gemm_nvf4_os_kernel<NvOsCfg<2, 32>, true>;
+      break;
+    case NV_OS16:
+      k = KT <= 8 ? gemm_nvf4_os_kernel<NvOsCfg<1, 16>, false> : KT <= 16 ? gemm_nvf4_os_kernel<NvOsCfg<2, 16>, false> : gemm_nvf4_os_kernel<NvOsCfg<2, 16>, true>;
+      break;
+    case NV_OS64:   // two / three m-tiles per workgroup: one slot per wave -- one shot up to K = 2048, refilled beyond
+      k = KT <= 8 ? gemm_nvf4_os_kernel<NvOsCfg<1, 32, 2>, false> : gemm_nvf4_os_kernel<NvOsCfg<1, 32, 2>, true>;
+      break;
+    case NV_OS96:
+      k = KT <= 8 ? gemm_nvf4_os_kernel<NvOsCfg<1, 32, 3>, false> : gemm_nvf4_os_kernel<NvOsCfg<1, 32, 3>, true>;
+      break;
+    case NV_D16:   // the decode form on the 16x16x32 MFMA: one shot up to K = 8192 (32x16 tiles: 4096)
+      k = KT <= 8    ? gemm_nvf4_os16_kernel<NvOs16Cfg<1>>
+          : KT <= 16 ? gemm_nvf4_os16_kernel<NvOs16Cfg<2>>
+          : KT <= 24 ? gemm_nvf4_os16_kernel<NvOs16Cfg<3>>
+          : KT <= 32 ? gemm_nvf4_os16_kernel<NvOs16Cfg<4>>
+                     : gemm_nvf4_os16_kernel<NvOs16Cfg<4>, true>;
+      break;
+    case NV_D32x16:
+      k = KT <= 8 ? gemm_nvf4_os16_kernel<NvOs16Cfg<1, 2>> : KT <= 16 ? gemm_nvf4_os16_kernel<NvOs16Cfg<2, 2>> : gemm_nvf4_os16_kernel<NvOs16Cfg<2, 2>, true>;
+      break;
+    case NV_D32:   // 16 rows x 32 / 48 / 56 columns per workgroup: K <= 4096 one shot, two refilled slots per wave beyond
+      k = KT <= 8 ? gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, 32, 2>> : KT <= 16 ? gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, 32, 2>> : gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, 32, 2>, true>;
+      break;
+    case NV_D48:
+      k = KT <= 8 ? gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, 48, 2>> : KT <= 16 ? gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, 48, 2>> : gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, 48, 2>, true>;
+      break;
+    case NV_D56A8:   // only A rows 0 ... 7 fetched (M <= 8)
+      k = KT <= 8 ? gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, 56, 1>> : KT <= 16 ? gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, 56, 1>> : gemm_nvf4_os16_kernel<NvOs16Cfg<2, 1, 56, 1>, true>;
+      break;
+    case NV_D56:   // all 16 A rows: 16 stages do not fit the LDS (164 KiB) -- one shot up to 8 stages, refilled slots beyond
+      k = KT <= 8 ? gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, 56, 2>> : gemm_nvf4_os16_kernel<NvOs16Cfg<1, 1, 56, 2>, true>;
+      break;
+    default: return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(k, dim3((unsigned)l.grid), dim3(512), 0, s, p);
   return hipSuccess;
 }
 

@@ -3,10 +3,12 @@
 A CASE is one kernel form of one NVFP4 GEMM op at one shape: (op, variant, lab options, m, n, k).
   op       "nv" matmul_nvf4_bf16_tn (_ws entry, to_blocked scales, the queried workspace) | "gnv" grouped_matmul_nvf4_bf16_tn (row-major scales, m = token rows over
            GROUPED_E experts in _mx_cases.group_counts' pattern, offs[-1] == m)
-  variant  "nv": the lab library's "nvf4_variant" (gemm_nvf4.hip.h launch_nvf4_gemm's numbering); "gnv": its "gemm_variant" 598 ... 601
+  variant  "nv": the lab library's "nvf4_variant" (gemm_nvf4.hip.h nvf4_launch_plan decodes it; the `variant` column of NV_FORMS); "gnv": its "gemm_variant" 598 ... 601
   options  deepp_grid: workgroups of the forced persistent kernel (variant 42), so that each walks several tiles
 
-What the product's plan (nvf4_plan: cfg, K ranges) can return, and the lab variant that runs the same kernel -- plan_variant() below:
+The forms are ONE list, gemm_nvf4.hip.h's enum NvForm with one NV_FORMS row each (tile, kernel family, forcing lab variant): its values are the cfg that
+qutlass_amd_debug_nvf4_plan reports and the form that qutlass_amd_debug_nvf4_launch_plan writes.  What the product's plan (nvf4_plan: cfg, K ranges) can return, and the
+lab variant that runs the same kernel -- plan_variant() below:
   cfg -1 -> 3 skinny split-K kernel | -2 -> 46, -4 ... -11 -> 48 ... 55 wave-owned forms (-3 = 47, 16 columns, stays lab-only) | 0 -> 42 persistent 256x256
   (K % 256 == 0, K >= 512) or 41 per-tile 256x256 | 4 -> 40 256x128 | 1, 2, 3 -> 5, 6, 7 128x128, 128x64, 64x64 in one pass, or 100 + 10 cfg + S: S K ranges into the
   caller's scratch + splitk_reduce_kernel<S> (the split kernel is one instantiation per tile, the reduce kernel one per S: every tile is run split and every S the
@@ -56,7 +58,7 @@ class Case(NamedTuple):
 
     @property
     def splits(self):
-        """K ranges a forced split launches (launch_nvf4_gemm: an even number of stages per range, none empty)"""
+        """K ranges a forced split launches (nvf4_launch_plan: an even number of stages per range, none empty)"""
         s, kt = self.requested_splits, stages(self.k)
         per = 2 * (-(-kt // (2 * s)))
         return -(-kt // per) if s > 1 else 1
