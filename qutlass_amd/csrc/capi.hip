@@ -1422,53 +1422,32 @@ QAMD_QUANT_INST(QK_GATED, false, METHOD_ABSMAX, false, false, QF_E4M3) QAMD_QUAN
 #endif
 
 // backward_t_bf16 / backward_qt_bf16 kernels live in unit 5 with the other rotation quantizers (MFMA results straight in VGPRs: a
-// v_accvgpr_read per accumulator register is 32 more VALU issues per tile)
-//   which: 1 = the round-3 kernel (8 waves per unit of 8 groups x 64 m, two barriers per unit); 2 = wave-owned 64-byte segments (units of 4
-//   groups, 12 - 16 waves per CU); 3 = wave-owned 128-byte lines (units of 8 groups, 8 waves per CU).  Product: QT 2, T 3 (bwd_kernel_choice).
-int launch_bwd_quant(const BwdTParams& p, bool qt, int which, bool hw, int grid, hipStream_t s);
+// v_accvgpr_read per accumulator register is 32 more VALU issues per tile).  Launches what stream_launch_plan planned (quartet_bwd.hip.h: STREAM_FORMS): one arm per
+// (form, op, e2m1 encoder), each naming one instantiation; the software encoder (!hw) is lab-only.  A form this build holds no kernel for is an error.
+int launch_bwd_quant(const char* name, const BwdTParams& p, bool qt, bool hw, const StreamLaunch& l, hipStream_t s);
 #if QAMD_DEF(5)
-int launch_bwd_quant(const BwdTParams& p, bool qt, int which, bool hw, int grid, hipStream_t s) {
-#define QAMD_BWD_GO(KERN, THREADS) hipLaunchKernelGGL((KERN), dim3(grid), dim3(THREADS), 0, s, p)
-  if (which >= 5 && which <= 8) {   // [r5] QT only: the wave-owned kernel with the input fetched as whole lines into a ring shared by the workgroup's four m-tiles
-#if QAMD_BENCH
-    if (which == 6) { QAMD_BWD_GO((bwd_qt_ring_kernel<true, 8, 4, true>), 256); return check_launch("bwd_qt_ring_kernel"); }
-    if (which == 7) { QAMD_BWD_GO((bwd_qt_ring_kernel<true, 8, 4, false>), 256); return check_launch("bwd_qt_ring_kernel"); }
-    if (which == 8) { QAMD_BWD_GO((bwd_qt_ring_kernel<true, 4, 3, true>), 256); return check_launch("bwd_qt_ring_kernel"); }
-    if (!hw) { QAMD_BWD_GO((bwd_qt_ring_kernel<false, 4, 3, false>), 256); return check_launch("bwd_qt_ring_kernel"); }
+int launch_bwd_quant(const char* name, const BwdTParams& p, bool qt, bool hw, const StreamLaunch& l, hipStream_t s) {
+  auto go = [&](auto kern, const char* what) { hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(l.threads), 0, s, p); return check_launch(what); };
+  constexpr auto arm = [](int form, bool qt_, bool hw_) { return form * 4 + qt_ * 2 + hw_; };   constexpr bool T = false, QT = true, SW = false, HW = true;
+  switch (arm(l.form, qt, hw)) {
+    case arm(BWD_ROUND3, T, HW): return go(bwd_quant_t_kernel<false, true>, "bwd_quant_t_kernel");   case arm(BWD_ROUND3, QT, HW): return go(bwd_quant_t_kernel<true, true>, "bwd_quant_t_kernel");
+    case arm(BWD_WAVE8, T, HW): return go(bwd_quant_tw_kernel<false, true, 8>, "bwd_quant_tw_kernel");
+    case arm(BWD_WAVE4, QT, HW): return go(bwd_quant_tw_kernel<true, true, 4>, "bwd_quant_tw_kernel");
+    case arm(QT_RING, QT, HW): return go(bwd_qt_ring_kernel<true, 4, 3, false>, "bwd_qt_ring_kernel");
+#if QAMD_BENCH   // the other op's unit size, [r6] BWD_WAVE2 (latency against write efficiency at small inputs), the software encoder, the whole-line lab forms
+    case arm(BWD_WAVE8, QT, HW): return go(bwd_quant_tw_kernel<true, true, 8>, "bwd_quant_tw_kernel");
+    case arm(BWD_WAVE4, T, HW): return go(bwd_quant_tw_kernel<false, true, 4>, "bwd_quant_tw_kernel");
+    case arm(BWD_WAVE2, T, HW): return go(bwd_quant_tw_kernel<false, true, 2>, "bwd_quant_tw_kernel");   case arm(BWD_WAVE2, QT, HW): return go(bwd_quant_tw_kernel<true, true, 2>, "bwd_quant_tw_kernel");
+    case arm(BWD_ROUND3, T, SW): return go(bwd_quant_t_kernel<false, false>, "bwd_quant_t_kernel");   case arm(BWD_ROUND3, QT, SW): return go(bwd_quant_t_kernel<true, false>, "bwd_quant_t_kernel");
+    case arm(BWD_WAVE8, T, SW): return go(bwd_quant_tw_kernel<false, false, 8>, "bwd_quant_tw_kernel");   case arm(BWD_WAVE8, QT, SW): return go(bwd_quant_tw_kernel<true, false, 8>, "bwd_quant_tw_kernel");
+    case arm(BWD_WAVE4, T, SW): return go(bwd_quant_tw_kernel<false, false, 4>, "bwd_quant_tw_kernel");   case arm(BWD_WAVE4, QT, SW): return go(bwd_quant_tw_kernel<true, false, 4>, "bwd_quant_tw_kernel");
+    case arm(QT_RING, QT, SW): return go(bwd_qt_ring_kernel<false, 4, 3, false>, "bwd_qt_ring_kernel");
+    case arm(QT_PANEL, QT, SW): return go(bwd_qt_panel_kernel<false>, "bwd_qt_panel_kernel");   case arm(QT_PANEL, QT, HW): return go(bwd_qt_panel_kernel<true>, "bwd_qt_panel_kernel");
+    case arm(QT_RING8_XR, QT, HW): return go(bwd_qt_ring_kernel<true, 8, 4, true>, "bwd_qt_ring_kernel");   case arm(QT_RING8, QT, HW): return go(bwd_qt_ring_kernel<true, 8, 4, false>, "bwd_qt_ring_kernel");
+    case arm(QT_RING4_XR, QT, HW): return go(bwd_qt_ring_kernel<true, 4, 3, true>, "bwd_qt_ring_kernel");
 #endif
-    QAMD_BWD_GO((bwd_qt_ring_kernel<true, 4, 3, false>), 256);
-    return check_launch("bwd_qt_ring_kernel");
   }
-#if QAMD_BENCH
-  if (which == 4) {   // QT only: whole-line panels ([256 n][256 m] per workgroup), quartet_bwd_lab.hip.h
-    if (!hw) { QAMD_BWD_GO((bwd_qt_panel_kernel<false>), 512); return check_launch("bwd_qt_panel_kernel"); }
-    QAMD_BWD_GO((bwd_qt_panel_kernel<true>), 512);
-    return check_launch("bwd_qt_panel_kernel");
-  }
-#endif
-  if (which == 1) {
-#if QAMD_BENCH
-    if (!hw) { if (qt) QAMD_BWD_GO((bwd_quant_t_kernel<true, false>), 512); else QAMD_BWD_GO((bwd_quant_t_kernel<false, false>), 512); return check_launch("bwd_quant_t_kernel"); }
-#endif
-    if (qt) QAMD_BWD_GO((bwd_quant_t_kernel<true, true>), 512); else QAMD_BWD_GO((bwd_quant_t_kernel<false, true>), 512);
-    return check_launch("bwd_quant_t_kernel");
-  }
-#if QAMD_BENCH
-  if (!hw) {
-    if (which == 3) { if (qt) QAMD_BWD_GO((bwd_quant_tw_kernel<true, false, 8>), 256); else QAMD_BWD_GO((bwd_quant_tw_kernel<false, false, 8>), 256); }
-    else            { if (qt) QAMD_BWD_GO((bwd_quant_tw_kernel<true, false, 4>), 256); else QAMD_BWD_GO((bwd_quant_tw_kernel<false, false, 4>), 256); }
-    return check_launch("bwd_quant_tw_kernel");
-  }
-  if (which == 9) {   // [r6] lab: units of 2 groups (32-byte output segments, twice the waves of variant 2) -- latency against write efficiency at small inputs
-    if (qt) QAMD_BWD_GO((bwd_quant_tw_kernel<true, true, 2>), 256); else QAMD_BWD_GO((bwd_quant_tw_kernel<false, true, 2>), 256);
-    return check_launch("bwd_quant_tw_kernel");
-  }
-  if (qt && which == 3) { QAMD_BWD_GO((bwd_quant_tw_kernel<true, true, 8>), 256); return check_launch("bwd_quant_tw_kernel"); }
-  if (!qt && which == 2) { QAMD_BWD_GO((bwd_quant_tw_kernel<false, true, 4>), 256); return check_launch("bwd_quant_tw_kernel"); }
-#endif
-  if (qt) QAMD_BWD_GO((bwd_quant_tw_kernel<true, true, 4>), 256); else QAMD_BWD_GO((bwd_quant_tw_kernel<false, true, 8>), 256);
-#undef QAMD_BWD_GO
-  return check_launch("bwd_quant_tw_kernel");
+  return fail(QAMD_ERR_INVALID, "%s: this build holds no kernel for form %d%s", name, l.form, hw ? "" : " with the software encoder");
 }
 #endif
 
@@ -2404,111 +2383,83 @@ int qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn(const void* x, const void* h,
   return check_launch("gemm_mx_fusedq_kernel");
 }
 
-// which backward_t / backward_qt kernel (see launch_bwd_quant), from the A/B on one box (profiles/ab_bwd_r4k_variants.txt; nu = units of 8 groups x
-// 64 m): the wave-owned kernels need a few units per wave to amortise their pipeline fill, below that the round-3 kernel (8 waves share a unit)
-// stays.  QT: 64-byte segments with 16 waves per CU (4096^2 cold 10.2 -> 8.5 us, 8192^2 30.9 -> 26.6); T: whole lines with 8 waves per CU
-// (8192^2 cold 38.0 -> 36.5, 2048 x 14336 17.7 -> 15.2; the 64-byte form ties with the round-3 kernel there).  In the product build the product
-// kernels are the only instantiations: QT never takes 3, T never 2.  Lab: option "bwd_variant" (low 4 bits) forces 1 / 2 / 3.
-// [r5] QT, large inputs with M % 128 == 0: 5 = the wave-owned kernel fed through a shared whole-line ring (bwd_qt_ring_kernel).  Cold it wins from ~12 units per CU
-// (profiles/ab_bwd_r5x_ring_threshold.txt: 14336 x 4096 22.1 -> 20.6 us, 8192^2 26.1 -> 22.4, 8192 x 16384 55.1 -> 43.5; 11008 x 4096 ties, 6144^2 15.1 -> 15.5), warm
-// (input in the MALL) the plain kernel stays ahead until ~32 per CU -- the rule goes by the cold numbers, as every streaming-op figure of the design record does.
-static int bwd_kernel_rule(bool qt, int64_t nu, int64_t cu, bool ring_ok = false) {
-  if (qt) return (ring_ok && nu >= 12 * cu) ? 5 : nu >= 3 * cu ? 2 : 1;
-  return nu >= 6 * cu ? 3 : 1;
+// ---- the QAT-backward data-prep ops: check, fill the parameters, stream_launch_plan (quartet_bwd.hip.h: which kernel form, how many workgroups), launch ----
+// (bwd_check: backward_t_bf16 / backward_qt_bf16, m_mult 8 / 32; rows_check: the two _rows ops, n a multiple of 128 -- need_n says so -- / 256: every check, in the entries' order)
+static int bwd_check(const char* name, int m_mult, bool null_arg, int64_t B, int64_t N, int64_t M) {
+  if (null_arg) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (B <= 0 || N <= 0 || M <= 0 || N % 32 || M % m_mult) return fail(QAMD_ERR_INVALID, "%s: need N %% 32 == 0 and M %% %d == 0 (got B=%lld N=%lld M=%lld)", name, m_mult, (long long)B, (long long)N, (long long)M);
+  if (B * N * M >= (1ll << 40) || M >= (1ll << 24) || N >= (1ll << 26)) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);   // 32 input rows / 64 output rows < 2^31 bytes
+  if (B * (N / 32) * cdiv(M, 64) >= (1ll << 31) - 65536) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);   // (BwdTParams::tiles_m: the kernels index tiles in 32 bits)
+  return QAMD_OK;
 }
-static int bwd_kernel_choice(bool qt, int64_t nu, bool ring_ok = false) {
-  const int v = opt_bwd_variant() & 15;
-  if (v >= 1 && v <= 9) return v;
-  return bwd_kernel_rule(qt, nu, chip_cus(), ring_ok);
+static int rows_check(const char* name, int n_mult, const char* need_n, bool null_arg, int64_t m, int64_t m_pad, int64_t n) {
+  if (null_arg) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (m <= 0 || n <= 0 || n % n_mult || m_pad < m || m_pad % 128)
+    return fail(QAMD_ERR_INVALID, "%s: need m > 0, %s and the output row extent a multiple of 128 >= m (got m=%lld m_pad=%lld n=%lld)", name, need_n, (long long)m, (long long)m_pad, (long long)n);
+  if (m_pad >= (1ll << 31) || n >= (1ll << 31) || (m_pad / 128) * (n / 128) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);
+  return QAMD_OK;
 }
-// column tiles (of 128) per workgroup of backward_bf16_square_double_mxfp8: 4 (16 waves, 16-byte row-scale pieces) when n allows and every CU still gets a workgroup
-static int sq_column_tiles_rule(int64_t m_pad, int64_t n, int64_t cu) { return (n % 512 == 0 && (m_pad / 128) * (n / 512) >= cu) ? 4 : 1; }
 
 int qutlass_amd_backward_t_bf16(const void* x, const void* h, int64_t B, int64_t N, int64_t M, void* out_e2m1,
                                 void* out_e8m0, void* stream) {
   const char* name = "backward_t_bf16";
-  if (!x || !h || !out_e2m1 || !out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (B <= 0 || N <= 0 || M <= 0 || N % 32 || M % 8)
-    return fail(QAMD_ERR_INVALID, "%s: need N %% 32 == 0 and M %% 8 == 0 (got B=%lld N=%lld M=%lld)", name, (long long)B, (long long)N, (long long)M);
-  if (B * N * M >= (1ll << 40) || M >= (1ll << 24) || N >= (1ll << 26)) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);   // 32 input rows / 64 output rows < 2^31 bytes
+  if (const int rc = bwd_check(name, 8, !x || !h || !out_e2m1 || !out_e8m0, B, N, M)) return rc;
   BwdTParams p{};
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_e8m0;
-  p.B = (int)B; p.N = (int)N; p.M = (int)M; p.tiles_m = (int)cdiv(M, 64);
-  if (B * (N / 32) * p.tiles_m >= (1ll << 31) - 65536) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);
-  const int64_t ntw = B * p.tiles_m * cdiv(N / 32, 8);   // units: 8 scale groups (256 n) x 64 m = 64 whole output lines
-  const int which0 = bwd_kernel_choice(false, ntw);
-  const int which = (which0 >= 4 && which0 != 9) ? bwd_kernel_rule(false, ntw, chip_cus()) : which0;   // (4 .. 8 = QT-only kernels)
-  p.abl = opt_bwd_variant() >> 4;
-  const int64_t nuw = B * p.tiles_m * cdiv(N / 32, which == 3 ? 8 : which == 9 ? 2 : 4);   // wave units
-  const int grid = which == 1 ? (int)std::min<int64_t>(ntw, chip_cus() * 2) : (int)std::min<int64_t>(cdiv(nuw, 4), chip_cus() * (which == 3 ? 2 : which == 9 ? 4 : 3));
-  return launch_bwd_quant(p, false, which, opt_hw_fp4(), grid, (hipStream_t)stream);
+  p.B = (int)B; p.N = (int)N; p.M = (int)M; p.tiles_m = (int)cdiv(M, 64); p.abl = opt_bwd_variant() >> 4;
+  return launch_bwd_quant(name, p, false, opt_hw_fp4(), stream_launch_plan(OP_T, B, N, M, chip_cus(), opt_bwd_variant() & 15, false), (hipStream_t)stream);
 }
 
 int qutlass_amd_backward_qt_bf16(const void* x_e2m1, const void* x_e8m0, const void* h, const float* alpha, int64_t B,
                                  int64_t N, int64_t M, void* out_e2m1, void* out_e8m0, void* stream) {
   const char* name = "backward_qt_bf16";
-  if (!x_e2m1 || !x_e8m0 || !h || !alpha || !out_e2m1 || !out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (B <= 0 || N <= 0 || M <= 0 || N % 32 || M % 32)
-    return fail(QAMD_ERR_INVALID, "%s: need N %% 32 == 0 and M %% 32 == 0 (got B=%lld N=%lld M=%lld)", name, (long long)B, (long long)N, (long long)M);
-  if (B * N * M >= (1ll << 40) || M >= (1ll << 24) || N >= (1ll << 26)) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);   // 32 input rows / 64 output rows < 2^31 bytes
+  if (const int rc = bwd_check(name, 32, !x_e2m1 || !x_e8m0 || !h || !alpha || !out_e2m1 || !out_e8m0, B, N, M)) return rc;
   BwdTParams p{};
   p.xq = (const uint8_t*)x_e2m1; p.xs = (const uint8_t*)x_e8m0; p.h = (const uint16_t*)h; p.alpha = alpha;
   p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_e8m0;
-  p.B = (int)B; p.N = (int)N; p.M = (int)M; p.tiles_m = (int)cdiv(M, 64);
-  if (B * (N / 32) * p.tiles_m >= (1ll << 31) - 65536) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);
-  // virtual tiles: units of 4 sibling m-tiles (bwd_quant_t_kernel's tile order); the grid is a multiple of 32 workgroups (4 siblings x 8 XCDs)
-  const int64_t ntw = B * cdiv(p.tiles_m, 4) * 4 * cdiv(N / 32, 8);
-  // 49 KB of LDS per workgroup: three fit a CU.  A round of three per CU takes ~1.24x a round of two (8192^2: 6 rounds 20.7 us against 8 rounds
-  // 22.2 us; 4096^2, 2 rounds either way: 9.3 against 8.5 us): three when that wins the round count
-  const int64_t cu = chip_cus();
-  const int per_cu = 1.24 * (double)cdiv(ntw, 3 * cu) < (double)cdiv(ntw, 2 * cu) ? 3 : 2;
-  const int grid = (int)std::max<int64_t>(32, std::min<int64_t>(cdiv(ntw, 32) * 32, cu * per_cu / 32 * 32));
-  // [r4] wave-owned output segments: the four waves of a workgroup take four consecutive m-tiles -- the siblings that share QT's 128-byte input lines
-  const int64_t nu = B * p.tiles_m * cdiv(N / 32, 8);
+  p.B = (int)B; p.N = (int)N; p.M = (int)M; p.tiles_m = (int)cdiv(M, 64); p.abl = opt_bwd_variant() >> 4;
   // (the ring kernel fetches by LDS-DMA: 16-byte pieces of the codes, dword pieces of the scale bytes -- an offset view that breaks either alignment takes the other kernels)
-  const int which = bwd_kernel_choice(true, nu, M % 128 == 0 && (uintptr_t)x_e2m1 % 16 == 0 && (uintptr_t)x_e8m0 % 4 == 0);
-  p.abl = opt_bwd_variant() >> 4;
-  const int64_t nuw = B * p.tiles_m * cdiv(N / 32, which == 3 ? 8 : which == 9 ? 2 : 4);
-  const int gridw = (int)std::min<int64_t>(cdiv(nuw, 4), cu * (which == 3 ? 2 : which == 9 ? 5 : 4));
-  if (which >= 5 && which <= 8) {   // [r5] ring kernels: units of NG groups x 256 m
-    if (M % 128) return fail(QAMD_ERR_INVALID, "%s: the ring kernel needs M %% 128 == 0", name);
-    const int ng = (which == 6 || which == 7) ? 8 : 4;
-    const int64_t ur = B * cdiv(M, 256) * cdiv(N / 32, ng);
-    return launch_bwd_quant(p, true, which, opt_hw_fp4(), (int)std::min<int64_t>(ur, std::max<int64_t>(8, cu * (ng == 8 ? 2 : 3) / 8 * 8)), (hipStream_t)stream);   // (>= 8: a part with fewer than 3 visible CUs must not get an empty grid)
+  const int v = opt_bwd_variant() & 15;
+  const StreamLaunch l = stream_launch_plan(OP_QT, B, N, M, chip_cus(), v, (uintptr_t)x_e2m1 % 16 == 0 && (uintptr_t)x_e8m0 % 4 == 0);
+  if (l.form == SF_NONE) return fail(QAMD_ERR_INVALID, "%s: the %s kernel needs M %% 128 == 0", name, v == QT_PANEL ? "panel" : "ring");   // (lab: a forced whole-line form)
+  return launch_bwd_quant(name, p, true, opt_hw_fp4(), l, (hipStream_t)stream);
+}
+
+// the square-double and transposer kernels live in this unit; as launch_bwd_quant: one arm per form, each naming one instantiation
+static int launch_square_double(const char* name, const SqParams& p, const StreamLaunch& l, hipStream_t s) {
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(l.threads), 0, s, p); return check_launch("bwd_square_double_mxfp8_kernel"); };
+  switch (l.form) {
+    case SQ_CT1: return go(bwd_square_double_mxfp8_kernel<1, 1>);
+    case SQ_CT4: return go(bwd_square_double_mxfp8_kernel<4, 1>);
+#if QAMD_BENCH
+    case SQ_CT8: return go(bwd_square_double_mxfp8_kernel<4, 2>);   // two tiles per wave
+#endif
   }
-  if (which == 4) {   // [r5] panel kernel: units of 8 groups x 256 m, two workgroups per CU (persistent grids step by a multiple of the 8 XCDs)
-    if (M % 128) return fail(QAMD_ERR_INVALID, "%s: the panel kernel needs M %% 128 == 0", name);
-    const int64_t up = B * cdiv(M, 256) * cdiv(N / 32, 8);
-    return launch_bwd_quant(p, true, 4, opt_hw_fp4(), (int)std::min<int64_t>(up, std::max<int64_t>(8, cu * 2 / 8 * 8)), (hipStream_t)stream);
+  return fail(QAMD_ERR_INVALID, "%s: this build holds no kernel for form %d", name, l.form);
+}
+static int launch_transpose(const char* name, const TrParams& p, const StreamLaunch& l, hipStream_t s) {
+  auto go = [&](auto kern, const char* what) { hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(l.threads), 0, s, p); return check_launch(what); };
+  switch (l.form) {
+    case TR_ONE_SHOT: return go(mxfp4_transpose_mxfp8_kernel<128, 128>, "mxfp4_transpose_mxfp8_kernel");
+#if QAMD_BENCH
+    case TR_NC256: return go(mxfp4_transpose_mxfp8_kernel<256>, "mxfp4_transpose_mxfp8_kernel");
+    case TR_MR256: return go(mxfp4_transpose_mxfp8_kernel<128, 256>, "mxfp4_transpose_mxfp8_kernel");
+    case TR_WAVE4: return go(mxfp4_transpose_mxfp8_tw_kernel<4>, "mxfp4_transpose_mxfp8_tw_kernel");
+    case TR_WAVE2: return go(mxfp4_transpose_mxfp8_tw_kernel<2>, "mxfp4_transpose_mxfp8_tw_kernel");
+    case TR_PP4: case TR_PP3: case TR_PP2: case TR_PP6: return go(mxfp4_transpose_mxfp8_pp_kernel<128, 128>, "mxfp4_transpose_mxfp8_pp_kernel");   // (one kernel; the forms differ in the grid)
+#endif
   }
-  return launch_bwd_quant(p, true, which, opt_hw_fp4(), which == 1 ? grid : gridw, (hipStream_t)stream);
+  return fail(QAMD_ERR_INVALID, "%s: this build holds no kernel for form %d", name, l.form);
 }
 
 int qutlass_amd_backward_bf16_square_double_mxfp8_rows(const void* x, int64_t m, int64_t m_pad, int64_t n, void* y, void* row_scales,
                                                        void* col_scales, void* stream) {
   const char* name = "backward_bf16_square_double_mxfp8";
-  if (!x || !y || !row_scales || !col_scales) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (m <= 0 || n <= 0 || n % 128 || m_pad < m || m_pad % 128)
-    return fail(QAMD_ERR_INVALID, "%s: need m > 0, n a positive multiple of 128 and the output row extent a multiple of 128 >= m (got m=%lld m_pad=%lld n=%lld)", name,
-                (long long)m, (long long)m_pad, (long long)n);
-  if (m_pad >= (1ll << 31) || n >= (1ll << 31) || (m_pad / 128) * (n / 128) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);
+  if (const int rc = rows_check(name, 128, "n a positive multiple of 128", !x || !y || !row_scales || !col_scales, m, m_pad, n)) return rc;
   SqParams p;
   p.x = (const uint16_t*)x; p.y = (uint8_t*)y; p.row_sf = (uint8_t*)row_scales; p.col_sf = (uint8_t*)col_scales;
   p.m = (int)m; p.n = (int)n; p.m_pad = (int)m_pad; p.abl = opt_bwd_variant() >> 4;
-  // [r4] 512 columns per workgroup (16 waves: the row scales leave as 16-byte pieces) when that still gives every CU a workgroup; lab: option
-  // "transpose_nc" = 1 forces the 4-wave form, 4 / 8 the 512- / 1024-column forms
-  {
-    const int64_t rb = m_pad / 128, cu = chip_cus();
-    int ct = sq_column_tiles_rule(m_pad, n, cu);   // (1024 columns, two tiles per wave: slower again except warm at 8192^2 -- profiles/ab_sq_abl_r4ae.txt)
-#if QAMD_BENCH
-    if (opt_transpose_nc() == 1) ct = 1;
-    if ((opt_transpose_nc() == 8 && n % 1024 == 0) || (opt_transpose_nc() == 4 && n % 512 == 0)) ct = opt_transpose_nc();
-    if (ct == 8) { hipLaunchKernelGGL((bwd_square_double_mxfp8_kernel<4, 2>), dim3((unsigned)(rb * (n / 1024))), dim3(1024), 0, (hipStream_t)stream, p); return check_launch("bwd_square_double_mxfp8_kernel"); }
-#endif
-    if (ct == 4) hipLaunchKernelGGL((bwd_square_double_mxfp8_kernel<4, 1>), dim3((unsigned)(rb * (n / 512))), dim3(1024), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((bwd_square_double_mxfp8_kernel<1, 1>), dim3((unsigned)(rb * (n / 128))), dim3(256), 0, (hipStream_t)stream, p);
-  }
-  return check_launch("bwd_square_double_mxfp8_kernel");
+  return launch_square_double(name, p, stream_launch_plan(OP_SQ, m_pad, n, 0, chip_cus(), opt_transpose_nc(), false), (hipStream_t)stream);
 }
 
 int qutlass_amd_backward_bf16_square_double_mxfp8(const void* x, int64_t m, int64_t n, void* y, void* row_scales,
@@ -2520,55 +2471,11 @@ int qutlass_amd_backward_bf16_square_double_mxfp8(const void* x, int64_t m, int6
 int qutlass_amd_mxfp4_transpose_mxfp8_rows(const void* x_fp4, const void* scales, int64_t m, int64_t m_pad, int64_t n, void* y,
                                            void* out_e8m0, void* stream) {
   const char* name = "mxfp4_transpose_mxfp8";
-  if (!x_fp4 || !scales || !y || !out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (m <= 0 || n <= 0 || n % 256 || m_pad < m || m_pad % 128)
-    return fail(QAMD_ERR_INVALID, "%s: need m > 0, n %% 256 == 0 and the output row extent a multiple of 128 >= m (got m=%lld m_pad=%lld n=%lld)", name, (long long)m,
-                (long long)m_pad, (long long)n);
-  if (m_pad >= (1ll << 31) || n >= (1ll << 31) || (m_pad / 128) * (n / 128) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: tensor too large", name);
+  if (const int rc = rows_check(name, 256, "n % 256 == 0", !x_fp4 || !scales || !y || !out_e8m0, m, m_pad, n)) return rc;
   TrParams p;
   p.xq = (const uint8_t*)x_fp4; p.xs = (const uint8_t*)scales; p.y = (uint8_t*)y; p.out_sf = (uint8_t*)out_e8m0;
   p.m = (int)m; p.n = (int)n; p.m_pad = (int)m_pad; p.abl = opt_bwd_variant() >> 4;
-  // [r4] A wave-owned-lines form of this op (mxfp4_transpose_mxfp8_tw_kernel: persistent waves, no workgroup barrier, whole 128-byte lines or
-  // 64-byte segments) is byte-identical and NOT faster (8192^2 cold 30.7 / 35.0 us against 28.4, warm 21.4 / 22.5 against 21.2;
-  // profiles/ab_transpose_r4o.txt): the one-shot kernel stays the product, the other lives in the lab build (option "transpose_nc" = 4 / 2).
-#if QAMD_BENCH
-  const int64_t cu = chip_cus();
-  const int tw = (m_pad < (1ll << 25) && (opt_transpose_nc() == 4 || opt_transpose_nc() == 2)) ? opt_transpose_nc() : 0;   // (64 output rows within one buffer window)
-  if (opt_transpose_nc() == 256) {
-    hipLaunchKernelGGL(mxfp4_transpose_mxfp8_kernel<256>, dim3((unsigned)((m_pad / 128) * (n / 256))), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("mxfp4_transpose_mxfp8_kernel");
-  }
-  if (tw == 4) {
-    const int64_t units = (m_pad / 128) * (n / 64);
-    hipLaunchKernelGGL(mxfp4_transpose_mxfp8_tw_kernel<4>, dim3((unsigned)std::min<int64_t>(cdiv(units, 4), cu * 2)), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("mxfp4_transpose_mxfp8_tw_kernel");
-  }
-  if (tw == 2) {
-    const int64_t units = (m_pad / 64) * (n / 64);
-    hipLaunchKernelGGL(mxfp4_transpose_mxfp8_tw_kernel<2>, dim3((unsigned)std::min<int64_t>(cdiv(units, 4), cu * 3)), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("mxfp4_transpose_mxfp8_tw_kernel");
-  }
-#endif
-  // [r4] 256 rows per workgroup (8 waves, 8-byte scale pieces per output row instead of 4) is byte-identical and slower -- the two workgroup barriers then
-  // wait for eight waves: 8192^2 cold 28.6 -> 31.5 us (profiles/ab_transpose_r4ak_8wave.txt); lab only: option "transpose_nc" = 3
-#if QAMD_BENCH
-  if (opt_transpose_nc() == 3 && m_pad % 256 == 0) {
-    hipLaunchKernelGGL((mxfp4_transpose_mxfp8_kernel<128, 256>), dim3((unsigned)((m_pad / 256) * (n / 128))), dim3(512), 0, (hipStream_t)stream, p);
-    return check_launch("mxfp4_transpose_mxfp8_kernel");
-  }
-#endif
-#if QAMD_BENCH
-  if (opt_transpose_nc() >= 5 && opt_transpose_nc() <= 8) {   // [r5] the persistent form with the next tile's rows in flight: 5 / 6 / 7 / 8 = 4 / 3 / 2 / 6 workgroups' worth of grid per CU
-    const int64_t tiles = (m_pad / 128) * (n / 128);
-    const int per_cu = opt_transpose_nc() == 5 ? 4 : opt_transpose_nc() == 6 ? 3 : opt_transpose_nc() == 7 ? 2 : 6;
-    int64_t grid = std::min<int64_t>(tiles, chip_cus() * per_cu);
-    if (grid < tiles) grid = grid / 16 * 16;
-    hipLaunchKernelGGL((mxfp4_transpose_mxfp8_pp_kernel<128, 128>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("mxfp4_transpose_mxfp8_pp_kernel");
-  }
-#endif
-  hipLaunchKernelGGL((mxfp4_transpose_mxfp8_kernel<128, 128>), dim3((unsigned)((m_pad / 128) * (n / 128))), dim3(256), 0, (hipStream_t)stream, p);
-  return check_launch("mxfp4_transpose_mxfp8_kernel");
+  return launch_transpose(name, p, stream_launch_plan(OP_TR, m_pad, n, 0, chip_cus(), opt_transpose_nc(), false), (hipStream_t)stream);
 }
 
 int qutlass_amd_mxfp4_transpose_mxfp8(const void* x_fp4, const void* scales, int64_t m, int64_t n, void* y,
@@ -2619,16 +2526,25 @@ int qutlass_amd_debug_ada_plan(int64_t M, int64_t N, int64_t K, int* out, int ca
   return debug_plan(name, M, N, K / 2, 64, out, cap, [&](int64_t m, int64_t n) { return MxPlan().add(ada_plan(m, n, K, 256), 0, n); });
 }
 
-// [r4] debug only (not declared in the public header): the kernel rules of the QAT-backward data-prep ops on a 256-CU part, no GPU touched.
-//   op 0 / 1: backward_t_bf16 / backward_qt_bf16 (a, b, c) = (B, N, M) -> 1 = the round-3 kernel, 2 = wave-owned 64-byte segments, 3 = wave-owned 128-byte lines, 5 = [r5] QT: 2 fed through the shared whole-line ring
-//   op 2: backward_bf16_square_double_mxfp8 (a, b) = (m_pad, n) -> column tiles per workgroup (1 or 4)
+// [r4] debug only (not declared in the public header): the form (quartet_bwd.hip.h StreamForm) the product rules pick on a 256-CU part, no GPU touched.  op 0 / 1: backward_t_bf16 /
+// backward_qt_bf16 (a, b, c) = (B, N, M) -> 1, 3 / 1, 2, 5; op 2: backward_bf16_square_double_mxfp8 (a, b) = (m_pad, n) -> column tiles per workgroup (1 or 4)
 int qutlass_amd_debug_stream_plan(int op, int64_t a, int64_t b, int64_t c) {
-  if (op == 0 || op == 1) {
-    if (a <= 0 || b <= 0 || c <= 0 || b % 32) return -1;
-    return bwd_kernel_rule(op == 1, a * cdiv(c, 64) * cdiv(b / 32, 8), 256, op == 1 && c % 128 == 0);
-  }
-  if (op == 2) return (a <= 0 || b <= 0 || a % 128 || b % 128) ? -1 : sq_column_tiles_rule(a, b, 256);
+  if (op == OP_T || op == OP_QT) return (a <= 0 || b <= 0 || c <= 0 || b % 32) ? -1 : stream_launch_plan(op, a, b, c, 256, 0, true).form;
+  if (op == OP_SQ) return (a <= 0 || b <= 0 || a % 128 || b % 128) ? -1 : stream_launch_plan(op, a, b, 0, 256, 0, false).form;
   return -1;
+}
+
+// debug only (not declared in the public header): the whole launch of the four ops (stream_launch_plan, the function their entries run) on a part of `cus` CUs, after the entry's
+// own argument checks, no GPU touched.  op 0 / 1: (a, b, c) = (B, N, M); op 2 / 3 = the _rows forms of square-double / the transposer: (a, b, c) = (m_pad, n, m).  variant: the lab's
+// "bwd_variant" (low 4 bits) / "transpose_nc", 0 = the product rules; ring_aligned: what backward_qt_bf16 finds of its operands' addresses.  out[0 .. 2] = {form, workgroups,
+// threads per workgroup}; returns 1, or -1 for arguments the op rejects and for a form this build holds no kernel for (the product library: any variant but 0).
+int qutlass_amd_debug_stream_launch_plan(int op, int64_t a, int64_t b, int64_t c, int cus, int variant, int ring_aligned, int* out) {
+  const char* name = "debug_stream_launch_plan";
+  if (!out || cus <= 0 || op < OP_T || op > OP_TR || (op <= OP_QT ? bwd_check(name, op == OP_QT ? 32 : 8, false, a, b, c) : rows_check(name, op == OP_SQ ? 128 : 256, "", false, c, a, b))) return -1;
+  const StreamLaunch l = stream_launch_plan(op, a, b, c, cus, variant, ring_aligned != 0);
+  if (l.form == SF_NONE) return -1;
+  out[0] = l.form; out[1] = (int)l.grid; out[2] = l.threads;
+  return 1;
 }
 
 // [r4] debug only (not declared in the public header): the grouped-raster decode of the persistent kernels (common.hip.h raster_decode, the SAME function the

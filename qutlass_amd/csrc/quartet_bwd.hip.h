@@ -1206,4 +1206,88 @@ __global__ __launch_bounds__(256) void mxfp4_transpose_mxfp8_tw_kernel(const TrP
   }
 }
 
+// ---- host side: the ONE list of the kernel forms behind the four ops, and the launch plan that every C entry and debug entry of them reads (capi.hip) ----
+enum StreamOp : int { OP_T = 0, OP_QT = 1, OP_SQ = 2, OP_TR = 3 };   // backward_t_bf16, backward_qt_bf16, backward_bf16_square_double_mxfp8(_rows), mxfp4_transpose_mxfp8(_rows)
+// A form's value is what qutlass_amd_debug_stream_plan reports AND the lab option value that forces it: the low 4 bits of "bwd_variant" for T / QT, "transpose_nc"
+// for the two _rows ops (which is why values repeat across ops: a form is looked up by (op, value)).  SF_NONE: a forced form that refuses the call / (product) any forcing
+enum StreamForm : int {
+  SF_NONE = 0, BWD_ROUND3 = 1,                   // bwd_quant_t_kernel: 8 waves share a unit of 8 groups x 64 m, two barriers per unit
+  BWD_WAVE4 = 2, BWD_WAVE8 = 3, BWD_WAVE2 = 9,   // bwd_quant_tw_kernel: a wave owns a unit of 4 / 8 / 2 groups x 64 m = 64-byte segments / whole 128-byte lines / 32-byte segments of output
+  QT_PANEL = 4,                                  // lab/quartet_bwd_lab.hip.h bwd_qt_panel_kernel: whole-line panels, [256 n][256 m] per workgroup
+  QT_RING = 5, QT_RING8_XR = 6, QT_RING8 = 7, QT_RING4_XR = 8,   // bwd_qt_ring_kernel: BWD_WAVE4 fed through a shared whole-line ring (NG 4, 3 slots); NG 8, 4 slots; _XR: 16 quads per XCD
+  SQ_CT1 = 1, SQ_CT4 = 4, SQ_CT8 = 8,            // bwd_square_double_mxfp8_kernel: column tiles (of 128) per workgroup
+  TR_ONE_SHOT = 128, TR_NC256 = 256, TR_MR256 = 3,   // mxfp4_transpose_mxfp8_kernel: the product <128, 128>; 256 columns / 256 rows (8 waves) per workgroup
+  TR_WAVE4 = 4, TR_WAVE2 = 2,                    // mxfp4_transpose_mxfp8_tw_kernel: wave-owned whole lines (128 rows) / 64-byte segments (64 rows) of 64 columns
+  TR_PP4 = 5, TR_PP3 = 6, TR_PP2 = 7, TR_PP6 = 8,    // lab mxfp4_transpose_mxfp8_pp_kernel: persistent, the next tile's rows in flight; 4 / 3 / 2 / 6 workgroups per CU
+};
+// One row per (op, form).  threads: of a workgroup.  A unit = groups scale groups (32 n each) x rows m, a workgroup takes `units` of them at a time.  per_cu > 0: a persistent
+// grid of per_cu workgroups per CU, cut down to a multiple of step and never below step (step 8: one share per XCD; a part with fewer than 3 visible CUs must not get
+// an empty grid); per_cu 0: one workgroup per `units` units, except QT's BWD_ROUND3 (stream_launch_plan).  lab: the kernel exists in the lab library only.
+struct StreamFormRow { int op, form, threads, groups, rows, units, per_cu, step; bool lab; };
+constexpr StreamFormRow STREAM_FORMS[] = {
+    {OP_T, BWD_ROUND3, 512, 8, 64, 1, 2, 1, false}, {OP_T, BWD_WAVE8, 256, 8, 64, 4, 2, 1, false}, {OP_T, BWD_WAVE4, 256, 4, 64, 4, 3, 1, true}, {OP_T, BWD_WAVE2, 256, 2, 64, 4, 4, 1, true},
+    {OP_QT, BWD_ROUND3, 512, 8, 64, 1, 0, 32, false}, {OP_QT, BWD_WAVE4, 256, 4, 64, 4, 4, 1, false}, {OP_QT, QT_RING, 256, 4, 256, 1, 3, 8, false},
+    {OP_QT, BWD_WAVE8, 256, 8, 64, 4, 2, 1, true}, {OP_QT, BWD_WAVE2, 256, 2, 64, 4, 5, 1, true}, {OP_QT, QT_PANEL, 512, 8, 256, 1, 2, 8, true},
+    {OP_QT, QT_RING8_XR, 256, 8, 256, 1, 2, 8, true}, {OP_QT, QT_RING8, 256, 8, 256, 1, 2, 8, true}, {OP_QT, QT_RING4_XR, 256, 4, 256, 1, 3, 8, true},
+    {OP_SQ, SQ_CT1, 256, 4, 128, 1, 0, 1, false}, {OP_SQ, SQ_CT4, 1024, 16, 128, 1, 0, 1, false}, {OP_SQ, SQ_CT8, 1024, 32, 128, 1, 0, 1, true},
+    {OP_TR, TR_ONE_SHOT, 256, 4, 128, 1, 0, 1, false}, {OP_TR, TR_NC256, 256, 8, 128, 1, 0, 1, true}, {OP_TR, TR_MR256, 512, 4, 256, 1, 0, 1, true},
+    {OP_TR, TR_WAVE4, 256, 2, 128, 4, 2, 1, true}, {OP_TR, TR_WAVE2, 256, 2, 64, 4, 3, 1, true}, {OP_TR, TR_PP4, 256, 4, 128, 1, 4, 16, true},
+    {OP_TR, TR_PP3, 256, 4, 128, 1, 3, 16, true}, {OP_TR, TR_PP2, 256, 4, 128, 1, 2, 16, true}, {OP_TR, TR_PP6, 256, 4, 128, 1, 6, 16, true},
+};
+constexpr const StreamFormRow* stream_form(int op, int form) {
+  for (const StreamFormRow& f : STREAM_FORMS)
+    if (f.op == op && f.form == form) return &f;
+  return nullptr;
+}
+struct StreamLaunch { int form = SF_NONE; int64_t grid = 0; int threads = 0; };
+// The launch of one call: a pure function of the shape, the CU count (capi.hip chip_cus; the debug entries pass their own) and the forcing variant.
+//   (a, n, m): T / QT (B, N, M); the _rows ops (m_pad, n, unused) -- already checked by the entry.  ring_aligned (QT): the operands' addresses allow QT_RING's LDS-DMA pieces
+//   variant: 0 = the product rules below, all the product library knows.  Lab: the form of that value when the op has one (else the product rules); a whole-line QT form
+//     refuses M % 128 != 0 (SF_NONE); a forced form of the _rows ops whose unit does not divide the tensor (or TR_WAVE*: 64 output rows beyond one buffer window) leaves
+//     the call to the product rules
+inline StreamLaunch stream_launch_plan(int op, int64_t a, int64_t n, int64_t m, int64_t cus, int variant, bool ring_aligned) {
+  auto cdiv = [](int64_t x, int64_t y) { return (x + y - 1) / y; };
+  const bool bwd = op == OP_T || op == OP_QT;
+  const int64_t batch = bwd ? a : 1, extent = bwd ? m : a, G = n / 32;
+#if !QAMD_BENCH
+  if (variant != 0) return {};
+#endif
+  const StreamFormRow* f = variant != 0 ? stream_form(op, variant) : nullptr;
+  if (f && bwd && f->rows == 256 && m % 128) return {};
+  if (f && !bwd && (extent % f->rows || G % f->groups || (f->units > 1 && extent >= (1ll << 25)))) f = nullptr;
+  if (!f && bwd) {
+    // which backward_t / backward_qt kernel, from the A/B on one box (profiles/ab_bwd_r4k_variants.txt; nu = units of 8 groups x
+    // 64 m): the wave-owned kernels need a few units per wave to amortise their pipeline fill, below that the round-3 kernel (8 waves share a unit)
+    // stays.  QT: 64-byte segments with 16 waves per CU (4096^2 cold 10.2 -> 8.5 us, 8192^2 30.9 -> 26.6); T: whole lines with 8 waves per CU
+    // (8192^2 cold 38.0 -> 36.5, 2048 x 14336 17.7 -> 15.2; the 64-byte form ties with the round-3 kernel there).  In the product build the product
+    // kernels are the only instantiations: QT never takes 3, T never 2.
+    // [r5] QT, large inputs with M % 128 == 0: 5 = the wave-owned kernel fed through a shared whole-line ring (bwd_qt_ring_kernel).  Cold it wins from ~12 units per CU
+    // (profiles/ab_bwd_r5x_ring_threshold.txt: 14336 x 4096 22.1 -> 20.6 us, 8192^2 26.1 -> 22.4, 8192 x 16384 55.1 -> 43.5; 11008 x 4096 ties, 6144^2 15.1 -> 15.5), warm
+    // (input in the MALL) the plain kernel stays ahead until ~32 per CU -- the rule goes by the cold numbers, as every streaming-op figure of the design record does.
+    const int64_t nu = batch * cdiv(m, 64) * cdiv(G, 8);
+    f = stream_form(op, op == OP_T ? (nu >= 6 * cus ? BWD_WAVE8 : BWD_ROUND3) : (ring_aligned && m % 128 == 0 && nu >= 12 * cus) ? QT_RING : nu >= 3 * cus ? BWD_WAVE4 : BWD_ROUND3);
+  } else if (!f && op == OP_SQ) {
+    // [r4] 512 columns per workgroup (16 waves: the row scales leave as 16-byte pieces) when n allows and every CU still gets a workgroup
+    // (1024 columns, two tiles per wave: slower again except warm at 8192^2 -- profiles/ab_sq_abl_r4ae.txt)
+    f = stream_form(op, (n % 512 == 0 && (a / 128) * (n / 512) >= cus) ? SQ_CT4 : SQ_CT1);
+  } else if (!f) {
+    // [r4] the wave-owned-lines forms (persistent waves, no workgroup barrier) are byte-identical and NOT faster (8192^2 cold 30.7 / 35.0 us against 28.4, warm 21.4 / 22.5
+    // against 21.2; profiles/ab_transpose_r4o.txt); 256 rows per workgroup (8-byte scale pieces per output row instead of 4) is byte-identical and slower -- the two workgroup
+    // barriers then wait for eight waves: 8192^2 cold 28.6 -> 31.5 us (profiles/ab_transpose_r4ak_8wave.txt): the one-shot kernel stays the product
+    f = stream_form(op, TR_ONE_SHOT);
+  }
+  int64_t units = batch * cdiv(extent, f->rows) * cdiv(G, f->groups), per_cu = f->per_cu;
+  if (op == OP_QT && f->form == BWD_ROUND3) {
+    // virtual tiles: units of 4 sibling m-tiles (bwd_quant_t_kernel's tile order); the grid is a multiple of 32 workgroups (4 siblings x 8 XCDs)
+    units = batch * cdiv(cdiv(m, 64), 4) * 4 * cdiv(G, 8);
+    // 49 KB of LDS per workgroup: three fit a CU.  A round of three per CU takes ~1.24x a round of two (8192^2: 6 rounds 20.7 us against 8 rounds
+    // 22.2 us; 4096^2, 2 rounds either way: 9.3 against 8.5 us): three when that wins the round count
+    per_cu = 1.24 * (double)cdiv(units, 3 * cus) < (double)cdiv(units, 2 * cus) ? 3 : 2;
+    units = cdiv(units, f->step) * f->step;
+  }
+  StreamLaunch r{f->form, cdiv(units, f->units), f->threads};
+  if (per_cu) r.grid = std::min(r.grid, std::max<int64_t>(f->step, cus * per_cu / f->step * f->step));
+  return r;
+}
+
 }  // namespace qamd

@@ -780,7 +780,7 @@ def test_in_tree_binaries_are_not_older_than_their_sources():
 
 
 def test_backward_op_kernel_rules(lib):
-    """[r4] Which kernel backward_t_bf16 / backward_qt_bf16 / backward_bf16_square_double_mxfp8 launch (capi.hip: bwd_kernel_rule, sq_column_tiles_rule), through
+    """[r4] Which kernel backward_t_bf16 / backward_qt_bf16 / backward_bf16_square_double_mxfp8 launch (quartet_bwd.hip.h: stream_launch_plan), through
     the dry-run hook (256-CU part): the thresholds of the one-box A/Bs, profiles/ab_bwd_r4m.txt and ab_sq_abl_r4ae.txt."""
     f = lib.qutlass_amd_debug_stream_plan
     f.restype = ctypes.c_int

@@ -301,7 +301,7 @@ def test_stream_k_mx_graph_replay(q):
 
 # ------------------------------------------------------------------------------------------------
 # [r4] backward_t_bf16 / backward_qt_bf16: wave-owned output lines (bwd_quant_tw_kernel, quartet_bwd.hip.h).  Three kernels sit behind one entry
-# point (capi.hip: bwd_kernel_choice): 1 = the round-3 kernel (small tensors), 2 = units of 4 scale groups (QT), 3 = units of 8 (T).  Each is
+# point (quartet_bwd.hip.h: stream_launch_plan): 1 = the round-3 kernel (small tensors), 2 = units of 4 scale groups (QT), 3 = units of 8 (T).  Each is
 # forced through the LAB build on ragged shapes against the oracle (quartet_bwd_sm120.cu:304-323 / :407-426), and the product rule is checked
 # against the round-3 kernel, byte for byte, on tensors large enough to take the new kernels.
 # ------------------------------------------------------------------------------------------------
@@ -340,7 +340,7 @@ def test_backward_wave_owned_kernels_equal_the_oracle_on_ragged_shapes(q, varian
 
 @pytest.mark.gpu
 def test_backward_product_rule_takes_the_wave_owned_kernels_and_equals_the_round3_kernel(q):
-    """tensors above the thresholds of bwd_kernel_choice (QT: 3 units per CU, T: 6), ragged in M and in the group count: the PRODUCT library's bytes
+    """tensors above the thresholds of stream_launch_plan (QT: 3 units per CU, T: 6), ragged in M and in the group count: the PRODUCT library's bytes
     (whatever kernel its rule picks) equal the round-3 kernel's, forced through the lab build -- and equal the lab build's own rule."""
     g = torch.Generator(device=DEV).manual_seed(5)
     h = _hadamard32()
