@@ -1454,8 +1454,8 @@ int launch_bwd_quant(const char* name, const BwdTParams& p, bool qt, bool hw, co
 // The clamped-SwiGLU kernels and moe_combine's bias form (quantize.hip.h) live in unit 5 with the other quantizers: the fused arm for R = 32 / 64 x method x
 // bias, the streaming activation with and without a bias, the combine.  The C entries (unit 1) have checked everything; these only pick the instantiation.
 int launch_swiglu_oai_quant(int rot, int method, bool bias, const QuantParams& p, hipStream_t s, int grid);
-int launch_swiglu_oai_stream(const SwigluOaiParams& p, int grid, hipStream_t s);
-int launch_moe_combine_bias(const MoeCombineBiasParams& p, int grid, hipStream_t s);
+int launch_swiglu_oai_stream(const SwigluOaiParams& p, const RowStreamLaunch& l, hipStream_t s);
+int launch_moe_combine_bias(const MoeCombineBiasParams& p, const RowStreamLaunch& l, hipStream_t s);
 #if QAMD_DEF(5)
 int launch_swiglu_oai_quant(int rot, int method, bool bias, const QuantParams& p, hipStream_t s, int grid) {
   auto go = [&](auto r_, auto m_) {
@@ -1469,13 +1469,13 @@ int launch_swiglu_oai_quant(int rot, int method, bool bias, const QuantParams& p
   else { if (method == QAMD_METHOD_QUEST) go(R64{}, Quest{}); else go(R64{}, AbsMax{}); }
   return check_launch("fused_swiglu_oai_quantize_kernel");
 }
-int launch_swiglu_oai_stream(const SwigluOaiParams& p, int grid, hipStream_t s) {
-  if (p.bias) hipLaunchKernelGGL(swiglu_oai_mul_bf16_kernel<true>, dim3(grid), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(swiglu_oai_mul_bf16_kernel<false>, dim3(grid), dim3(256), 0, s, p);
+int launch_swiglu_oai_stream(const SwigluOaiParams& p, const RowStreamLaunch& l, hipStream_t s) {
+  if (p.bias) hipLaunchKernelGGL(swiglu_oai_mul_bf16_kernel<true>, dim3(l.grid), dim3(l.threads), 0, s, p);
+  else hipLaunchKernelGGL(swiglu_oai_mul_bf16_kernel<false>, dim3(l.grid), dim3(l.threads), 0, s, p);
   return check_launch("swiglu_oai_mul_bf16_kernel");
 }
-int launch_moe_combine_bias(const MoeCombineBiasParams& p, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(moe_combine_bias_bf16_kernel<0>, dim3(grid), dim3(256), 0, s, p);
+int launch_moe_combine_bias(const MoeCombineBiasParams& p, const RowStreamLaunch& l, hipStream_t s) {
+  hipLaunchKernelGGL(moe_combine_bias_bf16_kernel<0>, dim3(l.grid), dim3(l.threads), 0, s, p);
   return check_launch("moe_combine_bias_bf16_kernel");
 }
 #endif
@@ -1919,8 +1919,8 @@ int qutlass_amd_silu_mul_bf16(const void* x, int64_t rows, int64_t inter, void* 
   if (!x || !out) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   SiluMulParams p;
   p.x = (const uint16_t*)x; p.out = (uint16_t*)out; p.chunks = rows * (inter / 8); p.cpr = (uint32_t)(inter / 8);
-  const int grid = (int)std::min<int64_t>(cdiv(p.chunks, 256), (int64_t)chip_cus() * 8);
-  hipLaunchKernelGGL(silu_mul_bf16_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  const RowStreamLaunch l = row_stream_plan(p.chunks, chip_cus());
+  hipLaunchKernelGGL(silu_mul_bf16_kernel<0>, dim3(l.grid), dim3(l.threads), 0, (hipStream_t)stream, p);
   return check_launch("silu_mul_bf16_kernel");
 }
 
@@ -2031,28 +2031,6 @@ int qutlass_amd_fused_gather_quantize_mxf8(const void* x, const void* h, int rot
                                     fmt);
 }
 
-// Combine: out[t] = sum_k w[t][k] * y[pos[t][k]] in the order and with the roundings moe_combine_bf16_kernel states (quantize.hip.h); slots outside [0, m) are skipped.
-int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, void* out, void* stream) {
-  const char* name = "moe_combine";
-  if (m < 0 || t < 0 || hdim <= 0 || m >= (1ll << 31) || t >= (1ll << 31) || hdim >= (1ll << 31))
-    return fail(QAMD_ERR_INVALID, "%s: bad shape (y (%lld, %lld), %lld tokens)", name, (long long)m, (long long)hdim, (long long)t);
-  if (hdim % 8) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of 8", name, (long long)hdim);
-  if (topk < 1 || topk > 32) return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, 32] (got %lld)", name, (long long)topk);
-  if (((uintptr_t)y | (uintptr_t)out) % 16) return fail(QAMD_ERR_INVALID, "%s: y and out must be 16-byte aligned", name);
-  if (t == 0) return QAMD_OK;
-  if ((!y && m > 0) || !pos || !weights || !out) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (m == 0) {   // no row to name: every slot is skipped and every sum is its start, +0 (the kernel reads row 0 for a skipped slot, so it wants one row)
-    if (hipMemsetAsync(out, 0, (size_t)(t * hdim * 2), (hipStream_t)stream) != hipSuccess) return fail(QAMD_ERR_HIP, "%s: hipMemsetAsync failed", name);
-    return QAMD_OK;
-  }
-  MoeCombineParams p;
-  p.y = (const uint16_t*)y; p.pos = pos; p.w = weights; p.out = (uint16_t*)out;
-  p.chunks = t * (hdim / 8); p.cpr = (uint32_t)(hdim / 8); p.m = (uint32_t)m; p.topk = (int)topk;
-  const int grid = (int)std::min<int64_t>(cdiv(p.chunks, 256), (int64_t)chip_cus() * 8);
-  hipLaunchKernelGGL(moe_combine_bf16_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-  return check_launch("moe_combine_bf16_kernel");
-}
-
 // ---- gpt-oss: the clamped SwiGLU with per-expert biases (quantize.hip.h, swiglu_oai_mul8), alone and fused into the MXFP4 quantizer; moe_combine with the down bias ----
 // alpha and limit -> the kernels' constants (SwigluOaiAct).  alpha * log2 e = c_hi + c_lo in fp64, c_hi rounded to 16 significant bits: with the gate's 8 the
 // product c_hi * gate is exact in fp32.  Outside [2^-100, 2^100] -- where c_hi or ln 2 * c_lo would leave fp32's normal range -- every element takes the fp64 path.
@@ -2094,8 +2072,7 @@ int qutlass_amd_swiglu_oai_mul_bf16(const void* x, int64_t rows, int64_t inter, 
   if (!x || !out) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   p.x = (const uint16_t*)x; p.out = (uint16_t*)out; p.bias = (const uint16_t*)bias; p.offs = offs; p.E = bias ? (int)e : 0;
   p.chunks = rows * (inter / 8); p.cpr = (uint32_t)(inter / 8);
-  const int grid = (int)std::min<int64_t>(cdiv(p.chunks, 256), (int64_t)chip_cus() * 8);
-  return launch_swiglu_oai_stream(p, grid, (hipStream_t)stream);
+  return launch_swiglu_oai_stream(p, row_stream_plan(p.chunks, chip_cus()), (hipStream_t)stream);
 }
 
 // fusedQuantizeMx(swiglu_oai_and_mul(x, ...), h) in one launch, byte for byte: the gated quantizer's chain with the activation's checks; flat scales only
@@ -2124,82 +2101,91 @@ int qutlass_amd_fused_swiglu_oai_quantize_mx(const void* x, const void* h, int r
   return launch_swiglu_oai_quant(rot, method, bias != nullptr, p, (hipStream_t)stream, grid);
 }
 
-// moe_combine with the down projection's per-expert bias added to every gathered row in bf16 (moe_combine_bias_bf16_kernel, quantize.hip.h)
-int qutlass_amd_moe_combine_bias_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, const void* bias,
-                                      const int32_t* offs, int64_t e, void* out, void* stream) {
+// Combine: out[t] = sum_k w[t][k] * y[pos[t][k]] in the order and with the roundings moe_combine_bf16_kernel states (quantize.hip.h); slots outside [0, m) are skipped.
+// has_bias: the form with the down projection's per-expert bias added to every gathered row in bf16 (moe_combine_bias_bf16_kernel); else bias, offs and e are not read.
+static int combine_impl(bool has_bias, const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, const void* bias,
+                        const int32_t* offs, int64_t e, void* out, void* stream) {
   const char* name = "moe_combine";
   if (m < 0 || t < 0 || hdim <= 0 || m >= (1ll << 31) || t >= (1ll << 31) || hdim >= (1ll << 31))
     return fail(QAMD_ERR_INVALID, "%s: bad shape (y (%lld, %lld), %lld tokens)", name, (long long)m, (long long)hdim, (long long)t);
   if (hdim % 8) return fail(QAMD_ERR_INVALID, "%s: the row length %lld must be a multiple of 8", name, (long long)hdim);
   if (topk < 1 || topk > 32) return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, 32] (got %lld)", name, (long long)topk);
   if (((uintptr_t)y | (uintptr_t)out) % 16) return fail(QAMD_ERR_INVALID, "%s: y and out must be 16-byte aligned", name);
-  if (int rc = swiglu_oai_check_bias(name, bias, offs, e)) return rc;
+  if (has_bias) if (int rc = swiglu_oai_check_bias(name, bias, offs, e)) return rc;
   if (t == 0) return QAMD_OK;
-  if ((!y && m > 0) || !pos || !weights || !out || !bias) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  if (m == 0) {   // no row to name: every slot is skipped and every sum is its start, +0
+  if ((!y && m > 0) || !pos || !weights || !out || (has_bias && !bias)) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (m == 0) {   // no row to name: every slot is skipped and every sum is its start, +0 (the kernels read row 0 for a skipped slot, so they want one row)
     if (hipMemsetAsync(out, 0, (size_t)(t * hdim * 2), (hipStream_t)stream) != hipSuccess) return fail(QAMD_ERR_HIP, "%s: hipMemsetAsync failed", name);
     return QAMD_OK;
   }
-  MoeCombineBiasParams p;
+  MoeCombineBiasParams p;   // (the plain kernel takes its first member)
   p.c.y = (const uint16_t*)y; p.c.pos = pos; p.c.w = weights; p.c.out = (uint16_t*)out;
   p.c.chunks = t * (hdim / 8); p.c.cpr = (uint32_t)(hdim / 8); p.c.m = (uint32_t)m; p.c.topk = (int)topk;
   p.bias = (const uint16_t*)bias; p.offs = offs; p.E = (int)e;
-  const int grid = (int)std::min<int64_t>(cdiv(p.c.chunks, 256), (int64_t)chip_cus() * 8);
-  return launch_moe_combine_bias(p, grid, (hipStream_t)stream);
+  const RowStreamLaunch l = row_stream_plan(p.c.chunks, chip_cus());
+  if (has_bias) return launch_moe_combine_bias(p, l, (hipStream_t)stream);
+  hipLaunchKernelGGL(moe_combine_bf16_kernel<0>, dim3(l.grid), dim3(l.threads), 0, (hipStream_t)stream, p.c);
+  return check_launch("moe_combine_bf16_kernel");
+}
+int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, void* out, void* stream) {
+  return combine_impl(false, y, m, hdim, pos, weights, t, topk, nullptr, nullptr, 0, out, stream);
+}
+int qutlass_amd_moe_combine_bias_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk, const void* bias,
+                                      const int32_t* offs, int64_t e, void* out, void* stream) {
+  return combine_impl(true, y, m, hdim, pos, weights, t, topk, bias, offs, e, out, stream);
 }
 
 // ---- MoE routing: the front of the chain (moe_route.hip.h) ---------------------------------------------------------------------------------------------------
 // Router logits -> top-k ids (exact: logit descending, expert index ascending) and softmax weights; one wave per token, one launch, no workspace.
+// Both routers: topk_check (the checks they share), their own checks and fill, moe_topk_plan (moe_route.hip.h), launch_topk -- one arm per kernel of the family, an error for any other.
 extern "C++" {
-template <typename T, bool LOADV>
-static void launch_topk_softmax(const MoeTopkParams& p, int grid, hipStream_t s) {
-  const int per_lane = (p.e + 63) / 64;   // columns a lane has to hold: 1 .. 16, in whole vectors of 16 bytes
-#define QAMD_TOPK_ARM(R_) hipLaunchKernelGGL((moe_topk_softmax_kernel<T, R_, LOADV>), dim3(grid), dim3(256), 0, s, p)
-  if constexpr (sizeof(T) == 4) { if (per_lane <= 4) { QAMD_TOPK_ARM(4); return; } }
-  if (per_lane <= 8) { QAMD_TOPK_ARM(8); return; }
-  QAMD_TOPK_ARM(16);
-#undef QAMD_TOPK_ARM
+struct TopkSoftmax { static constexpr const char* what = "moe_topk_softmax_kernel"; template <typename T, int R, bool V> static auto kernel() { return moe_topk_softmax_kernel<T, R, V>; } };
+struct TopkGrouped { static constexpr const char* what = "moe_topk_grouped_kernel"; template <typename T, int R, bool V> static auto kernel() { return moe_topk_grouped_kernel<T, R, V>; } };
+template <typename F, typename P>
+static int launch_topk(const char* name, int elem_bytes, const MoeTopkLaunch& l, const P& p, hipStream_t s) {
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), 0, s, p); return check_launch(F::what); };
+  constexpr auto arm = [](int eb, int r, bool v) { return eb * 64 + r * 2 + v; };   constexpr bool V = true, S = false;   using bf16 = uint16_t;   // (V / S: 16-byte vector loads / single columns)
+  switch (arm(elem_bytes, l.R, l.loadv)) {
+    case arm(2, 8, V): return go(F::template kernel<bf16, 8, V>());     case arm(2, 8, S): return go(F::template kernel<bf16, 8, S>());
+    case arm(2, 16, V): return go(F::template kernel<bf16, 16, V>());   case arm(2, 16, S): return go(F::template kernel<bf16, 16, S>());
+    case arm(4, 4, V): return go(F::template kernel<float, 4, V>());    case arm(4, 4, S): return go(F::template kernel<float, 4, S>());
+    case arm(4, 8, V): return go(F::template kernel<float, 8, V>());    case arm(4, 8, S): return go(F::template kernel<float, 8, S>());
+    case arm(4, 16, V): return go(F::template kernel<float, 16, V>());  case arm(4, 16, S): return go(F::template kernel<float, 16, S>());
+  }
+  return fail(QAMD_ERR_INVALID, "%s: this build holds no kernel for R = %d with %d-byte logits", name, l.R, elem_bytes);
+}
+template <typename IdT>   // the expert sort (further down): one launch or three, as moe_sort_plan says
+static void launch_moe_sort(const MoeSortParams& p, const MoeSortLaunch& l, hipStream_t s) {
+  if (l.launches == 1) { hipLaunchKernelGGL((moe_sort_kernel<IdT, 0>), dim3(1), dim3(MOE_SORT_NT), 0, s, p); return; }
+  hipLaunchKernelGGL((moe_sort_kernel<IdT, 1>), dim3(l.rows), dim3(MOE_SORT_NT), 0, s, p);
+  hipLaunchKernelGGL(moe_sort_scan_kernel<0>, dim3(1), dim3(MOE_SORT_NT), 0, s, p);
+  hipLaunchKernelGGL((moe_sort_kernel<IdT, 3>), dim3(l.rows), dim3(MOE_SORT_NT), 0, s, p);
 }
 }   // extern "C++"
-
-int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids, void* stream) {
-  const char* name = "moe_topk_softmax";
+static int topk_check(const char* name, int elem_bytes, int64_t t, int64_t e) {
   if (elem_bytes != 2 && elem_bytes != 4) return fail(QAMD_ERR_INVALID, "%s: logits must be bf16 (elem_bytes 2) or float32 (4), got elem_bytes %d", name, elem_bytes);
   if (t < 0 || t >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld tokens)", name, (long long)t);
   if (e < 1 || e > 1024) return fail(QAMD_ERR_INVALID, "%s: bad shape: the number of experts must be in [1, 1024] (got %lld)", name, (long long)e);
+  return QAMD_OK;
+}
+
+int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids, void* stream) {
+  const char* name = "moe_topk_softmax";
+  if (int rc = topk_check(name, elem_bytes, t, e)) return rc;
   if (topk < 1 || topk > 32 || topk > e) return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, min(E, 32)] (got %lld for E = %lld)", name, (long long)topk, (long long)e);
   if ((uintptr_t)logits % elem_bytes || (uintptr_t)weights % 4 || (uintptr_t)ids % 4) return fail(QAMD_ERR_INVALID, "%s: logits, weights and ids must be aligned to their element size", name);
   if (t == 0) return QAMD_OK;
   if (!logits || !weights || !ids) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   MoeTopkParams p;
   p.logits = logits; p.weights = weights; p.ids = ids; p.t = t; p.e = (int)e; p.topk = (int)topk; p.renorm = renormalize ? 1 : 0;
-  const int grid = (int)std::min<int64_t>(cdiv(t, 4), (int64_t)chip_cus() * 16);
-  const bool vec = (e * elem_bytes) % 16 == 0 && (uintptr_t)logits % 16 == 0;   // every row starts on a 16-byte boundary: 16-byte loads (same layout, same bits, either way)
-  hipStream_t s = (hipStream_t)stream;
-  if (elem_bytes == 2) { if (vec) launch_topk_softmax<uint16_t, true>(p, grid, s); else launch_topk_softmax<uint16_t, false>(p, grid, s); }
-  else { if (vec) launch_topk_softmax<float, true>(p, grid, s); else launch_topk_softmax<float, false>(p, grid, s); }
-  return check_launch("moe_topk_softmax_kernel");
+  return launch_topk<TopkSoftmax>(name, elem_bytes, moe_topk_plan(elem_bytes, e, t, (uintptr_t)logits % 16 == 0, chip_cus()), p, (hipStream_t)stream);
 }
 
 // Grouped top-k (DeepSeek-V2 / V3, Kimi-K2 routers): scores, a selection bias, a top-k inside the best groups; the same launch shape as moe_topk_softmax.
-extern "C++" {
-template <typename T, bool LOADV>
-static void launch_topk_grouped(const MoeGroupedParams& p, int grid, hipStream_t s) {
-  const int per_lane = (p.e + 63) / 64;
-#define QAMD_TOPKG_ARM(R_) hipLaunchKernelGGL((moe_topk_grouped_kernel<T, R_, LOADV>), dim3(grid), dim3(256), 0, s, p)
-  if constexpr (sizeof(T) == 4) { if (per_lane <= 4) { QAMD_TOPKG_ARM(4); return; } }
-  if (per_lane <= 8) { QAMD_TOPKG_ARM(8); return; }
-  QAMD_TOPKG_ARM(16);
-#undef QAMD_TOPKG_ARM
-}
-}   // extern "C++"
-
 int qutlass_amd_moe_topk_grouped(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
                                  const float* bias, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids, float* scores, void* stream) {
   const char* name = "moe_topk_grouped";
-  if (elem_bytes != 2 && elem_bytes != 4) return fail(QAMD_ERR_INVALID, "%s: logits must be bf16 (elem_bytes 2) or float32 (4), got elem_bytes %d", name, elem_bytes);
-  if (t < 0 || t >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (%lld tokens)", name, (long long)t);
-  if (e < 1 || e > 1024) return fail(QAMD_ERR_INVALID, "%s: bad shape: the number of experts must be in [1, 1024] (got %lld)", name, (long long)e);
+  if (int rc = topk_check(name, elem_bytes, t, e)) return rc;
   if (n_group < 1 || n_group > 64) return fail(QAMD_ERR_INVALID, "%s: bad shape: n_group must be in [1, 64] (got %lld)", name, (long long)n_group);
   if (e % n_group != 0) return fail(QAMD_ERR_INVALID, "%s: bad shape: n_group must divide E (got n_group = %lld for E = %lld)", name, (long long)n_group, (long long)e);
   if (topk_group < 1 || topk_group > n_group)
@@ -2220,45 +2206,14 @@ int qutlass_amd_moe_topk_grouped(const void* logits, int elem_bytes, int64_t t, 
   while ((n_group << (p.lg_l + 1)) <= 64) ++p.lg_l;   // L lanes per group in the group stage
   p.magic = (uint32_t)(((1ll << 22) + p.s - 1) / p.s);
   p.scale = routed_scaling_factor;
-  const int grid = (int)std::min<int64_t>(cdiv(t, 4), (int64_t)chip_cus() * 16);
-  // 16-byte loads and stores where every row of the logits (and of the scores, if asked for) starts on a 16-byte boundary: same layout, same bits, either way
-  const bool vec = (e * elem_bytes) % 16 == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)scores % 16 == 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (elem_bytes == 2) { if (vec) launch_topk_grouped<uint16_t, true>(p, grid, s); else launch_topk_grouped<uint16_t, false>(p, grid, s); }
-  else { if (vec) launch_topk_grouped<float, true>(p, grid, s); else launch_topk_grouped<float, false>(p, grid, s); }
-  return check_launch("moe_topk_grouped_kernel");
+  const bool aligned = (uintptr_t)logits % 16 == 0 && (uintptr_t)scores % 16 == 0;   // the scores, if asked for, are stored as 16-byte vectors too
+  return launch_topk<TopkGrouped>(name, elem_bytes, moe_topk_plan(elem_bytes, e, t, aligned, chip_cus()), p, (hipStream_t)stream);
 }
 
-// Expert sort.  Up to MOE_SORT_ONE_LAUNCH_MAX slots: one workgroup, one launch.  Beyond: count, scan, scatter -- three launches over caller scratch, workgroups of
-// `spb` consecutive slots (at least 4096 = 8 chunks of 64 per wave, and never more than 256 workgroups: the scratch stays below 1.01 MiB however large n is).
-// The bound is measured (profiles/bench_moe_route_mi355x.txt): one workgroup costs 2.6 + 2.2 us per 1024 slots (E = 8; 2.7 + 3.2 at E = 128),
-// three launches 18-19 us (24-25) from 4096 to 16384 slots; at 6144 slots one workgroup still wins (15.9 vs 18.5, 22.2 vs 23.9 us), at 8192 it has lost
-// (20.4 vs 19.0, 28.6 vs 24.7).  6144 is the largest measured size at which one launch is faster for both expert counts.
-constexpr int64_t MOE_SORT_ONE_LAUNCH_MAX = 6144;
-static int64_t moe_sort_one_launch_max() { return opt_moe_sort_one_launch_max() > 0 ? opt_moe_sort_one_launch_max() : MOE_SORT_ONE_LAUNCH_MAX; }
-static void moe_sort_geometry(int64_t n, int64_t& spb, int& rows) {
-  spb = cdiv(std::max<int64_t>(4096, cdiv(n, 256)), 512) * 512;
-  rows = (int)cdiv(n, spb);
-}
-
+// Expert sort: moe_sort_plan (moe_route.hip.h) -- the size of the scratch, the entry's check of it, the geometry it fills in and the launches all read that one result.
 int64_t qutlass_amd_moe_sort_workspace_bytes(int64_t n, int64_t num_experts) {
-  if (n <= moe_sort_one_launch_max() || n >= (1ll << 31) || num_experts < 1 || num_experts > 1024) return 0;
-  // sized by min(256, ceil(n / 4096)) rows, which the geometry never exceeds and which, unlike its row count, never shrinks as n grows
-  return (std::min<int64_t>(256, cdiv(n, 4096)) + 1) * (num_experts + 1) * 4;
+  return n >= (1ll << 31) || num_experts < 1 || num_experts > 1024 ? 0 : moe_sort_plan(n, num_experts, opt_moe_sort_one_launch_max()).ws_bytes;
 }
-
-extern "C++" {
-template <typename IdT>
-static void launch_moe_sort(MoeSortParams& p, hipStream_t s) {
-  if (!p.ws) {
-    hipLaunchKernelGGL((moe_sort_kernel<IdT, 0>), dim3(1), dim3(MOE_SORT_NT), 0, s, p);
-    return;
-  }
-  hipLaunchKernelGGL((moe_sort_kernel<IdT, 1>), dim3(p.rows), dim3(MOE_SORT_NT), 0, s, p);
-  hipLaunchKernelGGL(moe_sort_scan_kernel<0>, dim3(1), dim3(MOE_SORT_NT), 0, s, p);
-  hipLaunchKernelGGL((moe_sort_kernel<IdT, 3>), dim3(p.rows), dim3(MOE_SORT_NT), 0, s, p);
-}
-}   // extern "C++"
 
 int qutlass_amd_moe_sort(const void* topk_ids, int id_bytes, int64_t t, int64_t topk, int64_t num_experts, const int32_t* expert_map, int64_t g, int32_t* src_row,
                          int32_t* offs, int32_t* pos, void* workspace, int64_t workspace_bytes, void* stream) {
@@ -2270,20 +2225,19 @@ int qutlass_amd_moe_sort(const void* topk_ids, int id_bytes, int64_t t, int64_t 
   if (g < 0 || g >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: bad shape (expert_map of %lld entries)", name, (long long)g);
   if ((uintptr_t)topk_ids % id_bytes || ((uintptr_t)expert_map | (uintptr_t)src_row | (uintptr_t)offs | (uintptr_t)pos | (uintptr_t)workspace) % 4)
     return fail(QAMD_ERR_INVALID, "%s: topk_ids, expert_map, the results and the workspace must be aligned to their element size", name);
-  const int64_t n = t * topk, need = qutlass_amd_moe_sort_workspace_bytes(n, num_experts);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return fail(QAMD_ERR_INVALID, "%s: %lld slots need a workspace of %lld bytes (qutlass_amd_moe_sort_workspace_bytes), got %lld", name, (long long)n, (long long)need,
+  const int64_t n = t * topk;
+  const MoeSortLaunch l = moe_sort_plan(n, num_experts, opt_moe_sort_one_launch_max());
+  if (l.ws_bytes > 0 && (!workspace || workspace_bytes < l.ws_bytes))
+    return fail(QAMD_ERR_INVALID, "%s: %lld slots need a workspace of %lld bytes (qutlass_amd_moe_sort_workspace_bytes), got %lld", name, (long long)n, (long long)l.ws_bytes,
                 (long long)(workspace ? workspace_bytes : 0));
   if (n == 0) return QAMD_OK;
   if (!topk_ids || !src_row || !offs || !pos) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   MoeSortParams p;
-  p.ids = topk_ids; p.map = expert_map; p.src_row = src_row; p.offs = offs; p.pos = pos; p.ws = need > 0 ? (uint32_t*)workspace : nullptr;
-  p.n = n; p.g = (int)g; p.e = (int)num_experts; p.topk = (int)topk;
+  p.ids = topk_ids; p.map = expert_map; p.src_row = src_row; p.offs = offs; p.pos = pos; p.ws = l.launches == 3 ? (uint32_t*)workspace : nullptr;
+  p.n = n; p.g = (int)g; p.e = (int)num_experts; p.topk = (int)topk; p.spb = l.spb; p.rows = l.rows;
   p.nbits = 0;
   while ((num_experts >> p.nbits) != 0) ++p.nbits;   // keys are 0 .. E
-  if (need > 0) moe_sort_geometry(n, p.spb, p.rows);
-  else { p.spb = cdiv(n, 512) * 512; p.rows = 1; }
-  if (id_bytes == 8) launch_moe_sort<int64_t>(p, (hipStream_t)stream); else launch_moe_sort<int32_t>(p, (hipStream_t)stream);
+  if (id_bytes == 8) launch_moe_sort<int64_t>(p, l, (hipStream_t)stream); else launch_moe_sort<int32_t>(p, l, (hipStream_t)stream);
   return check_launch("moe_sort_kernel");
 }
 
@@ -2299,16 +2253,54 @@ int qutlass_amd_moe_sort(const void* topk_ids, int id_bytes, int64_t t, int64_t 
 //      8192^2, 23.4 vs 26.5 at 4096 x 14336 -- device time, every size measured (profiles/ab_blocked_quant_r3y.txt); with the GEMM behind it: 4096 x 14336 x 4096
 //      123.2 vs 124.5 us (profiles/bench_r4c.json).  It never returns 3: the reference's three-launch flow stays available as fusedQuantizeMx + to_blocked + matmul.
 // Thresholds scale with the CU count of the current device.  No GPU work.
-int qutlass_amd_activation_path_launches(int64_t M, int64_t N, int64_t K, int rot) {
-  if (M <= 0 || N <= 0 || K <= 0) return 2;
-  const int cus = chip_cus();
-  if (M > 16 || rot != 32 || N >= 32ll * cus || K % 128) return 2;
+static int activation_path_plan(int64_t M, int64_t N, int64_t K, int rot, int cus) {
+  if (M <= 0 || N <= 0 || K <= 0 || M > 16 || rot != 32 || N >= 32ll * cus || K % 128) return 2;
   // [r6] re-taken after the decode forms made the GEMM of the two-launch path faster (N = K = 4096, M <= 16: 4.6-5.3 -> 2.85-3.0 us; tools/calib_actpath.py,
   // profiles/calib_actpath_r7.txt): two launches now take 5.2-5.7 us at N = K = 4096 where the one-launch kernel takes 5.1 / 5.3 / 6.2 / 8.1 (M = 1 / 4 / 8 / 16), 6.4 against
   // 8.4-8.8 at 4096 x 8192 -- one launch keeps M <= 4 with K <= 4096 (4096 x 6144: a tie) and M <= 8 with K <= 2048 (3.8-4.4 against 4.6-4.9); rounds 3-5: M <= 4: K <= 8192,
   // M <= 8: K <= 6144, M <= 16: K <= 4096
   return K <= (M <= 4 ? 4096 : M <= 8 ? 2048 : 0) ? 1 : 2;
 }
+int qutlass_amd_activation_path_launches(int64_t M, int64_t N, int64_t K, int rot) { return activation_path_plan(M, N, K, rot, chip_cus()); }
+
+#if QAMD_BENCH
+// [r6] lab ("gemm_variant" 580): the hand-off form of the one-launch layer (gemm_mx_os16_fq_kernel: the quantizer's body on the first workgroups, the decode form's K walk
+// behind one arrival counter) on a scratch buffer the LAB library allocates once -- an experiment's plumbing, not an API (the product would take caller scratch)
+static int fusedq_lab_handoff(const char* name, const void* x, const void* h, int method, const void* B, const void* B_sf, const float* alpha, void* D, int64_t M,
+                              int64_t N, int64_t K, int tn, hipStream_t st) {
+  static void* scratch = nullptr;
+  if (!scratch && hipMalloc(&scratch, 1 << 20) != hipSuccess) return fail(QAMD_ERR_HIP, "%s: lab scratch", name);
+  const int64_t CB = cdiv(K / 32, 4);
+  FqOsParams P;
+  P.q.x = (const uint16_t*)x; P.q.h = (const uint16_t*)h; P.q.out = (uint8_t*)scratch; P.q.out_sf = (uint8_t*)scratch + (256 << 10); P.q.out_mask = nullptr; P.q.global_scale = nullptr;
+  P.q.numel = M * K; P.q.ntiles = (int)cdiv(M * K, 1024); P.q.sf_rows = (int)M; P.q.sf_cols = (int)(K / 32);
+  GemmParams& g = P.g;
+  g.A = (const uint8_t*)scratch; g.B = (const uint8_t*)B; g.SFA = (const uint8_t*)scratch + (256 << 10); g.SFB = (const uint8_t*)B_sf; g.alpha = alpha; g.D = (uint16_t*)D;
+  g.M = (int)M; g.N = (int)N; g.K = (int)K; g.ldd = (int)N;
+  g.a_bytes = (uint32_t)(M * (K / 2)); g.b_bytes = (uint32_t)(N * (K / 2)); g.sfa_bytes = (uint32_t)(CB * 512); g.sfb_bytes = (uint32_t)(cdiv(N, 128) * CB * 512);
+  g.pp_shift = 0; g.pp_flags = 0; g.dbg = nullptr; g.ws = nullptr; g.splits = 1; g.ctr = nullptr; g.tag = 0; g.sk_tiles = 0;
+  g.tiles_m = 1; g.tiles_n = (int)cdiv(N, tn); g.raster_magic = 0;
+  P.flag = (unsigned long long*)((uint8_t*)scratch + (512 << 10));
+  P.tag = (next_launch_tag() & ((1ull << 56) - 1)) << 8;
+  P.nq = (int)std::min<int64_t>(cdiv(P.q.ntiles, 4), g.tiles_n);
+  const int64_t KT = cdiv(K, 256);
+  const dim3 grid(g.tiles_n), block(256);
+#define QAMD_FQOS(TN_, SPW_)                                                                                                                     \
+  do {                                                                                                                                         \
+    if (method == QAMD_METHOD_ABSMAX) hipLaunchKernelGGL((gemm_mx_os16_fq_kernel<Os16Cfg<SPW_, 4, 0, TN_>, METHOD_ABSMAX>), grid, block, 0, st, P); \
+    else hipLaunchKernelGGL((gemm_mx_os16_fq_kernel<Os16Cfg<SPW_, 4, 0, TN_>, METHOD_QUEST>), grid, block, 0, st, P);                              \
+  } while (0)
+  if (tn == 16) { if (KT <= 16) QAMD_FQOS(16, 4); else QAMD_FQOS(16, 8); }
+  else if (tn == 32 && KT <= 16) QAMD_FQOS(32, 4);
+  else if (tn == 48 && KT <= 16) QAMD_FQOS(48, 4);
+  else if (tn == 56 && KT <= 16) QAMD_FQOS(56, 4);
+  else return fail(QAMD_ERR_INVALID, "%s: lab variant 580 has no instantiation for this shape", name);
+#undef QAMD_FQOS
+  return check_launch("gemm_mx_os16_fq_kernel");
+}
+#endif
+// rows per rotation tile: the smallest of 4 / 8 / 16 / 32 that holds the batch (fewer rows = more scale groups per tile = fewer rotate + quantize chains per K segment, gemm_mx_fusedq.hip.h)
+static int fusedq_plan(int64_t M) { return M <= 4 ? 4 : M <= 8 ? 8 : M <= 16 ? 16 : 32; }
 
 // decode-time activation path in one launch (gemm_mx_fusedq.hip.h): D = alpha * Q(x . h) (B . SFB)^T for M <= 32
 int qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn(const void* x, const void* h, int rot, int method, const void* B, const void* B_sf,
@@ -2322,41 +2314,7 @@ int qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn(const void* x, const void* h,
   if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
   if (N * (K / 2) >= (1ll << 31) || M * K * 2 >= (1ll << 31) || cdiv(N, 32) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: operand larger than 2 GiB is not supported", name);
 #if QAMD_BENCH
-  // [r6] lab ("gemm_variant" 580): the hand-off form of the one-launch layer (gemm_mx_os16_fq_kernel: the quantizer's body on the first workgroups, the decode form's K walk
-  // behind one arrival counter) on a scratch buffer the LAB library allocates once -- an experiment's plumbing, not an API (the product would take caller scratch)
-  if (opt_gemm_variant() == 580 && M <= 16 && K <= 8192 && os16_tn(N, chip_cus()) != 0) {
-    static void* scratch = nullptr;
-    if (!scratch && hipMalloc(&scratch, 1 << 20) != hipSuccess) return fail(QAMD_ERR_HIP, "%s: lab scratch", name);
-    const int64_t CB = cdiv(K / 32, 4);
-    FqOsParams P;
-    P.q.x = (const uint16_t*)x; P.q.h = (const uint16_t*)h; P.q.out = (uint8_t*)scratch; P.q.out_sf = (uint8_t*)scratch + (256 << 10); P.q.out_mask = nullptr; P.q.global_scale = nullptr;
-    P.q.numel = M * K; P.q.ntiles = (int)cdiv(M * K, 1024); P.q.sf_rows = (int)M; P.q.sf_cols = (int)(K / 32);
-    GemmParams& g = P.g;
-    g.A = (const uint8_t*)scratch; g.B = (const uint8_t*)B; g.SFA = (const uint8_t*)scratch + (256 << 10); g.SFB = (const uint8_t*)B_sf; g.alpha = alpha; g.D = (uint16_t*)D;
-    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.ldd = (int)N;
-    g.a_bytes = (uint32_t)(M * (K / 2)); g.b_bytes = (uint32_t)(N * (K / 2)); g.sfa_bytes = (uint32_t)(CB * 512); g.sfb_bytes = (uint32_t)(cdiv(N, 128) * CB * 512);
-    g.pp_shift = 0; g.pp_flags = 0; g.dbg = nullptr; g.ws = nullptr; g.splits = 1; g.ctr = nullptr; g.tag = 0; g.sk_tiles = 0;
-    const int tn = os16_tn(N, chip_cus());
-    g.tiles_m = 1; g.tiles_n = (int)cdiv(N, tn); g.raster_magic = 0;
-    P.flag = (unsigned long long*)((uint8_t*)scratch + (512 << 10));
-    P.tag = (next_launch_tag() & ((1ull << 56) - 1)) << 8;
-    P.nq = (int)std::min<int64_t>(cdiv(P.q.ntiles, 4), g.tiles_n);
-    const int64_t KT = cdiv(K, 256);
-    const dim3 grid(g.tiles_n), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define QAMD_FQOS(TN_, SPW_)                                                                                                                     \
-    do {                                                                                                                                         \
-      if (method == QAMD_METHOD_ABSMAX) hipLaunchKernelGGL((gemm_mx_os16_fq_kernel<Os16Cfg<SPW_, 4, 0, TN_>, METHOD_ABSMAX>), grid, block, 0, st, P); \
-      else hipLaunchKernelGGL((gemm_mx_os16_fq_kernel<Os16Cfg<SPW_, 4, 0, TN_>, METHOD_QUEST>), grid, block, 0, st, P);                              \
-    } while (0)
-    if (tn == 16) { if (KT <= 16) QAMD_FQOS(16, 4); else QAMD_FQOS(16, 8); }
-    else if (tn == 32 && KT <= 16) QAMD_FQOS(32, 4);
-    else if (tn == 48 && KT <= 16) QAMD_FQOS(48, 4);
-    else if (tn == 56 && KT <= 16) QAMD_FQOS(56, 4);
-    else return fail(QAMD_ERR_INVALID, "%s: lab variant 580 has no instantiation for this shape", name);
-#undef QAMD_FQOS
-    return check_launch("gemm_mx_os16_fq_kernel");
-  }
+  if (const int tn = opt_gemm_variant() == 580 && M <= 16 && K <= 8192 ? os16_tn(N, chip_cus()) : 0) return fusedq_lab_handoff(name, x, h, method, B, B_sf, alpha, D, M, N, K, tn, (hipStream_t)stream);
 #endif
   FusedQParams p;
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.B = (const uint8_t*)B; p.SFB = (const uint8_t*)B_sf; p.alpha = alpha; p.D = (uint16_t*)D;
@@ -2364,22 +2322,19 @@ int qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn(const void* x, const void* h,
   p.x_bytes = (uint32_t)(M * K * 2); p.b_bytes = (uint32_t)(N * (K / 2)); p.sfb_bytes = (uint32_t)(cdiv(N, 128) * cdiv(K / 32, 4) * 512);
   const dim3 grid((unsigned)cdiv(N, 32), 1), block(512);
   hipStream_t s = (hipStream_t)stream;
-  const bool hw = opt_hw_fp4();
-  // rows per rotation tile: the smallest of 4 / 8 / 16 / 32 that holds the batch (fewer rows = more scale groups per tile = fewer
-  // rotate + quantize chains per K segment, gemm_mx_fusedq.hip.h)
-  const int vr = M <= 4 ? 4 : M <= 8 ? 8 : M <= 16 ? 16 : 32;
-#define QAMD_FQ(METH_, HW_, VR_) hipLaunchKernelGGL((gemm_mx_fusedq_kernel<METH_, HW_, VR_>), grid, block, 0, s, p)
-#define QAMD_FQ_VR(METH_, HW_) \
-  switch (vr) { case 4: QAMD_FQ(METH_, HW_, 4); break; case 8: QAMD_FQ(METH_, HW_, 8); break; case 16: QAMD_FQ(METH_, HW_, 16); break; default: QAMD_FQ(METH_, HW_, 32); }
+  auto go = [&](auto meth_, auto hw_) {   // (method, e2m1 encoder: integral constants; the software encoder is lab-only) x the plan's rows per rotation tile
+    switch (fusedq_plan(M)) {
+      case 4: hipLaunchKernelGGL((gemm_mx_fusedq_kernel<meth_(), hw_(), 4>), grid, block, 0, s, p); break;
+      case 8: hipLaunchKernelGGL((gemm_mx_fusedq_kernel<meth_(), hw_(), 8>), grid, block, 0, s, p); break;
+      case 16: hipLaunchKernelGGL((gemm_mx_fusedq_kernel<meth_(), hw_(), 16>), grid, block, 0, s, p); break;
+      default: hipLaunchKernelGGL((gemm_mx_fusedq_kernel<meth_(), hw_(), 32>), grid, block, 0, s, p);
+    }
+  };
+  using Quest = std::integral_constant<int, METHOD_QUEST>; using AbsMax = std::integral_constant<int, METHOD_ABSMAX>;
 #if QAMD_BENCH
-  if (!hw) {
-    if (method == QAMD_METHOD_ABSMAX) { QAMD_FQ_VR(METHOD_ABSMAX, false) } else { QAMD_FQ_VR(METHOD_QUEST, false) }
-  } else
+  if (!opt_hw_fp4()) { if (method == QAMD_METHOD_ABSMAX) go(AbsMax{}, std::false_type{}); else go(Quest{}, std::false_type{}); } else
 #endif
-  if (method == QAMD_METHOD_ABSMAX) { QAMD_FQ_VR(METHOD_ABSMAX, true) } else { QAMD_FQ_VR(METHOD_QUEST, true) }
-  (void)hw;
-#undef QAMD_FQ_VR
-#undef QAMD_FQ
+  if (method == QAMD_METHOD_ABSMAX) go(AbsMax{}, std::true_type{}); else go(Quest{}, std::true_type{});
   return check_launch("gemm_mx_fusedq_kernel");
 }
 
@@ -2545,6 +2500,22 @@ int qutlass_amd_debug_stream_launch_plan(int op, int64_t a, int64_t b, int64_t c
   if (l.form == SF_NONE) return -1;
   out[0] = l.form; out[1] = (int)l.grid; out[2] = l.threads;
   return 1;
+}
+
+// debug only (not declared in the public header): the launch plans of the ops around the grouped GEMMs on a part of `cus` CUs -- the functions their entries run -- after the entries'
+// own checks of these arguments, no GPU touched.  Returns the number of ints written to out, or -1: an argument the op rejects, no such op, cus <= 0, a null out, cap too small.
+//   op 0  row_stream_plan (silu_and_mul, swiglu_oai_and_mul, both moe_combine forms): a = chunks > 0 -> {workgroups, threads};   op 3  fusedq_plan: a = M -> {rows per rotation tile}
+//   op 1  moe_topk_plan (both routers): a = elem_bytes, b = E, c = T, plus bit 62 of c when every row's pointers are 16-byte aligned -> {R, vector loads, workgroups, threads}
+//   op 2  moe_sort_plan: (a, b, c) = (T * topk, E, the one-launch bound or 0 for the product's) -> {launches, slots per workgroup, rows, workspace bytes};   op 4  activation_path_plan at rot = 32: (M, N, K) -> {launches}
+int qutlass_amd_debug_moe_launch_plan(int op, int64_t a, int64_t b, int64_t c, int cus, int* out, int cap) {
+  const int64_t t = c & ~(1ll << 62);
+  auto put = [&](std::initializer_list<int64_t> v) { return (int)v.size() <= cap ? (std::copy(v.begin(), v.end(), out), (int)v.size()) : -1; };
+  if (!out || cus <= 0) return -1;
+  if (op == 0 && a > 0) { const RowStreamLaunch l = row_stream_plan(a, cus); return put({l.grid, l.threads}); }
+  if (op == 1 && a == (int)a && !topk_check("debug_moe_launch_plan", (int)a, t, b)) { const MoeTopkLaunch l = moe_topk_plan((int)a, b, t, c >> 62 & 1, cus); return put({l.R, l.loadv, l.grid, l.threads}); }
+  if (op == 2 && a >= 0 && a < (1ll << 31) && b >= 1 && b <= 1024 && c >= 0) { const MoeSortLaunch l = moe_sort_plan(a, b, c); return put({l.launches, l.spb, l.rows, l.ws_bytes}); }
+  if (op == 3 && a >= 1 && a <= 32) return put({fusedq_plan(a)});
+  return op == 4 ? put({activation_path_plan(a, b, c, 32, cus)}) : -1;
 }
 
 // [r4] debug only (not declared in the public header): the grouped-raster decode of the persistent kernels (common.hip.h raster_decode, the SAME function the

@@ -339,6 +339,14 @@ __global__ __launch_bounds__(256) void moe_topk_grouped_kernel(const MoeGroupedP
   }
 }
 
+// The launch of either router: a pure function of the shape, the CU count and whether the entry found its pointers 16-byte aligned (with a row length of whole vectors: 16-byte loads
+// and stores; same layout, same bits, either way).  R = the smallest instantiated size with R * 64 >= E: 8 or 16, and 4 for float32 logits alone (four floats fill a vector, four bf16 do not).
+struct MoeTopkLaunch { int R; bool loadv; int grid, threads; };
+inline MoeTopkLaunch moe_topk_plan(int elem_bytes, int64_t e, int64_t t, bool rows_16B_aligned, int64_t cus) {
+  const int64_t per_lane = (e + 63) / 64;   // columns a lane has to hold: 1 .. 16, in whole vectors of 16 bytes
+  return {elem_bytes == 4 && per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : 16, rows_16B_aligned && (e * elem_bytes) % 16 == 0, (int)std::min<int64_t>((t + 3) / 4, cus * 16), 256};
+}
+
 // ---- expert sort ------------------------------------------------------------------------------------------------------------------------------------------
 // A counting sort on key = expert id, or E for a dropped slot (an id outside [0, E), before or after expert_map).  Stability comes from the order of the counts,
 // not from any order of execution: a workgroup takes `spb` consecutive slots, each of its 8 waves a consecutive run of 64-slot chunks, and
@@ -512,6 +520,22 @@ __global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_scan_kernel(const MoeSor
       if (k < p.e) p.offs[k] = (int32_t)run;
     }
   }
+}
+
+// The launch of the sort: a pure function of the slots n = T * topk in [0, 2^31), E and the one-launch bound (0 = the product's; the lab option "moe_sort_one_launch_max").  The scratch
+// is sized by min(256, ceil(n / 4096)) rows, which the row count never exceeds (spb >= 4096 and spb >= n / 256) and which, unlike it, never shrinks as n grows.
+// Up to MOE_SORT_ONE_LAUNCH_MAX slots: one workgroup, one launch.  Beyond: count, scan, scatter -- three launches over caller scratch, workgroups of
+// `spb` consecutive slots (at least 4096 = 8 chunks of 64 per wave, and never more than 256 workgroups: the scratch stays below 1.01 MiB however large n is).
+// The bound is measured (profiles/bench_moe_route_mi355x.txt): one workgroup costs 2.6 + 2.2 us per 1024 slots (E = 8; 2.7 + 3.2 at E = 128),
+// three launches 18-19 us (24-25) from 4096 to 16384 slots; at 6144 slots one workgroup still wins (15.9 vs 18.5, 22.2 vs 23.9 us), at 8192 it has lost
+// (20.4 vs 19.0, 28.6 vs 24.7).  6144 is the largest measured size at which one launch is faster for both expert counts.
+constexpr int64_t MOE_SORT_ONE_LAUNCH_MAX = 6144;
+struct MoeSortLaunch { int launches; int64_t spb; int rows; int64_t ws_bytes; };   // 1 or 3; MoeSortParams::spb, ::rows; the caller's scratch (0 for one launch)
+inline MoeSortLaunch moe_sort_plan(int64_t n, int64_t num_experts, int64_t one_launch_max) {
+  auto cdiv = [](int64_t x, int64_t y) { return (x + y - 1) / y; };
+  if (n <= (one_launch_max > 0 ? one_launch_max : MOE_SORT_ONE_LAUNCH_MAX)) return {1, cdiv(n, 512) * 512, 1, 0};
+  const int64_t spb = cdiv(std::max<int64_t>(4096, cdiv(n, 256)), 512) * 512;
+  return {3, spb, (int)cdiv(n, spb), (std::min<int64_t>(256, cdiv(n, 4096)) + 1) * (num_experts + 1) * 4};
 }
 
 }  // namespace qamd

@@ -1099,6 +1099,11 @@ __global__ __launch_bounds__(256) void fused_gather_quantize_mxf8_kernel(const Q
   fused_quantize_body<R, false, METHOD_ABSMAX, false, true, false, true, false, true, false, FMT>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// The launch of the four row-stream ops below (silu_and_mul, swiglu_oai_and_mul, moe_combine with and without a bias): a pure function of the 16-byte chunks to write and
+// the CU count (capi.hip chip_cus; the debug entry passes its own).  A thread per chunk until ROW_STREAM_WG_PER_CU workgroups per CU are out; the kernels stride over the rest.
+constexpr int ROW_STREAM_WG_PER_CU = 8;   struct RowStreamLaunch { int grid, threads; };
+inline RowStreamLaunch row_stream_plan(int64_t chunks, int64_t cus) { return {(int)std::min<int64_t>((chunks + 255) / 256, cus * ROW_STREAM_WG_PER_CU), 256}; }
+
 // silu_and_mul: x (rows, 2 I) bf16 -> out (rows, I) bf16, out[r][c] = act(x[r][c], x[r][I + c]) (silu_mul8 above).  Streaming, 4 B in + 2 B out per element: a
 // thread takes 16-byte chunks (8 elements; I % 8 == 0) chunk = first + k * step, kept as (row, chunk within the row) with a carry-propagating add -- no division in
 // the loop -- and 64-bit addresses, so neither operand has a size limit below rows, I < 2^31.
