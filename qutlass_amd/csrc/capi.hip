@@ -12,6 +12,7 @@
 #include "../../include/qutlass_amd.h"
 #include "gemm_mx.hip.h"
 #include "gemm_mx_deepp.hip.h"
+#include "gemm_mx_deepp16.hip.h"
 #if QAMD_BENCH   // csrc/lab/: sources of the LAB library only -- not read by the product build, not shipped by setup.py
 #include "lab/gemm_mx_duo.hip.h"         // [r6] the 8-wave persistent kernel (built, bit-identical, slower under the power cap: DESIGN.md section 7)
 #include "lab/gemm_mx_deepp_lab.hip.h"   // the lab copy (namespace qamd::labk): traces, ablations, stream-K, retirement experiments
@@ -197,7 +198,9 @@ inline int deepp_grid(int tiles) {
 }
 
 // persistent deep schedule (gemm_mx_deepp.hip.h): one workgroup per CU walks the tiles; 136 KiB of static LDS
-template <class C, bool TRACE = false, int ST_AUX = 0, int LAB = 0>
+// ONEFORM: MFMA shape of the one-tile form (grid == tile count, even stage count): 0 = the product's choice (kDeeppOneTile16, gemm_mx_deepp16.hip.h); 32 / 16 force
+// v_mfma_scale_f32_32x32x64 / _16x16x128 (lab: "gemm_variant" 190 / 191, so that both can be timed in one process and small grids reach either)
+template <class C, bool TRACE = false, int ST_AUX = 0, int LAB = 0, int ONEFORM = 0>
 int launch_gemm_deepp(GemmParams p, hipStream_t s) {
   p.tiles_m = (int)cdiv(p.M, C::BM);
   p.tiles_n = (int)cdiv(p.N, C::BN);
@@ -224,7 +227,12 @@ int launch_gemm_deepp(GemmParams p, hipStream_t s) {
   const bool odd = (kt & 1) && kt >= 3, one = grid == p.tiles_m * p.tiles_n;
   if (odd && one) hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX, true, true>), dim3(grid), dim3(C::THREADS), 0, s, p);
   else if (odd) hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX, true, false>), dim3(grid), dim3(C::THREADS), 0, s, p);
-  else if (one) hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX, false, true>), dim3(grid), dim3(C::THREADS), 0, s, p);
+  else if (one) {
+    static_assert(ONEFORM == 0 || ONEFORM == 16 || ONEFORM == 32, "one-tile form");
+    static_assert(ONEFORM == 0 || QAMD_BENCH, "forced one-tile forms: lab build only");
+    if constexpr (ONEFORM == 16 || (ONEFORM == 0 && kDeeppOneTile16)) hipLaunchKernelGGL((gemm_mx_deepp16_kernel<C, ST_AUX>), dim3(grid), dim3(C::THREADS), 0, s, p);
+    else hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX, false, true>), dim3(grid), dim3(C::THREADS), 0, s, p);
+  }
   else hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX>), dim3(grid), dim3(C::THREADS), 0, s, p);
   return check_launch("gemm_mx_deepp_kernel");
 }
@@ -737,7 +745,10 @@ int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name
 #if QAMD_BENCH
     if (v == 89) return launch_gemm_deepp_sk<GemmCfg<256, 256, 2, 2, 4, false>>(p, s);
 #endif
-    if (v == 90) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17>(p, s);
+    // The one-tile form of 90: the product's is the 16x16x128 one (kDeeppOneTile16).  In the LAB library 90 keeps the 32x32x64 form and 191 is the product's: the kernels the
+    // tests compare 90 with bit for bit (the 8-wave kernel 87 / 88, the ring and stream-K kernels) all group K by 64 per MFMA, and outside the exact regime of
+    // docs/history.md section 3.1 the grouping shows (random bytes with scale bytes 121 ... 129 at 4096^3: 23 of 16.8 M outputs differ in their last bf16 bit).
+    if (v == 90) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, QAMD_BENCH ? 32 : 0>(p, s);
     if (v == 98) return launch_gemm_hetero<GemmCfg<256, 256, 2, 2, 4, false>, GemmCfg<128, 128, 2, 2, 4, false, 0, 4>, 17>(p, s);
     // [r6] K split inside the workgroup (gemm_mx_ks.hip.h): 561 = 32x32 tiles, 562 = 32x64.  Ring depth by the K stage count: a short K pays for a deep ring's prologue
     // (4096^2 weights, M <= 64: 4.16 us 4-deep, 4.47 us 8-deep), a long one needs the stages in flight (8192^2: 9.4 us 4-deep, 7.4 us 6-deep; profiles/calib_ks_r6*.txt)
@@ -766,6 +777,9 @@ int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name
     if (v == 87) return launch_gemm_duo<GemmCfg<256, 256, 2, 4, 4, false>, 17, 1>(p, s);
     if (v == 86) return launch_gemm_duo<GemmCfg<256, 256, 2, 4, 4, false>, 17, 0, true>(p, s);
     if (v == 298) return launch_gemm_hetero<GemmCfg<256, 256, 2, 2, 4, false>, GemmCfg<128, 128, 2, 2, 4, false, 128, 4>, 17>(p, s);   // residual tiles with ABL_READS_FIRST
+    // 90 with the one-tile form forced (grid == tile count and an even stage count; any other launch runs as 90): 190 = 32x32x64 MFMAs, 191 = 16x16x128 (gemm_mx_deepp16.hip.h)
+    if (v == 190) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 32>(p, s);
+    if (v == 191) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 16>(p, s);
     if (v == 91) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, true, 17>(p, s);   //   + phase timestamps of workgroup 0 (qutlass_amd_debug_set_trace_buffer)
     if (v == 92) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 2>(p, s);       //   output stores nt
     if (v == 93) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 16>(p, s);      //   sc1

@@ -19,6 +19,7 @@
 #   fullcmp   tools/full_compare.py (configs C2, C3, C5: every output against the fp64 dequant-matmul oracle)
 #   absq / absf   tools/ab_sq_abl.py / ab_sf_stores.py (what the scale-byte stores of the transposing ops cost; square_double workgroup shapes)
 #   testq     the GPU tests of the quantizers            tracenv   stage + hand-off trace of the persistent NVFP4 kernel (lab variant 44)
+#   eub16     tests/native/energy_ubench16 (built here: scaled FP4 MFMA 32x32x64 against 16x16x128, joules per flop under the power cap, both shapes in one process)
 #   contention   tools/final_stage_contention.py (stage trace of the persistent MXFP4 kernel at 8 / 64 / 256 workgroups, same work per workgroup: is the final stage's cost the chip-wide store burst?)
 #   ablib / ablibnv / ablibmx / ablibmid   two BUILDS of the library side by side (tools/ab_lib_shapes.py, ab_lib_gemm.py): copy the old one to
 #             build/exp/libqamd_base.so first (or set AB_OLD / AB_NEW / AB_FMT); small + mid-size shapes, NVFP4 large, MXFP4 / MXFP8 large + headline
@@ -72,6 +73,7 @@ PY
     contention) timeout 300 python tools/final_stage_contention.py > $O/final_stage_contention.txt 2> $O/final_stage_contention.err; echo "contention rc=$?"; cat $O/final_stage_contention.txt; tail -3 $O/final_stage_contention.err ;;
     abmx)   timeout 900 python tools/ab_mxsk.py > $O/ab_mxsk.txt 2> $O/ab_mxsk.err; echo "abmx rc=$?"; cat $O/ab_mxsk.txt; tail -3 $O/ab_mxsk.err ;;
     hazard) (cd tests/native && hipcc --offload-arch=gfx950 -O2 store_hazard_probe.hip -o store_hazard_probe 2>/dev/null); timeout 120 tests/native/store_hazard_probe > $O/store_hazard_probe.txt 2>&1; echo "hazard rc=$?"; cat $O/store_hazard_probe.txt ;;
+    eub16) (cd tests/native && hipcc --offload-arch=gfx950 -O3 -w -std=c++17 energy_ubench16.hip -o energy_ubench16 -lrocm_smi64); timeout 300 tests/native/energy_ubench16 1.0 3 > $O/energy_ubench16.txt 2>&1; echo "eub16 rc=$?"; grep -E 'BANKS|COMPARE' $O/energy_ubench16.txt ;;
     xposeub) (cd tests/native && hipcc --offload-arch=gfx950 -O3 -w xpose_traffic_ubench.hip -o xpose_traffic_ubench); timeout 300 tests/native/xpose_traffic_ubench > $O/xpose_traffic_ubench.txt 2>&1; echo "xposeub rc=$?"; cat $O/xpose_traffic_ubench.txt ;;
     qtpanel) timeout 600 python tools/check_qt_panel.py > $O/check_qt_panel.txt 2>&1; echo "qtpanel rc=$?"; tail -15 $O/check_qt_panel.txt ;;
     powerdata) timeout 600 python tools/power_data_probe.py > $O/power_data_probe.txt 2> $O/power_data_probe.err; echo "powerdata rc=$?"; cat $O/power_data_probe.txt; tail -3 $O/power_data_probe.err ;;
