@@ -323,7 +323,7 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
 
 /*
  * EXTENSION (no reference counterpart): what a gpt-oss mixture-of-experts layer needs around the grouped GEMMs -- the clamped SwiGLU with the gate/up bias of the
- * row's expert, alone and fused into the MXFP4 quantizer, and moe_combine with the down projection's bias.  The reference model adds each bias to the bf16 GEMM result
+ * row's expert, alone and fused into the MXFP4 and the MXFP8 (e4m3) quantizer, and moe_combine with the down projection's bias.  The reference model adds each bias to the bf16 GEMM result
  * in bf16; so do these, in the op that reads the GEMM's output.
  *   x      bf16 (rows, 2 * inter), contiguous, 16-byte aligned, [gate | up] halves as above (gpt-oss stores the columns interleaved: de-interleave the weight, its
  *          scales and its bias once at load time)
@@ -345,6 +345,11 @@ int qutlass_amd_moe_combine_bf16(const void* y, int64_t m, int64_t hdim, const i
  * qutlass_amd_fused_swiglu_oai_quantize_mx: qutlass_amd_fused_quantize_mx applied to act viewed as (rows, inter), byte for byte, in one launch: flat scales in the
  * first rows * inter / 32 bytes, the rest of the caller's buffer untouched; rot 32 or 64 (128: QAMD_ERR_INVALID, the message names the two-call composition);
  * inter % rot == 0; both methods; hardware e2m1 convert, no clip mask, no blocked form.  LIMIT: x, and bias, below 2 GiB (rows * inter, e * inter < 2^29).
+ * qutlass_amd_fused_swiglu_oai_quantize_mxf8: qutlass_amd_fused_quantize_mxf8 (fmt e4m3) applied to act viewed as (rows, inter), byte for byte, in one launch -- the A
+ * operand of qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn: out_fp8 rows * inter bytes of e4m3 codes; flat scales in the first rows * inter / 32 bytes of out_e8m0, the
+ * rest of the caller's buffer untouched; rot 32 or 64 (128: QAMD_ERR_INVALID, the message names the two-call composition with fusedQuantizeMxf8); inter % rot == 0;
+ * abs-max is the only method; fmt must be QAMD_FP8_E4M3 (a forward activation is e4m3 only: QAMD_ERR_INVALID otherwise); no blocked form.  LIMIT and non-finite
+ * inputs as the MXFP4 entry: x, and bias, below 2 GiB (rows * inter, e * inter < 2^29); NaN / +-inf in gate, up or bias give unspecified bytes for their own rotation group.
  * qutlass_amd_moe_combine_bias_bf16: qutlass_amd_moe_combine_bf16 with bias bf16 (e, hdim), 16-byte aligned, and offs as above (required for e > 1):
  *     acc = +0.0f
  *     for k = 0 .. topk - 1, in this order:  p = pos[t][k];  if 0 <= p < m:
@@ -358,6 +363,8 @@ int qutlass_amd_swiglu_oai_mul_bf16(const void* x, int64_t rows, int64_t inter, 
                                     void* out, void* stream);
 int qutlass_amd_fused_swiglu_oai_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, float alpha, float limit,
                                              const void* bias, const int32_t* offs, int64_t e, void* out_e2m1, void* out_e8m0, void* stream);
+int qutlass_amd_fused_swiglu_oai_quantize_mxf8(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int fmt, float alpha, float limit,
+                                               const void* bias, const int32_t* offs, int64_t e, void* out_fp8, void* out_e8m0, void* stream);
 int qutlass_amd_moe_combine_bias_bf16(const void* y, int64_t m, int64_t hdim, const int32_t* pos, const float* weights, int64_t t, int64_t topk,
                                       const void* bias, const int32_t* offs, int64_t e, void* out, void* stream);
 

@@ -18,6 +18,7 @@ meaning, defaults and Python-level error behaviour):
     moe_topk_grouped, moe_route_grouped                   (extension: the grouped router of DeepSeek-V2 / V3 and Kimi-K2 -- sigmoid / softmax scores, selection bias, group-limited top-k)
     swiglu_oai_and_mul, fusedSwigluOaiQuantizeMx, moe_combine(bias=, offs=)  (extension: gpt-oss -- the clamped SwiGLU and the per-expert biases of both projections,
                                                           applied by the ops that read the grouped GEMMs' outputs; utils.split_interleaved_gate_up for the checkpoint layout)
+    fusedSwigluOaiQuantizeMxf8                            (extension: the same activation into e4m3 -- the A operand of the W4A8 grouped GEMM, one launch)
 
 All compute is hand-written HIP behind the C ABI of ``include/qutlass_amd.h``
 (``libqutlass_amd.so``); importing this package loads that library and registers
@@ -528,8 +529,9 @@ def _bf16_exact(v: float) -> bool:
         return False
 
 
-def _check_swiglu_oai(x, alpha, limit, bias, offs, rot=None):
-    """The Python-level checks of the two clamped-SwiGLU ops (a traced call leaves the shapes to the op's own checks)."""
+def _check_swiglu_oai(x, alpha, limit, bias, offs, rot=None, op="fusedSwigluOaiQuantizeMx", plain="fusedQuantizeMx"):
+    """The Python-level checks of the clamped-SwiGLU ops (a traced call leaves the shapes to the op's own checks); op / plain: the fused op and the plain quantizer
+    its R = 128 message names."""
     import math
 
     if torch.compiler.is_compiling():   # (the C entry repeats the value checks)
@@ -540,7 +542,7 @@ def _check_swiglu_oai(x, alpha, limit, bias, offs, rot=None):
     if not (math.isfinite(limit) and limit > 0 and _bf16_exact(limit)):
         raise ValueError(f"limit must be > 0, finite and exactly representable in bf16 (got {limit})")
     if rot == 128:
-        raise ValueError("rotation size 128 is not supported by fusedSwigluOaiQuantizeMx (R = 32 or 64): use swiglu_oai_and_mul followed by fusedQuantizeMx")
+        raise ValueError(f"rotation size 128 is not supported by {op} (R = 32 or 64): use swiglu_oai_and_mul followed by {plain}")
     if x.size(-1) % 2:
         raise ValueError(f"the last dimension of x must be 2 * I (got {x.size(-1)})")
     if bias is None:
@@ -608,6 +610,27 @@ def fusedSwigluOaiQuantizeMx(x: torch.Tensor, h: torch.Tensor, *, alpha: float =
     code = _method_code(method)
     alpha, limit = _check_swiglu_oai(x, alpha, limit, bias, offs, h.size(0) if h.dim() == 2 else None)
     return _quantize("swiglu_oai_quantize_mx", x, h, alpha, limit, bias, offs, code)
+
+
+def fusedSwigluOaiQuantizeMxf8(x: torch.Tensor, h: torch.Tensor, *, alpha: float = 1.702, limit: float = 7.0, bias: torch.Tensor | None = None,
+                               offs: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMxf8(swiglu_oai_and_mul(x, alpha=alpha, limit=limit, bias=bias, offs=offs), h)`` in ONE launch, byte for byte -- the down
+    projection's A operand of a gpt-oss W4A8 layer (grouped_matmul_mxf8_mxf4_bf16_tn: MXFP4 expert weights as stored against 8-bit tokens): fusedSwigluOaiQuantizeMx
+    with the MXFP8 epilogue (see swiglu_oai_and_mul for the arithmetic, fusedQuantizeMxf8 for the scale rule).  The (.., I) bf16 activation never goes through memory:
+    5 B moved per element instead of 8.5.  Returns float8_e4m3fn codes (.., I) and float8_e8m0fnu scales (padded_rows, padded_cols) as fusedQuantizeMxf8 does for a
+    (.., I) tensor: scales flat in the first rows * I / 32 bytes, padding untouched.  e4m3 only (a forward activation has no use for e5m2); abs-max only.
+    R in {32, 64} for the R x R rotation h (R = 128 raises -- use swiglu_oai_and_mul followed by fusedQuantizeMxf8); I % R == 0; no blocked form.  bias (E, 2 I) bf16
+    and offs (E,) int32 as in swiglu_oai_and_mul; malformed offs select some expert in [0, E).  x, and bias, below 2 GiB.  Non-finite gate / up / bias values give
+    unspecified bytes in their own rotation groups only.  No host sync: graph-capturable; traces under torch.compile.
+    Measured against the two launches (gpt-oss shapes, I = 2944, with bias, tokens x top-4; profiles/bench_swiglu_oai_mxf8_mi355x.txt): R = 32 wins from 128 tokens
+    on (1.08-1.17x; 1.26-1.28x at 4096 tokens, 78-80 against 100-102 us) and is level to SLOWER at 16 tokens (0.94-0.99x, 6.5-7.0 against 6.2-6.6 us); at R = 64 it is
+    SLOWER up to 128 tokens (0.67-0.69x at 16, 10.0-10.5 against 6.7-7.1 us; 0.91-0.95x at 128, 9.8-11.1 against 9.3-10.3 us) and wins only at prefill sizes
+    (1.15-1.17x at 4096 tokens): keep swiglu_oai_and_mul + fusedQuantizeMxf8 for R = 64 at decode sizes.  4.5-7.0x (R = 32) faster than the torch composition; as
+    fast as fusedSwigluOaiQuantizeMx on the same input (0.99-1.02x: the kernel is bound by the activation's vector work, not by the code bytes)."""
+    alpha, limit = _check_swiglu_oai(x, alpha, limit, bias, offs, h.size(0) if h.dim() == 2 else None, "fusedSwigluOaiQuantizeMxf8", "fusedQuantizeMxf8")
+    if torch.compiler.is_compiling():
+        return _ops_amd.swiglu_oai_quantize_mxf8(x, h, alpha, limit, bias, offs)
+    return ops.run_swiglu_oai_quant(ops.SWIGLU_OAI_MXF8, x, h, alpha, limit, bias, offs)
 
 
 def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor, *, bias: torch.Tensor | None = None, offs: torch.Tensor | None = None) -> torch.Tensor:

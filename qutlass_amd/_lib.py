@@ -55,6 +55,7 @@ SYMBOLS = {
     "qutlass_amd_moe_combine_bf16": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "qutlass_amd_swiglu_oai_mul_bf16": (_i32, [_vp, _i64, _i64, _f32, _f32, _vp, _vp, _i64, _vp, _vp]),
     "qutlass_amd_fused_swiglu_oai_quantize_mx": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "qutlass_amd_fused_swiglu_oai_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "qutlass_amd_moe_combine_bias_bf16": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "qutlass_amd_moe_topk_softmax": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "qutlass_amd_moe_topk_grouped": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, ctypes.c_float, _vp, _vp, _vp, _vp]),

@@ -1466,8 +1466,9 @@ int launch_bwd_quant(const char* name, const BwdTParams& p, bool qt, bool hw, co
 #endif
 
 // The clamped-SwiGLU kernels and moe_combine's bias form (quantize.hip.h) live in unit 5 with the other quantizers: the fused arm for R = 32 / 64 x method x
-// bias, the streaming activation with and without a bias, the combine.  The C entries (unit 1) have checked everything; these only pick the instantiation.
+// bias, its e4m3 form for R = 32 / 64 x bias, the streaming activation with and without a bias, the combine.  The C entries (unit 1) have checked everything; these only pick the instantiation.
 int launch_swiglu_oai_quant(int rot, int method, bool bias, const QuantParams& p, hipStream_t s, int grid);
+int launch_swiglu_oai_quant_mxf8(int rot, bool bias, const QuantParams& p, hipStream_t s, int grid);   // (the e4m3 form: abs-max only)
 int launch_swiglu_oai_stream(const SwigluOaiParams& p, const RowStreamLaunch& l, hipStream_t s);
 int launch_moe_combine_bias(const MoeCombineBiasParams& p, const RowStreamLaunch& l, hipStream_t s);
 #if QAMD_DEF(5)
@@ -1482,6 +1483,16 @@ int launch_swiglu_oai_quant(int rot, int method, bool bias, const QuantParams& p
   if (rot == 32) { if (method == QAMD_METHOD_QUEST) go(R32{}, Quest{}); else go(R32{}, AbsMax{}); }
   else { if (method == QAMD_METHOD_QUEST) go(R64{}, Quest{}); else go(R64{}, AbsMax{}); }
   return check_launch("fused_swiglu_oai_quantize_kernel");
+}
+int launch_swiglu_oai_quant_mxf8(int rot, bool bias, const QuantParams& p, hipStream_t s, int grid) {
+  if (rot == 32) {
+    if (bias) hipLaunchKernelGGL((fused_swiglu_oai_quantize_mxf8_kernel<32, true>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((fused_swiglu_oai_quantize_mxf8_kernel<32, false>), dim3(grid), dim3(256), 0, s, p);
+  } else {
+    if (bias) hipLaunchKernelGGL((fused_swiglu_oai_quantize_mxf8_kernel<64, true>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((fused_swiglu_oai_quantize_mxf8_kernel<64, false>), dim3(grid), dim3(256), 0, s, p);
+  }
+  return check_launch("fused_swiglu_oai_quantize_mxf8_kernel");
 }
 int launch_swiglu_oai_stream(const SwigluOaiParams& p, const RowStreamLaunch& l, hipStream_t s) {
   if (p.bias) hipLaunchKernelGGL(swiglu_oai_mul_bf16_kernel<true>, dim3(l.grid), dim3(l.threads), 0, s, p);
@@ -2045,7 +2056,7 @@ int qutlass_amd_fused_gather_quantize_mxf8(const void* x, const void* h, int rot
                                     fmt);
 }
 
-// ---- gpt-oss: the clamped SwiGLU with per-expert biases (quantize.hip.h, swiglu_oai_mul8), alone and fused into the MXFP4 quantizer; moe_combine with the down bias ----
+// ---- gpt-oss: the clamped SwiGLU with per-expert biases (quantize.hip.h, swiglu_oai_mul8), alone and fused into the MXFP4 and the MXFP8 (e4m3) quantizer; moe_combine with the down bias ----
 // alpha and limit -> the kernels' constants (SwigluOaiAct).  alpha * log2 e = c_hi + c_lo in fp64, c_hi rounded to 16 significant bits: with the gate's 8 the
 // product c_hi * gate is exact in fp32.  Outside [2^-100, 2^100] -- where c_hi or ln 2 * c_lo would leave fp32's normal range -- every element takes the fp64 path.
 static int swiglu_oai_act(const char* name, float alpha, float limit, SwigluOaiAct& a) {
@@ -2089,15 +2100,16 @@ int qutlass_amd_swiglu_oai_mul_bf16(const void* x, int64_t rows, int64_t inter, 
   return launch_swiglu_oai_stream(p, row_stream_plan(p.chunks, chip_cus()), (hipStream_t)stream);
 }
 
-// fusedQuantizeMx(swiglu_oai_and_mul(x, ...), h) in one launch, byte for byte: the gated quantizer's chain with the activation's checks; flat scales only
-int qutlass_amd_fused_swiglu_oai_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, float alpha, float limit, const void* bias,
-                                             const int32_t* offs, int64_t e, void* out_e2m1, void* out_e8m0, void* stream) {
-  const char* name = "fusedSwigluOaiQuantizeMx";
+// fusedQuantizeMx(swiglu_oai_and_mul(x, ...), h) -- f.fp8: fusedQuantizeMxf8(swiglu_oai_and_mul(x, ...), h, e4m3) -- in one launch, byte for byte: the gated
+// quantizer's chain with the activation's checks; flat scales only.  `how` is the method of the e2m1 entry and the fmt of the e4m3 one (quant_check_how).
+static int fused_swiglu_oai_quantize_impl(const char* name, const char* plain, const QuantFormat& f, const void* x, const void* h, int rot, int64_t rows, int64_t inter,
+                                          int how, float alpha, float limit, const void* bias, const int32_t* offs, int64_t e, void* out, void* out_e8m0, void* stream) {
   QuantParams p;
   if (rot == 128)
-    return fail(QAMD_ERR_INVALID, "%s: rotation size 128 is not supported; expected 32 or 64 (use swiglu_oai_and_mul followed by fusedQuantizeMx)", name);
+    return fail(QAMD_ERR_INVALID, "%s: rotation size 128 is not supported; expected 32 or 64 (use swiglu_oai_and_mul followed by %s)", name, plain);
   if (rot != 32 && rot != 64) return fail(QAMD_ERR_INVALID, "%s: Unsupported rotation size %d; expected 32 or 64.", name, rot);
-  if (int rc = quant_check_method(name, method)) return rc;
+  if (!f.fp8) { if (int rc = quant_check_method(name, how)) return rc; }
+  else if (how != QAMD_FP8_E4M3) return fail(QAMD_ERR_INVALID, "%s: invalid fmt %d; expected 0 (e4m3): a forward activation is e4m3 only", name, how);
   if (int rc = gated_common_check(name, x, rows, inter, rot)) return rc;
   if (rows * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: x (rows * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(rows * inter * 4));
   if (int rc = swiglu_oai_act(name, alpha, limit, p.oai)) return rc;
@@ -2106,13 +2118,27 @@ int qutlass_amd_fused_swiglu_oai_quantize_mx(const void* x, const void* h, int r
     if (e * inter >= (1ll << 29)) return fail(QAMD_ERR_INVALID, "%s: bias (E * 2 * inter * 2 = %lld bytes) must stay below 2 GiB", name, (long long)(e * inter * 4));
   }
   if (rows == 0) return QAMD_OK;
-  if (!x || !h || !out_e2m1 || !out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  if (!x || !h || !out || !out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
   if (int rc = quant_check_h(name, rot, h)) return rc;
-  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out_e2m1; p.out_sf = (uint8_t*)out_e8m0;
+  p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.out = (uint8_t*)out; p.out_sf = (uint8_t*)out_e8m0;
   p.out_mask = nullptr; p.global_scale = nullptr; p.inter = (int)inter;
   p.bias = (const uint16_t*)bias; p.offs = offs; p.E = bias ? (int)e : 0;
-  const int grid = quant_fill(p, kQuantMx, rot, rows * inter, inter, false);
-  return launch_swiglu_oai_quant(rot, method, bias != nullptr, p, (hipStream_t)stream, grid);
+  const int grid = quant_fill(p, f, rot, rows * inter, inter, false);
+  if (f.fp8) return launch_swiglu_oai_quant_mxf8(rot, bias != nullptr, p, (hipStream_t)stream, grid);
+  return launch_swiglu_oai_quant(rot, how, bias != nullptr, p, (hipStream_t)stream, grid);
+}
+
+int qutlass_amd_fused_swiglu_oai_quantize_mx(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int method, float alpha, float limit, const void* bias,
+                                             const int32_t* offs, int64_t e, void* out_e2m1, void* out_e8m0, void* stream) {
+  return fused_swiglu_oai_quantize_impl("fusedSwigluOaiQuantizeMx", "fusedQuantizeMx", kQuantMx, x, h, rot, rows, inter, method, alpha, limit, bias, offs, e, out_e2m1,
+                                        out_e8m0, stream);
+}
+
+// the W4A8 form: e4m3 codes (one byte per element) for the A operand of grouped_matmul_mxf8_mxf4_bf16_tn; abs-max is the only method, so fmt stands where method does
+int qutlass_amd_fused_swiglu_oai_quantize_mxf8(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int fmt, float alpha, float limit, const void* bias,
+                                               const int32_t* offs, int64_t e, void* out_fp8, void* out_e8m0, void* stream) {
+  return fused_swiglu_oai_quantize_impl("fusedSwigluOaiQuantizeMxf8", "fusedQuantizeMxf8", kQuantMxf8, x, h, rot, rows, inter, fmt, alpha, limit, bias, offs, e, out_fp8,
+                                        out_e8m0, stream);
 }
 
 // Combine: out[t] = sum_k w[t][k] * y[pos[t][k]] in the order and with the roundings moe_combine_bf16_kernel states (quantize.hip.h); slots outside [0, m) are skipped.

@@ -56,8 +56,8 @@ struct QuantParams {
   // rows -- row m of the operand takes global_scale[quant_group_of_row(offs, E, m)].  No other kernel reads them.  (E sits in the tail padding; offs grows the struct.)
   int E = 0;
   const int32_t* offs = nullptr;
-  // OAI kernels only (fusedSwigluOaiQuantizeMx): the gated layout, with act = swiglu_oai(gate, up) (swiglu_oai_mul8 below) in place of silu(gate) * up.  With a bias
-  // (ACT == ACT_OAI_BIAS): bias (E, 2 * inter) bf16 in the same [gate | up] halves, row m of x takes bias[quant_group_of_row(offs, E, m)]; E == 1 never reads offs.
+  // OAI kernels only (fusedSwigluOaiQuantizeMx, fusedSwigluOaiQuantizeMxf8): the gated layout, with act = swiglu_oai(gate, up) (swiglu_oai_mul8 below) in place of
+  // silu(gate) * up.  With a bias (ACT == ACT_OAI_BIAS): bias (E, 2 * inter) bf16 in the same [gate | up] halves, row m of x takes bias[quant_group_of_row(offs, E, m)]; E == 1 never reads offs.
   const uint16_t* bias = nullptr;
   SwigluOaiAct oai = {};
 };
@@ -418,7 +418,8 @@ __device__ __forceinline__ v4i swiglu_oai_mul8(const v4i g, const v4i u, const v
 //            right after the next tile's x loads, so the one global load has that tile's wait and this tile's MFMAs and epilogue to land -- and the epilogue lane
 //            picks its own row's value with a cross-lane read (ds_bpermute by (rem + row) / rpr, the split gather_off does).  Two registers: this tile's values and
 //            the next tile's.  There is no METHOD_QUEST instantiation: the NV Quest arm never reads gscale, so the grouped entries launch the single-scale Quest kernel.
-//   ACT    : (GATED, MX e2m1, flat scales) ACT_OAI / ACT_OAI_BIAS: the activation is the clamped SwiGLU, swiglu_oai_mul8, in place of silu_mul8 -- nothing else changes.
+//   ACT    : (GATED, MX e2m1 or -- abs-max -- e4m3, flat scales) ACT_OAI / ACT_OAI_BIAS: the activation is the clamped SwiGLU, swiglu_oai_mul8, in place of silu_mul8 --
+//            nothing else changes.
 //            ACT_OAI_BIAS adds the gate/up bias of the row's expert: a tile's loads fetch, next to gate and up, the two bias chunks at the same columns of row
 //            quant_group_of_row(offs, E, logical row) of bias = (E, 2 I), through a descriptor of their own (bias stays below 2 GiB; the host checks; the expert is
 //            clamped to [0, E), so malformed offs cannot address outside it).  The lookup is GSCALE's: offs in LDS, lane l searches for logical row (first row of
@@ -428,7 +429,9 @@ __device__ __forceinline__ v4i swiglu_oai_mul8(const v4i g, const v4i u, const v
 //            whole tile: they are L2 hits (every row of an expert shares them), and holding a tile's bias chunks in registers across a tile as well (24-34 more
 //            VGPRs, a wave per SIMD) measured 2-6 % slower.
 //   FMT    : QF_E2M1 (the default: everything above) or QF_E4M3 / QF_E5M2 -- the MXFP8 quantizers (MX abs-max without a clip mask; plain, BLK, GATED or GATHER):
-//            everything up to and including the MFMAs is the MX kernel, the epilogue is the FP8 arm below (one byte per element, a 32-byte run per group).
+//            everything up to and including the MFMAs is the MX kernel, the epilogue is the FP8 arm below (one byte per element, a 32-byte run per group).  With ACT_OAI /
+//            ACT_OAI_BIAS (e4m3, flat scales, R = 32 / 64) the two meet: the activation arm ends with the bf16 tile in xnext, the FP8 arm starts after the MFMAs and
+//            reads only acc, the tile's group index and the two output pointers, none of which the activation arm touches -- fusedSwigluOaiQuantizeMxf8.
 // -------------------------------------------------------------------------------------------------
 // The kernel's body as a device function of (workgroup index, workgroup count): fused_quantize_kernel below is its plain launch; [r6] the one-launch decode layer
 // (gemm_mx_os.hip.h gemm_mx_os16_fq_kernel) runs it on its first few workgroups.  PAD = false: the zero padding of the blocked scale layout is left out (a reader that
@@ -464,7 +467,8 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   static_assert(FMT == QF_E2M1 || ((FMT == QF_E4M3 || FMT == QF_E5M2) && !NV && METHOD == METHOD_ABSMAX && !MASK && !GSCALE && R >= 32),
                 "the MXFP8 arm: MX scales (so no R = 16), abs-max, no clip mask");
   static_assert(!GSCALE || (NV && METHOD == METHOD_ABSMAX && !BLK && !MASK && (GATED || GATHER)), "per-expert global scales: NV abs-max, flat scales, gathering or gated");
-  static_assert(ACT == ACT_SILU || (GATED && !NV && !BLK && !MASK && !GSCALE && FMT == QF_E2M1 && R >= 32 && R <= 64), "the clamped SwiGLU: gated MX e2m1, flat scales, R = 32 / 64");
+  static_assert(ACT == ACT_SILU || (GATED && !NV && !BLK && !MASK && !GSCALE && (FMT == QF_E2M1 || FMT == QF_E4M3) && R >= 32 && R <= 64),
+                "the clamped SwiGLU: gated MX e2m1 or e4m3, flat scales, R = 32 / 64");
   constexpr bool OAIB = ACT == ACT_OAI_BIAS;
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, GATHER ? (uint32_t)p.src_n * (uint32_t)p.inter * 2u : (uint32_t)(p.numel * (GATED ? 4 : 2)));
 
@@ -1097,6 +1101,11 @@ __global__ __launch_bounds__(256) void fused_silu_mul_quantize_mxf8_kernel(const
 template <int R, int FMT>
 __global__ __launch_bounds__(256) void fused_gather_quantize_mxf8_kernel(const QuantParams p) {
   fused_quantize_body<R, false, METHOD_ABSMAX, false, true, false, true, false, true, false, FMT>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+// the clamped-SwiGLU form (fusedSwigluOaiQuantizeMxf8): e4m3 with flat scales, R = 32 / 64, with or without the per-expert gate/up bias
+template <int R, bool BIAS>
+__global__ __launch_bounds__(256) void fused_swiglu_oai_quantize_mxf8_kernel(const QuantParams p) {
+  fused_quantize_body<R, false, METHOD_ABSMAX, false, true, false, true, true, false, false, QF_E4M3, BIAS ? ACT_OAI_BIAS : ACT_OAI>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The launch of the four row-stream ops below (silu_and_mul, swiglu_oai_and_mul, moe_combine with and without a bias): a pure function of the 16-byte chunks to write and

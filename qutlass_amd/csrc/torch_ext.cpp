@@ -518,7 +518,7 @@ void moeCombine_(const Tensor& Y, const Tensor& pos, const Tensor& weights, Tens
                                         OUT.data_ptr(), current_stream(Y)));
 }
 
-// ---- EXTENSION: gpt-oss -- the clamped SwiGLU with per-expert gate/up biases, alone and fused into the MXFP4 quantizer, and moe_combine with the down bias ------
+// ---- EXTENSION: gpt-oss -- the clamped SwiGLU with per-expert gate/up biases, alone and fused into the MXFP4 and the MXFP8 (e4m3) quantizer, and moe_combine with the down bias ------
 // bias: (E, 2 I) bf16, or an EMPTY tensor for "no bias"; offs: (E,) int32, or an empty tensor where there is no bias or E == 1.  The arithmetic is spelled out at
 // qutlass_amd_swiglu_oai_mul_bf16 (include/qutlass_amd.h).
 struct OaiBias {
@@ -567,20 +567,32 @@ void swigluOaiAndMul_(const Tensor& X, Tensor OUT, double alpha, double limit, c
   check_rc(qutlass_amd_swiglu_oai_mul_bf16(X.data_ptr(), rows, inter, (float)alpha, (float)limit, b.bias, b.offs, b.e, OUT.data_ptr(), current_stream(X)));
 }
 
-void fusedSwigluOaiQuantizeMx_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, double alpha, double limit, const Tensor& bias, const Tensor& offs,
-                               int64_t method) {
-  const char* op = "fusedSwigluOaiQuantizeMx";
-  const int64_t rot = quant_prelude(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, nullptr, &method);
+// fmt8 < 0: the MXFP4 op (plain = fusedQuantizeMx; method read); fmt8 >= 0: the e4m3 op (plain = fusedQuantizeMxf8; abs-max, method not read)
+void swiglu_oai_quantize(const char* op, const char* plain, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, double alpha, double limit, const Tensor& bias,
+                         const Tensor& offs, int64_t method, int fmt8 = -1) {
+  const int64_t rot = quant_prelude(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, nullptr, fmt8 < 0 ? &method : nullptr);
   STD_TORCH_CHECK(A.dim() >= 1 && A.size(A.dim() - 1) > 0 && A.size(A.dim() - 1) % 2 == 0, "the last dimension of A must be 2 * I");
   const int64_t inter = A.size(A.dim() - 1) / 2, rows = A.numel() / (2 * inter);
-  STD_TORCH_CHECK(rot != 128, "rotation size 128 is not supported; expected 32 or 64 (use swiglu_oai_and_mul followed by fusedQuantizeMx)");
+  STD_TORCH_CHECK(rot != 128, "rotation size 128 is not supported; expected 32 or 64 (use swiglu_oai_and_mul followed by ", plain, ")");
   STD_TORCH_CHECK(rot == 32 || rot == 64, "Unsupported rotation size ", rot, "; expected 32 or 64.");
   STD_TORCH_CHECK(inter % rot == 0, "the gate / up width must be divisible by", rot);
-  quant_check_out(false, OUT, OUT_sf, rows * inter, inter, false);
+  quant_check_out(false, OUT, OUT_sf, rows * inter, inter, false, fmt8 >= 0);
   const OaiBias b = oai_bias(op, A, bias, offs, 2 * inter);
   const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  check_rc(qutlass_amd_fused_swiglu_oai_quantize_mx(A.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, (float)alpha, (float)limit, b.bias, b.offs, b.e,
-                                                    OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+  if (fmt8 >= 0)
+    check_rc(qutlass_amd_fused_swiglu_oai_quantize_mxf8(A.data_ptr(), R.data_ptr(), (int)rot, rows, inter, fmt8, (float)alpha, (float)limit, b.bias, b.offs, b.e,
+                                                        OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+  else
+    check_rc(qutlass_amd_fused_swiglu_oai_quantize_mx(A.data_ptr(), R.data_ptr(), (int)rot, rows, inter, (int)method, (float)alpha, (float)limit, b.bias, b.offs, b.e,
+                                                      OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+}
+void fusedSwigluOaiQuantizeMx_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, double alpha, double limit, const Tensor& bias, const Tensor& offs,
+                               int64_t method) {
+  swiglu_oai_quantize("fusedSwigluOaiQuantizeMx", "fusedQuantizeMx", A, R, OUT, OUT_sf, alpha, limit, bias, offs, method);
+}
+// the W4A8 form: OUT (.., I) float8_e4m3fn (a forward activation: e4m3 only), OUT_sf as for the MX op
+void fusedSwigluOaiQuantizeMxf8_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf, double alpha, double limit, const Tensor& bias, const Tensor& offs) {
+  swiglu_oai_quantize("fusedSwigluOaiQuantizeMxf8", "fusedQuantizeMxf8", A, R, OUT, OUT_sf, alpha, limit, bias, offs, QAMD_METHOD_ABSMAX, mxf8_fmt(OUT, OUT_sf, true));
 }
 
 // moeCombineBias_: moeCombine_ with bias (E, H) bf16 added to every gathered row in bf16; offs (E,) int32, or empty for E == 1
@@ -827,6 +839,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("moeCombine_(Tensor Y, Tensor pos, Tensor weights, Tensor(a!) OUT) -> ()");
   m.def("swigluOaiAndMul_(Tensor X, Tensor(a!) OUT, float alpha, float limit, Tensor bias, Tensor offs) -> ()");
   m.def("fusedSwigluOaiQuantizeMx_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, float alpha, float limit, Tensor bias, Tensor offs, int method) -> ()");
+  m.def("fusedSwigluOaiQuantizeMxf8_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf, float alpha, float limit, Tensor bias, Tensor offs) -> ()");
   m.def("moeCombineBias_(Tensor Y, Tensor pos, Tensor weights, Tensor bias, Tensor offs, Tensor(a!) OUT) -> ()");
   m.def("moeTopkSoftmax_(Tensor logits, Tensor(a!) weights, Tensor(b!) ids, bool renormalize) -> ()");
   m.def("moeTopkGrouped_(Tensor logits, Tensor bias, Tensor(a!) weights, Tensor(b!) ids, Tensor(c!) scores, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor) -> ()");
@@ -884,6 +897,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("moeCombine_", TORCH_BOX(&moeCombine_));
   m.impl("swigluOaiAndMul_", TORCH_BOX(&swigluOaiAndMul_));
   m.impl("fusedSwigluOaiQuantizeMx_", TORCH_BOX(&fusedSwigluOaiQuantizeMx_));
+  m.impl("fusedSwigluOaiQuantizeMxf8_", TORCH_BOX(&fusedSwigluOaiQuantizeMxf8_));
   m.impl("moeCombineBias_", TORCH_BOX(&moeCombineBias_));
   m.impl("moeTopkSoftmax_", TORCH_BOX(&moeTopkSoftmax_));
   m.impl("moeTopkGrouped_", TORCH_BOX(&moeTopkGrouped_));

@@ -79,7 +79,7 @@ def _register_fakes() -> None:
                  "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
                  "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "fusedGatherQuantizeNvGrouped_", "fusedSiluMulQuantizeNvGrouped_",
                  "fusedQuantizeMxf8_", "fusedQuantizeMxf8Blocked_", "fusedSiluMulQuantizeMxf8_", "fusedGatherQuantizeMxf8_", "moeCombine_",
-                 "swigluOaiAndMul_", "fusedSwigluOaiQuantizeMx_", "moeCombineBias_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
+                 "swigluOaiAndMul_", "fusedSwigluOaiQuantizeMx_", "fusedSwigluOaiQuantizeMxf8_", "moeCombineBias_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
         rf(f"qutlass_amd::{name}")(fills)
 
     @rf("qutlass_amd::to_blocked")
@@ -116,6 +116,9 @@ def _define_functional_ops() -> None:
     for name, row in QUANT_OPS.items():
         op = custom_op(f"qutlass_amd::{name}", mutates_args=(), schema=row.schema)(lambda *args, _row=row: run_quant_op(_row, *args))
         op.register_fake(lambda *args, _row=row: alloc_quant(_row, *args))
+    # the e4m3 form of the clamped-SwiGLU quantizer: its record stands next to the table (see SWIGLU_OAI_MXF8), not in it
+    op = custom_op("qutlass_amd::swiglu_oai_quantize_mxf8", mutates_args=(), schema=SWIGLU_OAI_MXF8.schema)(lambda *args: run_swiglu_oai_quant(SWIGLU_OAI_MXF8, *args))
+    op.register_fake(lambda A, R, *rest: alloc_swiglu_oai_quant(SWIGLU_OAI_MXF8, A, R))
 
     # gated MLP: X is (.., 2 I) [gate | up]
     @custom_op("qutlass_amd::silu_and_mul", mutates_args=(), schema="(Tensor X) -> Tensor")
@@ -293,6 +296,10 @@ QUANT_OPS = {
     "silu_mul_quantize_mxf8": QuantOp("(Tensor A, Tensor R, ScalarType dtype, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeMxf8_", 2, _act, "mxf8", None),
     "gather_quantize_mxf8": QuantOp("(Tensor A, Tensor R, Tensor src_row, ScalarType dtype) -> (Tensor, Tensor)", "fusedGatherQuantizeMxf8_", 3, _gathered, "mxf8", False),
 }
+# The clamped SwiGLU into e4m3 -- the A operand of the W4A8 grouped GEMM.  Outside the table on purpose: the table's "mxf8" rows take a code dtype and every rotation,
+# this op is e4m3 only (no dtype argument), R = 32 / 64, and takes alpha / limit / bias / offs; it is registered beside the loop over QUANT_OPS.
+SWIGLU_OAI_MXF8 = QuantOp("(Tensor A, Tensor R, float alpha, float limit, Tensor? bias, Tensor? offs) -> (Tensor, Tensor)", "fusedSwigluOaiQuantizeMxf8_", 2, _act, "mxf8",
+                          False)
 
 
 def mxf8_dtype(dtype) -> torch.dtype:
@@ -321,8 +328,8 @@ def run_quant(row: QuantOp, *args):
 
 
 def run_quant_op(row: QuantOp, *args):
-    """run_quant -- or, for the one row whose op takes optional tensors, its own runner (the in-place twins take no None)."""
-    return (run_swiglu_oai_quant if row.twin == "fusedSwigluOaiQuantizeMx_" else run_quant)(row, *args)
+    """run_quant -- or, for the clamped-SwiGLU ops, which take optional tensors, their own runner (the in-place twins take no None)."""
+    return (run_swiglu_oai_quant if row.twin.startswith("fusedSwigluOaiQuantize") else run_quant)(row, *args)
 
 
 def _optional(x: torch.Tensor, t: torch.Tensor | None, dtype: torch.dtype) -> torch.Tensor:
@@ -330,10 +337,15 @@ def _optional(x: torch.Tensor, t: torch.Tensor | None, dtype: torch.dtype) -> to
     return x.new_empty((0,), dtype=dtype) if t is None else t
 
 
-def run_swiglu_oai_quant(row: QuantOp, A, R, alpha, limit, bias, offs, method):
-    """run_quant for the one op of the table with optional tensors."""
-    o = alloc_quant(row, A, R)
-    torch.ops.qutlass_amd.fusedSwigluOaiQuantizeMx_(A, R, o[0], o[1], alpha, limit, _optional(A, bias, A.dtype), _optional(A, offs, torch.int32), method)
+def alloc_swiglu_oai_quant(row: QuantOp, A, R):
+    """alloc_quant for the clamped-SwiGLU ops: the e4m3 form has no dtype argument (a forward activation is e4m3 only)."""
+    return alloc_quant(row, A, R, *((torch.float8_e4m3fn,) if row.fmt == "mxf8" else ()))
+
+
+def run_swiglu_oai_quant(row: QuantOp, A, R, alpha, limit, bias, offs, *method):
+    """run_quant for the ops with optional tensors: the MXFP4 row of the table (method: one int) and SWIGLU_OAI_MXF8 (abs-max only: no method)."""
+    o = alloc_swiglu_oai_quant(row, A, R)
+    getattr(torch.ops.qutlass_amd, row.twin)(A, R, o[0], o[1], alpha, limit, _optional(A, bias, A.dtype), _optional(A, offs, torch.int32), *method)
     return o
 
 
