@@ -8,9 +8,11 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 
 #include "../../include/qutlass_amd.h"
 #include "gemm_mx.hip.h"
+#include "gemm_mx_forms.hip.h"
 #include "gemm_mx_deepp.hip.h"
 #include "gemm_mx_deepp16.hip.h"
 #if QAMD_BENCH   // csrc/lab/: sources of the LAB library only -- not read by the product build, not shipped by setup.py
@@ -265,19 +267,24 @@ int launch_gemm_ks(GemmParams p, hipStream_t s) {
 // [r6] small-batch kernel whose waves own K stages (gemm_mx_os.hip.h): wave w owns stages w, w + 4, ...; the tile's whole K extent requested up front while it fits the
 // LDS (16 stages of 128 bytes per row for a 32-row tile, 12 for a 64-row tile), wave-owned rings beyond
 // (RM: row-major scale operands -- matmul_ada_mxf4_bf16_tn; TN: columns per workgroup, 32 or 16; EBITS 8: MXFP8, AFMT 1: e5m2 A operand; TM: rows per workgroup, 32 or 64)
+// the kernel by the K stage count, for the dense op (GRP false: p is GemmParams) and the grouped one (GroupedParams, row-major scales): slots per wave = ceil(KT / 4) up to
+// SMAX, the most that fit the LDS; wave-owned rings of SMAX slots beyond
+template <bool RM, int TN, int EBITS, int TM, int AFMT, bool GRP, class P>
+void launch_os_by_stages(int64_t KT, dim3 grid, const P& p, hipStream_t s) {
+  const dim3 block(256);
+  constexpr int SMAX = TM == 32 ? 4 : 3;
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<1, TN, EBITS, TM, AFMT>, RM, false, GRP>), grid, block, 0, s, p);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<2, TN, EBITS, TM, AFMT>, RM, false, GRP>), grid, block, 0, s, p);
+  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<3, TN, EBITS, TM, AFMT>, RM, false, GRP>), grid, block, 0, s, p);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, RM, false, GRP>), grid, block, 0, s, p);
+  else hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, RM, true, GRP>), grid, block, 0, s, p);
+}
 template <bool RM = false, int TN = 32, int EBITS = 4, int TM = 32, int AFMT = 0>
 int launch_gemm_os(GemmParams p, hipStream_t s) {
   p.tiles_m = (int)cdiv(p.M, TM);
   p.tiles_n = (int)cdiv(p.N, TN);
   p.ws = nullptr; p.splits = 1; p.ctr = nullptr; p.tag = 0;
-  const int64_t KT = cdiv((int64_t)p.K * EBITS / 8, 128);
-  const dim3 grid(p.tiles_m * p.tiles_n), block(256);
-  constexpr int SMAX = TM == 32 ? 4 : 3;   // slots per wave that fit the LDS
-  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<1, TN, EBITS, TM, AFMT>, RM>), grid, block, 0, s, p);
-  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<2, TN, EBITS, TM, AFMT>, RM>), grid, block, 0, s, p);
-  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<3, TN, EBITS, TM, AFMT>, RM>), grid, block, 0, s, p);
-  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, RM>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, RM, true>), grid, block, 0, s, p);   // wave-owned rings of SMAX slots
+  launch_os_by_stages<RM, TN, EBITS, TM, AFMT, false>(cdiv((int64_t)p.K * EBITS / 8, 128), dim3(p.tiles_m * p.tiles_n), p, s);
   return check_launch("gemm_mx_os_kernel");
 }
 // [r6] its decode form (gemm_mx_os16_kernel: 16 x TN tiles on the 16x16x128 MFMA, rows in tiles of 16): one shot while the tile's K extent fits the LDS (SMAX slots per wave),
@@ -299,11 +306,11 @@ int launch_gemm_os16(GemmParams p, hipStream_t s) {
   else hipLaunchKernelGGL((gemm_mx_os16_kernel<Os16Cfg<SMAX, EBITS, AFMT, TN>, true, RM>), grid, block, 0, s, p);
   return check_launch("gemm_mx_os16_kernel");
 }
-// columns per workgroup of the decode form for M <= 16: the narrowest of 16 / 32 / 48 / 56 / 64 that leaves at most one workgroup per CU; 0 = none does
-inline int os16_tn(int64_t N, int64_t cus) {
-  for (int tn : {16, 32, 48, 56, 64})
-    if (cdiv(N, tn) <= cus) return tn;
-  return 0;
+// the decode form for M <= 16: the narrowest of its column tiles (MX_FORMS: 16 / 32 / 48 / 56 / 64) that leaves at most one workgroup per CU; nullptr = none does
+inline const MxFormRow* os16_form(int64_t N, int64_t cus) {
+  for (const MxFormRow& f : MX_FORMS)
+    if (f.family == MXF_DECODE && cdiv(N, f.tn) <= cus) return &f;
+  return nullptr;
 }
 // [r6] M <= 16 against a weight too wide for 16-column workgroups: the decode form with 32 / 48 / 56 / 64 columns per workgroup (variants 572 ... 575) where it was measured ahead
 // (tools/calib_os2.py, profiles/calib_os16w_r7.txt; K in stages of 128 bytes per row).  MXFP4: N = 11008 / 12288 x K = 4096 5.0-5.2 -> 3.8-4.0 us (48 columns: 64 rows per
@@ -312,29 +319,19 @@ inline int os16_tn(int64_t N, int64_t cus) {
 // Past the one-shot range the wider forms lose (14336 x 8192: +3 %).  MXFP8: 32 columns -6 ... -12 % at K = 2048 ... 8192, 48 columns -9 % at 11008 x 4096; 14336 x 4096 loses.
 // Returns the variant or 0.
 inline int os16_wide_plan(int ebits, int64_t N, int64_t K, int64_t cus) {
-  const int tn = os16_tn(N, cus);
+  const MxFormRow* f = os16_form(N, cus);
+  const int tn = f ? f->tn : 0;
   const int64_t KT = cdiv(K * ebits / 8, 128);
   if (ebits == 4) {
-    if (tn == 32) return (KT >= 12 && KT <= 32) ? 572 : 0;
-    if (tn == 48) return (KT >= 8 && KT <= 24) ? 573 : 0;
-    if (tn == 56) return (KT >= 8 && KT <= 16) ? 574 : 0;
-    if (tn == 64) return (KT >= 8 && KT <= 16) ? 575 : 0;
+    if (tn == 32) return (KT >= 12 && KT <= 32) ? f->variant : 0;
+    if (tn == 48) return (KT >= 8 && KT <= 24) ? f->variant : 0;
+    if (tn == 56) return (KT >= 8 && KT <= 16) ? f->variant : 0;
+    if (tn == 64) return (KT >= 8 && KT <= 16) ? f->variant : 0;
     return 0;
   }
-  if (tn == 32) return (KT >= 16 && KT <= 64) ? 572 : 0;
-  if (tn == 48) return (KT >= 16 && KT <= 32) ? 573 : 0;
+  if (tn == 32) return (KT >= 16 && KT <= 64) ? f->variant : 0;
+  if (tn == 48) return (KT >= 16 && KT <= 32) ? f->variant : 0;
   return 0;
-}
-template <int EBITS, int AFMT, bool RM>
-int launch_gemm_os16_tn(int tn, const GemmParams& p, hipStream_t s) {
-  switch (tn) {
-    case 16: return launch_gemm_os16<EBITS, AFMT, RM, 16>(p, s);
-    case 32: return launch_gemm_os16<EBITS, AFMT, RM, 32>(p, s);
-    case 48: return launch_gemm_os16<EBITS, AFMT, RM, 48>(p, s);
-    case 56: return launch_gemm_os16<EBITS, AFMT, RM, 56>(p, s);
-    case 64: return launch_gemm_os16<EBITS, AFMT, RM, 64>(p, s);
-  }
-  return fail(QAMD_ERR_INVALID, "gemm_mx_os16: no column tile of %d", tn);
 }
 // Does the one-shot kernel take the shape, and with how many columns per workgroup?  Returns 0 (no), 32 or 16.  32x32 tiles, one per CU at most; 16 columns per
 // workgroup whenever that still leaves one workgroup per CU (N = 4096, M <= 32: 256 workgroups pulling half the bytes each -- 3.34 -> 3.22 us at K = 4096, 7.8 -> 6.9 at
@@ -343,7 +340,7 @@ int launch_gemm_os16_tn(int tn, const GemmParams& p, hipStream_t s) {
 // M < 8 against more than 32 stages on the LDS-free split-K kernel (4096 x 11008, M = 1: 6.07 vs 6.40 us).  ada: matmul_ada_mxf4_bf16_tn (row-major scales: its other
 // kernels are 25-45 % slower on every such shape).  profiles/calib_os_r6q.txt, calib_osring_r6q.txt, calib_ada_r6q.txt, calib_os16_r6s.txt
 inline int os_plan(int64_t M, int64_t N, int64_t K, int64_t cus, bool ada = false) {
-  const int64_t T32 = cdiv(M, 32) * cdiv(N, 32), T16 = cdiv(M, 32) * cdiv(N, 16), KT = cdiv(K, 256);
+  const int64_t T32 = mx_tiles<MXV_OS32>(M, N), T16 = mx_tiles<MXV_OS16>(M, N), KT = cdiv(K, 256);
   if (T32 > cus) return 0;
   const int tn = T16 <= cus ? 16 : 32;
   if (KT <= 16) return tn;
@@ -361,7 +358,7 @@ inline int os_plan(int64_t M, int64_t N, int64_t K, int64_t cus, bool ada = fals
 // ada: matmul_ada_mxf4_bf16_tn has no scratch argument, so no split-K plan competes -- every measured K wins there (4096 x 4096, M = 96 / 128: 6.5 / 6.7 -> 6.0 / 6.3 us;
 // x 8192: 10.1 -> 8.9; x 14336: 20.9 / 22.6 -> 14.4 / 15.3; profiles/calib_ada_570_r7.txt)
 inline bool os64_plan(int64_t M, int64_t N, int64_t K, int64_t cus, bool ada = false) {
-  const int64_t T32 = cdiv(M, 32) * cdiv(N, 32), T64 = cdiv(M, 64) * cdiv(N, 32), KT = cdiv(K, 256);
+  const int64_t T32 = mx_tiles<MXV_OS32>(M, N), T64 = mx_tiles<MXV_OS64>(M, N), KT = cdiv(K, 256);
   if (T32 <= cus || T64 > cus) return false;
   if (ada) return KT <= 64;
   return KT <= 12 || (KT >= 40 && KT <= 64) || (KT >= 32 && KT < 40 && T64 == cus && M <= 64);   // (the last: 8192^2, M = 64; 4096 x 8192, M = 128 -- two tile rows -- loses 3 %)
@@ -376,22 +373,22 @@ inline bool os64_plan(int64_t M, int64_t N, int64_t K, int64_t cus, bool ada = f
 //   * 64-row tiles where the 32-row ones overflow the chip: 17 ... 128 stages (4096 x 8192, M = 96 / 128: 15.6 / 14.8 -> 12.0 / 12.5 us; 8192 x 4096, M = 64: 11.3 -> 9.3;
 //     K <= 2048 ties, K = 28672 loses 13 %).
 inline int os8_plan(int64_t M, int64_t N, int64_t K, int64_t cus) {
-  const int64_t T32 = cdiv(M, 32) * cdiv(N, 32), T16 = cdiv(M, 32) * cdiv(N, 16), T64 = cdiv(M, 64) * cdiv(N, 32), KT = cdiv(K, 128);
+  const int64_t T32 = mx_tiles<MXV_OS32>(M, N), T16 = mx_tiles<MXV_OS16>(M, N), T64 = mx_tiles<MXV_OS64>(M, N), KT = cdiv(K, 128);
   if (M <= 16) {   // the decode form with 32 / 48 columns per workgroup
     if (const int v = os16_wide_plan(8, N, K, cus)) return v;
   }
   if (T32 <= cus) {
-    const int v = T16 <= cus ? 569 : 568;
+    const int v = T16 <= cus ? MXV_OS16 : MXV_OS32;
     const int64_t G = T16 <= cus ? T16 : T32;
     // decode form (16x16 tiles on the 16x16x128 MFMA) where those fit one per CU, up to 64 stages (N = K = 4096, M <= 16: 4.85-4.98 -> 3.65-3.82 us; K = 14336: +2 ... 4 %)
-    const bool d16 = cdiv(M, 16) * cdiv(N, 16) <= cus;
-    if (KT <= 40) return d16 ? 571 : v;
+    const bool d16 = mx_tiles<MXV_D16>(M, N) <= cus;
+    if (KT <= 40) return d16 ? MXV_D16 : v;
     if (4 * G < 3 * cus) return 0;
-    if (KT <= 64) return d16 ? 571 : v;
+    if (KT <= 64) return d16 ? MXV_D16 : v;
     if (KT <= 128) return (M <= 32 || N >= 4096) ? v : 0;
     return (KT <= 256 && M <= 32) ? v : 0;
   }
-  return (T64 <= cus && KT > 16 && KT <= 128) ? 570 : 0;
+  return (T64 <= cus && KT > 16 && KT <= 128) ? MXV_OS64 : 0;
 }
 
 // ---- grouped MXFP4 GEMM (gemm_mx_grouped.hip.h): one launch over E experts ----------------------------------------------------------------------------------------
@@ -414,14 +411,7 @@ int launch_grouped_os(GroupedParams q, hipStream_t s) {
   constexpr int TM = F.tile[I].tm, TN = F.tile[I].tn, EBITS = F.ebits;
   q.tiles_m = 1;
   q.tiles_n = (int)cdiv(q.N, TN);
-  const int64_t KT = cdiv((int64_t)q.K * EBITS / 8, 128);
-  const dim3 grid((int)grouped_workgroups(q.M, q.N, q.E, TM, TN)), block(256);
-  constexpr int SMAX = TM == 32 ? 4 : 3;   // slots per wave that fit the LDS (launch_gemm_os)
-  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<1, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
-  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<2, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
-  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<3, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
-  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, true, false, true>), grid, block, 0, s, q);
-  else hipLaunchKernelGGL((gemm_mx_os_kernel<OsCfg<SMAX, TN, EBITS, TM, AFMT>, true, true, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  launch_os_by_stages<true, TN, EBITS, TM, AFMT, true>(cdiv((int64_t)q.K * EBITS / 8, 128), dim3((int)grouped_workgroups(q.M, q.N, q.E, TM, TN)), q, s);
   return check_launch("gemm_mx_os_kernel (grouped)");
 }
 // form F.form0 + 3 (the ring form) of an MX format
@@ -529,6 +519,11 @@ inline int grouped_form(const GroupedFormat& F, GroupedPlan plan, int64_t M, int
   const int forced = opt_gemm_variant();
   return F.has(forced) ? forced : plan(M, N, K, E, chip_cus());
 }
+// the fields of GroupedParams the dense MX kernels' base brings along: the lab's options, no split-K, no raster
+inline void grouped_mx_defaults(GroupedParams& q) {
+  q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
+  q.ws = nullptr; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+}
 // the fields GroupedParams and NvGroupedParams share (different bases, the same names)
 template <class P>
 void grouped_fill(P& q, const GroupedFormat& F, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
@@ -623,25 +618,19 @@ inline bool hetero_wins(int64_t T, int cus) {
   return b < a;
 }
 
-// Tile/schedule variants (0 = auto; the lab library can force one through the "gemm_variant" option):
-//   PRODUCT (what the auto rules below can pick):
-//     90  persistent deep schedule, 256x256 (fp4: gemm_mx_deepp, fp8: gemm_mx_deepp8)      lab: 30 = the per-tile deep schedule of round 1
-//   LAB only, [r4]:  89  = 90 as a stream-K walk (tiles of a part-filled round cut along K, fp32 parts parked in caller scratch).  Correct and
+// Tile/schedule variants (0 = auto; the lab library can force one through the "gemm_variant" option).  The PRODUCT forms -- what the auto rules below can pick -- are the rows of
+// MX_FORMS (gemm_mx_forms.hip.h: number, family, tile, wave grid, ring depth, ops); launch_mx_form launches one from its row.  Every other number is LAB only
+// (dispatch_lab_variant; 44 ... 49 and 89 also in mx_launch):
+//   [r4]  89  = 90 as a stream-K walk (tiles of a part-filled round cut along K, fp32 parts parked in caller scratch).  Correct and
 //     deterministic (tests/test_gpu_round4.py) and NOT adopted: a cut tile moves 256 KiB of fp32 sums through memory twice, and a stream over G + T % G
 //     tiles cuts ~G - gcd tiles -- 128 ... 255 parked tiles = 64 ... 128 MB per launch at ~3.7 TB/s: +18 us at 384 tiles, +34 us at 320 (MXFP4,
 //     K = 4096: 74.8 / 86.1 us against 57.0 balanced / 48.2 heterogeneous); break-even only beyond K ~ 14336, where the heterogeneous launch still
 //     matches or beats it (MXFP8 3072 x 8192 x 28672: 612 us stream-K, 601 heterogeneous, 666 balanced).  profiles/ab_mxsk_r4c.txt
-//     98  heterogeneous launch: 90 over the full rounds + the residual tiles as 128x128 tiles in the same grid     lab: 99 = 3-deep ring for those
-//     24 / 25 / 27 / 28 / 29  pipelined schedule on a 2-deep ring: 128x128, 256x128 (8 waves), 128x64, 64x128, 64x64      58  256x128 on four waves, 3-deep ring
-//     70..73  ring schedule 64x64, 128x64, 64x128, 128x128 (+ split-K)          60  skinny split-K kernel (fp4, M <= 32)
-//   LAB only:
+//   30 = the per-tile deep schedule of round 1 (fp4, 256x256, 4 waves of 128x128, LDS-DMA)      99 = 98 with a 3-deep ring for the residual tiles
 //   1  256x256 ping-pong     5  256x256 lockstep     6..9  queue schedule (256x256, 128x128, 256x128, 128x256)
-//   20 / 24 / 25 / 26  simple schedule (256x256, 128x128, 256x128, 128x256)
-//   60  skinny split-K kernel (fp4, M <= 32 per tile, no LDS staging): auto for M <= 32
-//   30  deep schedule (fp4, 256x256, 4 waves of 128x128, LDS-DMA)      40  regstage (same tiling, copy through registers)
-//   31..36, 41..43, 50..56  ablations / traces / clock probes of those (bench only)
-//   2  128x128 lockstep (small M or N)                     3  256x128 lockstep    4  128x256 lockstep
-//   100+b / 200+b  ablations of variants 1 / 5 (bench only), b = OR of ABL_* bits
+//   20 / 224 / 225 / 26  simple schedule (256x256, 128x128, 256x128, 128x256)      170..173  the round-1 ring schedule on the tiles of 70..73
+//   40  regstage (the tiling of 30, copy through registers)      44..49  other shapes of the skinny split-K kernel (waves, segments per trip, chunk mapping)
+//   31..36, 41..43, 50..56  ablations / traces / clock probes of those (bench only)      2 / 3 / 4  128x128 (small M or N) / 256x128 / 128x256 lockstep
 // bench-only ablations of the 8-wave 256x256 MXFP4 schedules: 100 + b ping-pong, 200 + b lockstep, 300 + b queue, b = OR
 // of ABL_* bits.  Returns -1 for any other variant.
 #if QAMD_BENCH
@@ -662,31 +651,73 @@ int dispatch_ablation_mx4(int v, const GemmParams& p, hipStream_t s);
 #endif
 #endif   // QAMD_BENCH
 
-template <int EBITS, bool SPLIT>
-int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name) {
-#if QAMD_BENCH
-  if (p.pp_flags & 4096) {   // lab: "pp_flags" bit 12 = the round-1 ring / simple schedules wherever their pipelined successors are picked
-    if (v >= 70 && v <= 73) v += 100;
-    else if (v == 24 || v == 25 || (v >= 27 && v <= 29)) v += 200;
-  }
-#endif
-  switch (v) {
-    // pipelined schedule on a 2-deep LDS ring (gemm_mx_ringp with NSTAGE = 2: the LDS footprint of the round-1 "simple" schedule,
-    // two workgroups per CU, but the next stage's fragments are read during this stage's MFMAs): -3 .. -13 % against the
-    // simple schedule on every mid-size shape measured (profiles/native_r2_midtile2.log)
-    case 24: return launch_gemm<GemmCfg<128, 128, 2, 2, EBITS, SPLIT, 0, 2>, 9>(p, s);
-    case 25: return launch_gemm<GemmCfg<256, 128, 4, 2, EBITS, SPLIT, 0, 2>, 9>(p, s);
-    case 27: return launch_gemm<GemmCfg<128, 64, 2, 2, EBITS, SPLIT, 0, 2>, 9>(p, s);    // mid-size problems: more, smaller tiles
-    // [r3] 256x128 on FOUR waves of 128x64, 3-deep ring, one workgroup per CU: 0.75 KiB of LDS fragment reads per MFMA against 1 KiB for the 64x64 wave
+int launch_mx_skinny(bool rm, const GemmParams& p, hipStream_t s);   // the LDS-free split-K kernel (rm: row-major scales) is small and stays in unit 1, with the entries
+// Row I of MX_FORMS for the op (EBITS, AFMT: 1 = e5m2 A, RM: row-major scales = matmul_ada_mxf4_bf16_tn): the row holds what picks the kernel configuration
+template <int I, int EBITS, int AFMT, bool RM>
+int launch_mx_row(const GemmParams& p, hipStream_t s) {
+  constexpr MxFormRow F = MX_FORMS[I];
+  static_assert(F.product && (F.ops & mx_op(EBITS, AFMT, RM)) != 0, "the form has no kernel for this op");
+  constexpr bool SPLIT = EBITS == 8;   // GemmCfg F8SPLIT: the fp8 kernels' split register layout
+  if constexpr (F.family == MXF_PIPELINED || F.family == MXF_RING || F.family == MXF_PERSISTENT) {
+    using C = GemmCfg<F.tm, F.tn, F.wm, F.wn, EBITS, SPLIT, 0, F.depth, AFMT>;
+    // pipelined schedule on an LDS ring (gemm_mx_ringp; row-major scales: its scale fetch of matmul_ada_mxf4_bf16_tn): NSTAGE-deep ring, NSTAGE - 1 stages in flight, the
+    // next stage's fragments are read during this stage's MFMAs.  2-deep (24 ... 29): the LDS footprint of the round-1 "simple" schedule, two workgroups per CU: -3 .. -13 %
+    // against the simple schedule on every mid-size shape measured (profiles/native_r2_midtile2.log).
+    // [r3] 58: 256x128 on FOUR waves of 128x64, 3-deep ring, one workgroup per CU: 0.75 KiB of LDS fragment reads per MFMA against 1 KiB for the 64x64 wave
     // tiles of 24 / 25 -- half-chip outputs with a long K (2048 x 4096 x 8192: 36.9 -> 35.4 us, x 14336: 60.6 -> 57.1; profiles/native_r3_halftile.log)
-    case 58: return launch_gemm<GemmCfg<256, 128, 2, 2, EBITS, SPLIT, 0, 3>, 9>(p, s);
-    case 28: return launch_gemm<GemmCfg<64, 128, 2, 2, EBITS, SPLIT, 0, 2>, 9>(p, s);
-    case 29: return launch_gemm<GemmCfg<64, 64, 2, 2, EBITS, SPLIT, 0, 2>, 9>(p, s);
-    case 70: return launch_gemm<GemmCfg<64, 64, 2, 2, EBITS, SPLIT, 0, 3>, 9>(p, s);     // pipelined ring schedule: NSTAGE-deep LDS ring, NSTAGE-1 stages in flight,
-    case 71: return launch_gemm<GemmCfg<128, 64, 2, 2, EBITS, SPLIT, 0, 3>, 9>(p, s);    //   fragments of the next stage read during this stage's MFMAs
-    case 72: return launch_gemm<GemmCfg<64, 128, 2, 2, EBITS, SPLIT, 0, 3>, 9>(p, s);
-    case 73: return launch_gemm<GemmCfg<128, 128, 2, 2, EBITS, SPLIT, 0, 3>, 9>(p, s);
+    if constexpr (F.family != MXF_PERSISTENT) return launch_gemm<C, RM ? 10 : 9>(p, s);
+    // persistent deep schedule; output stores write through (sc0 sc1): nothing dirty is left for the end-of-kernel L2
+    // write-back (4096^3: 34.6 -> 33.4 .. 34.4 us, never slower; profiles/native_r2_store_policy.log)
+    // The one-tile form of 90: the product's is the 16x16x128 one (kDeeppOneTile16).  In the LAB library 90 keeps the 32x32x64 form and 191 is the product's: the kernels the
+    // tests compare 90 with bit for bit (the 8-wave kernel 87 / 88, the ring and stream-K kernels) all group K by 64 per MFMA, and outside the exact regime of
+    // docs/history.md section 3.1 the grouping shows (random bytes with scale bytes 121 ... 129 at 4096^3: 23 of 16.8 M outputs differ in their last bf16 bit).
+    else if constexpr (EBITS == 4) return launch_gemm_deepp<C, false, 17, 0, QAMD_BENCH ? 32 : 0>(p, s);
+    else return launch_gemm_deepp8<C>(p, s);
+  } else if constexpr (F.family == MXF_HETERO) {
+    using CB = GemmCfg<F.tm, F.tn, F.wm, F.wn, EBITS, SPLIT, 0, 2, AFMT>;
+    using CT = GemmCfg<F.tm / 2, F.tn / 2, F.wm, F.wn, EBITS, SPLIT, 0, F.depth, AFMT>;
+    static_assert(CB::BM == kMxForm<MXV_PERSISTENT>.tm && CB::BN == kMxForm<MXV_PERSISTENT>.tn, "the full rounds run the persistent form");
+    return launch_gemm_hetero<CB, CT, 17>(p, s);
+  } else if constexpr (F.family == MXF_SKINNY) {
+    return launch_mx_skinny(RM, p, s);
+  } else if constexpr (F.family == MXF_KSPLIT) {
+    // [r6] K split inside the workgroup (gemm_mx_ks.hip.h).  Ring depth by the K stage count: a short K pays for a deep ring's prologue
+    // (4096^2 weights, M <= 64: 4.16 us 4-deep, 4.47 us 8-deep), a long one needs the stages in flight (8192^2: 9.4 us 4-deep, 7.4 us 6-deep; profiles/calib_ks_r6*.txt)
+    static_assert(KsCfg<F.tm, F.tn, F.depth>::TM == F.tm && KsCfg<F.tm, F.tn, F.depth>::TN == F.tn && F.depth == 4, "the K-split configuration is the row's");
+    return cdiv(p.K, 256) > 24 ? launch_gemm_ks<F.tm, F.tn, 6>(p, s) : launch_gemm_ks<F.tm, F.tn, F.depth>(p, s);
+  } else if constexpr (F.family == MXF_OS) {
+    // [r6] tiles on wave-owned K stages (gemm_mx_os.hip.h): one shot up to 16 stages (12 for the 64-row tile: two m-tiles per stage owner), wave-owned rings beyond
+    static_assert(OsCfg<1, F.tn, EBITS, F.tm, AFMT>::TM == F.tm && OsCfg<1, F.tn, EBITS, F.tm, AFMT>::TN == F.tn, "the wave-owned configuration is the row's");
+    return launch_gemm_os<RM, F.tn, EBITS, F.tm, AFMT>(p, s);
+  } else {
+    // [r6] decode form: 16 x (16 / 32 / 48 / 56 / 64) tiles on the 16x16x128 MFMA
+    static_assert(F.family == MXF_DECODE && Os16Cfg<1, EBITS, AFMT, F.tn>::TM == F.tm && Os16Cfg<1, EBITS, AFMT, F.tn>::TN == F.tn, "the decode configuration is the row's");
+    return launch_gemm_os16<EBITS, AFMT, RM, F.tn>(p, s);
+  }
+}
+// The ONE product dispatcher: variant v of MX_FORMS for the op.  A (form, op) pair the row's mask does not list is an error, as is a number without a row (MXFP8 with
+// an e5m2 A operand -- qutlass_amd_matmul_mxf8_bf16_{tn,nn}_fmt -- has the forms the auto rules can pick, nothing else).  One flat chain of comparisons: a switch.
+template <int I, int EBITS, int AFMT, bool RM>
+inline bool try_mx_row(int v, const GemmParams& p, hipStream_t s, int& rc) {
+  if constexpr (MX_FORMS[I].product && (MX_FORMS[I].ops & mx_op(EBITS, AFMT, RM)) != 0) {
+    if (v == MX_FORMS[I].variant) { rc = launch_mx_row<I, EBITS, AFMT, RM>(p, s); return true; }
+  }
+  return false;
+}
+template <int EBITS, int AFMT, bool RM, int... I>
+int launch_mx_form(int v, const GemmParams& p, hipStream_t s, const char* name, std::integer_sequence<int, I...>) {
+  int rc = 0;
+  if ((try_mx_row<I, EBITS, AFMT, RM>(v, p, s, rc) || ...)) return rc;
+  if (AFMT == 1) return fail(QAMD_ERR_INVALID, "%s: gemm_variant %d has no e5m2-operand instantiation", name, v);
+  return fail(QAMD_ERR_INVALID, "%s: unknown gemm_variant %d", name, v);
+}
+
 #if QAMD_BENCH
+// the numbers MX_FORMS does not own (blocked scales, e2m1 / e4m3 A)
+template <int EBITS>
+int dispatch_lab_variant(int v, const GemmParams& p, hipStream_t s, const char* name) {
+  constexpr bool SPLIT = EBITS == 8;
+  switch (v) {
     case 273: return launch_gemm<GemmCfg<128, 128, 2, 2, EBITS, SPLIT, 128, 3>, 9>(p, s);   // lab: 73 with the next stage's reads packed into the first MFMAs (ABL_READS_FIRST)
     case 272: return launch_gemm<GemmCfg<64, 128, 2, 2, EBITS, SPLIT, 128, 3>, 9>(p, s);
     case 270: return launch_gemm<GemmCfg<64, 64, 2, 2, EBITS, SPLIT, 128, 3>, 9>(p, s);
@@ -722,46 +753,13 @@ int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name
     case 83: return launch_gemm<GemmCfg<64, 64, 2, 2, EBITS, SPLIT, 34, 3>, 7>(p, s);    //   DMA + barriers only
     case 84: return launch_gemm<GemmCfg<64, 64, 2, 2, EBITS, SPLIT, 35, 3>, 7>(p, s);    //   barriers only
     case 78: return launch_gemm<GemmCfg<64, 64, 2, 2, EBITS, SPLIT, 16, 3>, 7>(p, s);    //   per-wave timeline of workgroup 0
-#endif
   }
   if constexpr (EBITS == 8) {
-#if QAMD_BENCH
     if (v == 89) return launch_gemm_deepp_sk<GemmCfg<256, 256, 2, 2, 8, true>>(p, s);
-#endif
-    if (v == 90) return launch_gemm_deepp8<GemmCfg<256, 256, 2, 2, 8, true>>(p, s);   // persistent deep schedule, fp8
-    // [r6] small batches on wave-owned K stages (gemm_mx_os.hip.h, EBITS = 8): 32x32 / 32x16 / 64x32 tiles
-    if (v == 568) return launch_gemm_os<false, 32, 8>(p, s);
-    if (v == 569) return launch_gemm_os<false, 16, 8>(p, s);
-    if (v == 570) return launch_gemm_os<false, 32, 8, 64>(p, s);
-    if (v >= 571 && v <= 575) return launch_gemm_os16_tn<8, 0, false>(v == 571 ? 16 : v == 572 ? 32 : v == 573 ? 48 : v == 574 ? 56 : 64, p, s);
-    if (v == 98) return launch_gemm_hetero<GemmCfg<256, 256, 2, 2, 8, true>, GemmCfg<128, 128, 2, 2, 8, true, 0, 4>, 17>(p, s);
-#if QAMD_BENCH
     if (v == 30) return launch_gemm<GemmCfg<256, 256, 2, 2, 8, true>, 4>(p, s);   // per-tile deep schedule (round 1)
-#endif
   }
   if constexpr (EBITS == 4) {
-    // persistent deep schedule; output stores write through (sc0 sc1): nothing dirty is left for the end-of-kernel L2
-    // write-back (4096^3: 34.6 -> 33.4 .. 34.4 us, never slower; profiles/native_r2_store_policy.log)
-#if QAMD_BENCH
     if (v == 89) return launch_gemm_deepp_sk<GemmCfg<256, 256, 2, 2, 4, false>>(p, s);
-#endif
-    // The one-tile form of 90: the product's is the 16x16x128 one (kDeeppOneTile16).  In the LAB library 90 keeps the 32x32x64 form and 191 is the product's: the kernels the
-    // tests compare 90 with bit for bit (the 8-wave kernel 87 / 88, the ring and stream-K kernels) all group K by 64 per MFMA, and outside the exact regime of
-    // docs/history.md section 3.1 the grouping shows (random bytes with scale bytes 121 ... 129 at 4096^3: 23 of 16.8 M outputs differ in their last bf16 bit).
-    if (v == 90) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, QAMD_BENCH ? 32 : 0>(p, s);
-    if (v == 98) return launch_gemm_hetero<GemmCfg<256, 256, 2, 2, 4, false>, GemmCfg<128, 128, 2, 2, 4, false, 0, 4>, 17>(p, s);
-    // [r6] K split inside the workgroup (gemm_mx_ks.hip.h): 561 = 32x32 tiles, 562 = 32x64.  Ring depth by the K stage count: a short K pays for a deep ring's prologue
-    // (4096^2 weights, M <= 64: 4.16 us 4-deep, 4.47 us 8-deep), a long one needs the stages in flight (8192^2: 9.4 us 4-deep, 7.4 us 6-deep; profiles/calib_ks_r6*.txt)
-    if (v == 561 || v == 562) {
-      const bool deep = cdiv(p.K, 256) > 24;
-      if (v == 561) return deep ? launch_gemm_ks<32, 32, 6>(p, s) : launch_gemm_ks<32, 32, 4>(p, s);
-      return deep ? launch_gemm_ks<32, 64, 6>(p, s) : launch_gemm_ks<32, 64, 4>(p, s);
-    }
-    if (v == 568) return launch_gemm_os<false>(p, s);       // [r6] 32x32 tiles on wave-owned K stages (gemm_mx_os.hip.h): one shot up to 16 stages, wave-owned rings beyond
-    if (v == 569) return launch_gemm_os<false, 16>(p, s);   // [r6] the same with 16 columns per workgroup
-    if (v == 570) return launch_gemm_os<false, 32, 4, 64>(p, s);   // [r6] 64x32 tiles (two m-tiles per stage owner)
-    if (v >= 571 && v <= 575) return launch_gemm_os16_tn<4, 0, false>(v == 571 ? 16 : v == 572 ? 32 : v == 573 ? 48 : v == 574 ? 56 : 64, p, s);   // [r6] decode form: 16 x (16 / 32 / 48 / 56 / 64) tiles on the 16x16x128 MFMA
-#if QAMD_BENCH
     if (v == 99) return launch_gemm_hetero<GemmCfg<256, 256, 2, 2, 4, false>, GemmCfg<128, 128, 2, 2, 4, false, 0, 3>, 17>(p, s);
     // [r6] lab: the other tiles / ring depths of the in-workgroup K-split kernel (563 = 64x32, 564 = 64x64; 565 - 567 = 32x32 with a 4 / 8 / 6-deep ring)
     if (v == 563 || v == 564) {
@@ -818,43 +816,34 @@ int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name
       case 22: return launch_gemm<GemmCfg<256, 256, 2, 4, 4, false, 9>, 3>(p, s);   //   no DMA, no epilogue
       case 23: return launch_gemm<GemmCfg<256, 256, 2, 4, 4, false, 10>, 3>(p, s);  //   no MFMA, no epilogue
     }
-#endif
   }
-#if QAMD_BENCH
   if constexpr (EBITS == 4 && !SPLIT) {
     const int rc = dispatch_ablation_mx4(v, p, s);
     if (rc >= 0) return rc;
   }
-#endif
   return fail(QAMD_ERR_INVALID, "%s: unknown gemm_variant %d", name, v);
 }
+#endif
 
-// MXFP8 with an e5m2 A operand (extension, include/qutlass_amd.h qutlass_amd_matmul_mxf8_bf16_{tn,nn}_fmt): the variants the
-// auto rules can pick, nothing else.
-int dispatch_variant_a5(int v, const GemmParams& p, hipStream_t s, const char* name)
-#if QAMD_DEF(4)   // (the e5m2-operand MXFP8 kernels ride with the NVFP4 unit: balances the parallel build)
-{
-  switch (v) {
-    case 24: return launch_gemm<GemmCfg<128, 128, 2, 2, 8, true, 0, 2, 1>, 9>(p, s);
-    case 25: return launch_gemm<GemmCfg<256, 128, 4, 2, 8, true, 0, 2, 1>, 9>(p, s);
-    case 27: return launch_gemm<GemmCfg<128, 64, 2, 2, 8, true, 0, 2, 1>, 9>(p, s);
-    case 58: return launch_gemm<GemmCfg<256, 128, 2, 2, 8, true, 0, 3, 1>, 9>(p, s);
-    case 28: return launch_gemm<GemmCfg<64, 128, 2, 2, 8, true, 0, 2, 1>, 9>(p, s);
-    case 29: return launch_gemm<GemmCfg<64, 64, 2, 2, 8, true, 0, 2, 1>, 9>(p, s);
-    case 90: return launch_gemm_deepp8<GemmCfg<256, 256, 2, 2, 8, true, 0, 2, 1>>(p, s);
-    case 98: return launch_gemm_hetero<GemmCfg<256, 256, 2, 2, 8, true, 0, 2, 1>, GemmCfg<128, 128, 2, 2, 8, true, 0, 4, 1>, 17>(p, s);
-    case 70: return launch_gemm<GemmCfg<64, 64, 2, 2, 8, true, 0, 3, 1>, 9>(p, s);
-    case 71: return launch_gemm<GemmCfg<128, 64, 2, 2, 8, true, 0, 3, 1>, 9>(p, s);
-    case 72: return launch_gemm<GemmCfg<64, 128, 2, 2, 8, true, 0, 3, 1>, 9>(p, s);
-    case 73: return launch_gemm<GemmCfg<128, 128, 2, 2, 8, true, 0, 3, 1>, 9>(p, s);
-    case 568: return launch_gemm_os<false, 32, 8, 32, 1>(p, s);   // [r6] small batches on wave-owned K stages, e5m2 A
-    case 569: return launch_gemm_os<false, 16, 8, 32, 1>(p, s);
-    case 570: return launch_gemm_os<false, 32, 8, 64, 1>(p, s);
-    case 571: case 572: case 573: case 574: case 575: return launch_gemm_os16_tn<8, 1, false>(v == 571 ? 16 : v == 572 ? 32 : v == 573 ? 48 : v == 574 ? 56 : 64, p, s);
+template <int EBITS, int AFMT, bool RM>
+int dispatch_variant(int v, const GemmParams& p, hipStream_t s, const char* name) {
+#if QAMD_BENCH
+  if constexpr (AFMT == 0 && !RM) {
+    if (p.pp_flags & 4096) {   // lab: "pp_flags" bit 12 = the round-1 ring / simple schedules wherever their pipelined successors are picked
+      const MxFormRow* f = mx_form(v);
+      if (f && f->family == MXF_RING) v += 100;
+      else if (f && f->family == MXF_PIPELINED && f->depth == 2) v += 200;   // (the simple schedule is 2-deep: the 3-deep 256x128 form has no round-1 twin)
+    }
+    if (!mx_form(v)) return dispatch_lab_variant<EBITS>(v, p, s, name);
   }
-  return fail(QAMD_ERR_INVALID, "%s: gemm_variant %d has no e5m2-operand instantiation", name, v);
+#endif
+  return launch_mx_form<EBITS, AFMT, RM>(v, p, s, name, std::make_integer_sequence<int, MX_NFORMS>());
 }
-int launch_nn_fused_a5(const GemmParams& p, hipStream_t s, bool per_tile) {
+
+// the e5m2-operand MXFP8 kernels ride with the NVFP4 unit: balances the parallel build
+int launch_nn_fused_a5(const GemmParams& p, hipStream_t s, bool per_tile)
+#if QAMD_DEF(4)
+{
 #if QAMD_BENCH
   if (per_tile) return launch_gemm<GemmCfg<256, 256, 2, 2, 8, true, 0, 2, 1>, 6>(p, s);
 #endif
@@ -863,25 +852,30 @@ int launch_nn_fused_a5(const GemmParams& p, hipStream_t s, bool per_tile) {
 }
 #else
 ;
-int launch_nn_fused_a5(const GemmParams& p, hipStream_t s, bool per_tile);
 #endif
 
+// fp4 / fp8 / fp8 with an e5m2 A are emitted in units 2 / 3 / 4; the row-major-scale op's forms are small and stay with its entry (unit 1)
 #if QAMD_TU != 0
 #if QAMD_TU == 2
-template int dispatch_variant<4, false>(int, const GemmParams&, hipStream_t, const char*);
+template int dispatch_variant<4, 0, false>(int, const GemmParams&, hipStream_t, const char*);
 #else
-extern template int dispatch_variant<4, false>(int, const GemmParams&, hipStream_t, const char*);
+extern template int dispatch_variant<4, 0, false>(int, const GemmParams&, hipStream_t, const char*);
 #endif
 #if QAMD_TU == 3
-template int dispatch_variant<8, true>(int, const GemmParams&, hipStream_t, const char*);
+template int dispatch_variant<8, 0, false>(int, const GemmParams&, hipStream_t, const char*);
 #if QAMD_BENCH
 template int launch_gemm<GemmCfg<256, 256, 2, 2, 8, true>, 6>(GemmParams, hipStream_t);   // lab: per-tile kernel on the (K, M) operand (round 1)
 #endif
 #else
-extern template int dispatch_variant<8, true>(int, const GemmParams&, hipStream_t, const char*);
+extern template int dispatch_variant<8, 0, false>(int, const GemmParams&, hipStream_t, const char*);
 #if QAMD_BENCH
 extern template int launch_gemm<GemmCfg<256, 256, 2, 2, 8, true>, 6>(GemmParams, hipStream_t);
 #endif
+#endif
+#if QAMD_TU == 4
+template int dispatch_variant<8, 1, false>(int, const GemmParams&, hipStream_t, const char*);
+#else
+extern template int dispatch_variant<8, 1, false>(int, const GemmParams&, hipStream_t, const char*);
 #endif
 #endif
 
@@ -900,20 +894,15 @@ int launch_nvf4_grouped_host(const NvGroupedParams& q, hipStream_t s, int form);
 // enough to pay for the second pass (>= 32 stages: fp4 K >= 8192).  One function so that the launcher and qutlass_amd_gemm_splitk_workspace_bytes
 // agree.  Measured: profiles/native_r1_ring.log.
 struct SmallPlan { int variant; int splits; };   // variant 0: not this regime
-// tile of a ring variant (70: 64x64, 71: 128x64, 72: 64x128, 73: 128x128)
-inline void ring_tile(int variant, int& bm, int& bn) {
-  bm = (variant == 71 || variant == 73) ? 128 : 64;
-  bn = (variant == 72 || variant == 73) ? 128 : 64;
-}
 // split-K scratch: [splits][M][N] fp32 partials (lab library: then, 256-byte aligned, one 64-bit arrival slot per output tile
 // for the fused-reduction experiment)
 inline int64_t splitk_partial_bytes(int64_t M, int64_t N, int splits) { return (int64_t)splits * M * N * 4; }
 inline int64_t splitk_ctr_offset(int64_t M, int64_t N, int splits) { return (splitk_partial_bytes(M, N, splits) + 255) / 256 * 256; }
 inline int64_t splitk_ws_bytes(int variant, int64_t M, int64_t N, int splits) {
 #if QAMD_BENCH
-  int bm, bn;
-  ring_tile(variant, bm, bn);
-  return splitk_ctr_offset(M, N, splits) + cdiv(M, bm) * cdiv(N, bn) * 8;
+  const MxFormRow* f = mx_form(variant);   // a ring form (only those split); a number without a row: the smallest ring tile, which has the most arrival slots
+  if (!f) f = &kMxForm<MXV_RING64>;
+  return splitk_ctr_offset(M, N, splits) + cdiv(M, f->tm) * cdiv(N, f->tn) * 8;
 #else
   (void)variant;
   return splitk_partial_bytes(M, N, splits);
@@ -922,7 +911,7 @@ inline int64_t splitk_ws_bytes(int variant, int64_t M, int64_t N, int splits) {
 // the round-1/2 rule: thresholds on the tile counts (fitted on sweeps of the in-stream C++ harness, profiles/native_r1_ring.log, native_r2_tilesplit.log)
 template <int EBITS>
 SmallPlan plan_small_rule(int64_t M, int64_t N, int64_t K, int64_t cus, bool may_split) {
-  const int64_t T64 = cdiv(M, 64) * cdiv(N, 64), T128 = cdiv(M, 128) * cdiv(N, 128);
+  const int64_t T64 = mx_tiles<MXV_RING64>(M, N), T128 = mx_tiles<MXV_RING128>(M, N);
   if (T64 <= cus) {
     const int64_t KT = cdiv(K * EBITS / 8, 128);
     int64_t S = 1;
@@ -937,10 +926,10 @@ SmallPlan plan_small_rule(int64_t M, int64_t N, int64_t K, int64_t cus, bool may
       // profiles/native_r2_tilesplit.log)
       if (S == 2 && KT < 48) S = 1;
     }
-    return {70, (int)S};
+    return {MXV_RING64, (int)S};
   }
-  if (T64 <= 2 * cus) return {N >= M ? 72 : 71, 1};
-  if (M > 64 && N > 64 && T128 <= cus) return {73, 1};
+  if (T64 <= 2 * cus) return {N >= M ? MXV_RING64x128 : MXV_RING128x64, 1};
+  if (M > 64 && N > 64 && T128 <= cus) return {MXV_RING128, 1};
   return {0, 1};
 }
 
@@ -957,7 +946,11 @@ SmallPlan plan_small_rule(int64_t M, int64_t N, int64_t K, int64_t cus, bool may
 template <int EBITS>
 SmallPlan plan_small(int64_t M, int64_t N, int64_t K, int64_t cus, bool may_split) {
   const SmallPlan cur = plan_small_rule<EBITS>(M, N, K, cus, may_split);
-  if (cur.variant != 70 && cur.variant != 72 && cur.variant != 73) return cur;      // (71: M > N, not calibrated)
+  static constexpr MxFormRow CAND[3] = {kMxForm<MXV_RING64>, kMxForm<MXV_RING64x128>, kMxForm<MXV_RING128>};      // (MXV_RING128x64: M > N, not calibrated)
+  int ccur = -1;
+  for (int c = 0; c < 3; ++c)
+    if (cur.variant == CAND[c].variant) ccur = c;
+  if (ccur < 0) return cur;
   //                                   64x64  64x128 128x128
   static constexpr double A4[3] = {6.07, 6.04, 6.30}, B4[3] = {3.41, 4.80, 6.58}, E4[3] = {0.99, 1.2, 1.2};
   static constexpr double A8[3] = {3.31, 3.79, 2.91}, B8[3] = {3.87, 4.83, 6.41}, E8[3] = {0.90, 1.2, 1.2};
@@ -965,18 +958,16 @@ SmallPlan plan_small(int64_t M, int64_t N, int64_t K, int64_t cus, bool may_spli
   const double* B = EBITS == 4 ? B4 : B8;
   const double* E = EBITS == 4 ? E4 : E8;
   const double r0 = EBITS == 4 ? 1.39 : 3.86, bw = EBITS == 4 ? 2.63e6 : 2.79e6;
-  static constexpr int VAR[3] = {70, 72, 73}, BM[3] = {64, 64, 128}, BN[3] = {64, 128, 128};
   const int64_t KT = cdiv(K * EBITS / 8, 128);
   auto price = [&](int c, int S, int* s2) {
     const int64_t per = cdiv(KT, S), S2 = cdiv(KT, per);
-    const double n = (double)(cdiv(M, BM[c]) * cdiv(N, BN[c]) * S2) / (double)cus;
+    const double n = (double)(cdiv(M, CAND[c].tm) * cdiv(N, CAND[c].tn) * S2) / (double)cus;
     double t = A[c] + (n <= 1.0 ? 1.0 : std::ceil(n) * E[c]) * B[c] * (double)per / 16.0;
     if (S2 > 1) t += r0 + (double)(S2 + 1) * (double)M * (double)N * 4.0 / bw;
     *s2 = (int)S2;
     return t;
   };
   int s2;
-  const int ccur = cur.variant == 70 ? 0 : cur.variant == 72 ? 1 : 2;
   const double t_cur = price(ccur, cur.splits, &s2);
   SmallPlan best = cur;
   double t_best = t_cur;
@@ -985,14 +976,14 @@ SmallPlan plan_small(int64_t M, int64_t N, int64_t K, int64_t cus, bool may_spli
       if (S > 1 && cdiv(KT, S) < 4) continue;
       const double t = price(c, S, &s2);
       if (S > 1 && s2 < 2) continue;
-      if (t < t_best) { t_best = t; best = {VAR[c], s2}; }
+      if (t < t_best) { t_best = t; best = {CAND[c].variant, s2}; }
     }
   SmallPlan res = (t_best >= 12.0 && t_best < 0.92 * t_cur) ? best : cur;
   // A long K (>= 96 stages) on 64x128 tiles, single pass: 128x128 tiles in two K ranges while those still fit one per CU -- the guard above leaves these alone (the fit
   // is coarse there), the GPU-only measurement does not: all ten such shapes of the calibration grid gain 8 ... 25 % (MXFP8 384 / 512 x 4096 x 14336 38.6 / 43.0 -> 32.1 /
   // 36.1 us, MXFP4 256 x 8192 x 28672 46.1 -> 42.2, 384 x 5120 x 25600 41.0 -> 36.2), every shape with fewer stages ties or loses
   // (profiles/calib_mx_small_r3_graph_m192_1024.txt, profiles/instream_mx_plan_check_r3.txt)
-  if (may_split && N % 4 == 0 && res.variant == 72 && res.splits == 1 && KT >= 96 && 2 * cdiv(M, 128) * cdiv(N, 128) <= cus) res = {73, 2};
+  if (may_split && N % 4 == 0 && res.variant == MXV_RING64x128 && res.splits == 1 && KT >= 96 && 2 * mx_tiles<MXV_RING128>(M, N) <= cus) res = {MXV_RING128, 2};
   return res;
 }
 
@@ -1003,10 +994,10 @@ SmallPlan plan_small(int64_t M, int64_t N, int64_t K, int64_t cus, bool may_spli
 //     (N = 4096, K = 14336: M <= 16 8.1-9.1 us split against 9.2-9.4; M = 64 11.4 against 9.8).
 // Where it applies it is 11 ... 30 % faster (N = K = 4096: M <= 64 4.9-5.3 -> 4.1-4.5 us; 8192^2: M <= 32 8.8-11.1 -> 7.4-7.8 us), M = 1 ... 8 included (the LDS-free
 // split-K kernel: 4.55-4.92 us at N = K = 4096).  32x64 tiles: only where 32x32 tiles just overflow the chip and 32x64 nearly fill it (N = 14336: -6 %).
-// Returns the variant (568 / 569 / 570 / 571 / 561 / 562) or 0.
+// Returns the variant (a wave-owned, decode or K-split row of MX_FORMS) or 0.
 inline int ks_plan(int64_t M, int64_t N, int64_t K, int64_t cus) {
   const int64_t KT = cdiv(K, 256);
-  const int64_t T32 = cdiv(M, 32) * cdiv(N, 32);
+  const int64_t T32 = mx_tiles<MXV_KS32>(M, N);
   // [r6] K <= 4096: the tile's whole K extent fits the LDS -- the one-shot kernel (gemm_mx_os.hip.h), no ring and no barrier in the K walk: N = K = 4096, M = 1 ... 64
   // 4.05-4.39 -> 3.34-3.67 us, N = K = 2048 3.15-3.26 -> 2.62-2.77 (profiles/calib_os_r6q.txt); its wave-owned-ring form for longer K and 16 columns per workgroup where os_plan says so
   // (4096 x 8192, M <= 32: 5.8-7.1 -> 5.5-5.7 us); past one tile per CU the ring plans below keep the shape
@@ -1016,13 +1007,13 @@ inline int ks_plan(int64_t M, int64_t N, int64_t K, int64_t cus) {
   if (const int tn = os_plan(M, N, K, cus)) {
     // [r6] decode form (gemm_mx_os16_kernel, 16x16 tiles on the 16x16x128 MFMA) wherever those fit one per CU: a third fewer bytes through each CU's LDS-DMA path
     // (N = K = 4096, M <= 16: 3.25-3.31 -> 2.86-2.92 us; K = 8192 5.0-5.2 -> 3.7-4.1; K = 14336 6.8-7.0 -> 6.1-6.5; two per CU (N = 8192) lose 9 %; profiles/calib_os16_r7.txt)
-    if (cdiv(M, 16) * cdiv(N, 16) <= cus) return 571;
-    return tn == 16 ? 569 : 568;
+    if (mx_tiles<MXV_D16>(M, N) <= cus) return MXV_D16;
+    return tn == 16 ? MXV_OS16 : MXV_OS32;
   }
-  if (os64_plan(M, N, K, cus)) return 570;   // [r6] 64x32 tiles on wave-owned K stages where 32x32 tiles overflow the chip
-  if (T32 <= cus && (KT <= 24 || (2 * T32 > cus && KT <= 64))) return 561;   // (K > 16384 was not calibrated, and a split-K plan on larger tiles moves fewer bytes per CU there)
-  const int64_t T64 = cdiv(M, 32) * cdiv(N, 64);
-  if (M <= 32 && T32 > cus && T64 <= cus && 8 * T64 >= 7 * cus && KT <= 24) return 562;
+  if (os64_plan(M, N, K, cus)) return MXV_OS64;   // [r6] 64x32 tiles on wave-owned K stages where 32x32 tiles overflow the chip
+  if (T32 <= cus && (KT <= 24 || (2 * T32 > cus && KT <= 64))) return MXV_KS32;   // (K > 16384 was not calibrated, and a split-K plan on larger tiles moves fewer bytes per CU there)
+  const int64_t T64 = mx_tiles<MXV_KS32x64>(M, N);
+  if (M <= 32 && T32 > cus && T64 <= cus && 8 * T64 >= 7 * cus && KT <= 24) return MXV_KS32x64;
   return 0;
 }
 
@@ -1045,7 +1036,7 @@ int for_each_range(const char* name, int64_t M, int64_t N, int64_t rowbytes, int
   return QAMD_OK;
 }
 
-// One launch of a range: `variant` (dispatch_variant's numbering) over columns [c0, c0 + n) of the range, K in `splits` ranges (> 1: fp32 partials in the
+// One launch of a range: `variant` (an MxVariant, or a lab number) over columns [c0, c0 + n) of the range, K in `splits` ranges (> 1: fp32 partials in the
 // caller's scratch, then the reduce pass).  A range takes at most two launches (the lab's two-launch experiment, "pp_flags" bit 13).
 // ws: split-K scratch of the range's split form, what the caller's scratch must hold for the split to be taken (0: none)
 struct MxLaunch { int variant; int64_t c0, n; int splits; };
@@ -1073,8 +1064,8 @@ MxPlan mx_plan(int a_fmt, int64_t M, int64_t N, int64_t K, int64_t ldd, int64_t 
     splits = (int)cdiv(KT, cdiv(KT, splits));
     return r.add(v, 0, N, can_split(v, splits) ? splits : 1);
   };
-  if (variant == 77) return ring(70, pl.variant == 70 ? pl.splits : 1);   // lab: 64x64 ring (+ split-K) whatever M
-  if (variant >= 70 && variant <= 73 && opt_splitk_force() > 0) return ring(variant, opt_splitk_force());   // lab: forced tile x forced split
+  if (variant == 77) return ring(MXV_RING64, pl.variant == MXV_RING64 ? pl.splits : 1);   // lab: 64x64 ring (+ split-K) whatever M
+  if (opt_splitk_force() > 0 && mx_form(variant) && mx_form(variant)->family == MXF_RING) return ring(variant, opt_splitk_force());   // lab: forced tile x forced split
   // small batch (M <= 32): weight-bandwidth bound.  With fewer than 128 64-row tiles (N < 8192) the split-K kernel without
   // LDS staging wins (gemm_mx_skinny.hip.h: N = K = 4096, M = 16: 5.9 us vs 7.1 us for the ring kernel on 64 CUs); from
   // 128 tiles on, the 64x64 ring kernel streams the weight through full-line LDS-DMA and wins (N = 14336, K = 4096: 6.9 us
@@ -1090,77 +1081,76 @@ MxPlan mx_plan(int a_fmt, int64_t M, int64_t N, int64_t K, int64_t ldd, int64_t 
   }
   const bool split = pl.variant && can_split(pl.variant, pl.splits);
   const bool skinny_auto = variant == 0 && !split && ((M <= 8 && cdiv(N, 64) <= cus / 2) || (M <= 24 && cdiv(N, 64) <= cus / 8));
-  if (EBITS == 4 && (variant == 60 || (variant >= 44 && variant <= 49) || skinny_auto)) return r.add(variant ? variant : 60, 0, N);
+  if (EBITS == 4 && (variant == MXV_SKINNY || (variant >= 44 && variant <= 49) || skinny_auto)) return r.add(variant ? variant : MXV_SKINNY, 0, N);
   if (variant == 0 && !(pp & 256) && pl.variant) return ring(pl.variant, pl.splits);
   if (variant == 0) {
     // auto (measured, profiles/native_r1_schedules.log, profiles/bench_sweep_*.txt): the largest tile that still gives
     // every CU work -- 256x256 ("deep" schedule, 4 waves of 128x128), then 128x128, 128x64 / 64x128, 64x64 (simple
     // schedule, several workgroups per CU).  (fp4 with M <= 32 went to the split-K kernel above.)
-    auto tiles = [&](int bm, int bn) { return cdiv(M, bm) * cdiv(N, bn); };
     const int64_t want = cus * 3 / 4;   // 3/4 of the CUs
     // no point in tiles taller than the problem; 64x64 until 64x128 tiles fill the chip 1.5 times (weight-bandwidth
     // bound: N = 28672, K = 4096, M = 32: 12.6 us with 448 tiles of 64x64 vs 14.3 us with 224 of 64x128)
-    if (M <= 64) variant = (tiles(64, 128) >= cus * 3 / 2) ? 28 : 29;
-    else if (N <= 64) variant = (tiles(128, 64) >= want) ? 27 : 29;
+    if (M <= 64) variant = (mx_tiles<MXV_P64x128>(M, N) >= cus * 3 / 2) ? MXV_P64x128 : MXV_P64;
+    else if (N <= 64) variant = (mx_tiles<MXV_P128x64>(M, N) >= want) ? MXV_P128x64 : MXV_P64;
     // [r3] at most 128 rows against a wide weight (more 128x128 tiles than CUs): the 256-row persistent tile would be half empty -- 128x128 tiles, two workgroups
     // per CU (96 x 57344 x 8192: 52.4 -> 42.7 us, 128 x 51200 x 5120: 32.7 -> 26.8, MXFP8 96 x 57344 x 8192 113.5 -> 100.3; profiles/calib_mx_small_r3.txt)
-    else if (M <= 128 && tiles(128, 128) >= want) variant = 24;
+    else if (M <= 128 && mx_tiles<MXV_P128>(M, N) >= want) variant = MXV_P128;
     // [r3] ... or more than HALF of them with K >= 8 stages: the smaller tiles then no longer fit one round (128x128: two per CU, 256x128: one per CU --
     // both hold exactly cus / 2 tiles' worth of 256x256 output), and a second, part-filled round costs more than idle CUs do:
     // 2560 x 4096 x 4096 (160 tiles) 34.6 -> 28.8 us, 1536 x 6144 x 4096 33.2 -> 28.3, 2048 x 5120 x 5120 42.2 -> 35.3, MXFP8 2560 x 4096 x 4096
     // 49.3 -> 39.4, K = 14336 likewise (146.9 -> 120.9); at exactly half (2048 x 4096: 128 tiles) the small tiles tie or win
     // (tools/calib_tiles.py, profiles/calib_tiles_r3.txt; found by tools/dip_scan.py: a LARGER batch ran faster)
-    else if (tiles(256, 256) >= want || (2 * tiles(256, 256) > cus && cdiv(K * EBITS / 8, 128) >= 8)) {
+    else if (mx_tiles<MXV_PERSISTENT>(M, N) >= want || (2 * mx_tiles<MXV_PERSISTENT>(M, N) > cus && cdiv(K * EBITS / 8, 128) >= 8)) {
       // the persistent deep schedule (one workgroup per CU walks the tiles, epilogue folded into the last K stage), fp4 and
       // fp8; its epilogue addresses a tile with 32-bit byte offsets, so absurdly wide outputs stay with 256x128 simple tiles
-      const int big = ldd < (1ll << 22) ? 90 : 25;
+      const int big = ldd < (1ll << 22) ? MXV_PERSISTENT : MXV_P256x128_W8;
       variant = big;
       // Wave quantisation: T tiles on `cus` CUs run ceil(T / cus) rounds, the last one part-filled (4096 x 5120: 320 tiles =
       // 1.25 rounds).  [r3] The residual tiles run as 128x128 quarter tiles on extra workgroups of the SAME launch
       // (gemm_mx_hetero_kernel: dispatched CU by CU as the persistent workgroups retire) whenever the cost model says so;
       // otherwise ONE persistent launch with balanced rounds (deepp_grid).
-      const int64_t tm = cdiv(M, 256), tn = cdiv(N, 256), T = tm * tn;
-      bool hetero_ok = big == 90 && !(pp & 64);   // (lab, "pp_flags" bit 6: balanced rounds only)
+      constexpr MxFormRow BIG = kMxForm<MXV_PERSISTENT>;
+      const int64_t tm = cdiv(M, BIG.tm), tn = cdiv(N, BIG.tn), T = tm * tn;
+      bool hetero_ok = big == MXV_PERSISTENT && !(pp & 64);   // (lab, "pp_flags" bit 6: balanced rounds only)
 #if QAMD_BENCH
       // lab, "pp_flags" bit 13: the round-1/2 form of the same idea INSTEAD -- the trailing tile columns as a SECOND launch of smaller
       // tiles (kept for the A/B in profiles/native_r3_heterobench.log)
       const int64_t full = (T / cus) * cus, main_cols = (tm > 0) ? full / tm : 0;
       const bool two_launch = (pp & 8192) != 0;
       if (two_launch && hetero_ok && full >= cus && full < 3 * cus && main_cols >= 1 && main_cols < tn && (T - main_cols * tm) <= 80) {
-        const int64_t n1 = main_cols * 256, Nt = N - n1;
-        auto tt = [&](int bm, int bn) { return cdiv(M, bm) * cdiv(Nt, bn); };
-        const int vt = (tt(256, 128) >= want) ? 25 : (tt(128, 128) >= want) ? 24 : (tt(128, 64) >= want) ? 27 : 29;
+        const int64_t n1 = main_cols * BIG.tn, Nt = N - n1;
+        const int vt = (mx_tiles<MXV_P256x128_W8>(M, Nt) >= want) ? MXV_P256x128_W8 : (mx_tiles<MXV_P128>(M, Nt) >= want) ? MXV_P128 : (mx_tiles<MXV_P128x64>(M, Nt) >= want) ? MXV_P128x64 : MXV_P64;
         return r.add(big, 0, n1).add(vt, n1, Nt);
       }
       if (two_launch) hetero_ok = false;
 #endif
-      if (hetero_ok && hetero_wins(T, cus)) variant = 98;
+      if (hetero_ok && hetero_wins(T, cus)) variant = MXV_HETERO;
     }
-    else if (tiles(128, 128) >= want) {
+    else if (mx_tiles<MXV_P128>(M, N) >= want) {
       // [r3] half-chip outputs (fewer than `want` tiles of 256x256): with a long K (>= 32 stages) the 256x128 tile on four waves wins 5-6 %
       // over 128x128 tiles on two workgroups per CU; with K = 4096 the two tie (22.97 vs 22.95 us at 2048 x 4096 x 4096) and 128x128 stays
       const int64_t KTs = cdiv(K * EBITS / 8, 128);
       // (MXFP8 likewise: 2048 x 4096 x 4096 34.9 -> 32.7 us, x 8192 63.2 -> 57.1 us; K = 2048 = 16 stages: -2 %, stays)
-      variant = (M >= 256 && KTs >= 32 && tiles(256, 128) >= want) ? 58 : 24;
+      variant = (M >= 256 && KTs >= 32 && mx_tiles<MXV_P256x128>(M, N) >= want) ? MXV_P256x128 : MXV_P128;
       // [r3] ... and, at the same K, whenever the 128x128 grid no longer fits one tile per CU while the 256x128 grid still does: the CUs that hold
       // two 128x128 tiles set the kernel's time.  MXFP8 768 x 6144 x 4096 28.3 -> 23.5 us, 1024 x 5120 x 5120 36.9 -> 29.6, 1024 x 5120 x 25600
       // 145.3 -> 120.8; MXFP4 1024 x 5120 x 25600 83.5 -> 75.2.  Not below 32 stages: MXFP4 2048 x 4096 x 4096 23.6 against 26.6 on the 256x128 tile
       // (profiles/calib_tiles_r3.txt)
-      if (M >= 256 && KTs >= 32 && tiles(128, 128) > cus && tiles(256, 128) <= cus) variant = 58;
+      if (M >= 256 && KTs >= 32 && mx_tiles<MXV_P128>(M, N) > cus && mx_tiles<MXV_P256x128>(M, N) <= cus) variant = MXV_P256x128;
     }
-    else if (tiles(128, 64) >= want || tiles(64, 128) >= want) variant = (N >= M) ? 27 : 28;
-    else variant = 29;
+    else if (mx_tiles<MXV_P128x64>(M, N) >= want || mx_tiles<MXV_P64x128>(M, N) >= want) variant = (N >= M) ? MXV_P128x64 : MXV_P64x128;
+    else variant = MXV_P64;
   }
   if (variant == 89) {   // (lab: forced stream-K; falls back to the persistent kernel when the shape has nothing to cut or the scratch is missing)
-    const int64_t T = cdiv(M, 256) * cdiv(N, 256), KTe = (cdiv(K * EBITS / 8, 128) + 1) / 2 * 2;
+    const int64_t T = mx_tiles<MXV_PERSISTENT>(M, N), KTe = (cdiv(K * EBITS / 8, 128) + 1) / 2 * 2;
     const bool ok = a_fmt == 0 && avail >= sk_ws_bytes(cus) && T % cus != 0 && T > cus && KTe >= 8 && (K * EBITS / 8) % 256 == 0 && ldd < (1ll << 22);
-    if (!ok) variant = 90;
+    if (!ok) variant = MXV_PERSISTENT;
   }
   return r.add(variant, 0, N);
 }
 
-// matmul_ada_mxf4_bf16_tn (row-major scales): the variant of the kernel with row-major scale fetch, in dispatch_variant's numbering -- 60 the LDS-free split-K
-// kernel, 70 the 64x64 ring (lab: 178 = its round-1 schedule), 568 / 569 / 570 the wave-owned kernel with 32x32 / 32x16 / 64x32 tiles, 571 ... 575 its decode form
+// matmul_ada_mxf4_bf16_tn (row-major scales): the form of the kernel with row-major scale fetch, a row of MX_FORMS with MXOP_ADA -- the LDS-free split-K
+// kernel, the 64x64 ring (lab: 178 = its round-1 schedule), the wave-owned kernel with 32x32 / 32x16 / 64x32 tiles, its decode form
 // with 16 / 32 / 48 / 56 / 64 columns per workgroup.  Never split-K: the op has no scratch argument.
 inline int ada_plan(int64_t M, int64_t N, int64_t K, int cus) {
   // Same regimes as matmul_mxf4_bf16_tn: the LDS-free split-K kernel while the weight has fewer than 128 64-row tiles;
@@ -1170,21 +1160,22 @@ inline int ada_plan(int64_t M, int64_t N, int64_t K, int cus) {
   const int forced = opt_gemm_variant();
   const int64_t T64 = cdiv(N, 64);   // (no split-K here -- the op has no scratch argument -- so a long K on few tiles stays with the split-K kernel:
                                      //  8 x 8192 x 28672: 27.9 us vs 34.2 us on 128 workgroups of the ring kernel)
-  const bool ring = forced == 70 || (forced != 60 && (M > 32 || T64 >= cus || (T64 >= cus / 2 && K < 16384)));
+  const bool ring = forced == MXV_RING64 || (forced != MXV_SKINNY && (M > 32 || T64 >= cus || (T64 >= cus / 2 && K < 16384)));
   // [r6] K <= 4096 and at most one 32x32 tile per CU: the one-shot kernel with row-major scale pieces (gemm_mx_os.hip.h; "gemm_variant" 568 forces it where it fits)
   const int os_tn = forced == 0 ? os_plan(M, N, K, cus, true) : 0;
-  const bool os16 = forced == 569 || os_tn == 16;   // 16 columns per workgroup
+  const bool os16 = forced == MXV_OS16 || os_tn == 16;   // 16 columns per workgroup
   // [r6] ... its decode form (16x16 tiles on the 16x16x128 MFMA) where those fit one per CU (matmul_mxf4_bf16_tn's rule, ks_plan)
-  if (forced >= 571 && forced <= 575) return forced;
-  if (os_tn != 0 && cdiv(M, 16) * cdiv(N, 16) <= cus) return 571;
+  const MxFormRow* ff = mx_form(forced);
+  if (ff && ff->family == MXF_DECODE) return forced;
+  if (os_tn != 0 && mx_tiles<MXV_D16>(M, N) <= cus) return MXV_D16;
   if (forced == 0 && M <= 16) {
     if (const int v = os16_wide_plan(4, N, K, cus)) return v;   // (wider column tiles: matmul_mxf4_bf16_tn's rule)
   }
-  const bool os64 = forced == 570 || (forced == 0 && os_tn == 0 && os64_plan(M, N, K, cus, true));   // 64x32 tiles where the 32-row tiles overflow the chip (os64_plan)
-  const bool oneshot = (forced >= 568 && forced <= 570) ? cdiv(M, 32) * cdiv(N, 32) <= 4 * cus : (os_tn != 0 || os64);
-  if (oneshot) return os64 ? 570 : os16 ? 569 : 568;
-  if (ring) return forced == 178 ? 178 : 70;
-  return 60;
+  const bool os64 = forced == MXV_OS64 || (forced == 0 && os_tn == 0 && os64_plan(M, N, K, cus, true));   // 64x32 tiles where the 32-row tiles overflow the chip (os64_plan)
+  const bool oneshot = (ff && ff->family == MXF_OS) ? mx_tiles<MXV_OS32>(M, N) <= 4 * cus : (os_tn != 0 || os64);
+  if (oneshot) return os64 ? MXV_OS64 : os16 ? MXV_OS16 : MXV_OS32;
+  if (ring) return forced == 178 ? 178 : MXV_RING64;
+  return MXV_SKINNY;
 }
 
 // ---- the executor.  The operands of one MX GEMM: scales in the to_blocked layout (128-row blocks of ceil(K / 128) 512-byte pieces: the TN and NN ops) or row-major (rows, K / 32)
@@ -1224,6 +1215,13 @@ inline SkinnyParams skinny_params(const GemmParams& p) {
   return q;
 }
 
+int launch_mx_skinny(bool rm, const GemmParams& p, hipStream_t s) {
+  constexpr MxFormRow F = kMxForm<MXV_SKINNY>;   // wm waves; depth segments per wave per trip: 32 b128 loads in flight per wave
+  if (rm) launch_skinny<false, F.wm, F.depth, false>(skinny_params(p), s);
+  else launch_skinny<true, F.wm, F.depth, false>(skinny_params(p), s);
+  return check_launch("gemm_mx_skinny_kernel");
+}
+
 // the second launch of a split: sum the `splits` K ranges of fp32 partials in ws in fixed z order, alpha, bf16 (deterministic; gemm_mx.hip.h)
 inline int splitk_reduce(const char* name, int splits, const void* ws, uint16_t* D, const float* alpha, int M, int N, int ldd, hipStream_t s) {
   const int64_t quads = (int64_t)M * (N / 4);
@@ -1242,27 +1240,24 @@ template <int EBITS>
 int mx_launch(const char* name, const MxLaunch& l, GemmParams p, void* ws, int a_fmt, hipStream_t s) {
   // one place decides which instantiation family a variant number is looked up in
   auto dispatch = [&](int v) -> int {
-    if (EBITS == 8 && a_fmt == 1) return dispatch_variant_a5(v, p, s, name);
-    return dispatch_variant<EBITS, EBITS == 8>(v, p, s, name);
+    if (EBITS == 8 && a_fmt == 1) return dispatch_variant<8, 1, false>(v, p, s, name);
+    return dispatch_variant<EBITS, 0, false>(v, p, s, name);
   };
-  if (EBITS == 4 && (l.variant == 60 || (l.variant >= 44 && l.variant <= 49))) {
-    const SkinnyParams q = skinny_params(p);
-    switch (l.variant) {   // 44..49: lab-only shapes of the split-K kernel (waves, segments per trip, chunk mapping)
 #if QAMD_BENCH
+  if (EBITS == 4 && l.variant >= 44 && l.variant <= 49) {   // lab-only shapes of the split-K kernel (waves, segments per trip, chunk mapping)
+    const SkinnyParams q = skinny_params(p);
+    switch (l.variant) {
       case 44: launch_skinny<true, 8, 2, true>(q, s); break;
       case 45: launch_skinny<true, 4, 2, false>(q, s); break;
       case 46: launch_skinny<true, 4, 2, true>(q, s); break;
       case 47: launch_skinny<true, 8, 2, false>(q, s); break;
       case 48: launch_skinny<true, 8, 1, true>(q, s); break;
       case 49: launch_skinny<true, 4, 4, true>(q, s); break;
-#endif
-      default: launch_skinny<true, 8, 4, false>(q, s);   // 4 segments per wave per trip: 32 b128 loads in flight per wave
     }
     return check_launch("gemm_mx_skinny_kernel");
   }
-#if QAMD_BENCH
   if (l.variant == 89) {   // lab: stream-K over the caller's scratch (the persistent kernel when that is not 16-byte aligned)
-    if ((uintptr_t)ws % 16) return dispatch(90);
+    if ((uintptr_t)ws % 16) return dispatch(MXV_PERSISTENT);
     const int cus = chip_cus();
     p.sk_tiles = (int)(cus + cdiv(p.M, 256) * cdiv(p.N, 256) % cus);
     p.ws = (float*)ws;
@@ -1639,7 +1634,7 @@ int64_t qutlass_amd_gemm_splitk_workspace_bytes(int ebits, int64_t M, int64_t N,
   int64_t need = (ebits == 4 ? mx_plan<4>(0, M, N, K, N, INT64_MAX, cus) : mx_plan<8>(0, M, N, K, N, INT64_MAX, cus)).ws;
 #if QAMD_BENCH
   if (opt_gemm_variant() == 89) need = std::max<int64_t>(need, sk_ws_bytes(cus));   // lab: forced stream-K
-  if (opt_splitk_force() > 1) need = std::max<int64_t>(need, splitk_ws_bytes(70, M, N, 8));   // lab: room for any forced tile x split
+  if (opt_splitk_force() > 1) need = std::max<int64_t>(need, splitk_ws_bytes(MXV_RING64, M, N, 8));   // lab: room for any forced tile x split
 #endif
   return need;
 }
@@ -1676,17 +1671,11 @@ int qutlass_amd_matmul_ada_mxf4_bf16_tn(const void* A, const void* B, const void
   const hipStream_t s = (hipStream_t)stream;
   return for_each_range(name, M, N, K / 2, 64, [&](int64_t r0, int64_t c0, int64_t m, int64_t n) -> int {
     const GemmParams p = mx_params(x, r0, c0, m, n);
-    switch (const int v = ada_plan(m, n, K, chip_cus())) {
-      case 60: launch_skinny<false, 8, 4, false>(skinny_params(p), s); return check_launch("gemm_mx_skinny_kernel");
-      case 70: return launch_gemm<GemmCfg<64, 64, 2, 2, 4, false, 0, 3>, 10>(p, s);
+    const int v = ada_plan(m, n, K, chip_cus());
 #if QAMD_BENCH
-      case 178: return launch_gemm<GemmCfg<64, 64, 2, 2, 4, false, 0, 3>, 8>(p, s);   // round-1 ring schedule
+    if (v == 178) return launch_gemm<GemmCfg<64, 64, 2, 2, 4, false, 0, 3>, 8>(p, s);   // round-1 ring schedule
 #endif
-      case 568: return launch_gemm_os<true>(p, s);
-      case 569: return launch_gemm_os<true, 16>(p, s);
-      case 570: return launch_gemm_os<true, 32, 4, 64>(p, s);
-      default: return launch_gemm_os16_tn<4, 0, true>(v == 571 ? 16 : v == 572 ? 32 : v == 573 ? 48 : v == 574 ? 56 : 64, p, s);
-    }
+    return dispatch_variant<4, 0, true>(v, p, s, name);
   });
 }
 
@@ -1697,8 +1686,7 @@ int qutlass_amd_grouped_matmul_mxf4_bf16_tn(const void* A, const void* B, const 
   if (M == 0) return QAMD_OK;
   GroupedParams q;
   grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
-  q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
-  q.ws = nullptr; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  grouped_mx_defaults(q);
   const int v = grouped_form(F, grouped_plan, M, N, K, E);
   return launch_grouped_mx<GRP_MXF4, GroupedRingCfg>(v, q, (hipStream_t)stream);   // (the ring form: matmul_ada_mxf4_bf16_tn's ring tiles)
 }
@@ -1711,8 +1699,7 @@ int qutlass_amd_grouped_matmul_mxf8_bf16_tn(const void* A, const void* B, const 
   if (M == 0) return QAMD_OK;
   GroupedParams q;
   grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
-  q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
-  q.ws = nullptr; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  grouped_mx_defaults(q);
   const int v = grouped_form(F, grouped8_plan, M, N, K, E);
   hipStream_t s = (hipStream_t)stream;
   return a_format == QAMD_FP8_E5M2 ? launch_grouped_mx<GRP_MXF8, GroupedRing8Cfg<1>, 1>(v, q, s) : launch_grouped_mx<GRP_MXF8, GroupedRing8Cfg<0>, 0>(v, q, s);
@@ -1725,8 +1712,7 @@ int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, c
   if (M == 0) return QAMD_OK;
   GroupedParams q;
   grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
-  q.pp_shift = opt_pp_shift(); q.pp_flags = opt_pp_flags(); q.dbg = opt_dbg();
-  q.ws = nullptr; q.ctr = nullptr; q.tag = 0; q.raster_magic = 0; q.sk_tiles = 0;
+  grouped_mx_defaults(q);
   return launch_grouped_w4a8(grouped_form(F, grouped_w4a8_plan, M, N, K, E), q, (hipStream_t)stream);
 }
 
@@ -2354,7 +2340,7 @@ int qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn(const void* x, const void* h,
   if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
   if (N * (K / 2) >= (1ll << 31) || M * K * 2 >= (1ll << 31) || cdiv(N, 32) >= (1ll << 31)) return fail(QAMD_ERR_INVALID, "%s: operand larger than 2 GiB is not supported", name);
 #if QAMD_BENCH
-  if (const int tn = opt_gemm_variant() == 580 && M <= 16 && K <= 8192 ? os16_tn(N, chip_cus()) : 0) return fusedq_lab_handoff(name, x, h, method, B, B_sf, alpha, D, M, N, K, tn, (hipStream_t)stream);
+  if (const MxFormRow* f = opt_gemm_variant() == 580 && M <= 16 && K <= 8192 ? os16_form(N, chip_cus()) : nullptr) return fusedq_lab_handoff(name, x, h, method, B, B_sf, alpha, D, M, N, K, f->tn, (hipStream_t)stream);
 #endif
   FusedQParams p;
   p.x = (const uint16_t*)x; p.h = (const uint16_t*)h; p.B = (const uint8_t*)B; p.SFB = (const uint8_t*)B_sf; p.alpha = alpha; p.D = (uint16_t*)D;
@@ -2511,6 +2497,16 @@ int qutlass_amd_debug_gemm_plan(int ebits, int64_t M, int64_t N, int64_t K, int6
   return debug_plan(name, M, N, K * ebits / 8, 256, out, cap, [&](int64_t m, int64_t n) {
     return ebits == 4 ? mx_plan<4>(0, m, n, K, N, avail, 256) : mx_plan<8>(0, m, n, K, N, avail, 256);
   });
+}
+
+// debug only (not declared in the public header): MX_FORMS, nine ints per row in the order of MxFormRow's fields; writes the first min(cap / 9, rows) rows, returns the row count
+int qutlass_amd_debug_mx_forms(int* out, int cap) {
+  for (int i = 0; i < MX_NFORMS && 9 * (i + 1) <= cap; ++i) {
+    const MxFormRow& f = MX_FORMS[i];
+    const int row[9] = {f.variant, f.family, f.tm, f.tn, f.wm, f.wn, f.depth, f.ops, (int)f.product};
+    std::copy(row, row + 9, out + 9 * i);
+  }
+  return MX_NFORMS;
 }
 
 // debug only (not declared in the public header): the same for matmul_ada_mxf4_bf16_tn (ada_plan; K splits are always 1)

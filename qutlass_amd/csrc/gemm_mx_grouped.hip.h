@@ -211,7 +211,7 @@ __device__ __forceinline__ bool grouped_setup(const GroupedParams& pk, GroupedVi
 // type of its own (same constants): the body's templates are instantiated for this kernel alone, so the compiler's view of the plain kernel's instantiation -- called
 // from that kernel only -- and with it that kernel's code stay exactly as they were.
 struct GroupedRingCfg : GemmCfg<64, 64, 2, 2, 4, false, 0, 3> {};
-// grouped_matmul_mxf8_bf16_tn's: the tiles of matmul_mxf8_bf16_tn's product ring (split 8-bit fragments, dispatch_variant<8, true>), A e4m3 (AFMT 0) or e5m2 (1)
+// grouped_matmul_mxf8_bf16_tn's: the tiles of matmul_mxf8_bf16_tn's product ring (split 8-bit fragments, MX_FORMS MXV_RING64 for MXFP8), A e4m3 (AFMT 0) or e5m2 (1)
 template <int AFMT>
 struct GroupedRing8Cfg : GemmCfg<64, 64, 2, 2, 8, true, 0, 3, AFMT> {};
 template <class C>

@@ -5,7 +5,7 @@ A CASE is one kernel form of one MX GEMM op at one shape: (op, a5, variant, lab 
            "nn" matmul_mxf8_bf16_nn (_fmt entry; A stored (K, M)) | "g4" / "g8" grouped_matmul_mxf{4,8}_bf16_tn (m = token rows over GROUPED_E experts, offs[-1] == m) |
            "g48" grouped_matmul_mxf8_mxf4_bf16_tn (W4A8: e4m3 tokens against e2m1 weights; its reference is tests/_w4a8_model.py, the oracle has no mixed kind)
   a5       MXFP8 only: A in e5m2
-  variant  the lab library's "gemm_variant" (capi.hip dispatch_variant's numbering; 62 / 63: the two operand paths of the NN op; 590 ... 597, 602 ... 604: the grouped forms)
+  variant  the lab library's "gemm_variant" (the MxVariant numbers of csrc/gemm_mx_forms.hip.h MX_FORMS, which tests read through qutlass_amd_debug_mx_forms; 62 / 63: the two operand paths of the NN op; 590 ... 597, 602 ... 604: the grouped forms)
   options  further lab options: deepp_grid (persistent workgroups, so that each walks several tiles), splitk_force (K ranges of a forced ring tile: the _ws entry with scratch)
 
 Shapes are the smallest at which a form can still go wrong: two tiles plus a ragged remainder in M (not a multiple of 16) and in N (a multiple of 8, not of the tile), a K

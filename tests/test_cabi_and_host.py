@@ -560,7 +560,7 @@ def test_auto_dispatch_rules_dry_run(lib):
 
 def test_ada_dispatch_rule(lib):
     """matmul_ada_mxf4_bf16_tn's kernel choice (capi.hip ada_plan: row-major scales, no scratch so no split-K) on a 256-CU part, through its debug entry:
-    (variant, N of the launch, K splits) per launch, in dispatch_variant's numbering."""
+    (variant, N of the launch, K splits) per launch, in the numbering of csrc/gemm_mx_forms.hip.h MX_FORMS."""
     f = lib.qutlass_amd_debug_ada_plan   # debug entry, deliberately not in the public header
     f.restype = ctypes.c_int
     f.argtypes = [ctypes.c_int64] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
