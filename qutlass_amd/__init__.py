@@ -212,7 +212,14 @@ def _quantize(op: str, *args):
     twin; under torch.compile: the functional op (see ops.py)."""
     if torch.compiler.is_compiling():
         return getattr(_ops_amd, op)(*args)
-    return ops.run_quant_op(ops.QUANT_OPS[op], *args)
+    return ops.run_quant(ops.QUANT_OPS[op], *args)
+
+
+def _output(op: str, *args):
+    """The same for every other op that fills results allocated here (a row of ops.OUTPUT_OPS)."""
+    if torch.compiler.is_compiling():
+        return getattr(_ops_amd, op)(*args)
+    return ops.run_output(ops.OUTPUT_OPS[op], *args)
 
 
 def fusedQuantizeMx(a: torch.Tensor, b: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest",
@@ -227,12 +234,7 @@ def fusedQuantizeMx(a: torch.Tensor, b: torch.Tensor, *, method: Literal["quest"
         return _quantize("quantize_mx", a, b, code)
     if method != "quest":
         raise ValueError("return_mask is only supported for method 'quest'")
-    if torch.compiler.is_compiling():
-        return _ops_amd.quantize_mx_mask(a, b)
-    xh_e2m1, xh_e8m0 = ops.alloc_quant(ops.QUANT_OPS["quantize_mx"], a)
-    clip_mask = torch.empty(*a.shape[:-1], a.size(-1) // 8, dtype=torch.uint8, device=a.device)
-    _ops_amd.fusedQuantizeMxMask_(a, b, xh_e2m1, xh_e8m0, clip_mask)
-    return xh_e2m1, xh_e8m0, clip_mask
+    return _output("quantize_mx_mask", a, b)
 
 
 def fusedQuantizeNv(a: torch.Tensor, b: torch.Tensor, global_scale: torch.Tensor, *,
@@ -261,11 +263,7 @@ def silu_and_mul(x: torch.Tensor) -> torch.Tensor:
         s = bf16(g / (1 + exp(-g)))  (correctly rounded: fp32 arithmetic, fp64 near a bf16 tie),   act = bf16(float(s) * float(u))
 
     i.e. what ``torch.nn.functional.silu(gate) * up`` computes in bf16.  I % 8 == 0; no size limit below 2^31 rows / columns."""
-    if torch.compiler.is_compiling():
-        return _ops_amd.silu_and_mul(x)
-    out = torch.empty(*x.shape[:-1], x.size(-1) // 2, dtype=x.dtype, device=x.device)
-    _ops_amd.siluAndMul_(x, out)
-    return out
+    return _output("silu_and_mul", x)
 
 
 def _silu_mul_quantize(op: str, x, *args):
@@ -341,11 +339,7 @@ def moe_topk_softmax(logits: torch.Tensor, topk: int, *, renormalize: bool = Tru
         raise ValueError(f"logits must be (T, E) (got {tuple(logits.shape)})")
     if not 1 <= topk <= min(logits.size(1), 32):
         raise ValueError(f"topk must be in [1, min(E, 32)] (got topk = {topk} for E = {logits.size(1)})")
-    if torch.compiler.is_compiling():
-        return _ops_amd.moe_topk_softmax(logits, topk, renormalize)
-    weights, ids = ops._alloc_topk(logits, topk)
-    _ops_amd.moeTopkSoftmax_(logits, weights, ids, renormalize)
-    return weights, ids
+    return _output("moe_topk_softmax", logits, topk, renormalize)
 
 
 def moe_sort_fused(topk_ids: torch.Tensor, num_experts: int, *, expert_map: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -359,9 +353,7 @@ def moe_sort_fused(topk_ids: torch.Tensor, num_experts: int, *, expert_map: torc
     expert with pos = -1 and are not counted in offs, as in moe_sort.  No host sync: graph-capturable; traces under torch.compile."""
     if topk_ids.dim() != 2:
         raise ValueError(f"topk_ids must be (T, topk) (got {tuple(topk_ids.shape)})")
-    if torch.compiler.is_compiling():
-        return _ops_amd.moe_sort_fused(topk_ids, expert_map, num_experts)
-    return ops.run_moe_sort(topk_ids, expert_map, num_experts)
+    return _output("moe_sort_fused", topk_ids, expert_map, num_experts)
 
 
 def moe_route(logits: torch.Tensor, topk: int, num_experts: int | None = None, *, renormalize: bool = True,
@@ -417,8 +409,8 @@ def moe_topk_grouped(logits: torch.Tensor, topk: int, *, n_group: int = 1, topk_
     logits bf16 or float32, contiguous; 1 <= E <= 1024, 1 <= n_group <= 64, E % n_group == 0, 1 <= topk_group <= n_group, 1 <= topk <= min(32, topk_group * S);
     T == 0 returns empty tensors.  No host sync, no workspace: graph-capturable; traces under torch.compile."""
     _check_grouped(logits, topk, n_group, topk_group, bias, scoring)
-    run = _ops_amd.moe_topk_grouped if torch.compiler.is_compiling() else ops.run_moe_topk_grouped
-    weights, ids, scores = run(logits, bias, topk, n_group, topk_group, _lib.MOE_SCORING[scoring], renormalize, float(routed_scaling_factor), return_scores)
+    weights, ids, scores = _output("moe_topk_grouped", logits, bias, topk, n_group, topk_group, _lib.MOE_SCORING[scoring], renormalize, float(routed_scaling_factor),
+                                   return_scores)
     return (weights, ids, scores) if return_scores else (weights, ids)
 
 
@@ -590,9 +582,7 @@ def swiglu_oai_and_mul(x: torch.Tensor, *, alpha: float = 1.702, limit: float = 
     Measured 4.5-5.4x faster (with fusedQuantizeMx behind it) than the torch composition of bias add, clamp, sigmoid and multiply (README;
     profiles/bench_swiglu_oai_mi355x.txt)."""
     alpha, limit = _check_swiglu_oai(x, alpha, limit, bias, offs)
-    if torch.compiler.is_compiling():
-        return _ops_amd.swiglu_oai_and_mul(x, alpha, limit, bias, offs)
-    return ops.run_swiglu_oai(x, alpha, limit, bias, offs)
+    return _output("swiglu_oai_and_mul", x, alpha, limit, bias, offs)
 
 
 def fusedSwigluOaiQuantizeMx(x: torch.Tensor, h: torch.Tensor, *, alpha: float = 1.702, limit: float = 7.0, bias: torch.Tensor | None = None,
@@ -628,9 +618,7 @@ def fusedSwigluOaiQuantizeMxf8(x: torch.Tensor, h: torch.Tensor, *, alpha: float
     (1.15-1.17x at 4096 tokens): keep swiglu_oai_and_mul + fusedQuantizeMxf8 for R = 64 at decode sizes.  4.5-7.0x (R = 32) faster than the torch composition; as
     fast as fusedSwigluOaiQuantizeMx on the same input (0.99-1.02x: the kernel is bound by the activation's vector work, not by the code bytes)."""
     alpha, limit = _check_swiglu_oai(x, alpha, limit, bias, offs, h.size(0) if h.dim() == 2 else None, "fusedSwigluOaiQuantizeMxf8", "fusedQuantizeMxf8")
-    if torch.compiler.is_compiling():
-        return _ops_amd.swiglu_oai_quantize_mxf8(x, h, alpha, limit, bias, offs)
-    return ops.run_swiglu_oai_quant(ops.SWIGLU_OAI_MXF8, x, h, alpha, limit, bias, offs)
+    return _quantize("swiglu_oai_quantize_mxf8", x, h, alpha, limit, bias, offs)
 
 
 def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor, *, bias: torch.Tensor | None = None, offs: torch.Tensor | None = None) -> torch.Tensor:
@@ -656,15 +644,10 @@ def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor, *, bi
             if bias.dim() != 2 or bias.size(1) != y.size(-1):
                 raise ValueError(f"bias must be (E, H) = (E, {y.size(-1)}) (got {tuple(bias.shape)})")
             _check_bias_offs(bias, offs)
-            return ops.run_moe_combine_bias(y, pos, weights, bias, offs)
-        return _ops_amd.moe_combine_bias(y, pos, weights, bias, offs)
+        return _output("moe_combine_bias", y, pos, weights, bias, offs)
     if offs is not None:
         raise ValueError("offs without a bias")
-    if torch.compiler.is_compiling():
-        return _ops_amd.moe_combine(y, pos, weights)
-    out = torch.empty(pos.size(0), y.size(-1), dtype=y.dtype, device=y.device)
-    _ops_amd.moeCombine_(y, pos, weights, out)
-    return out
+    return _output("moe_combine", y, pos, weights)
 
 
 def _decode_single_launch_wins(m: int, n: int, k: int, rot: int, device: torch.device | None = None) -> bool:
@@ -704,34 +687,33 @@ def backward_t_bf16(x: torch.Tensor, h: torch.Tensor, xh_e2m1: torch.Tensor = No
                     xh_e8m0: torch.Tensor = None) -> tuple[torch.Tensor, torch.Tensor]:
     """qutlass/__init__.py:206-243: abs-max MXFP4 of x^T (last two dims swapped) rotated per 32 along the old
     second-to-last dim.  Outputs (.., M, N/2) float4_e2m1fn_x2 and (.., M, N/32) e8m0 for x of shape (.., N, M)."""
-    if xh_e2m1 is None and xh_e8m0 is None and torch.compiler.is_compiling():
-        assert x.dtype == h.dtype == torch.bfloat16 and x.is_contiguous() and h.is_contiguous()
-        return _ops_amd.backward_t(x, h)
-    if xh_e2m1 is None:
-        xh_e2m1 = torch.empty(*x.shape[:-2], x.size(-1), x.size(-2) // 2, dtype=torch.float4_e2m1fn_x2, device=h.device)
-    if xh_e8m0 is None:
-        xh_e8m0 = torch.empty(*x.shape[:-2], x.size(-1), x.size(-2) // 32, dtype=torch.float8_e8m0fnu, device=h.device)
-    assert x.dtype == h.dtype == torch.bfloat16
+    assert x.dtype == h.dtype == torch.bfloat16 and x.is_contiguous() and h.is_contiguous()
+    if xh_e2m1 is None and xh_e8m0 is None:
+        return _output("backward_t", x, h)
+    xh_e2m1, xh_e8m0 = _provided("backward_t", (x, h), xh_e2m1, xh_e8m0)
     assert xh_e2m1.dtype == torch.float4_e2m1fn_x2 and xh_e8m0.dtype == torch.float8_e8m0fnu
-    assert x.is_contiguous() and h.is_contiguous() and xh_e2m1.is_contiguous() and xh_e8m0.is_contiguous()
+    assert xh_e2m1.is_contiguous() and xh_e8m0.is_contiguous()
     _ops_amd.backward_t_bf16_(x, h, xh_e2m1, xh_e8m0)
     return xh_e2m1, xh_e8m0
+
+
+def _provided(op: str, args, xh_e2m1, xh_e8m0):
+    """The results of backward_t_bf16 / backward_qt_bf16 where the caller provides some: the others from the op's row.  Its allocator puts them on h's device, as the
+    reference's wrappers do (and the fake kernel with it); for every valid call that is x's device."""
+    if xh_e2m1 is not None and xh_e8m0 is not None:
+        return xh_e2m1, xh_e8m0
+    fresh = ops.OUTPUT_OPS[op].alloc(*args)
+    return fresh[0] if xh_e2m1 is None else xh_e2m1, fresh[1] if xh_e8m0 is None else xh_e8m0
 
 
 def backward_qt_bf16(x_e2m1: torch.Tensor, x_e8m0: torch.Tensor, h: torch.Tensor, alpha: torch.Tensor,
                      xh_e2m1: torch.Tensor = None, xh_e8m0: torch.Tensor = None) -> tuple[torch.Tensor, torch.Tensor]:
     """qutlass/__init__.py:246-286: the same on an MXFP4 operand (x_e2m1 (.., N, M/2), x_e8m0 (.., N, M/32))."""
-    if xh_e2m1 is None and xh_e8m0 is None and torch.compiler.is_compiling():
-        assert x_e2m1.is_contiguous() and x_e8m0.is_contiguous() and h.is_contiguous()
-        return _ops_amd.backward_qt(x_e2m1, x_e8m0, h, alpha)
-    if xh_e2m1 is None:
-        xh_e2m1 = torch.empty(*x_e2m1.shape[:-2], x_e2m1.size(-1) * 2, x_e2m1.size(-2) // 2,
-                              dtype=torch.float4_e2m1fn_x2, device=h.device)
-    if xh_e8m0 is None:
-        xh_e8m0 = torch.empty(*x_e8m0.shape[:-2], x_e8m0.size(-1) * 32, x_e8m0.size(-2) // 32,
-                              dtype=torch.float8_e8m0fnu, device=h.device)
-    assert (x_e2m1.is_contiguous() and x_e8m0.is_contiguous() and h.is_contiguous()
-            and xh_e2m1.is_contiguous() and xh_e8m0.is_contiguous())
+    assert x_e2m1.is_contiguous() and x_e8m0.is_contiguous() and h.is_contiguous()
+    if xh_e2m1 is None and xh_e8m0 is None:
+        return _output("backward_qt", x_e2m1, x_e8m0, h, alpha)
+    xh_e2m1, xh_e8m0 = _provided("backward_qt", (x_e2m1, x_e8m0, h, alpha), xh_e2m1, xh_e8m0)
+    assert xh_e2m1.is_contiguous() and xh_e8m0.is_contiguous()
     _ops_amd.backward_qt_bf16_(x_e2m1, x_e8m0, h, alpha, xh_e2m1, xh_e8m0)
     return xh_e2m1, xh_e8m0
 
@@ -739,29 +721,14 @@ def backward_qt_bf16(x_e2m1: torch.Tensor, x_e8m0: torch.Tensor, h: torch.Tensor
 def backward_bf16_square_double_mxfp8(x_bf16: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """qutlass/__init__.py:288-297: e4m3 with one e8m0 per 32 x 32 block, returned row-wise (m_pad, n/32) and column-wise
     (n, m_pad/32), m_pad = rows rounded up to 128.  The missing rows are zeros INSIDE the kernel: no padded copy of x."""
-    if torch.compiler.is_compiling():
-        return _ops_amd.square_double_mxfp8(x_bf16)
-    m, n = x_bf16.shape
-    m_pad = ceil_div(m, 128) * 128
-    x_fp8 = torch.empty(m_pad, n, device=x_bf16.device, dtype=torch.float8_e4m3fn)
-    row_scales = torch.empty(m_pad, n // 32, device=x_bf16.device, dtype=torch.float8_e8m0fnu)
-    column_scales = torch.empty(n, m_pad // 32, device=x_bf16.device, dtype=torch.float8_e8m0fnu)
-    _ops_amd.backward_bf16_square_double_mxfp8_(x_bf16, x_fp8, row_scales, column_scales)
-    return x_fp8, row_scales, column_scales
+    return _output("square_double_mxfp8", x_bf16)
 
 
 def mxfp4_transpose_mxfp8(x_fp4: torch.Tensor, scales: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """qutlass/__init__.py:299-315: MXFP4 (m, n/2) + e8m0 (m, n/32) -> transposed e4m3 (n, m_pad) + e8m0 (n, m_pad/32), m_pad = rows
     rounded up to 256 as in the reference.  The padding rows (zero codes, unit scales) exist only inside the kernel: x_fp4 is
     not copied and `scales` is not written (the reference's own "TODO: padding in kernel")."""
-    if torch.compiler.is_compiling():
-        return _ops_amd.transpose_mxfp8(x_fp4, scales)
-    m = x_fp4.shape[0]
-    m_pad = ceil_div(m, 256) * 256
-    x_fp8 = torch.empty(x_fp4.shape[1] * 2, m_pad, device=x_fp4.device, dtype=torch.float8_e4m3fn)
-    shared_exps = torch.empty(x_fp4.shape[1] * 2, m_pad // 32, device=x_fp4.device, dtype=torch.float8_e8m0fnu)
-    _ops_amd.mxfp4_transpose_mxfp8_(x_fp4, scales, x_fp8, shared_exps)
-    return x_fp8, shared_exps
+    return _output("transpose_mxfp8", x_fp4, scales)
 
 
 _OUT_OF_SCOPE = ()

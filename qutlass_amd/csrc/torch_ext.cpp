@@ -43,36 +43,40 @@ struct Named {
 
 std::string arg_desc(int pos, const char* name) { return "argument #" + std::to_string(pos) + " '" + name + "'"; }
 
-// ---- the three generic checks of include/bindings_utils.h, table-driven ------------------------------------------
-// List: a braced list of {tensor, name} (the default: a braced argument deduces nothing), or a std::vector<Named> where the list is put together at run time
-template <class List = std::initializer_list<Named>>
-void require_contiguous(const char* op, const List& args) {
+// ---- the three generic checks of include/bindings_utils.h, once per op, in the reference's order ------------------------------------------
+// Every tensor of `args` contiguous (argument numbers count from 0); then every tensor of `args` and of `device_only` -- tensors that need not be contiguous: a
+// one-element alpha or global scale -- on a GPU; then all of them on the device of the first (numbers count through both lists).  same_gpu false: no third pass
+// (the QAT-backward ops, as the reference).  head: the tensor the third pass compares with where it is not args[0] -- an optional tensor is checked on its own,
+// against the op's first tensor as argument #0.
+// Lists: braced lists of {tensor, name} (the default: a braced argument deduces nothing), or std::vector<Named> where a list is put together at run time
+using Args = std::initializer_list<Named>;
+
+template <class List = Args, class DeviceOnly = Args>
+void check_tensors(const char* op, const List& args, const DeviceOnly& device_only = {}, bool same_gpu = true, const Named* head = nullptr) {
   int pos = 0;
   for (const Named& a : args) {
     STD_TORCH_CHECK(a.t.is_contiguous(), "Expected contiguous tensor, but got non-contiguous tensor for ", arg_desc(pos, a.name),
                     " (while checking arguments for ", op, ")");
     ++pos;
   }
-}
-
-template <class List = std::initializer_list<Named>>
-void require_gpu(const char* op, const List& args) {
-  for (const Named& a : args)
+  const auto on_gpu = [op](const Named& a) {
     STD_TORCH_CHECK(a.t.is_cuda(), "Expected tensor to have cuda DeviceType, but got tensor with ", a.t.is_cpu() ? "cpu" : "another",
                     " DeviceType (while checking arguments for ", op, ")");
-}
-
-template <class List = std::initializer_list<Named>>
-void require_same_gpu(const char* op, const List& args) {
-  const Named& first = *args.begin();
-  int pos = 0;
-  for (const Named& a : args) {
+  };
+  for (const Named& a : args) on_gpu(a);
+  for (const Named& a : device_only) on_gpu(a);
+  if (!same_gpu) return;
+  const Named& first = head ? *head : *args.begin();
+  pos = head ? 1 : 0;
+  const auto same = [op, &first, &pos](const Named& a) {
     if (pos > 0)
       STD_TORCH_CHECK(a.t.get_device_index() == first.t.get_device_index(), "Expected tensor for ", arg_desc(0, first.name),
                       " to have the same device as tensor for ", arg_desc(pos, a.name), "; but device ", first.t.get_device_index(),
                       " does not equal ", a.t.get_device_index(), " (while checking arguments for ", op, ")");
     ++pos;
-  }
+  };
+  for (const Named& a : args) same(a);
+  for (const Named& a : device_only) same(a);
 }
 
 // dtype through the C shim: Tensor::scalar_type() goes through the stable IValue conversion, which in torch 2.10 does
@@ -92,6 +96,14 @@ void* current_stream(const Tensor& t) {   // include/common.h:40-45
 void check_rc(int rc) { STD_TORCH_CHECK(rc == QAMD_OK, qutlass_amd_last_error()); }
 
 // ---- block-scaled GEMMs --------------------------------------------------------------------------------------------
+// scratch of a GEMM, from torch's stream-ordered caching allocator: 0 bytes -- the shape needs none -- allocate nothing and give a null pointer
+struct Workspace {
+  int64_t bytes;
+  Tensor t;
+  Workspace(const Tensor& like, int64_t n) : bytes(n), t(n > 0 ? torch::stable::new_empty(like, {n}, ScalarType::Byte) : Tensor()) {}
+  void* ptr() const { return bytes > 0 ? t.data_ptr() : nullptr; }
+};
+
 enum class Gemm { MXF4, NVF4, MXF8_TN, MXF8_NN, ADA_MXF4 };
 
 template <Gemm G>
@@ -99,10 +111,8 @@ Tensor matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor
   constexpr bool fp8 = G == Gemm::MXF8_TN || G == Gemm::MXF8_NN;
   constexpr bool nn = G == Gemm::MXF8_NN;
   const char* op = G == Gemm::ADA_MXF4 ? "matmul_ada_mxf4_bf16_tn" : G == Gemm::MXF4 ? "matmul_mxf4_bf16_tn" : G == Gemm::NVF4 ? "matmul_nvf4_bf16_tn" : G == Gemm::MXF8_TN ? "matmul_mxf8_bf16_tn" : "matmul_mxf8_bf16_nn";
-  if (fp8) require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}});
-  else require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}});
-  require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}});
-  require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}});
+  if (fp8) check_tensors(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}});
+  else check_tensors(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}}, {{alpha, "alpha"}});   // (the reference's FP4 GEMMs do not ask for a contiguous alpha)
 
   const ScalarType data_t = fp8 ? ScalarType::Float8_e4m3fn : ScalarType::Byte;
   const ScalarType sf_t = G == Gemm::NVF4 ? ScalarType::Float8_e4m3fn : ScalarType::Float8_e8m0fnu;
@@ -150,29 +160,22 @@ Tensor matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor
   int rc;
   if (G == Gemm::ADA_MXF4) rc = qutlass_amd_matmul_ada_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, out.data_ptr(), M, N, K, s);
   else if (G == Gemm::MXF4 || G == Gemm::MXF8_TN) {
-    // small outputs with a long K split K over scratch from torch's stream-ordered caching allocator (the reference
-    // allocates its CUTLASS workspace per call as well, gemm.cu:160-162); 0 bytes = the shape does not split
-    const int64_t ws_bytes = qutlass_amd_gemm_splitk_workspace_bytes(fp8 ? 8 : 4, M, N, K);
-    Tensor ws = ws_bytes > 0 ? torch::stable::new_empty(A, {ws_bytes}, ScalarType::Byte) : Tensor();
-    void* wp = ws_bytes > 0 ? ws.data_ptr() : nullptr;
+    // small outputs with a long K split K over scratch (the reference allocates its CUTLASS workspace per call as well, gemm.cu:160-162); 0 bytes = the shape does not split
+    const Workspace ws(A, qutlass_amd_gemm_splitk_workspace_bytes(fp8 ? 8 : 4, M, N, K));
     rc = fp8 ? qutlass_amd_matmul_mxf8_bf16_tn_fmt(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, out.data_ptr(), M, N, K,
-                                                   a_e5m2 ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3, QAMD_FP8_E4M3, wp, ws_bytes, s)
-             : qutlass_amd_matmul_mxf4_bf16_tn_ws(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, out.data_ptr(), M, N, K, wp, ws_bytes, s);
+                                                   a_e5m2 ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3, QAMD_FP8_E4M3, ws.ptr(), ws.bytes, s)
+             : qutlass_amd_matmul_mxf4_bf16_tn_ws(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, out.data_ptr(), M, N, K, ws.ptr(), ws.bytes, s);
   }
   else if (G == Gemm::NVF4) {
     // [r3] the same for NVFP4: outputs of a few dozen 128x128 tiles with a long K split K (M = 256, N = 4096, K = 14336: 54.7 -> 39.2 us)
-    const int64_t ws_bytes = qutlass_amd_nvf4_splitk_workspace_bytes(M, N, K);
-    Tensor ws = ws_bytes > 0 ? torch::stable::new_empty(A, {ws_bytes}, ScalarType::Byte) : Tensor();
-    rc = qutlass_amd_matmul_nvf4_bf16_tn_ws(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, out.data_ptr(), M, N, K,
-                                            ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, s);
+    const Workspace ws(A, qutlass_amd_nvf4_splitk_workspace_bytes(M, N, K));
+    rc = qutlass_amd_matmul_nvf4_bf16_tn_ws(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, out.data_ptr(), M, N, K, ws.ptr(), ws.bytes, s);
   }
   else {
-    // scratch for the (K, M) -> (M, K) re-layout of small problems, from torch's stream-ordered caching allocator; shapes
-    // that read the (K, M) operand in place need none (0 bytes: nothing is allocated)
-    const int64_t ws_bytes = qutlass_amd_mxf8_nn_workspace_bytes_for(M, N, K);
-    Tensor ws = ws_bytes > 0 ? torch::stable::new_empty(A, {ws_bytes}, ScalarType::Byte) : Tensor();
+    // scratch for the (K, M) -> (M, K) re-layout of small problems; shapes that read the (K, M) operand in place need none
+    const Workspace ws(A, qutlass_amd_mxf8_nn_workspace_bytes_for(M, N, K));
     rc = qutlass_amd_matmul_mxf8_bf16_nn_fmt(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, out.data_ptr(), M, N, K,
-                                             a_e5m2 ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3, QAMD_FP8_E4M3, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, s);
+                                             a_e5m2 ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3, QAMD_FP8_E4M3, ws.ptr(), ws.bytes, s);
   }
   check_rc(rc);
   return out;
@@ -191,9 +194,7 @@ Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, cons
   constexpr bool w4a8 = G == Grouped::MXF8_MXF4;
   constexpr bool fp8 = G == Grouped::MXF8;
   const char* op = G == Grouped::MXF4 ? "grouped_matmul_mxf4" : G == Grouped::NVF4 ? "grouped_matmul_nvf4" : w4a8 ? "grouped_matmul_mxf8_mxf4" : "grouped_matmul_mxf8";
-  require_contiguous(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  require_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
-  require_same_gpu(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  check_tensors(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
   const ScalarType data_t = fp8 ? ScalarType::Float8_e4m3fn : ScalarType::Byte;                  // either operand
   const ScalarType a_alt = fp8 ? ScalarType::Float8_e5m2 : ScalarType::Float4_e2m1fn_x2;         // ... or, for A
   const ScalarType b_alt = fp8 ? ScalarType::Float8_e4m3fn : ScalarType::Float4_e2m1fn_x2;       // ... for B (MXF8: e4m3 only)
@@ -254,11 +255,10 @@ int64_t nbytes(const Tensor& t) { return t.numel() * (int64_t)t.element_size(); 
 // method: checked here for the ops whose schema carries it; the blocked ops leave it to the C ABI.  Returns the rotation size.
 // offs (the *Grouped_ ops, the last of ts): one global scale per expert -- gscale is then (E,) for offs (E,) int32, and must be contiguous like everything else.
 int64_t quant_prelude(const char* op, std::vector<Named> ts, const Tensor* gscale, const int64_t* method = nullptr, const Tensor* offs = nullptr) {
+  std::vector<Named> device_only;
   if (offs) ts.push_back({*gscale, "global_scales"});
-  require_contiguous(op, ts);
-  if (gscale && !offs) ts.push_back({*gscale, "global_scale"});
-  require_gpu(op, ts);
-  require_same_gpu(op, ts);
+  else if (gscale) device_only.push_back({*gscale, "global_scale"});
+  check_tensors(op, ts, device_only);
   const Tensor& R = ts[1].t;
   STD_TORCH_CHECK(has_dtype(ts[0].t, ScalarType::BFloat16), "A must be bf16");
   STD_TORCH_CHECK(has_dtype(R, ScalarType::BFloat16), "B must be bf16");
@@ -392,16 +392,25 @@ void fusedQuantizeNvBlocked(const Tensor& A, const Tensor& R, Tensor OUT, Tensor
 
 // ---- EXTENSION: the gated-MLP activation act = silu(gate) * up of X = (.., 2 I) [gate | up], alone and fused into the quantizers ----------
 // OUT / OUT_sf are sized as for the plain quantizers on a (.., I) tensor.  method: 0 quest, 1 abs_max; blocked: scales in the to_blocked layout.
-void siluAndMul_(const Tensor& X, Tensor OUT) {
-  const char* op = "siluAndMul_";
-  require_contiguous(op, {{X, "X"}, {OUT, "OUT"}});
-  require_gpu(op, {{X, "X"}, {OUT, "OUT"}});
-  require_same_gpu(op, {{X, "X"}, {OUT, "OUT"}});
+struct GateUp {
+  int64_t rows, inter;
+};
+GateUp gate_up_shape(const Tensor& X, const char* name) {   // X (.., 2 I) as `rows` rows of [gate | up], I = inter
+  STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of ", name, " must be 2 * I");
+  const int64_t inter = X.size(X.dim() - 1) / 2;
+  return {X.numel() / (2 * inter), inter};
+}
+// siluAndMul_ and swigluOaiAndMul_: X (.., 2 I) bf16 -> OUT of at least rows * I bf16
+GateUp activation_checks(const char* op, const Tensor& X, const Tensor& OUT) {
+  check_tensors(op, {{X, "X"}, {OUT, "OUT"}});
   STD_TORCH_CHECK(has_dtype(X, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "X and OUT must be bf16");
-  STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of X must be 2 * I");
-  const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
-  STD_TORCH_CHECK(inter % 8 == 0, "the gate / up width must be divisible by", 8);
-  STD_TORCH_CHECK(OUT.numel() >= rows * inter, "OUT is too small");
+  const GateUp g = gate_up_shape(X, "X");
+  STD_TORCH_CHECK(g.inter % 8 == 0, "the gate / up width must be divisible by", 8);
+  STD_TORCH_CHECK(OUT.numel() >= g.rows * g.inter, "OUT is too small");
+  return g;
+}
+void siluAndMul_(const Tensor& X, Tensor OUT) {
+  const auto [rows, inter] = activation_checks("siluAndMul_", X, OUT);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
   check_rc(qutlass_amd_silu_mul_bf16(X.data_ptr(), rows, inter, OUT.data_ptr(), current_stream(X)));
 }
@@ -412,8 +421,7 @@ void silu_mul_quantize(const char* op, const Tensor& X, const Tensor& R, Tensor&
   std::vector<Named> ts{{X, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
   if (offs) ts.push_back({*offs, "offs"});
   const int64_t rot = quant_prelude(op, ts, gscale, &method, offs);
-  STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of A must be 2 * I");
-  const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
+  const auto [rows, inter] = gate_up_shape(X, "A");
   quant_check_rot(gscale, rot);
   STD_TORCH_CHECK(inter % quant_rp(rot) == 0, "the gate / up width must be divisible by", quant_rp(rot));
   quant_check_out(gscale, OUT, OUT_sf, rows * inter, inter, blocked, fmt8 >= 0);
@@ -498,26 +506,6 @@ void fusedGatherQuantizeMxf8_(const Tensor& A, const Tensor& R, const Tensor& sr
   gather_quantize("fusedGatherQuantizeMxf8", A, R, src_row, OUT, OUT_sf, nullptr, QAMD_METHOD_ABSMAX, nullptr, mxf8_fmt(OUT, OUT_sf));
 }
 
-// moeCombine_: OUT[t] = sum_k weights[t][k] * Y[pos[t][k]] (the arithmetic is spelled out at qutlass_amd_moe_combine_bf16); slots with pos outside [0, M) are skipped
-void moeCombine_(const Tensor& Y, const Tensor& pos, const Tensor& weights, Tensor OUT) {
-  const char* op = "moeCombine_";
-  require_contiguous(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
-  require_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
-  require_same_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
-  STD_TORCH_CHECK(has_dtype(Y, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "Y and OUT must be bf16");
-  STD_TORCH_CHECK(has_dtype(pos, ScalarType::Int), "pos must be int32");
-  STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
-  STD_TORCH_CHECK(Y.dim() == 2 && Y.size(1) > 0, "Y must be 2D (M, H)");
-  STD_TORCH_CHECK(pos.dim() == 2 && weights.dim() == 2 && pos.size(0) == weights.size(0) && pos.size(1) == weights.size(1), "pos and weights must both be (T, topk)");
-  const int64_t M = Y.size(0), H = Y.size(1), T = pos.size(0), topk = pos.size(1);
-  STD_TORCH_CHECK(H % 8 == 0, "the row length of Y must be divisible by", 8);
-  STD_TORCH_CHECK(topk >= 1 && topk <= 32, "topk must be in [1, 32] (got ", topk, ")");
-  STD_TORCH_CHECK(OUT.numel() >= T * H, "OUT is too small");
-  const torch::stable::accelerator::DeviceGuard guard(Y.get_device_index());
-  check_rc(qutlass_amd_moe_combine_bf16(Y.data_ptr(), M, H, static_cast<const int32_t*>(pos.data_ptr()), static_cast<const float*>(weights.data_ptr()), T, topk,
-                                        OUT.data_ptr(), current_stream(Y)));
-}
-
 // ---- EXTENSION: gpt-oss -- the clamped SwiGLU with per-expert gate/up biases, alone and fused into the MXFP4 and the MXFP8 (e4m3) quantizer, and moe_combine with the down bias ------
 // bias: (E, 2 I) bf16, or an EMPTY tensor for "no bias"; offs: (E,) int32, or an empty tensor where there is no bias or E == 1.  The arithmetic is spelled out at
 // qutlass_amd_swiglu_oai_mul_bf16 (include/qutlass_amd.h).
@@ -532,9 +520,8 @@ OaiBias oai_bias(const char* op, const Tensor& X, const Tensor& bias, const Tens
     STD_TORCH_CHECK(offs.numel() == 0, "offs without a bias");
     return b;
   }
-  require_contiguous(op, {{bias, "bias"}});
-  require_gpu(op, {{bias, "bias"}});
-  require_same_gpu(op, {{X, "X"}, {bias, "bias"}});
+  const Named x{X, "X"};
+  check_tensors(op, {{bias, "bias"}}, {}, true, &x);
   STD_TORCH_CHECK(has_dtype(bias, ScalarType::BFloat16), "bias must be bf16");
   STD_TORCH_CHECK(bias.dim() == 2 && bias.size(1) == width, "bias must be (E, ", width, ")");
   b.bias = bias.data_ptr();
@@ -544,25 +531,15 @@ OaiBias oai_bias(const char* op, const Tensor& X, const Tensor& bias, const Tens
     STD_TORCH_CHECK(b.e == 1, "a bias of E = ", b.e, " experts needs offs");
     return b;
   }
-  require_contiguous(op, {{offs, "offs"}});
-  require_gpu(op, {{offs, "offs"}});
-  require_same_gpu(op, {{X, "X"}, {offs, "offs"}});
+  check_tensors(op, {{offs, "offs"}}, {}, true, &x);
   STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.dim() == 1 && offs.size(0) == b.e, "offs must be an int32 tensor of E = ", b.e, " elements");
   b.offs = static_cast<const int32_t*>(offs.data_ptr());
   return b;
 }
 
 void swigluOaiAndMul_(const Tensor& X, Tensor OUT, double alpha, double limit, const Tensor& bias, const Tensor& offs) {
-  const char* op = "swigluOaiAndMul_";
-  require_contiguous(op, {{X, "X"}, {OUT, "OUT"}});
-  require_gpu(op, {{X, "X"}, {OUT, "OUT"}});
-  require_same_gpu(op, {{X, "X"}, {OUT, "OUT"}});
-  STD_TORCH_CHECK(has_dtype(X, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "X and OUT must be bf16");
-  STD_TORCH_CHECK(X.dim() >= 1 && X.size(X.dim() - 1) > 0 && X.size(X.dim() - 1) % 2 == 0, "the last dimension of X must be 2 * I");
-  const int64_t inter = X.size(X.dim() - 1) / 2, rows = X.numel() / (2 * inter);
-  STD_TORCH_CHECK(inter % 8 == 0, "the gate / up width must be divisible by", 8);
-  STD_TORCH_CHECK(OUT.numel() >= rows * inter, "OUT is too small");
-  const OaiBias b = oai_bias(op, X, bias, offs, 2 * inter);
+  const auto [rows, inter] = activation_checks("swigluOaiAndMul_", X, OUT);
+  const OaiBias b = oai_bias("swigluOaiAndMul_", X, bias, offs, 2 * inter);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
   check_rc(qutlass_amd_swiglu_oai_mul_bf16(X.data_ptr(), rows, inter, (float)alpha, (float)limit, b.bias, b.offs, b.e, OUT.data_ptr(), current_stream(X)));
 }
@@ -571,8 +548,7 @@ void swigluOaiAndMul_(const Tensor& X, Tensor OUT, double alpha, double limit, c
 void swiglu_oai_quantize(const char* op, const char* plain, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, double alpha, double limit, const Tensor& bias,
                          const Tensor& offs, int64_t method, int fmt8 = -1) {
   const int64_t rot = quant_prelude(op, {{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}}, nullptr, fmt8 < 0 ? &method : nullptr);
-  STD_TORCH_CHECK(A.dim() >= 1 && A.size(A.dim() - 1) > 0 && A.size(A.dim() - 1) % 2 == 0, "the last dimension of A must be 2 * I");
-  const int64_t inter = A.size(A.dim() - 1) / 2, rows = A.numel() / (2 * inter);
+  const auto [rows, inter] = gate_up_shape(A, "A");
   STD_TORCH_CHECK(rot != 128, "rotation size 128 is not supported; expected 32 or 64 (use swiglu_oai_and_mul followed by ", plain, ")");
   STD_TORCH_CHECK(rot == 32 || rot == 64, "Unsupported rotation size ", rot, "; expected 32 or 64.");
   STD_TORCH_CHECK(inter % rot == 0, "the gate / up width must be divisible by", rot);
@@ -595,12 +571,10 @@ void fusedSwigluOaiQuantizeMxf8_(const Tensor& A, const Tensor& R, Tensor OUT, T
   swiglu_oai_quantize("fusedSwigluOaiQuantizeMxf8", "fusedQuantizeMxf8", A, R, OUT, OUT_sf, alpha, limit, bias, offs, QAMD_METHOD_ABSMAX, mxf8_fmt(OUT, OUT_sf, true));
 }
 
-// moeCombineBias_: moeCombine_ with bias (E, H) bf16 added to every gathered row in bf16; offs (E,) int32, or empty for E == 1
-void moeCombineBias_(const Tensor& Y, const Tensor& pos, const Tensor& weights, const Tensor& bias, const Tensor& offs, Tensor OUT) {
-  const char* op = "moeCombineBias_";
-  require_contiguous(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
-  require_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
-  require_same_gpu(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
+// moeCombine_: OUT[t] = sum_k weights[t][k] * Y[pos[t][k]] (the arithmetic is spelled out at qutlass_amd_moe_combine_bf16); slots with pos outside [0, M) are skipped
+// moeCombineBias_ (bias != nullptr): the same with bias (E, H) bf16 added to every gathered row in bf16; offs (E,) int32, or empty for E == 1
+void moe_combine(const char* op, const Tensor& Y, const Tensor& pos, const Tensor& weights, const Tensor* bias, const Tensor* offs, Tensor& OUT) {
+  check_tensors(op, {{Y, "Y"}, {pos, "pos"}, {weights, "weights"}, {OUT, "OUT"}});
   STD_TORCH_CHECK(has_dtype(Y, ScalarType::BFloat16) && has_dtype(OUT, ScalarType::BFloat16), "Y and OUT must be bf16");
   STD_TORCH_CHECK(has_dtype(pos, ScalarType::Int), "pos must be int32");
   STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
@@ -610,20 +584,26 @@ void moeCombineBias_(const Tensor& Y, const Tensor& pos, const Tensor& weights, 
   STD_TORCH_CHECK(H % 8 == 0, "the row length of Y must be divisible by", 8);
   STD_TORCH_CHECK(topk >= 1 && topk <= 32, "topk must be in [1, 32] (got ", topk, ")");
   STD_TORCH_CHECK(OUT.numel() >= T * H, "OUT is too small");
-  STD_TORCH_CHECK(bias.numel() > 0, "bias must be (E, ", H, ")");
-  const OaiBias b = oai_bias(op, Y, bias, offs, H);
+  OaiBias b;
+  if (bias) {
+    STD_TORCH_CHECK(bias->numel() > 0, "bias must be (E, ", H, ")");
+    b = oai_bias(op, Y, *bias, *offs, H);
+  }
   const torch::stable::accelerator::DeviceGuard guard(Y.get_device_index());
-  check_rc(qutlass_amd_moe_combine_bias_bf16(Y.data_ptr(), M, H, static_cast<const int32_t*>(pos.data_ptr()), static_cast<const float*>(weights.data_ptr()), T, topk,
-                                             b.bias, b.offs, b.e, OUT.data_ptr(), current_stream(Y)));
+  const int32_t* p = static_cast<const int32_t*>(pos.data_ptr());
+  const float* w = static_cast<const float*>(weights.data_ptr());
+  check_rc(bias ? qutlass_amd_moe_combine_bias_bf16(Y.data_ptr(), M, H, p, w, T, topk, b.bias, b.offs, b.e, OUT.data_ptr(), current_stream(Y))
+                : qutlass_amd_moe_combine_bf16(Y.data_ptr(), M, H, p, w, T, topk, OUT.data_ptr(), current_stream(Y)));
+}
+void moeCombine_(const Tensor& Y, const Tensor& pos, const Tensor& weights, Tensor OUT) { moe_combine("moeCombine_", Y, pos, weights, nullptr, nullptr, OUT); }
+void moeCombineBias_(const Tensor& Y, const Tensor& pos, const Tensor& weights, const Tensor& bias, const Tensor& offs, Tensor OUT) {
+  moe_combine("moeCombineBias_", Y, pos, weights, &bias, &offs, OUT);
 }
 
 // ---- EXTENSION: MoE routing in front of the dispatch ---------------------------------------------------------------------------------------------
 // moeTopkSoftmax_: router logits (T, E) bf16 / float32 -> weights (T, topk) float32 and ids (T, topk) int32; topk is the outputs' second dimension
-void moeTopkSoftmax_(const Tensor& logits, Tensor weights, Tensor ids, bool renormalize) {
-  const char* op = "moeTopkSoftmax_";
-  require_contiguous(op, {{logits, "logits"}, {weights, "weights"}, {ids, "ids"}});
-  require_gpu(op, {{logits, "logits"}, {weights, "weights"}, {ids, "ids"}});
-  require_same_gpu(op, {{logits, "logits"}, {weights, "weights"}, {ids, "ids"}});
+// the checks both routers make behind the generic ones; returns whether the logits are float32
+bool topk_checks(const Tensor& logits, const Tensor& weights, const Tensor& ids) {
   const bool f32 = has_dtype(logits, ScalarType::Float);
   STD_TORCH_CHECK(f32 || has_dtype(logits, ScalarType::BFloat16), "logits must be bf16 or float32");
   STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
@@ -631,6 +611,11 @@ void moeTopkSoftmax_(const Tensor& logits, Tensor weights, Tensor ids, bool reno
   STD_TORCH_CHECK(logits.dim() == 2, "logits must be 2D (T, E)");
   STD_TORCH_CHECK(weights.dim() == 2 && ids.dim() == 2 && weights.size(0) == logits.size(0) && ids.size(0) == logits.size(0) && weights.size(1) == ids.size(1),
                   "weights and ids must both be (T, topk)");
+  return f32;
+}
+void moeTopkSoftmax_(const Tensor& logits, Tensor weights, Tensor ids, bool renormalize) {
+  check_tensors("moeTopkSoftmax_", {{logits, "logits"}, {weights, "weights"}, {ids, "ids"}});
+  const bool f32 = topk_checks(logits, weights, ids);
   const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
   check_rc(qutlass_amd_moe_topk_softmax(logits.data_ptr(), f32 ? 4 : 2, logits.size(0), logits.size(1), ids.size(1), renormalize ? 1 : 0,
                                         static_cast<float*>(weights.data_ptr()), static_cast<int32_t*>(ids.data_ptr()), current_stream(logits)));
@@ -639,17 +624,8 @@ void moeTopkSoftmax_(const Tensor& logits, Tensor weights, Tensor ids, bool reno
 // moeTopkGrouped_: the grouped router (qutlass_amd_moe_topk_grouped); topk is the outputs' second dimension; an EMPTY bias means "no bias", an EMPTY scores "not asked for"
 void moeTopkGrouped_(const Tensor& logits, const Tensor& bias, Tensor weights, Tensor ids, Tensor scores, int64_t n_group, int64_t topk_group, int64_t scoring,
                      bool renormalize, double routed_scaling_factor) {
-  const char* op = "moeTopkGrouped_";
-  require_contiguous(op, {{logits, "logits"}, {bias, "bias"}, {weights, "weights"}, {ids, "ids"}, {scores, "scores"}});
-  require_gpu(op, {{logits, "logits"}, {bias, "bias"}, {weights, "weights"}, {ids, "ids"}, {scores, "scores"}});
-  require_same_gpu(op, {{logits, "logits"}, {bias, "bias"}, {weights, "weights"}, {ids, "ids"}, {scores, "scores"}});
-  const bool f32 = has_dtype(logits, ScalarType::Float);
-  STD_TORCH_CHECK(f32 || has_dtype(logits, ScalarType::BFloat16), "logits must be bf16 or float32");
-  STD_TORCH_CHECK(has_dtype(weights, ScalarType::Float), "weights must be float32");
-  STD_TORCH_CHECK(has_dtype(ids, ScalarType::Int), "ids must be int32");
-  STD_TORCH_CHECK(logits.dim() == 2, "logits must be 2D (T, E)");
-  STD_TORCH_CHECK(weights.dim() == 2 && ids.dim() == 2 && weights.size(0) == logits.size(0) && ids.size(0) == logits.size(0) && weights.size(1) == ids.size(1),
-                  "weights and ids must both be (T, topk)");
+  check_tensors("moeTopkGrouped_", {{logits, "logits"}, {bias, "bias"}, {weights, "weights"}, {ids, "ids"}, {scores, "scores"}});
+  const bool f32 = topk_checks(logits, weights, ids);
   const bool use_bias = bias.numel() > 0, want_scores = scores.numel() > 0;
   STD_TORCH_CHECK(!use_bias || (has_dtype(bias, ScalarType::Float) && bias.dim() == 1 && bias.size(0) == logits.size(1)), "bias must be a float32 tensor of (E,)");
   STD_TORCH_CHECK(!want_scores || (has_dtype(scores, ScalarType::Float) && scores.dim() == 2 && scores.size(0) == logits.size(0) && scores.size(1) == logits.size(1)),
@@ -665,9 +641,8 @@ void moeTopkGrouped_(const Tensor& logits, const Tensor& bias, Tensor weights, T
 // caller scratch of at least qutlass_amd_moe_sort_workspace_bytes bytes (it may be empty below the one-launch bound)
 void moeSort_(const Tensor& topk_ids, const Tensor& expert_map, int64_t num_experts, Tensor src_row, Tensor offs, Tensor pos, Tensor workspace) {
   const char* op = "moeSort_";
-  require_contiguous(op, {{topk_ids, "topk_ids"}, {src_row, "src_row"}, {offs, "offs"}, {pos, "pos"}, {workspace, "workspace"}});
-  require_gpu(op, {{topk_ids, "topk_ids"}, {src_row, "src_row"}, {offs, "offs"}, {pos, "pos"}, {workspace, "workspace"}});
-  require_same_gpu(op, {{topk_ids, "topk_ids"}, {src_row, "src_row"}, {offs, "offs"}, {pos, "pos"}, {workspace, "workspace"}});
+  const Named ids{topk_ids, "topk_ids"};
+  check_tensors(op, {ids, {src_row, "src_row"}, {offs, "offs"}, {pos, "pos"}, {workspace, "workspace"}});
   const bool i64 = has_dtype(topk_ids, ScalarType::Long);
   STD_TORCH_CHECK(i64 || has_dtype(topk_ids, ScalarType::Int), "topk_ids must be int32 or int64");
   STD_TORCH_CHECK(topk_ids.dim() == 2, "topk_ids must be 2D (T, topk)");
@@ -677,9 +652,7 @@ void moeSort_(const Tensor& topk_ids, const Tensor& expert_map, int64_t num_expe
   const bool use_map = expert_map.numel() > 0;
   int64_t G = 0;
   if (use_map) {
-    require_contiguous(op, {{expert_map, "expert_map"}});
-    require_gpu(op, {{expert_map, "expert_map"}});
-    require_same_gpu(op, {{topk_ids, "topk_ids"}, {expert_map, "expert_map"}});
+    check_tensors(op, {{expert_map, "expert_map"}}, {}, true, &ids);
     STD_TORCH_CHECK(has_dtype(expert_map, ScalarType::Int) && expert_map.dim() == 1, "expert_map must be a 1D int32 tensor");
     G = expert_map.size(0);
   }
@@ -692,9 +665,7 @@ void moeSort_(const Tensor& topk_ids, const Tensor& expert_map, int64_t num_expe
 // ---- EXTENSION: rotate + quantize + MXFP4 GEMM in one launch for decode batches (M <= 32) ---------------------------------------
 Tensor fusedQuantizeMatmulMxf4(const Tensor& X, const Tensor& R, const Tensor& B, const Tensor& B_sf, const Tensor& alpha, int64_t method) {
   const char* op = "fusedQuantizeMatmulMxf4";
-  require_contiguous(op, {{X, "X"}, {R, "R"}, {B, "B"}, {B_sf, "B_sf"}});
-  require_gpu(op, {{X, "X"}, {R, "R"}, {B, "B"}, {B_sf, "B_sf"}, {alpha, "alpha"}});
-  require_same_gpu(op, {{X, "X"}, {R, "R"}, {B, "B"}, {B_sf, "B_sf"}, {alpha, "alpha"}});
+  check_tensors(op, {{X, "X"}, {R, "R"}, {B, "B"}, {B_sf, "B_sf"}}, {{alpha, "alpha"}});
   STD_TORCH_CHECK(has_dtype(X, ScalarType::BFloat16) && has_dtype(R, ScalarType::BFloat16), "X and R must be bf16");
   STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte), "B must be uint8");
   STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e8m0fnu), "B_sf must be float8_e8m0fnu");
@@ -716,8 +687,7 @@ Tensor fusedQuantizeMatmulMxf4(const Tensor& X, const Tensor& R, const Tensor& B
 //      contiguity, qutlass/__init__.py:206-315 -- the C ABI checks the shape constraints) --------------------------------
 void backward_t_bf16(const Tensor& x, const Tensor& h, Tensor xh_e2m1, Tensor xh_e8m0) {
   const char* op = "backward_t_bf16";
-  require_contiguous(op, {{x, "x"}, {h, "h"}, {xh_e2m1, "xh_e2m1"}, {xh_e8m0, "xh_e8m0"}});
-  require_gpu(op, {{x, "x"}, {h, "h"}, {xh_e2m1, "xh_e2m1"}, {xh_e8m0, "xh_e8m0"}});
+  check_tensors(op, {{x, "x"}, {h, "h"}, {xh_e2m1, "xh_e2m1"}, {xh_e8m0, "xh_e8m0"}}, {}, false);
   STD_TORCH_CHECK(has_dtype(x, ScalarType::BFloat16) && has_dtype(h, ScalarType::BFloat16), "x and h must be bf16");
   STD_TORCH_CHECK(x.dim() >= 2 && h.numel() == 32 * 32, "x must be at least 2-D and h 32 x 32");
   const int64_t M = x.size(x.dim() - 1), N = x.size(x.dim() - 2), B = x.numel() / (M * N);
@@ -728,8 +698,7 @@ void backward_t_bf16(const Tensor& x, const Tensor& h, Tensor xh_e2m1, Tensor xh
 
 void backward_qt_bf16(const Tensor& x_e2m1, const Tensor& x_e8m0, const Tensor& h, const Tensor& alpha, Tensor xh_e2m1, Tensor xh_e8m0) {
   const char* op = "backward_qt_bf16";
-  require_contiguous(op, {{x_e2m1, "x_e2m1"}, {x_e8m0, "x_e8m0"}, {h, "h"}, {xh_e2m1, "xh_e2m1"}, {xh_e8m0, "xh_e8m0"}});
-  require_gpu(op, {{x_e2m1, "x_e2m1"}, {x_e8m0, "x_e8m0"}, {h, "h"}, {alpha, "alpha"}, {xh_e2m1, "xh_e2m1"}, {xh_e8m0, "xh_e8m0"}});
+  check_tensors(op, {{x_e2m1, "x_e2m1"}, {x_e8m0, "x_e8m0"}, {h, "h"}, {xh_e2m1, "xh_e2m1"}, {xh_e8m0, "xh_e8m0"}}, {{alpha, "alpha"}}, false);
   STD_TORCH_CHECK(has_dtype(h, ScalarType::BFloat16) && has_dtype(alpha, ScalarType::Float), "h must be bf16 and alpha float");
   STD_TORCH_CHECK(x_e2m1.dim() >= 2 && x_e2m1.element_size() == 1 && x_e8m0.element_size() == 1 && h.numel() == 32 * 32,
                   "x_e2m1 / x_e8m0 must be 1-byte tensors of at least 2 dimensions and h 32 x 32");
@@ -743,8 +712,7 @@ void backward_qt_bf16(const Tensor& x_e2m1, const Tensor& x_e8m0, const Tensor& 
 
 void backward_bf16_square_double_mxfp8(const Tensor& x_bf16, Tensor x_fp8, Tensor row_scales, Tensor column_scales) {
   const char* op = "backward_bf16_square_double_mxfp8";
-  require_contiguous(op, {{x_bf16, "x_bf16"}, {x_fp8, "x_fp8"}, {row_scales, "row_scales"}, {column_scales, "column_scales"}});
-  require_gpu(op, {{x_bf16, "x_bf16"}, {x_fp8, "x_fp8"}, {row_scales, "row_scales"}, {column_scales, "column_scales"}});
+  check_tensors(op, {{x_bf16, "x_bf16"}, {x_fp8, "x_fp8"}, {row_scales, "row_scales"}, {column_scales, "column_scales"}}, {}, false);
   STD_TORCH_CHECK(has_dtype(x_bf16, ScalarType::BFloat16) && x_bf16.dim() == 2, "x_bf16 must be a 2-D bf16 tensor");
   // x_bf16 may have any row count m: the outputs carry the padded extent m_pad = x_fp8.size(0) (a multiple of 128 >= m) and the kernel
   // treats the missing rows as zeros (the reference pads x_bf16 with a copy before the call, qutlass/__init__.py:288-290)
@@ -759,8 +727,7 @@ void backward_bf16_square_double_mxfp8(const Tensor& x_bf16, Tensor x_fp8, Tenso
 
 void mxfp4_transpose_mxfp8(const Tensor& x_fp4, const Tensor& scales, Tensor x_fp8, Tensor shared_exps) {
   const char* op = "mxfp4_transpose_mxfp8";
-  require_contiguous(op, {{x_fp4, "x_fp4"}, {scales, "scales"}, {x_fp8, "x_fp8"}, {shared_exps, "shared_exps"}});
-  require_gpu(op, {{x_fp4, "x_fp4"}, {scales, "scales"}, {x_fp8, "x_fp8"}, {shared_exps, "shared_exps"}});
+  check_tensors(op, {{x_fp4, "x_fp4"}, {scales, "scales"}, {x_fp8, "x_fp8"}, {shared_exps, "shared_exps"}}, {}, false);
   STD_TORCH_CHECK(x_fp4.dim() == 2 && x_fp4.element_size() == 1 && scales.element_size() == 1, "x_fp4 must be a 2-D 1-byte tensor, scales 1-byte");
   // any row count m: x_fp8 is (n, m_pad) with m_pad a multiple of 128 >= m; rows m .. m_pad-1 count as zero codes with unit scales
   // inside the kernel -- `scales` is read-only and needs only its m real rows (the reference pads x_fp4 with a copy and writes 1.0 into

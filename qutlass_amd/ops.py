@@ -23,6 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 EXT_PATH = os.environ.get("QUTLASS_AMD_OP_LIBRARY") or os.path.join(os.path.dirname(_HERE), "qutlass", "_CUDA.abi3.so")
 
 _registered = False
+_AMD = torch.ops.qutlass_amd   # (the namespace object: the runners below look the in-place twins up on it once per call)
 
 
 def register_torch_ops() -> None:
@@ -75,12 +76,8 @@ def _register_fakes() -> None:
     def fills(*args):
         return None
 
-    for name in ("fusedQuantizeMx_", "fusedQuantizeNv_", "fusedQuantizeMxMask_", "fusedQuantizeMxBlocked", "fusedQuantizeNvBlocked",
-                 "siluAndMul_", "fusedSiluMulQuantizeMx_", "fusedSiluMulQuantizeNv_",
-                 "fusedGatherQuantizeMx_", "fusedGatherQuantizeNv_", "fusedGatherQuantizeNvGrouped_", "fusedSiluMulQuantizeNvGrouped_",
-                 "fusedQuantizeMxf8_", "fusedQuantizeMxf8Blocked_", "fusedSiluMulQuantizeMxf8_", "fusedGatherQuantizeMxf8_", "moeCombine_",
-                 "swigluOaiAndMul_", "fusedSwigluOaiQuantizeMx_", "fusedSwigluOaiQuantizeMxf8_", "moeCombineBias_", "moeTopkSoftmax_", "moeTopkGrouped_", "moeSort_", "backward_t_bf16_", "backward_qt_bf16_", "backward_bf16_square_double_mxfp8_", "mxfp4_transpose_mxfp8_"):
-        rf(f"qutlass_amd::{name}")(fills)
+    for row in (*QUANT_OPS.values(), *OUTPUT_OPS.values()):   # every in-place op is the twin of one row: none is called directly
+        rf(f"qutlass_amd::{row.twin}")(fills)
 
     @rf("qutlass_amd::to_blocked")
     def _(input_matrix):
@@ -109,138 +106,12 @@ def _define_functional_ops() -> None:
         return
     from torch.library import custom_op
 
-    amd = torch.ops.qutlass_amd
-    have_training_ops = hasattr(amd, "backward_t_bf16_")
-
-    # the rotate + quantize family: one registration per row of QUANT_OPS
-    for name, row in QUANT_OPS.items():
-        op = custom_op(f"qutlass_amd::{name}", mutates_args=(), schema=row.schema)(lambda *args, _row=row: run_quant_op(_row, *args))
-        op.register_fake(lambda *args, _row=row: alloc_quant(_row, *args))
-    # the e4m3 form of the clamped-SwiGLU quantizer: its record stands next to the table (see SWIGLU_OAI_MXF8), not in it
-    op = custom_op("qutlass_amd::swiglu_oai_quantize_mxf8", mutates_args=(), schema=SWIGLU_OAI_MXF8.schema)(lambda *args: run_swiglu_oai_quant(SWIGLU_OAI_MXF8, *args))
-    op.register_fake(lambda A, R, *rest: alloc_swiglu_oai_quant(SWIGLU_OAI_MXF8, A, R))
-
-    # gated MLP: X is (.., 2 I) [gate | up]
-    @custom_op("qutlass_amd::silu_and_mul", mutates_args=(), schema="(Tensor X) -> Tensor")
-    def silu_and_mul(X):
-        o = X.new_empty(_act(X))
-        amd.siluAndMul_(X, o)
-        return o
-
-    silu_and_mul.register_fake(lambda X: X.new_empty(_act(X)))
-
-    def _combined(Y, pos):
-        return Y.new_empty((pos.size(0), Y.size(-1)))
-
-    @custom_op("qutlass_amd::moe_combine", mutates_args=(), schema="(Tensor Y, Tensor pos, Tensor weights) -> Tensor")
-    def moe_combine(Y, pos, weights):
-        o = _combined(Y, pos)
-        amd.moeCombine_(Y, pos, weights, o)
-        return o
-
-    moe_combine.register_fake(lambda Y, pos, weights: _combined(Y, pos))
-
-    # gpt-oss: the clamped SwiGLU with an optional per-expert bias (E, 2 I) and the grouped GEMMs' offs (E,); moe_combine with the down bias (E, H)
-    @custom_op("qutlass_amd::swiglu_oai_and_mul", mutates_args=(), schema="(Tensor X, float alpha, float limit, Tensor? bias, Tensor? offs) -> Tensor")
-    def swiglu_oai_and_mul(X, alpha, limit, bias, offs):
-        return run_swiglu_oai(X, alpha, limit, bias, offs)
-
-    swiglu_oai_and_mul.register_fake(lambda X, alpha, limit, bias, offs: X.new_empty(_act(X)))
-
-    @custom_op("qutlass_amd::moe_combine_bias", mutates_args=(), schema="(Tensor Y, Tensor pos, Tensor weights, Tensor bias, Tensor? offs) -> Tensor")
-    def moe_combine_bias(Y, pos, weights, bias, offs):
-        return run_moe_combine_bias(Y, pos, weights, bias, offs)
-
-    moe_combine_bias.register_fake(lambda Y, pos, weights, bias, offs: _combined(Y, pos))
-
-    # MoE routing: (T, E) logits -> (T, topk) weights and ids; (T, topk) ids -> src_row (T * topk), offs (num_experts), pos (T, topk)
-    @custom_op("qutlass_amd::moe_topk_softmax", mutates_args=(), schema="(Tensor logits, int topk, bool renormalize) -> (Tensor, Tensor)")
-    def moe_topk_softmax(logits, topk, renormalize):
-        o = _alloc_topk(logits, topk)
-        amd.moeTopkSoftmax_(logits, o[0], o[1], renormalize)
-        return o
-
-    moe_topk_softmax.register_fake(lambda logits, topk, renormalize: _alloc_topk(logits, topk))
-
-    # the grouped router: the third result is the (T, E) scores, or an empty tensor when they are not asked for
-    @custom_op("qutlass_amd::moe_topk_grouped", mutates_args=(),
-               schema="(Tensor logits, Tensor? bias, int topk, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor, bool return_scores) -> (Tensor, Tensor, Tensor)")
-    def moe_topk_grouped(logits, bias, topk, n_group, topk_group, scoring, renormalize, routed_scaling_factor, return_scores):
-        return run_moe_topk_grouped(logits, bias, topk, n_group, topk_group, scoring, renormalize, routed_scaling_factor, return_scores)
-
-    moe_topk_grouped.register_fake(lambda logits, bias, topk, n_group, topk_group, scoring, renormalize, routed_scaling_factor, return_scores:
-                                   _alloc_topk(logits, topk) + (_alloc_scores(logits, return_scores),))
-
-    @custom_op("qutlass_amd::moe_sort_fused", mutates_args=(), schema="(Tensor topk_ids, Tensor? expert_map, int num_experts) -> (Tensor, Tensor, Tensor)")
-    def moe_sort_fused(topk_ids, expert_map, num_experts):
-        return run_moe_sort(topk_ids, expert_map, num_experts)
-
-    moe_sort_fused.register_fake(lambda topk_ids, expert_map, num_experts: _alloc_sort(topk_ids, num_experts))
-
-    if not have_training_ops:   # QUTLASS_MINIMAL_BUILD: inference ops only
-        return
-
-    def _mask(a):
-        return alloc_quant(QUANT_OPS["quantize_mx"], a) + (a.new_empty((*a.shape[:-1], a.size(-1) // 8), dtype=torch.uint8),)
-
-    @custom_op("qutlass_amd::quantize_mx_mask", mutates_args=(), schema="(Tensor A, Tensor R) -> (Tensor, Tensor, Tensor)")
-    def quantize_mx_mask(A, R):
-        o = _mask(A)
-        amd.fusedQuantizeMxMask_(A, R, o[0], o[1], o[2])
-        return o
-
-    quantize_mx_mask.register_fake(lambda A, R: _mask(A))
-
-    def _bt(x):   # (.., N, M) -> (.., M, N/2) e2m1x2, (.., M, N/32) e8m0
-        return (x.new_empty((*x.shape[:-2], x.size(-1), x.size(-2) // 2), dtype=torch.float4_e2m1fn_x2),
-                x.new_empty((*x.shape[:-2], x.size(-1), x.size(-2) // 32), dtype=torch.float8_e8m0fnu))
-
-    @custom_op("qutlass_amd::backward_t", mutates_args=(), schema="(Tensor x, Tensor h) -> (Tensor, Tensor)")
-    def backward_t(x, h):
-        o = _bt(x)
-        amd.backward_t_bf16_(x, h, o[0], o[1])
-        return o
-
-    backward_t.register_fake(lambda x, h: _bt(x))
-
-    def _bqt(c, s):
-        return (c.new_empty((*c.shape[:-2], c.size(-1) * 2, c.size(-2) // 2), dtype=torch.float4_e2m1fn_x2),
-                c.new_empty((*s.shape[:-2], s.size(-1) * 32, s.size(-2) // 32), dtype=torch.float8_e8m0fnu))
-
-    @custom_op("qutlass_amd::backward_qt", mutates_args=(), schema="(Tensor x_e2m1, Tensor x_e8m0, Tensor h, Tensor alpha) -> (Tensor, Tensor)")
-    def backward_qt(x_e2m1, x_e8m0, h, alpha):
-        o = _bqt(x_e2m1, x_e8m0)
-        amd.backward_qt_bf16_(x_e2m1, x_e8m0, h, alpha, o[0], o[1])
-        return o
-
-    backward_qt.register_fake(lambda x_e2m1, x_e8m0, h, alpha: _bqt(x_e2m1, x_e8m0))
-
-    def _sq(x):
-        m, n = x.shape
-        mp = (m + 127) // 128 * 128
-        return (x.new_empty((mp, n), dtype=torch.float8_e4m3fn), x.new_empty((mp, n // 32), dtype=torch.float8_e8m0fnu),
-                x.new_empty((n, mp // 32), dtype=torch.float8_e8m0fnu))
-
-    @custom_op("qutlass_amd::square_double_mxfp8", mutates_args=(), schema="(Tensor x_bf16) -> (Tensor, Tensor, Tensor)")
-    def square_double_mxfp8(x_bf16):
-        o = _sq(x_bf16)
-        amd.backward_bf16_square_double_mxfp8_(x_bf16, o[0], o[1], o[2])
-        return o
-
-    square_double_mxfp8.register_fake(lambda x_bf16: _sq(x_bf16))
-
-    def _tr(x, s):
-        m, n = x.shape[0], x.shape[1] * 2
-        mp = (m + 255) // 256 * 256
-        return x.new_empty((n, mp), dtype=torch.float8_e4m3fn), x.new_empty((n, mp // 32), dtype=torch.float8_e8m0fnu)
-
-    @custom_op("qutlass_amd::transpose_mxfp8", mutates_args=(), schema="(Tensor x_fp4, Tensor scales) -> (Tensor, Tensor)")
-    def transpose_mxfp8(x_fp4, scales):
-        o = _tr(x_fp4, scales)
-        amd.mxfp4_transpose_mxfp8_(x_fp4, scales, o[0], o[1])
-        return o
-
-    transpose_mxfp8.register_fake(lambda x_fp4, scales: _tr(x_fp4, scales))
+    for table, run, alloc in ((QUANT_OPS, run_quant, alloc_quant), (OUTPUT_OPS, run_output, lambda row, *args: row.alloc(*args))):
+        for name, row in table.items():
+            if not hasattr(torch.ops.qutlass_amd, row.twin):   # QUTLASS_MINIMAL_BUILD: inference ops only
+                continue
+            op = custom_op(f"qutlass_amd::{name}", mutates_args=(), schema=row.schema)(lambda *args, _row=row, _run=run: _run(_row, *args))
+            op.register_fake(lambda *args, _row=row, _alloc=alloc: _alloc(_row, *args))   # the fake IS the row's allocator
 
 
 # ---- the rotate + quantize family: the functional ops `qutlass_amd::<name>`, their fake kernels and the eager wrappers of __init__.py come from this table ----------
@@ -250,6 +121,8 @@ def _define_functional_ops() -> None:
 # fmt:     a key of QUANT_FORMATS;  blocked: scales flat in the to_blocked() layout -- fixed by the op, or None where it is the op's last argument
 # The "mxf8" ops have no method: the argument behind the leading tensors is the code dtype (float8_e4m3fn / float8_e5m2).  It decides what is allocated and is not
 # passed on to the twin, which reads the format off OUT's dtype.
+# dtype:    ("mxf8") the code dtype where the op fixes it and has no such argument -- like blocked: fixed by the op, or None where it is an argument
+# optional: (argument index, dtype or None for A's) of the `Tensor?` arguments; the twin takes an empty tensor for None
 class QuantOp(NamedTuple):
     schema: str
     twin: str
@@ -257,6 +130,8 @@ class QuantOp(NamedTuple):
     operand: Callable
     fmt: str
     blocked: bool | None
+    dtype: torch.dtype | None = None
+    optional: tuple = ()
 
 
 def _same(A, R=None):
@@ -271,6 +146,7 @@ def _gathered(A, R, src_row):   # MoE dispatch: the operand is A[src_row], (M, K
     return (src_row.size(0), A.size(-1))
 
 
+_OAI_OPTIONAL = ((4, None), (5, torch.int32))   # bias in A's dtype, offs
 QUANT_FORMATS = {"mx": (32, torch.float8_e8m0fnu), "nv": (16, torch.float8_e4m3fn), "mxf8": (32, torch.float8_e8m0fnu)}   # elements per scale, scale dtype
 MXF8_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2)   # code dtypes of the "mxf8" ops; "mx" and "nv" pack two e2m1 codes per uint8
 QUANT_OPS = {
@@ -282,7 +158,7 @@ QUANT_OPS = {
     "silu_mul_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor global_scale, int method, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeNv_", 2, _act, "nv", None),
     # gpt-oss: the clamped SwiGLU in place of silu * up, with the gate/up bias of the row's expert (None: no bias; offs None: one expert); flat scales
     "swiglu_oai_quantize_mx": QuantOp("(Tensor A, Tensor R, float alpha, float limit, Tensor? bias, Tensor? offs, int method) -> (Tensor, Tensor)",
-                                      "fusedSwigluOaiQuantizeMx_", 2, _act, "mx", False),
+                                      "fusedSwigluOaiQuantizeMx_", 2, _act, "mx", False, None, _OAI_OPTIONAL),
     "gather_quantize_mx": QuantOp("(Tensor A, Tensor R, Tensor src_row, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeMx_", 3, _gathered, "mx", False),
     "gather_quantize_nv": QuantOp("(Tensor A, Tensor R, Tensor src_row, Tensor global_scale, int method) -> (Tensor, Tensor)", "fusedGatherQuantizeNv_", 3, _gathered, "nv", False),
     # one global scale per expert: global_scales (E,) with the grouped GEMMs' offs (E,)
@@ -295,11 +171,10 @@ QUANT_OPS = {
     "quantize_mxf8_blocked": QuantOp("(Tensor A, Tensor R, ScalarType dtype) -> (Tensor, Tensor)", "fusedQuantizeMxf8Blocked_", 2, _same, "mxf8", True),
     "silu_mul_quantize_mxf8": QuantOp("(Tensor A, Tensor R, ScalarType dtype, bool blocked) -> (Tensor, Tensor)", "fusedSiluMulQuantizeMxf8_", 2, _act, "mxf8", None),
     "gather_quantize_mxf8": QuantOp("(Tensor A, Tensor R, Tensor src_row, ScalarType dtype) -> (Tensor, Tensor)", "fusedGatherQuantizeMxf8_", 3, _gathered, "mxf8", False),
+    # the clamped SwiGLU into e4m3 -- the A operand of the W4A8 grouped GEMM: e4m3 only (a forward activation; no dtype argument), abs-max only (no method), R = 32 / 64
+    "swiglu_oai_quantize_mxf8": QuantOp("(Tensor A, Tensor R, float alpha, float limit, Tensor? bias, Tensor? offs) -> (Tensor, Tensor)", "fusedSwigluOaiQuantizeMxf8_", 2,
+                                        _act, "mxf8", False, torch.float8_e4m3fn, _OAI_OPTIONAL),
 }
-# The clamped SwiGLU into e4m3 -- the A operand of the W4A8 grouped GEMM.  Outside the table on purpose: the table's "mxf8" rows take a code dtype and every rotation,
-# this op is e4m3 only (no dtype argument), R = 32 / 64, and takes alpha / limit / bias / offs; it is registered beside the loop over QUANT_OPS.
-SWIGLU_OAI_MXF8 = QuantOp("(Tensor A, Tensor R, float alpha, float limit, Tensor? bias, Tensor? offs) -> (Tensor, Tensor)", "fusedSwigluOaiQuantizeMxf8_", 2, _act, "mxf8",
-                          False)
 
 
 def mxf8_dtype(dtype) -> torch.dtype:
@@ -316,20 +191,8 @@ def alloc_quant(row: QuantOp, *args):
     group, sf_dtype = QUANT_FORMATS[row.fmt]
     pr, pc = padded_scale_shape(math.prod(shape) // shape[-1], shape[-1], group)
     blocked = args[-1] if row.blocked is None else row.blocked
-    codes = args[0].new_empty(shape, dtype=mxf8_dtype(args[row.lead])) if row.fmt == "mxf8" else args[0].new_empty((*shape[:-1], shape[-1] // 2), dtype=torch.uint8)
+    codes = args[0].new_empty(shape, dtype=row.dtype or mxf8_dtype(args[row.lead])) if row.fmt == "mxf8" else args[0].new_empty((*shape[:-1], shape[-1] // 2), dtype=torch.uint8)
     return codes, args[0].new_empty((pr * pc,) if blocked else (pr, pc), dtype=sf_dtype)
-
-
-def run_quant(row: QuantOp, *args):
-    """Allocate, then the in-place twin."""
-    o = alloc_quant(row, *args)
-    getattr(torch.ops.qutlass_amd, row.twin)(*args[:row.lead], o[0], o[1], *args[row.lead + (row.fmt == "mxf8"):])
-    return o
-
-
-def run_quant_op(row: QuantOp, *args):
-    """run_quant -- or, for the clamped-SwiGLU ops, which take optional tensors, their own runner (the in-place twins take no None)."""
-    return (run_swiglu_oai_quant if row.twin.startswith("fusedSwigluOaiQuantize") else run_quant)(row, *args)
 
 
 def _optional(x: torch.Tensor, t: torch.Tensor | None, dtype: torch.dtype) -> torch.Tensor:
@@ -337,67 +200,136 @@ def _optional(x: torch.Tensor, t: torch.Tensor | None, dtype: torch.dtype) -> to
     return x.new_empty((0,), dtype=dtype) if t is None else t
 
 
-def alloc_swiglu_oai_quant(row: QuantOp, A, R):
-    """alloc_quant for the clamped-SwiGLU ops: the e4m3 form has no dtype argument (a forward activation is e4m3 only)."""
-    return alloc_quant(row, A, R, *((torch.float8_e4m3fn,) if row.fmt == "mxf8" else ()))
+def _no_none(args, optional):
+    """args with the `Tensor?` ones of a row -- (index, dtype) pairs, dtype None: the first argument's -- as the in-place twin takes them"""
+    args = list(args)
+    for i, dtype in optional:
+        args[i] = _optional(args[0], args[i], dtype or args[0].dtype)
+    return args
 
 
-def run_swiglu_oai_quant(row: QuantOp, A, R, alpha, limit, bias, offs, *method):
-    """run_quant for the ops with optional tensors: the MXFP4 row of the table (method: one int) and SWIGLU_OAI_MXF8 (abs-max only: no method)."""
-    o = alloc_swiglu_oai_quant(row, A, R)
-    getattr(torch.ops.qutlass_amd, row.twin)(A, R, o[0], o[1], alpha, limit, _optional(A, bias, A.dtype), _optional(A, offs, torch.int32), *method)
+def run_quant(row: QuantOp, *args):
+    """Allocate, then the in-place twin."""
+    o = alloc_quant(row, *args)
+    if row.optional:
+        args = _no_none(args, row.optional)
+    lead = row.lead
+    getattr(_AMD, row.twin)(*args[:lead], o[0], o[1], *args[lead + (row.fmt == "mxf8" and row.dtype is None):])
     return o
 
 
-def run_swiglu_oai(X, alpha, limit, bias, offs):
-    o = X.new_empty(_act(X))
-    torch.ops.qutlass_amd.swigluOaiAndMul_(X, o, alpha, limit, _optional(X, bias, X.dtype), _optional(X, offs, torch.int32))
-    return o
+# ---- every other op that fills caller-allocated results: functional op, fake kernel and eager wrapper come from this table as well --------------------------------
+# schema:   of the functional op `qutlass_amd::<name>`
+# twin:     the in-place op of csrc/torch_ext.cpp (a trimmed op library has no training-only twins: their rows are not registered)
+# alloc:    the uninitialised results, from the functional op's arguments -- the one allocator of the fake kernel, the functional op and the eager wrapper
+# call:     (twin, results, *arguments): the twin's argument order
+# optional: as QuantOp's
+class OutputOp(NamedTuple):
+    schema: str
+    twin: str
+    alloc: Callable
+    call: Callable
+    optional: tuple = ()
 
 
-def run_moe_combine_bias(Y, pos, weights, bias, offs):
-    o = Y.new_empty((pos.size(0), Y.size(-1)))
-    torch.ops.qutlass_amd.moeCombineBias_(Y, pos, weights, bias, _optional(Y, offs, torch.int32), o)
-    return o
+def _alloc_act(X, *rest):   # gated MLP: X is (.., 2 I) [gate | up]
+    return X.new_empty((*X.shape[:-1], X.size(-1) // 2))
 
 
-def _alloc_topk(logits: torch.Tensor, topk: int):
+def _alloc_combined(Y, pos, *rest):   # (M, H) sorted rows, (T, topk) -> (T, H)
+    return Y.new_empty((pos.size(0), Y.size(-1)))
+
+
+def _alloc_topk(logits, topk, *rest):   # (T, E) logits -> (T, topk) weights and ids
     return logits.new_empty((logits.size(0), topk), dtype=torch.float32), logits.new_empty((logits.size(0), topk), dtype=torch.int32)
 
 
-def _alloc_scores(logits: torch.Tensor, wanted: bool):
-    return logits.new_empty(tuple(logits.shape) if wanted else (0,), dtype=torch.float32)
+def _alloc_topk_grouped(logits, bias, topk, *rest):   # the third result is the (T, E) scores, or an empty tensor when they are not asked for (rest[-1]: return_scores)
+    return _alloc_topk(logits, topk) + (logits.new_empty(tuple(logits.shape) if rest[-1] else (0,), dtype=torch.float32),)
 
 
-def run_moe_topk_grouped(logits: torch.Tensor, bias: torch.Tensor | None, topk: int, n_group: int, topk_group: int, scoring: int, renormalize: bool,
-                         routed_scaling_factor: float, return_scores: bool):
-    """Allocate weights, ids and scores (empty when not asked for), then the in-place op; an empty bias is its "no bias"."""
+def _call_topk_grouped(twin, o, logits, bias, topk, n_group, topk_group, scoring, renormalize, routed_scaling_factor, return_scores):
+    """(an empty bias is the in-place op's "no bias")"""
     if bias is not None and bias.numel() == 0:
         raise ValueError("bias must have E entries")
-    weights, ids = _alloc_topk(logits, topk)
-    scores = _alloc_scores(logits, return_scores)
-    no_bias = logits.new_empty((0,), dtype=torch.float32)
-    torch.ops.qutlass_amd.moeTopkGrouped_(logits, no_bias if bias is None else bias, weights, ids, scores, n_group, topk_group, scoring, renormalize,
-                                          routed_scaling_factor)
-    return weights, ids, scores
+    twin(logits, logits.new_empty((0,), dtype=torch.float32) if bias is None else bias, o[0], o[1], o[2], n_group, topk_group, scoring, renormalize, routed_scaling_factor)
 
 
-def _alloc_sort(topk_ids: torch.Tensor, num_experts: int):
+def _alloc_sort(topk_ids, expert_map, num_experts):
     """src_row, offs, pos; the kernels write every element, except that an empty sort launches nothing: offs is allocated as zeros always (one tiny fill), so no
     branch on the number of slots is traced"""
     return (topk_ids.new_empty((topk_ids.numel(),), dtype=torch.int32), topk_ids.new_zeros((num_experts,), dtype=torch.int32),
             topk_ids.new_empty(tuple(topk_ids.shape), dtype=torch.int32))
 
 
-def run_moe_sort(topk_ids: torch.Tensor, expert_map: torch.Tensor | None, num_experts: int):
-    """Allocate the three results and the scratch of the three-launch form (none up to the one-launch bound), then the in-place op."""
+def _call_sort(twin, o, topk_ids, expert_map, num_experts):
+    """with the scratch of the three-launch form (none up to the one-launch bound); an empty expert_map is the in-place op's "no map"."""
     if expert_map is not None and expert_map.numel() == 0:
         raise ValueError("expert_map must have at least one entry")
-    out = _alloc_sort(topk_ids, num_experts)
     ws = topk_ids.new_empty((_lib.load().qutlass_amd_moe_sort_workspace_bytes(topk_ids.numel(), num_experts) // 4,), dtype=torch.int32)
-    no_map = topk_ids.new_empty((0,), dtype=torch.int32)   # the in-place op's "no map"
-    torch.ops.qutlass_amd.moeSort_(topk_ids, no_map if expert_map is None else expert_map, num_experts, out[0], out[1], out[2], ws)
-    return out
+    twin(topk_ids, topk_ids.new_empty((0,), dtype=torch.int32) if expert_map is None else expert_map, num_experts, o[0], o[1], o[2], ws)
+
+
+def _alloc_mask(A, R):   # fusedQuantizeMx's results and the clip mask, one bit per element
+    return alloc_quant(QUANT_OPS["quantize_mx"], A) + (A.new_empty((*A.shape[:-1], A.size(-1) // 8), dtype=torch.uint8),)
+
+
+# The two QAT-backward transposes allocate on h's device, as the reference's wrappers do (for every valid call that is x's device).
+def _alloc_backward_t(x, h):   # (.., N, M) -> (.., M, N/2) e2m1x2, (.., M, N/32) e8m0
+    return (h.new_empty((*x.shape[:-2], x.size(-1), x.size(-2) // 2), dtype=torch.float4_e2m1fn_x2),
+            h.new_empty((*x.shape[:-2], x.size(-1), x.size(-2) // 32), dtype=torch.float8_e8m0fnu))
+
+
+def _alloc_backward_qt(c, s, h, alpha):   # the same from x_e2m1 (.., N, M/2) and x_e8m0 (.., N, M/32)
+    return (h.new_empty((*c.shape[:-2], c.size(-1) * 2, c.size(-2) // 2), dtype=torch.float4_e2m1fn_x2),
+            h.new_empty((*s.shape[:-2], s.size(-1) * 32, s.size(-2) // 32), dtype=torch.float8_e8m0fnu))
+
+
+def _alloc_square_double(x):   # (m, n) -> e4m3 (m_pad, n), row scales (m_pad, n/32), column scales (n, m_pad/32); m_pad: m rounded up to 128
+    mp, n = (x.size(0) + 127) // 128 * 128, x.size(1)
+    return (x.new_empty((mp, n), dtype=torch.float8_e4m3fn), x.new_empty((mp, n // 32), dtype=torch.float8_e8m0fnu),
+            x.new_empty((n, mp // 32), dtype=torch.float8_e8m0fnu))
+
+
+def _alloc_transpose(x, s):   # packed (m, n/2) -> e4m3 (n, m_pad), scales (n, m_pad/32); m_pad: m rounded up to 256, as in the reference
+    mp, n = (x.size(0) + 255) // 256 * 256, x.size(1) * 2
+    return x.new_empty((n, mp), dtype=torch.float8_e4m3fn), x.new_empty((n, mp // 32), dtype=torch.float8_e8m0fnu)
+
+
+OUTPUT_OPS = {
+    "silu_and_mul": OutputOp("(Tensor X) -> Tensor", "siluAndMul_", _alloc_act, lambda twin, o, X: twin(X, o)),
+    "moe_combine": OutputOp("(Tensor Y, Tensor pos, Tensor weights) -> Tensor", "moeCombine_", _alloc_combined, lambda twin, o, Y, pos, weights: twin(Y, pos, weights, o)),
+    # gpt-oss: the clamped SwiGLU with an optional per-expert bias (E, 2 I) and the grouped GEMMs' offs (E,); moe_combine with the down bias (E, H)
+    "swiglu_oai_and_mul": OutputOp("(Tensor X, float alpha, float limit, Tensor? bias, Tensor? offs) -> Tensor", "swigluOaiAndMul_", _alloc_act,
+                                   lambda twin, o, X, alpha, limit, bias, offs: twin(X, o, alpha, limit, bias, offs), ((3, None), (4, torch.int32))),
+    "moe_combine_bias": OutputOp("(Tensor Y, Tensor pos, Tensor weights, Tensor bias, Tensor? offs) -> Tensor", "moeCombineBias_", _alloc_combined,
+                                 lambda twin, o, Y, pos, weights, bias, offs: twin(Y, pos, weights, bias, offs, o), ((4, torch.int32),)),
+    # MoE routing: (T, E) logits -> (T, topk) weights and ids; (T, topk) ids -> src_row (T * topk), offs (num_experts), pos (T, topk)
+    "moe_topk_softmax": OutputOp("(Tensor logits, int topk, bool renormalize) -> (Tensor, Tensor)", "moeTopkSoftmax_", _alloc_topk,
+                                 lambda twin, o, logits, topk, renormalize: twin(logits, o[0], o[1], renormalize)),
+    "moe_topk_grouped": OutputOp("(Tensor logits, Tensor? bias, int topk, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor, "
+                                 "bool return_scores) -> (Tensor, Tensor, Tensor)", "moeTopkGrouped_", _alloc_topk_grouped, _call_topk_grouped),
+    "moe_sort_fused": OutputOp("(Tensor topk_ids, Tensor? expert_map, int num_experts) -> (Tensor, Tensor, Tensor)", "moeSort_", _alloc_sort, _call_sort),
+    # training only: the clip-mask quantizer and the QAT-backward data preparation
+    "quantize_mx_mask": OutputOp("(Tensor A, Tensor R) -> (Tensor, Tensor, Tensor)", "fusedQuantizeMxMask_", _alloc_mask, lambda twin, o, A, R: twin(A, R, *o)),
+    "backward_t": OutputOp("(Tensor x, Tensor h) -> (Tensor, Tensor)", "backward_t_bf16_", _alloc_backward_t, lambda twin, o, x, h: twin(x, h, *o)),
+    "backward_qt": OutputOp("(Tensor x_e2m1, Tensor x_e8m0, Tensor h, Tensor alpha) -> (Tensor, Tensor)", "backward_qt_bf16_", _alloc_backward_qt,
+                            lambda twin, o, x_e2m1, x_e8m0, h, alpha: twin(x_e2m1, x_e8m0, h, alpha, *o)),
+    "square_double_mxfp8": OutputOp("(Tensor x_bf16) -> (Tensor, Tensor, Tensor)", "backward_bf16_square_double_mxfp8_", _alloc_square_double,
+                                    lambda twin, o, x_bf16: twin(x_bf16, *o)),
+    "transpose_mxfp8": OutputOp("(Tensor x_fp4, Tensor scales) -> (Tensor, Tensor)", "mxfp4_transpose_mxfp8_", _alloc_transpose,
+                                lambda twin, o, x_fp4, scales: twin(x_fp4, scales, *o)),
+}
+
+
+def run_output(row: OutputOp, *args):
+    """Allocate, then the in-place twin."""
+    _, twin, alloc, call, optional = row
+    o = alloc(*args)
+    if optional:
+        args = _no_none(args, optional)
+    call(getattr(_AMD, twin), o, *args)
+    return o
 
 
 def to_blocked(input_matrix: torch.Tensor) -> torch.Tensor:

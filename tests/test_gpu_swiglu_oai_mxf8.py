@@ -166,7 +166,7 @@ def test_scale_padding_keeps_its_fill(q, R):
     M, inter = 33, 3 * R
     x = (torch.randn(M, 2 * inter, generator=gen) * 4.0).to(BF16).to(DEV)
     bias, offs = _bias(3, 2 * inter, gen), torch.tensor([10, 20, 33], dtype=I32, device=DEV)
-    codes, sf = q.ops.alloc_swiglu_oai_quant(q.ops.SWIGLU_OAI_MXF8, x, h)
+    codes, sf = q.ops.alloc_quant(q.ops.QUANT_OPS["swiglu_oai_quantize_mxf8"], x, h)
     n = M * inter // 32
     assert sf.numel() > n and codes.dtype == E4M3 and codes.shape == (M, inter)
     sf.view(torch.uint8).fill_(0xAB)

@@ -31,13 +31,14 @@ def _args(row, R, rows, blocked):
 def test_extents_agree_with_the_allocator(name):
     row = ops.QUANT_OPS[name]
     group, _ = ops.QUANT_FORMATS[row.fmt]
-    for R in ROTS[row.fmt]:
+    for R in ((32, 64) if name == "swiglu_oai_quantize_mxf8" else ROTS[row.fmt]):
         for blocked in ([False, True] if row.blocked is None else [row.blocked]):
             for rows in fp.BLOCKED_ROWS + (fp.M_ROWS,):
                 lead, k = _args(row, R, rows, blocked)
-                for dtype in (ops.MXF8_DTYPES if row.fmt == "mxf8" else (None,)):
+                for dtype in (ops.MXF8_DTYPES if row.fmt == "mxf8" and row.dtype is None else (None,)):   # (a row that fixes its code dtype has no such argument)
                     tail = ([dtype] if dtype is not None else []) + [blocked]      # alloc_quant reads the code dtype behind the leading tensors and `blocked` last
                     codes, sf = ops.alloc_quant(row, *lead, *tail)
+                    assert codes.dtype == (torch.uint8 if row.fmt != "mxf8" else dtype or row.dtype), (name, codes.dtype)
                     ext = fp.quant_extents(row.fmt, (rows, k), blocked, fp8_codes=row.fmt == "mxf8")
                     assert ext["OUT"] == (codes.numel() * codes.element_size(),) * 2, (name, R, rows)
                     pr, pc = padded_scale_shape(rows, k, group)

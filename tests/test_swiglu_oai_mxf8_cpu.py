@@ -122,7 +122,8 @@ def test_schema_of_the_twin():
     assert written == ["OUT", "OUT_sf"] and len(schema.returns) == 0, str(schema)
     assert [a.name for a in schema.arguments] == ["A", "R", "OUT", "OUT_sf", "alpha", "limit", "bias", "offs"], str(schema)    # no method: abs-max only
     assert torch._library.simple_registry.singleton.find("qutlass_amd::fusedSwigluOaiQuantizeMxf8_").fake_impl.kernel is not None
-    assert q.ops.SWIGLU_OAI_MXF8.twin == "fusedSwigluOaiQuantizeMxf8_" and q.ops.SWIGLU_OAI_MXF8.fmt == "mxf8"
+    row = q.ops.QUANT_OPS["swiglu_oai_quantize_mxf8"]
+    assert row.twin == "fusedSwigluOaiQuantizeMxf8_" and row.fmt == "mxf8"
 
 
 def test_schema_of_the_functional_op():
@@ -189,7 +190,7 @@ def test_wrapper_value_errors():
 
 def test_eager_calls_take_the_twin_through_the_shared_runner(monkeypatch):
     seen = []
-    monkeypatch.setattr(q.ops, "run_swiglu_oai_quant", lambda row, *a: seen.append((row.twin, a[2:])) or "ran")
+    monkeypatch.setattr(q.ops, "run_quant", lambda row, *a: seen.append((row.twin, a[2:])) or "ran")
     x, h = _meta(4, 128), _meta(32, 32)
     assert q.fusedSwigluOaiQuantizeMxf8(x, h) == "ran"
     assert q.fusedSwigluOaiQuantizeMx(x, h, method="abs_max") == "ran"
@@ -203,10 +204,12 @@ def test_exported_and_documented():
     assert "fusedSwigluOaiQuantizeMxf8" in q.__doc__
 
 
-def test_the_quantizer_table_is_unchanged():
-    """the new op's record stands NEXT to the table: the tests that enumerate QUANT_OPS build each row's call from its format, which does not describe this op"""
+def test_the_op_is_the_last_row_of_the_quantizer_table():
+    """the op's record stands IN the table, behind the fifteen rows that were there before it: a row may fix its code dtype, as it may fix `blocked`"""
     assert list(q.ops.QUANT_OPS) == [
         "quantize_mx", "quantize_nv", "quantize_mx_blocked", "quantize_nv_blocked", "silu_mul_quantize_mx", "silu_mul_quantize_nv", "swiglu_oai_quantize_mx",
         "gather_quantize_mx", "gather_quantize_nv", "gather_quantize_nv_grouped", "silu_mul_quantize_nv_grouped", "quantize_mxf8", "quantize_mxf8_blocked",
-        "silu_mul_quantize_mxf8", "gather_quantize_mxf8"]
-    assert q.ops.SWIGLU_OAI_MXF8 not in q.ops.QUANT_OPS.values()
+        "silu_mul_quantize_mxf8", "gather_quantize_mxf8", "swiglu_oai_quantize_mxf8"]
+    row = q.ops.QUANT_OPS["swiglu_oai_quantize_mxf8"]
+    assert row.twin == "fusedSwigluOaiQuantizeMxf8_" and row.fmt == "mxf8" and row.dtype == torch.float8_e4m3fn and row.blocked is False
+    assert not hasattr(q.ops, "SWIGLU_OAI_MXF8")
