@@ -480,6 +480,27 @@ int qutlass_amd_moe_sort(const void* topk_ids, int id_bytes, int64_t t, int64_t 
                          int32_t* src_row, int32_t* offs, int32_t* pos, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * EXTENSION: the whole routing of a decode step in ONE launch of one workgroup: qutlass_amd_moe_topk_softmax (respectively qutlass_amd_moe_topk_grouped without
+ * scores) followed by qutlass_amd_moe_sort on the ids it returns, with the same five results bit for bit -- the kernels run the routers' and the sort's own device
+ * code, and the sort reads its keys from LDS where the router left them instead of reading ids back from memory.
+ *   arguments  those of the matching moe_topk entry without `scores`, then num_experts, expert_map (nullable), g_entries, src_row, offs, pos of
+ *              qutlass_amd_moe_sort.  No workspace.
+ *   limits     0 <= t <= 64; every other limit and every argument check is the two entries' (made before any HIP call); an expert_map has at least one entry.
+ *              t > 64 returns QAMD_ERR_INVALID: run the two entries instead.  t == 0 returns QAMD_OK without a launch and writes nothing (the caller zero-fills offs).
+ * These entries ALWAYS run the one launch.  qutlass_amd_moe_route_fused_max_tokens() is the measured bound, in [0, 64], up to which that is the faster form on an
+ * MI355X for every router measured; the torch ops qutlass_amd::moe_route_fused / moe_route_grouped_fused take the one launch up to it and the
+ * two entries beyond.
+ */
+int64_t qutlass_amd_moe_route_fused_max_tokens(void);
+int qutlass_amd_moe_route_fused(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids,
+                                int64_t num_experts, const int32_t* expert_map /* nullable */, int64_t g_entries, int32_t* src_row, int32_t* offs, int32_t* pos,
+                                void* stream);
+int qutlass_amd_moe_route_grouped_fused(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
+                                        const float* bias /* nullable */, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids,
+                                        int64_t num_experts, const int32_t* expert_map /* nullable */, int64_t g_entries, int32_t* src_row, int32_t* offs,
+                                        int32_t* pos, void* stream);
+
+/*
  * EXTENSION: the measured launch-count rule of the activation path y = Q(x h) W^T of one linear layer (reference flow: qutlass/__init__.py:149-180 ->
  * qutlass/utils.py:160-193 -> qutlass/__init__.py:34-76, three launches): returns 1 where the one-launch decode kernel below wins (M <= 16, R = 32, short K,
  * a weight of fewer than 32 x CUs rows), else 2 (quantizer with GEMM-ready scales + GEMM).  Pure host arithmetic on the current device's CU count; what

@@ -16,6 +16,7 @@ meaning, defaults and Python-level error behaviour):
     fusedQuantizeMxf8 [Blocked], fusedGatherQuantizeMxf8, fusedSiluMulQuantizeMxf8 [Blocked]  (extension: the MXFP8 quantizers -- the operands of the three MXFP8 GEMMs)
     moe_topk_softmax, moe_sort_fused, moe_route           (extension: MoE routing in HIP -- router logits to ids, weights and the sorted-row metadata)
     moe_topk_grouped, moe_route_grouped                   (extension: the grouped router of DeepSeek-V2 / V3 and Kimi-K2 -- sigmoid / softmax scores, selection bias, group-limited top-k)
+    moe_route_fused, moe_route_grouped_fused              (extension: both routings in ONE launch for decode batches -- router and sort in one workgroup, the same bits)
     swiglu_oai_and_mul, fusedSwigluOaiQuantizeMx, moe_combine(bias=, offs=)  (extension: gpt-oss -- the clamped SwiGLU and the per-expert biases of both projections,
                                                           applied by the ops that read the grouped GEMMs' outputs; utils.split_interleaved_gate_up for the checkpoint layout)
     fusedSwigluOaiQuantizeMxf8                            (extension: the same activation into e4m3 -- the A operand of the W4A8 grouped GEMM, one launch)
@@ -422,6 +423,38 @@ def moe_route_grouped(logits: torch.Tensor, topk: int, num_experts: int | None =
     weights, ids = moe_topk_grouped(logits, topk, n_group=n_group, topk_group=topk_group, bias=bias, scoring=scoring, renormalize=renormalize,
                                     routed_scaling_factor=routed_scaling_factor)
     return (weights, ids) + tuple(moe_sort_fused(ids, logits.size(1) if num_experts is None else num_experts, expert_map=expert_map))
+
+
+def _check_expert_map(expert_map):
+    if expert_map is not None and expert_map.numel() == 0:
+        raise ValueError("expert_map must have at least one entry")
+
+
+def moe_route_fused(logits: torch.Tensor, topk: int, num_experts: int | None = None, *, renormalize: bool = True,
+                    expert_map: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``moe_route(logits, topk, num_experts, renormalize=renormalize, expert_map=expert_map)`` -- the same five results (weights, ids, src_row, offs, pos),
+    bit for bit -- in ONE launch for decode batches: up to ``qutlass_amd_moe_route_fused_max_tokens()`` tokens (a measured bound, at most 64) one workgroup routes its
+    tokens, a wave per token, and sorts the T * topk slots it has just produced, their keys handed over in LDS; the kernel runs moe_topk_softmax's and moe_sort_fused's
+    own device code.  Beyond the bound the op runs those two, so it takes every T.  The same limits and ValueErrors as moe_route; T == 0 returns empty tensors and an
+    all-zero offs.  A functional op that allocates its results without a fill -- one graph node up to the bound -- (``torch.ops.qutlass_amd.moe_route_fused``): no host sync, graph-capturable, traces under
+    torch.compile."""
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be (T, E) (got {tuple(logits.shape)})")
+    if not 1 <= topk <= min(logits.size(1), 32):
+        raise ValueError(f"topk must be in [1, min(E, 32)] (got topk = {topk} for E = {logits.size(1)})")
+    _check_expert_map(expert_map)
+    return _ops_amd.moe_route_fused(logits, expert_map, topk, logits.size(1) if num_experts is None else num_experts, renormalize)
+
+
+def moe_route_grouped_fused(logits: torch.Tensor, topk: int, num_experts: int | None = None, *, n_group: int = 1, topk_group: int = 1, bias: torch.Tensor | None = None,
+                            scoring: str = "sigmoid", renormalize: bool = True, routed_scaling_factor: float = 1.0,
+                            expert_map: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``moe_route_grouped`` with the same arguments and the same five results, bit for bit, in ONE launch for decode batches -- moe_route_fused with the
+    grouped router (moe_topk_grouped's device code) in front; the two-launch form beyond the same measured bound."""
+    _check_grouped(logits, topk, n_group, topk_group, bias, scoring)
+    _check_expert_map(expert_map)
+    return _ops_amd.moe_route_grouped_fused(logits, bias, expert_map, topk, logits.size(1) if num_experts is None else num_experts, n_group, topk_group,
+                                            _lib.MOE_SCORING[scoring], renormalize, float(routed_scaling_factor))
 
 
 def fusedGatherQuantizeMx(x: torch.Tensor, h: torch.Tensor, src_row: torch.Tensor, *,

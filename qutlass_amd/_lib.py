@@ -61,6 +61,9 @@ SYMBOLS = {
     "qutlass_amd_moe_topk_grouped": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "qutlass_amd_moe_sort_workspace_bytes": (_i64, [_i64, _i64]),
     "qutlass_amd_moe_sort": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "qutlass_amd_moe_route_fused_max_tokens": (_i64, []),
+    "qutlass_amd_moe_route_fused": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "qutlass_amd_moe_route_grouped_fused": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, ctypes.c_float, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "qutlass_amd_fused_quantize_matmul_mxf4_bf16_tn": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "qutlass_amd_activation_path_launches": (_i32, [_i64, _i64, _i64, _i32]),
     "qutlass_amd_to_blocked": (_i32, [_vp, _i64, _i64, _vp, _vp]),

@@ -2167,9 +2167,11 @@ int qutlass_amd_moe_combine_bias_bf16(const void* y, int64_t m, int64_t hdim, co
 extern "C++" {
 struct TopkSoftmax { static constexpr const char* what = "moe_topk_softmax_kernel"; template <typename T, int R, bool V> static auto kernel() { return moe_topk_softmax_kernel<T, R, V>; } };
 struct TopkGrouped { static constexpr const char* what = "moe_topk_grouped_kernel"; template <typename T, int R, bool V> static auto kernel() { return moe_topk_grouped_kernel<T, R, V>; } };
-template <typename F, typename P>
-static int launch_topk(const char* name, int elem_bytes, const MoeTopkLaunch& l, const P& p, hipStream_t s) {
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), 0, s, p); return check_launch(F::what); };
+struct RouteFused { static constexpr const char* what = "moe_route_fused_kernel"; template <typename T, int R, bool V> static auto kernel() { return moe_route_fused_kernel<T, R, V>; } };
+struct RouteGroupedFused { static constexpr const char* what = "moe_route_grouped_fused_kernel"; template <typename T, int R, bool V> static auto kernel() { return moe_route_grouped_fused_kernel<T, R, V>; } };
+template <typename F, typename... P>   // p: the kernel's arguments -- the router's parameters, and the sort's behind them for the one-launch routing kernels
+static int launch_topk(const char* name, int elem_bytes, const MoeTopkLaunch& l, hipStream_t s, const P&... p) {
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), 0, s, p...); return check_launch(F::what); };
   constexpr auto arm = [](int eb, int r, bool v) { return eb * 64 + r * 2 + v; };   constexpr bool V = true, S = false;   using bf16 = uint16_t;   // (V / S: 16-byte vector loads / single columns)
   switch (arm(elem_bytes, l.R, l.loadv)) {
     case arm(2, 8, V): return go(F::template kernel<bf16, 8, V>());     case arm(2, 8, S): return go(F::template kernel<bf16, 8, S>());
@@ -2195,22 +2197,29 @@ static int topk_check(const char* name, int elem_bytes, int64_t t, int64_t e) {
   return QAMD_OK;
 }
 
-int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids, void* stream) {
-  const char* name = "moe_topk_softmax";
+// The softmax router's checks and kernel parameters: what qutlass_amd_moe_topk_softmax and qutlass_amd_moe_route_fused both do with these arguments (t == 0 passes with p not filled).
+static int topk_softmax_args(const char* name, const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids, MoeTopkParams& p) {
   if (int rc = topk_check(name, elem_bytes, t, e)) return rc;
   if (topk < 1 || topk > 32 || topk > e) return fail(QAMD_ERR_INVALID, "%s: bad shape: topk must be in [1, min(E, 32)] (got %lld for E = %lld)", name, (long long)topk, (long long)e);
   if ((uintptr_t)logits % elem_bytes || (uintptr_t)weights % 4 || (uintptr_t)ids % 4) return fail(QAMD_ERR_INVALID, "%s: logits, weights and ids must be aligned to their element size", name);
   if (t == 0) return QAMD_OK;
   if (!logits || !weights || !ids) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  MoeTopkParams p;
   p.logits = logits; p.weights = weights; p.ids = ids; p.t = t; p.e = (int)e; p.topk = (int)topk; p.renorm = renormalize ? 1 : 0;
-  return launch_topk<TopkSoftmax>(name, elem_bytes, moe_topk_plan(elem_bytes, e, t, (uintptr_t)logits % 16 == 0, chip_cus()), p, (hipStream_t)stream);
+  return QAMD_OK;
+}
+
+int qutlass_amd_moe_topk_softmax(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids, void* stream) {
+  const char* name = "moe_topk_softmax";
+  MoeTopkParams p;
+  if (int rc = topk_softmax_args(name, logits, elem_bytes, t, e, topk, renormalize, weights, ids, p)) return rc;
+  if (t == 0) return QAMD_OK;
+  return launch_topk<TopkSoftmax>(name, elem_bytes, moe_topk_plan(elem_bytes, e, t, (uintptr_t)logits % 16 == 0, chip_cus()), (hipStream_t)stream, p);
 }
 
 // Grouped top-k (DeepSeek-V2 / V3, Kimi-K2 routers): scores, a selection bias, a top-k inside the best groups; the same launch shape as moe_topk_softmax.
-int qutlass_amd_moe_topk_grouped(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
-                                 const float* bias, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids, float* scores, void* stream) {
-  const char* name = "moe_topk_grouped";
+// Its checks and kernel parameters, for qutlass_amd_moe_topk_grouped and qutlass_amd_moe_route_grouped_fused (t == 0 passes with p not filled).
+static int topk_grouped_args(const char* name, const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
+                             const float* bias, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids, float* scores, MoeGroupedParams& p) {
   if (int rc = topk_check(name, elem_bytes, t, e)) return rc;
   if (n_group < 1 || n_group > 64) return fail(QAMD_ERR_INVALID, "%s: bad shape: n_group must be in [1, 64] (got %lld)", name, (long long)n_group);
   if (e % n_group != 0) return fail(QAMD_ERR_INVALID, "%s: bad shape: n_group must divide E (got n_group = %lld for E = %lld)", name, (long long)n_group, (long long)e);
@@ -2225,15 +2234,67 @@ int qutlass_amd_moe_topk_grouped(const void* logits, int elem_bytes, int64_t t, 
     return fail(QAMD_ERR_INVALID, "%s: logits, bias, weights, ids and scores must be aligned to their element size", name);
   if (t == 0) return QAMD_OK;
   if (!logits || !weights || !ids) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
-  MoeGroupedParams p;
   p.logits = logits; p.bias = bias; p.weights = weights; p.ids = ids; p.scores = scores; p.t = t; p.e = (int)e; p.topk = (int)topk; p.renorm = renormalize ? 1 : 0;
   p.sigmoid = scoring == QAMD_MOE_SCORING_SIGMOID; p.n_group = (int)n_group; p.topk_group = (int)topk_group; p.s = (int)(e / n_group);
   p.lg_l = 0;
   while ((n_group << (p.lg_l + 1)) <= 64) ++p.lg_l;   // L lanes per group in the group stage
   p.magic = (uint32_t)(((1ll << 22) + p.s - 1) / p.s);
   p.scale = routed_scaling_factor;
+  return QAMD_OK;
+}
+
+int qutlass_amd_moe_topk_grouped(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
+                                 const float* bias, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids, float* scores, void* stream) {
+  const char* name = "moe_topk_grouped";
+  MoeGroupedParams p;
+  if (int rc = topk_grouped_args(name, logits, elem_bytes, t, e, topk, n_group, topk_group, scoring, bias, renormalize, routed_scaling_factor, weights, ids, scores, p)) return rc;
+  if (t == 0) return QAMD_OK;
   const bool aligned = (uintptr_t)logits % 16 == 0 && (uintptr_t)scores % 16 == 0;   // the scores, if asked for, are stored as 16-byte vectors too
-  return launch_topk<TopkGrouped>(name, elem_bytes, moe_topk_plan(elem_bytes, e, t, aligned, chip_cus()), p, (hipStream_t)stream);
+  return launch_topk<TopkGrouped>(name, elem_bytes, moe_topk_plan(elem_bytes, e, t, aligned, chip_cus()), (hipStream_t)stream, p);
+}
+
+// One-launch routing for decode (moe_route.hip.h): either router's checks above, then the sort's for the map and the three results, then ONE launch of one workgroup.
+// The sort's half of the checks and of the kernel's parameters (n > 0 slots; the ids are handed over in LDS, so sp.ids stays null).
+int64_t qutlass_amd_moe_route_fused_max_tokens(void) { return MOE_ROUTE_FUSED_TOKENS; }
+
+static int route_fused_sort_args(const char* name, int64_t t, int64_t topk, int64_t num_experts, const int32_t* expert_map, int64_t g, int32_t* src_row, int32_t* offs,
+                                 int32_t* pos, MoeSortParams& p) {
+  if (t > MOE_ROUTE_FUSED_MAX_T)
+    return fail(QAMD_ERR_INVALID, "%s: the one-launch routing takes at most %d tokens (got %lld): use the router and qutlass_amd_moe_sort beyond", name, MOE_ROUTE_FUSED_MAX_T, (long long)t);
+  if (num_experts < 1 || num_experts > 1024) return fail(QAMD_ERR_INVALID, "%s: bad shape: the number of experts must be in [1, 1024] (got %lld)", name, (long long)num_experts);
+  if (g < 0 || g >= (1ll << 31) || (expert_map && g == 0)) return fail(QAMD_ERR_INVALID, "%s: bad shape (expert_map of %lld entries)", name, (long long)g);
+  if (((uintptr_t)expert_map | (uintptr_t)src_row | (uintptr_t)offs | (uintptr_t)pos) % 4)
+    return fail(QAMD_ERR_INVALID, "%s: expert_map and the results must be aligned to their element size", name);
+  if (t == 0) return QAMD_OK;
+  if (!src_row || !offs || !pos) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", name);
+  p.ids = nullptr; p.map = expert_map; p.src_row = src_row; p.offs = offs; p.pos = pos; p.ws = nullptr;
+  p.n = t * topk; p.spb = cdiv(p.n, 512) * 512; p.rows = 1; p.g = (int)g; p.e = (int)num_experts; p.topk = (int)topk;
+  p.nbits = 0;
+  while ((num_experts >> p.nbits) != 0) ++p.nbits;   // keys are 0 .. E
+  return QAMD_OK;
+}
+
+int qutlass_amd_moe_route_fused(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int renormalize, float* weights, int32_t* ids, int64_t num_experts,
+                                const int32_t* expert_map, int64_t g_entries, int32_t* src_row, int32_t* offs, int32_t* pos, void* stream) {
+  const char* name = "moe_route_fused";
+  MoeTopkParams tp;
+  MoeSortParams sp;
+  if (int rc = topk_softmax_args(name, logits, elem_bytes, t, e, topk, renormalize, weights, ids, tp)) return rc;
+  if (int rc = route_fused_sort_args(name, t, topk, num_experts, expert_map, g_entries, src_row, offs, pos, sp)) return rc;
+  if (t == 0) return QAMD_OK;
+  return launch_topk<RouteFused>(name, elem_bytes, moe_route_fused_plan(elem_bytes, e, t, (uintptr_t)logits % 16 == 0), (hipStream_t)stream, tp, sp);
+}
+
+int qutlass_amd_moe_route_grouped_fused(const void* logits, int elem_bytes, int64_t t, int64_t e, int64_t topk, int64_t n_group, int64_t topk_group, int scoring,
+                                        const float* bias, int renormalize, float routed_scaling_factor, float* weights, int32_t* ids, int64_t num_experts,
+                                        const int32_t* expert_map, int64_t g_entries, int32_t* src_row, int32_t* offs, int32_t* pos, void* stream) {
+  const char* name = "moe_route_grouped_fused";
+  MoeGroupedParams tp;
+  MoeSortParams sp;
+  if (int rc = topk_grouped_args(name, logits, elem_bytes, t, e, topk, n_group, topk_group, scoring, bias, renormalize, routed_scaling_factor, weights, ids, nullptr, tp)) return rc;
+  if (int rc = route_fused_sort_args(name, t, topk, num_experts, expert_map, g_entries, src_row, offs, pos, sp)) return rc;
+  if (t == 0) return QAMD_OK;
+  return launch_topk<RouteGroupedFused>(name, elem_bytes, moe_route_fused_plan(elem_bytes, e, t, (uintptr_t)logits % 16 == 0), (hipStream_t)stream, tp, sp);
 }
 
 // Expert sort: moe_sort_plan (moe_route.hip.h) -- the size of the scratch, the entry's check of it, the geometry it fills in and the launches all read that one result.
@@ -2542,6 +2603,7 @@ int qutlass_amd_debug_stream_launch_plan(int op, int64_t a, int64_t b, int64_t c
 // own checks of these arguments, no GPU touched.  Returns the number of ints written to out, or -1: an argument the op rejects, no such op, cus <= 0, a null out, cap too small.
 //   op 0  row_stream_plan (silu_and_mul, swiglu_oai_and_mul, both moe_combine forms): a = chunks > 0 -> {workgroups, threads};   op 3  fusedq_plan: a = M -> {rows per rotation tile}
 //   op 1  moe_topk_plan (both routers): a = elem_bytes, b = E, c = T, plus bit 62 of c when every row's pointers are 16-byte aligned -> {R, vector loads, workgroups, threads}
+//   op 5  moe_route_fused_plan (both one-launch routing kernels): op 1's arguments with T <= 64 -> {op 1's R, op 1's vector loads, 1 workgroup, 512 threads}
 //   op 2  moe_sort_plan: (a, b, c) = (T * topk, E, the one-launch bound or 0 for the product's) -> {launches, slots per workgroup, rows, workspace bytes};   op 4  activation_path_plan at rot = 32: (M, N, K) -> {launches}
 int qutlass_amd_debug_moe_launch_plan(int op, int64_t a, int64_t b, int64_t c, int cus, int* out, int cap) {
   const int64_t t = c & ~(1ll << 62);
@@ -2549,6 +2611,7 @@ int qutlass_amd_debug_moe_launch_plan(int op, int64_t a, int64_t b, int64_t c, i
   if (!out || cus <= 0) return -1;
   if (op == 0 && a > 0) { const RowStreamLaunch l = row_stream_plan(a, cus); return put({l.grid, l.threads}); }
   if (op == 1 && a == (int)a && !topk_check("debug_moe_launch_plan", (int)a, t, b)) { const MoeTopkLaunch l = moe_topk_plan((int)a, b, t, c >> 62 & 1, cus); return put({l.R, l.loadv, l.grid, l.threads}); }
+  if (op == 5 && a == (int)a && t <= MOE_ROUTE_FUSED_MAX_T && !topk_check("debug_moe_launch_plan", (int)a, t, b)) { const MoeTopkLaunch l = moe_route_fused_plan((int)a, b, t, c >> 62 & 1); return put({l.R, l.loadv, l.grid, l.threads}); }
   if (op == 2 && a >= 0 && a < (1ll << 31) && b >= 1 && b <= 1024 && c >= 0) { const MoeSortLaunch l = moe_sort_plan(a, b, c); return put({l.launches, l.spb, l.rows, l.ws_bytes}); }
   if (op == 3 && a >= 1 && a <= 32) return put({fusedq_plan(a)});
   return op == 4 ? put({activation_path_plan(a, b, c, 32, cus)}) : -1;

@@ -4,6 +4,8 @@
 //                             experts of the best topk_group of n_group groups; selection runs on the biased score c, the weights are the unbiased scores
 //   moe_sort_kernel           (T, topk) expert ids -> src_row / offs / pos of a STABLE sort by expert: a counting sort without atomics and without any
 //                             workgroup waiting on another (one workgroup in one launch, or count / scan / scatter in three launches ordered by the stream)
+//   moe_route_fused_kernel, moe_route_grouped_fused_kernel   decode (T <= 64): either router and the one-workgroup sort in ONE launch of one workgroup -- the routers'
+//                             own code (moe_topk_*_rows.inc) and the sort's (moe_sort_workgroup) with one barrier between them, the sort keys handed over in LDS
 // All are plain wave64 code: no LDS in the first, 16 KiB of wave-private rows in the second (touched only when n_group > 1), 33 KiB of LDS counters in the third.
 #pragma once
 #include "common.hip.h"
@@ -43,85 +45,11 @@ struct MoeTopkParams {
 // there, before anything is struck out.  Lane k keeps round k's pick and writes slot k.  No LDS, no barrier, no workspace.
 template <typename T, int R, bool LOADV>
 __global__ __launch_bounds__(256) void moe_topk_softmax_kernel(const MoeTopkParams p) {
-  constexpr int VEC = 16 / (int)sizeof(T);
-  static_assert(R % VEC == 0, "whole vectors per lane");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t e = (uint32_t)p.e;
-  auto column = [lane](int r) { return (uint32_t)(((r / VEC) * 64 + lane) * VEC + r % VEC); };
-  for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < p.t; t += (int64_t)gridDim.x * 4) {
-    const T* row = (const T*)p.logits + t * p.e;
-    uint32_t key[R];
-    if constexpr (!LOADV) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const uint32_t j = column(r);
-        uint32_t bits = 0;
-        if (j < e) {
-          if constexpr (sizeof(T) == 2) bits = (uint32_t)((const uint16_t*)row)[j] << 16;
-          else bits = ((const uint32_t*)row)[j];
-        }
-        key[r] = j < e ? route_key(bits) : 0u;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < R / VEC; ++c) {
-        const uint32_t j0 = column(c * VEC);
-        v4i raw = {0, 0, 0, 0};
-        if (j0 < e) raw = *(const v4i*)(row + j0);   // E % VEC == 0: a vector is all inside the row or all outside
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-          uint32_t bits;
-          if constexpr (sizeof(T) == 2) bits = (i & 1) ? ((uint32_t)raw[i / 2] & 0xffff0000u) : ((uint32_t)raw[i / 2] << 16);
-          else bits = (uint32_t)raw[i];
-          key[c * VEC + i] = j0 < e ? route_key(bits) : 0u;
-        }
-      }
-    }
-    float m = 0.f, denom = 1.f, my_x = 0.f;
-    uint32_t my_id = 0;
-    for (int k = 0; k < p.topk; ++k) {
-      uint32_t hi = key[0];
-      int br = 0;
-#pragma unroll
-      for (int r = 1; r < R; ++r) {   // strictly greater: the lane's lowest column wins a tie
-        const bool g = key[r] > hi;
-        hi = g ? key[r] : hi;
-        br = g ? r : br;
-      }
-      uint32_t lo = 0;
-#pragma unroll
-      for (int r = 0; r < R; ++r) lo = br == r ? ~column(r) : lo;
-      lo = hi ? lo : 0u;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {   // max of (hi, lo): the largest key, then the smallest column
-        const uint32_t oh = (uint32_t)__shfl_xor((int)hi, off), ol = (uint32_t)__shfl_xor((int)lo, off);
-        const bool g = oh > hi || (oh == hi && ol > lo);
-        hi = g ? oh : hi;
-        lo = g ? ol : lo;
-      }
-      const uint32_t win = ~lo;   // (topk <= E: a candidate is always left, so win < E)
-      const float x = route_key_value(hi);
-      if (k == 0) {
-        m = x;
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < R; ++r) s += key[r] ? expf(route_key_value(key[r]) - m) : 0.f;
-        denom = wave_sum(s);
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r) key[r] = column(r) == win ? 0u : key[r];
-      if (lane == k) {
-        my_id = win;
-        my_x = x;
-      }
-    }
-    float w = lane < p.topk ? expf(my_x - m) / denom : 0.f;
-    if (p.renorm) w = w / wave_sum(w);
-    if (lane < p.topk) {
-      p.weights[t * p.topk + lane] = w;
-      p.ids[t * p.topk + lane] = (int32_t)my_id;
-    }
-  }
+#define MOE_ROWS_WAVES 4
+#define MOE_ROWS_EMIT(slot, id)
+#include "moe_topk_softmax_rows.inc"
+#undef MOE_ROWS_WAVES
+#undef MOE_ROWS_EMIT
 }
 
 // ---- grouped top-k ----------------------------------------------------------------------------------------------------------------------------------------
@@ -156,187 +84,12 @@ struct MoeGroupedParams {
 template <typename T, int R, bool LOADV>
 __global__ __launch_bounds__(256) void moe_topk_grouped_kernel(const MoeGroupedParams p) {
 #pragma clang fp contract(off)
-  constexpr int VEC = 16 / (int)sizeof(T);
-  static_assert(R % VEC == 0 && R % 4 == 0, "whole vectors per lane");
   __shared__ __attribute__((aligned(16))) float crow[4][1024];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t e = (uint32_t)p.e;
-  auto column = [lane](int r) { return (uint32_t)(((r / VEC) * 64 + lane) * VEC + r % VEC); };
-  const bool has_bias = p.bias != nullptr, grouped = p.n_group > 1;
-  float bias[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) bias[r] = has_bias && column(r) < e ? p.bias[column(r)] : 0.f;
-  // the group stage's lane roles: L lanes per group
-  const int L = 1 << p.lg_l, my_g = lane >> p.lg_l, sub = lane & (L - 1);
-  const bool g_active = my_g < p.n_group;
-  const int steps = (p.s + L - 1) >> p.lg_l;                     // walk steps (the last one may be past the group's end for some lanes)
-  const int rot = (p.s & 31) == 0 ? my_g % steps : 0;            // s % 32 == 0: s % L == 0 too, every lane has exactly `steps` elements
-
-  for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < p.t; t += (int64_t)gridDim.x * 4) {
-    const T* row = (const T*)p.logits + t * p.e;
-    float s[R];   // the logit, then the score
-    if constexpr (!LOADV) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const uint32_t j = column(r);
-        uint32_t bits = 0;
-        if (j < e) {
-          if constexpr (sizeof(T) == 2) bits = (uint32_t)((const uint16_t*)row)[j] << 16;
-          else bits = ((const uint32_t*)row)[j];
-        }
-        s[r] = __uint_as_float(bits);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < R / VEC; ++c) {
-        const uint32_t j0 = column(c * VEC);
-        v4i raw = {0, 0, 0, 0};
-        if (j0 < e) raw = *(const v4i*)(row + j0);   // E % VEC == 0: a vector is all inside the row or all outside
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-          uint32_t bits;
-          if constexpr (sizeof(T) == 2) bits = (i & 1) ? ((uint32_t)raw[i / 2] & 0xffff0000u) : ((uint32_t)raw[i / 2] << 16);
-          else bits = (uint32_t)raw[i];
-          s[c * VEC + i] = __uint_as_float(bits);
-        }
-      }
-    }
-    // scores
-    if (p.sigmoid) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) s[r] = 1.f / (1.f + expf(-s[r]));
-    } else {
-      float m = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < R; ++r) m = column(r) < e ? fmaxf(m, s[r]) : m;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) m = fmaxf(m, __shfl_xor(m, off));
-      float sum = 0.f;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        s[r] = column(r) < e ? expf(s[r] - m) : 0.f;
-        sum += s[r];
-      }
-      const float denom = wave_sum(sum);
-#pragma unroll
-      for (int r = 0; r < R; ++r) s[r] = s[r] / denom;
-    }
-    if (p.scores) {
-      float* out = p.scores + t * p.e;
-      if constexpr (LOADV) {   // the host takes this path only when the scores' rows start on 16-byte boundaries too
-#pragma unroll
-        for (int q4 = 0; q4 < R / 4; ++q4) {
-          const uint32_t j0 = column(q4 * 4);
-          if (j0 < e) *(v4f*)(out + j0) = v4f{s[q4 * 4], s[q4 * 4 + 1], s[q4 * 4 + 2], s[q4 * 4 + 3]};
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-          if (column(r) < e) out[column(r)] = s[r];
-      }
-    }
-    // choice values and their keys
-    uint32_t key[R];
-    if (!grouped) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) key[r] = column(r) < e ? route_key(__float_as_uint(has_bias ? s[r] + bias[r] : s[r])) : 0u;
-    } else {
-      float* mine = crow[wave];
-#pragma unroll
-      for (int q4 = 0; q4 < R / 4; ++q4) {
-        float c[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = q4 * 4 + i;
-          c[i] = has_bias ? s[r] + bias[r] : s[r];
-          key[r] = column(r) < e ? route_key(__float_as_uint(c[i])) : 0u;
-        }
-        *(v4f*)(mine + column(q4 * 4)) = v4f{c[0], c[1], c[2], c[3]};   // column(R - 1) < R * 64 <= 1024: columns past E land in the row's unused tail
-      }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      uint32_t k1 = 0, k2 = 0;   // the group's two largest keys so far (0 = none)
-      if (g_active) {
-        const float* grp = mine + my_g * p.s;
-        int i = rot;
-        for (int n = 0; n < steps; ++n) {
-          const int idx = sub + (i << p.lg_l);
-          if (idx < p.s) {
-            const uint32_t k = route_key(__float_as_uint(grp[idx]));
-            k2 = k > k1 ? k1 : (k > k2 ? k : k2);
-            k1 = k > k1 ? k : k1;
-          }
-          i = i + 1 == steps ? 0 : i + 1;
-        }
-      }
-      for (int off = 1; off < L; off <<= 1) {   // merge the top two of the L lanes of a group (lanes of one group differ in their low lg_l bits only)
-        const uint32_t o1 = (uint32_t)__shfl_xor((int)k1, off), o2 = (uint32_t)__shfl_xor((int)k2, off);
-        const uint32_t lo1 = k1 < o1 ? k1 : o1, hi2 = k2 > o2 ? k2 : o2;
-        k1 = k1 > o1 ? k1 : o1;
-        k2 = lo1 > hi2 ? lo1 : hi2;
-      }
-      uint32_t gk = k1;   // without a bias: the group's largest c
-      if (has_bias && k2 != 0u) gk = route_key(__float_as_uint(route_key_value(k1) + route_key_value(k2)));   // (a group of one expert scores that one value)
-      int rank = 0;
-      for (int g = 0; g < p.n_group; ++g) {
-        const uint32_t og = (uint32_t)__builtin_amdgcn_readlane((int)gk, g << p.lg_l);
-        rank += (og > gk || (og == gk && g < my_g)) ? 1 : 0;
-      }
-      const unsigned long long alive = __ballot(g_active && sub == 0 && rank < p.topk_group);   // bit (g << lg_l): group g survives
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const uint32_t g = (column(r) * p.magic) >> 22;   // column(r) < 1024; a column past E has key 0 already, whatever g says
-        key[r] = ((alive >> ((g << p.lg_l) & 63u)) & 1ull) ? key[r] : 0u;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the walk's reads are done before the next token's row is written
-      __builtin_amdgcn_wave_barrier();
-    }
-    // selection: topk rounds of (key descending, column ascending); lane k keeps round k's pick and its UNBIASED score
-    float my_s = 0.f;
-    uint32_t my_id = 0;
-    for (int k = 0; k < p.topk; ++k) {
-      uint32_t hi = key[0];
-      int br = 0;
-#pragma unroll
-      for (int r = 1; r < R; ++r) {   // strictly greater: the lane's lowest column wins a tie
-        const bool g = key[r] > hi;
-        hi = g ? key[r] : hi;
-        br = g ? r : br;
-      }
-      uint32_t lo = 0;
-#pragma unroll
-      for (int r = 0; r < R; ++r) lo = br == r ? ~column(r) : lo;
-      lo = hi ? lo : 0u;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t oh = (uint32_t)__shfl_xor((int)hi, off), ol = (uint32_t)__shfl_xor((int)lo, off);
-        const bool g = oh > hi || (oh == hi && ol > lo);
-        hi = g ? oh : hi;
-        lo = g ? ol : lo;
-      }
-      const uint32_t win = ~lo;   // (topk <= topk_group * s: a candidate is always left, so win < E)
-      float ws = 0.f;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const bool hit = column(r) == win;
-        ws = hit ? s[r] : ws;
-        key[r] = hit ? 0u : key[r];
-      }
-      const int owner = __builtin_amdgcn_readfirstlane((int)((win / VEC) & 63u));   // the lane that holds column `win` (every lane has the same win)
-      ws = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ws), owner));
-      if (lane == k) {
-        my_id = win;
-        my_s = ws;
-      }
-    }
-    float w = lane < p.topk ? my_s : 0.f;
-    if (p.renorm) w = w / wave_sum(w);
-    w = w * p.scale;
-    if (lane < p.topk) {
-      p.weights[t * p.topk + lane] = w;
-      p.ids[t * p.topk + lane] = (int32_t)my_id;
-    }
-  }
+#define MOE_ROWS_WAVES 4
+#define MOE_ROWS_EMIT(slot, id)
+#include "moe_topk_grouped_rows.inc"
+#undef MOE_ROWS_WAVES
+#undef MOE_ROWS_EMIT
 }
 
 // The launch of either router: a pure function of the shape, the CU count and whether the entry found its pointers 16-byte aligned (with a row length of whole vectors: 16-byte loads
@@ -370,11 +123,13 @@ struct MoeSortParams {
   int g, e, topk, nbits, rows;
 };
 
-template <typename IdT>
-__device__ __forceinline__ int moe_sort_key(const MoeSortParams& p, int64_t slot) {
-  long long id = (long long)((const IdT*)p.ids)[slot];
+__device__ __forceinline__ int moe_sort_key_of(const MoeSortParams& p, long long id) {
   if (p.map) id = (id >= 0 && id < p.g) ? (long long)p.map[id] : -1ll;   // an id outside [0, g) is dropped without reading the map
   return (id >= 0 && id < p.e) ? (int)id : p.e;
+}
+template <typename IdT>
+__device__ __forceinline__ int moe_sort_key(const MoeSortParams& p, int64_t slot) {
+  return moe_sort_key_of(p, (long long)((const IdT*)p.ids)[slot]);
 }
 
 // the lanes of the wave that are active and hold this lane's key
@@ -404,10 +159,11 @@ __device__ __forceinline__ uint32_t moe_sort_block_scan(uint32_t v, uint32_t* ws
   return base + inc - v;
 }
 
-template <typename IdT, int MODE>
-__global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_kernel(const MoeSortParams p) {
-  __shared__ uint32_t cnt[MOE_SORT_W * MOE_SORT_MAXK];
-  __shared__ uint32_t wsum[MOE_SORT_W];
+// One workgroup's part of the sort in the given MODE over the counters cnt (MOE_SORT_W * MOE_SORT_MAXK words of LDS) and wsum (MOE_SORT_W words): the code both
+// moe_sort_kernel and the one-launch routing kernels run.  key_of(slot) is the slot's key in [0, E]: read from the ids (moe_sort_key), or from the LDS array the
+// router of the same workgroup has just filled.
+template <int MODE, typename KeyOf>
+__device__ __forceinline__ void moe_sort_workgroup(const MoeSortParams& p, uint32_t* cnt, uint32_t* wsum, KeyOf key_of) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nk = p.e + 1;
   const int64_t b0 = (int64_t)blockIdx.x * p.spb, b1 = b0 + p.spb < p.n ? b0 + p.spb : p.n;
@@ -423,7 +179,7 @@ __global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_kernel(const MoeSortPara
   for (int c = c_begin; c < c_end; ++c) {
     const int64_t slot = b0 + (int64_t)c * 64 + lane;
     const bool active = slot < b1;
-    const int key = active ? moe_sort_key<IdT>(p, slot) : 0;
+    const int key = active ? key_of(slot) : 0;
     const unsigned long long peers = moe_sort_peers(key, active, p.nbits);
     if (active && (peers & below) == 0) mine[key] += (uint32_t)__popcll(peers);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -467,7 +223,7 @@ __global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_kernel(const MoeSortPara
     for (int c = c_begin; c < c_end; ++c) {
       const int64_t slot = b0 + (int64_t)c * 64 + lane;
       const bool active = slot < b1;
-      const int key = active ? moe_sort_key<IdT>(p, slot) : 0;
+      const int key = active ? key_of(slot) : 0;
       const unsigned long long peers = moe_sort_peers(key, active, p.nbits);
       const uint32_t first = mine[key];
       if (active) {
@@ -480,6 +236,60 @@ __global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_kernel(const MoeSortPara
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
   }
+}
+
+template <typename IdT, int MODE>
+__global__ __launch_bounds__(MOE_SORT_NT) void moe_sort_kernel(const MoeSortParams p) {
+  __shared__ uint32_t cnt[MOE_SORT_W * MOE_SORT_MAXK];
+  __shared__ uint32_t wsum[MOE_SORT_W];
+  moe_sort_workgroup<MODE>(p, cnt, wsum, [&p](int64_t slot) { return moe_sort_key<IdT>(p, slot); });
+}
+
+// ---- one-launch routing for decode: router and sort in one workgroup --------------------------------------------------------------------------------------
+// T <= MOE_ROUTE_FUSED_MAX_T tokens, so at most 64 * 32 = 2048 slots: ONE workgroup of MOE_SORT_NT threads.
+//   phase 1  wave w routes tokens w, w + 8, ... with the router's own code (moe_topk_softmax_rows.inc / moe_topk_grouped_rows.inc, the text of the routers' kernels:
+//            same lane-to-column map, same R / LOADV, same order of every sum -- the weights and ids are the two-launch ops' bit for bit) and writes weights and ids
+//            to global memory as they do; the lane that writes a slot also leaves its sort key -- moe_sort_key's rule on the id it holds in a register -- in a
+//            16-bit LDS array
+//   barrier  one __syncthreads(); no global fence: phase 2 reads only LDS
+//   phase 2  moe_sort_workgroup<0> (count, scan, scatter, offs) with the key of a slot taken from that array
+// LDS: the sort's 32.8 KiB of counters, 4 KiB of keys, 32 bytes of wave sums.  The grouped router's eight 4 KiB rows are dead after the barrier, and the counters
+// are cleared behind it: they share the counters' memory (32 KiB of its 32.8).  sp.ids is not read; sp.spb >= sp.n, sp.rows = 1.
+constexpr int MOE_ROUTE_FUSED_MAX_T = 64, MOE_ROUTE_FUSED_MAX_SLOTS = MOE_ROUTE_FUSED_MAX_T * 32;
+static_assert(MOE_SORT_W * MOE_SORT_MAXK >= MOE_SORT_W * 1024, "the counters hold a router row per wave");
+
+template <typename T, int R, bool LOADV>
+__global__ __launch_bounds__(MOE_SORT_NT) void moe_route_fused_kernel(const MoeTopkParams p, const MoeSortParams sp) {
+  __shared__ uint32_t cnt[MOE_SORT_W * MOE_SORT_MAXK];
+  __shared__ uint32_t wsum[MOE_SORT_W];
+  __shared__ uint16_t keys[MOE_ROUTE_FUSED_MAX_SLOTS];
+  {
+#define MOE_ROWS_WAVES MOE_SORT_W
+#define MOE_ROWS_EMIT(slot, id) keys[slot] = (uint16_t)moe_sort_key_of(sp, (long long)(id))
+#include "moe_topk_softmax_rows.inc"
+#undef MOE_ROWS_WAVES
+#undef MOE_ROWS_EMIT
+  }
+  __syncthreads();
+  moe_sort_workgroup<0>(sp, cnt, wsum, [&](int64_t slot) { return (int)keys[slot]; });
+}
+
+template <typename T, int R, bool LOADV>
+__global__ __launch_bounds__(MOE_SORT_NT) void moe_route_grouped_fused_kernel(const MoeGroupedParams p, const MoeSortParams sp) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) uint32_t cnt[MOE_SORT_W * MOE_SORT_MAXK];
+  __shared__ uint32_t wsum[MOE_SORT_W];
+  __shared__ uint16_t keys[MOE_ROUTE_FUSED_MAX_SLOTS];
+  {
+    float (*crow)[1024] = (float (*)[1024])cnt;   // phase 1: the counters' memory holds a 4 KiB row of choice values per wave
+#define MOE_ROWS_WAVES MOE_SORT_W
+#define MOE_ROWS_EMIT(slot, id) keys[slot] = (uint16_t)moe_sort_key_of(sp, (long long)(id))
+#include "moe_topk_grouped_rows.inc"
+#undef MOE_ROWS_WAVES
+#undef MOE_ROWS_EMIT
+  }
+  __syncthreads();
+  moe_sort_workgroup<0>(sp, cnt, wsum, [&](int64_t slot) { return (int)keys[slot]; });
 }
 
 // One workgroup: ws[r][k] (the count of key k in workgroup r's slots) -> the number of slots with key k in the workgroups before r; row `rows` gets every key's
@@ -537,5 +347,19 @@ inline MoeSortLaunch moe_sort_plan(int64_t n, int64_t num_experts, int64_t one_l
   const int64_t spb = cdiv(std::max<int64_t>(4096, cdiv(n, 256)), 512) * 512;
   return {3, spb, (int)cdiv(n, spb), (std::min<int64_t>(256, cdiv(n, 4096)) + 1) * (num_experts + 1) * 4};
 }
+
+// The launch of either one-launch routing kernel: the router's own R and load path (moe_topk_plan -- neither depends on the grid), one workgroup of the sort's size.
+inline MoeTopkLaunch moe_route_fused_plan(int elem_bytes, int64_t e, int64_t t, bool rows_16B_aligned) {
+  const MoeTopkLaunch l = moe_topk_plan(elem_bytes, e, t, rows_16B_aligned, 1);
+  return {l.R, l.loadv, 1, MOE_SORT_NT};
+}
+// Up to this many tokens the torch ops moe_route_fused / moe_route_grouped_fused take the one-launch kernels; beyond they run the router and the sort as two launches
+// (the C entries always run the one launch, up to MOE_ROUTE_FUSED_MAX_T).  The bound is measured (profiles/bench_moe_route_fused_mi355x.txt):
+// replayed graphs, one launch against moe_route / moe_route_grouped, T = 1 .. 8 (one token per wave): Mixtral-8x7B 5.3-5.8 against 8.3-8.6 us, gpt-oss-120b 6.7-7.3
+// against 9.5-9.9, Qwen3-30B-A3B 8.6-9.6 against 11.4-12.0, DeepSeek-V3 10.6-12.2 against 13.4-13.8, Kimi-K2 9.9-11.4 against 12.4-13.2 -- 1.6 to 3.3 us less, many
+// times either side's spread.  At T = 16 a wave routes two tokens in a row and the one launch has lost for four of the five (10.8 against 10.1 us .. 19.8 against
+// 14.1; Mixtral still 8.0 against 8.7), at 64 it takes 23-64 us against 9-15.  8 is the largest T of the sweep at which one launch is faster for every router.
+// The ops allocate their results without a fill, so up to the bound the op IS the one launch (op_us = fused_us in the file) and beyond it the two bare entries.
+constexpr int64_t MOE_ROUTE_FUSED_TOKENS = 8;
 
 }  // namespace qamd

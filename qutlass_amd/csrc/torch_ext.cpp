@@ -662,6 +662,66 @@ void moeSort_(const Tensor& topk_ids, const Tensor& expert_map, int64_t num_expe
                                 workspace.numel() > 0 ? workspace.data_ptr() : nullptr, nbytes(workspace), current_stream(topk_ids)));
 }
 
+// moe_route_fused / moe_route_grouped_fused: FUNCTIONAL ops -- the five results of the routing (weights, ids, src_row, offs, pos) are allocated here, as the grouped
+// GEMMs allocate theirs.  Up to qutlass_amd_moe_route_fused_max_tokens() tokens: the one-launch entry; beyond: the router's entry and qutlass_amd_moe_sort with its
+// scratch -- the same bits either way.  No fill: T > 0 is one graph node up to the bound (two, three or four beyond).  grouped: the arguments behind topk are read, else ignored.
+using Routed = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor>;
+Routed moe_route_fused_impl(const char* op, bool grouped, const Tensor& logits, const std::optional<Tensor>& bias, const std::optional<Tensor>& expert_map, int64_t topk,
+                            int64_t num_experts, int64_t n_group, int64_t topk_group, int64_t scoring, bool renormalize, double routed_scaling_factor) {
+  check_tensors(op, {{logits, "logits"}});
+  const bool f32 = has_dtype(logits, ScalarType::Float);
+  STD_TORCH_CHECK(f32 || has_dtype(logits, ScalarType::BFloat16), "logits must be bf16 or float32");
+  STD_TORCH_CHECK(logits.dim() == 2, "logits must be 2D (T, E)");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  STD_TORCH_CHECK(topk >= 1 && topk <= 32, "topk must be in [1, 32] (got ", topk, ")");
+  STD_TORCH_CHECK(num_experts >= 1 && num_experts <= 1024, "the number of experts must be in [1, 1024] (got ", num_experts, ")");
+  const Named lg{logits, "logits"};
+  const float* b = nullptr;
+  if (bias) {
+    check_tensors(op, {{*bias, "bias"}}, {}, true, &lg);
+    STD_TORCH_CHECK(grouped && has_dtype(*bias, ScalarType::Float) && bias->dim() == 1 && bias->size(0) == E, "bias must be a float32 tensor of (E,)");
+    b = static_cast<const float*>(bias->data_ptr());
+  }
+  const int32_t* map = nullptr;
+  int64_t G = 0;
+  if (expert_map) {
+    check_tensors(op, {{*expert_map, "expert_map"}}, {}, true, &lg);
+    STD_TORCH_CHECK(has_dtype(*expert_map, ScalarType::Int) && expert_map->dim() == 1 && expert_map->size(0) >= 1, "expert_map must be a 1D int32 tensor of at least one entry");
+    map = static_cast<const int32_t*>(expert_map->data_ptr());
+    G = expert_map->size(0);
+  }
+  Tensor weights = torch::stable::new_empty(logits, {T, topk}, ScalarType::Float), ids = torch::stable::new_empty(logits, {T, topk}, ScalarType::Int);
+  Tensor src_row = torch::stable::new_empty(logits, {T * topk}, ScalarType::Int);
+  // offs: every sort form writes all of it whenever there is a slot (one workgroup: moe_sort_workgroup<0>; three launches: moe_sort_scan_kernel), so no fill is
+  // launched; only T == 0, which launches nothing, needs the zeros.  (T is a concrete size in here: no branch is traced.)
+  Tensor offs = T > 0 ? torch::stable::new_empty(logits, {num_experts}, ScalarType::Int) : torch::stable::new_zeros(logits, {num_experts}, ScalarType::Int);
+  Tensor pos = torch::stable::new_empty(logits, {T, topk}, ScalarType::Int);
+  const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
+  void* s = current_stream(logits);
+  float* w = static_cast<float*>(weights.data_ptr());
+  int32_t *id = static_cast<int32_t*>(ids.data_ptr()), *sr = static_cast<int32_t*>(src_row.data_ptr()), *of = static_cast<int32_t*>(offs.data_ptr()),
+          *ps = static_cast<int32_t*>(pos.data_ptr());
+  const int eb = f32 ? 4 : 2, rn = renormalize ? 1 : 0;
+  if (T <= qutlass_amd_moe_route_fused_max_tokens()) {
+    check_rc(grouped ? qutlass_amd_moe_route_grouped_fused(logits.data_ptr(), eb, T, E, topk, n_group, topk_group, (int)scoring, b, rn, (float)routed_scaling_factor, w, id,
+                                                           num_experts, map, G, sr, of, ps, s)
+                     : qutlass_amd_moe_route_fused(logits.data_ptr(), eb, T, E, topk, rn, w, id, num_experts, map, G, sr, of, ps, s));
+  } else {
+    check_rc(grouped ? qutlass_amd_moe_topk_grouped(logits.data_ptr(), eb, T, E, topk, n_group, topk_group, (int)scoring, b, rn, (float)routed_scaling_factor, w, id, nullptr, s)
+                     : qutlass_amd_moe_topk_softmax(logits.data_ptr(), eb, T, E, topk, rn, w, id, s));
+    const Workspace ws(logits, qutlass_amd_moe_sort_workspace_bytes(T * topk, num_experts));
+    check_rc(qutlass_amd_moe_sort(id, 4, T, topk, num_experts, map, G, sr, of, ps, ws.ptr(), ws.bytes, s));
+  }
+  return Routed(weights, ids, src_row, offs, pos);
+}
+Routed moe_route_fused(const Tensor& logits, std::optional<Tensor> expert_map, int64_t topk, int64_t num_experts, bool renormalize) {
+  return moe_route_fused_impl("moe_route_fused", false, logits, std::nullopt, expert_map, topk, num_experts, 1, 1, 0, renormalize, 1.0);
+}
+Routed moe_route_grouped_fused(const Tensor& logits, std::optional<Tensor> bias, std::optional<Tensor> expert_map, int64_t topk, int64_t num_experts, int64_t n_group,
+                               int64_t topk_group, int64_t scoring, bool renormalize, double routed_scaling_factor) {
+  return moe_route_fused_impl("moe_route_grouped_fused", true, logits, bias, expert_map, topk, num_experts, n_group, topk_group, scoring, renormalize, routed_scaling_factor);
+}
+
 // ---- EXTENSION: rotate + quantize + MXFP4 GEMM in one launch for decode batches (M <= 32) ---------------------------------------
 Tensor fusedQuantizeMatmulMxf4(const Tensor& X, const Tensor& R, const Tensor& B, const Tensor& B_sf, const Tensor& alpha, int64_t method) {
   const char* op = "fusedQuantizeMatmulMxf4";
@@ -812,6 +872,9 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("moeTopkGrouped_(Tensor logits, Tensor bias, Tensor(a!) weights, Tensor(b!) ids, Tensor(c!) scores, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor) -> ()");
   m.def("moeSort_(Tensor topk_ids, Tensor expert_map, int num_experts, Tensor(a!) src_row, Tensor(b!) offs, Tensor(c!) pos, Tensor(d!) workspace) -> ()");
   m.def("fusedQuantizeMatmulMxf4(Tensor X, Tensor R, Tensor B, Tensor B_sf, Tensor alpha, int method) -> Tensor");
+  // the one-launch routing for decode: functional ops that allocate their five results (weights, ids, src_row, offs, pos); inference ops: in the minimal library too
+  m.def("moe_route_fused(Tensor logits, Tensor? expert_map, int topk, int num_experts, bool renormalize) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("moe_route_grouped_fused(Tensor logits, Tensor? bias, Tensor? expert_map, int topk, int num_experts, int n_group, int topk_group, int scoring, bool renormalize, float routed_scaling_factor) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // W4A8, inference op: in the minimal library too
@@ -874,6 +937,14 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("grouped_matmul_mxf8", TORCH_BOX(&grouped_matmul_mxf8));
   m.impl("grouped_matmul_mxf8_mxf4", TORCH_BOX(&grouped_matmul_mxf8_mxf4));
   m.impl("grouped_matmul_nvf4", TORCH_BOX(&grouped_matmul_nvf4));
+}
+
+// The functional routing ops are registered for no particular device, like the functional ops of qutlass_amd/ops.py (CompositeExplicitAutograd: one kernel whatever
+// the tensors' device; their own check_tensors turns a CPU tensor away with the message every op here gives).  The CUDA key stays the list of the ops that fill or
+// allocate one result each, which tests/test_gpu_ext_rejections.py walks.
+STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CompositeExplicitAutograd, m) {
+  m.impl("moe_route_fused", TORCH_BOX(&moe_route_fused));
+  m.impl("moe_route_grouped_fused", TORCH_BOX(&moe_route_grouped_fused));
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module

@@ -95,6 +95,19 @@ def _register_fakes() -> None:
     for name in ("grouped_matmul_mxf4", "grouped_matmul_mxf8", "grouped_matmul_nvf4", "grouped_matmul_mxf8_mxf4"):
         rf(f"qutlass_amd::{name}")(grouped_tn)
 
+    def routed(logits, topk, num_experts):   # the one-launch routing ops allocate their five results, like the grouped GEMMs: weights, ids, src_row, offs, pos
+        T, i32 = logits.size(0), torch.int32
+        return (logits.new_empty((T, topk), dtype=torch.float32), logits.new_empty((T, topk), dtype=i32), logits.new_empty((T * topk,), dtype=i32),
+                logits.new_empty((num_experts,), dtype=i32), logits.new_empty((T, topk), dtype=i32))
+
+    @rf("qutlass_amd::moe_route_fused")
+    def _(logits, expert_map, topk, num_experts, renormalize):
+        return routed(logits, topk, num_experts)
+
+    @rf("qutlass_amd::moe_route_grouped_fused")
+    def _(logits, bias, expert_map, topk, num_experts, n_group, topk_group, scoring, renormalize, routed_scaling_factor):
+        return routed(logits, topk, num_experts)
+
 
 def _define_functional_ops() -> None:
     """FUNCTIONAL forms of the output-filling ops (`qutlass_amd::quantize_mx` ...: allocate, call the in-place twin, return fresh tensors), defined in Python with
