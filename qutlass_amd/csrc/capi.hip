@@ -201,7 +201,8 @@ inline int deepp_grid(int tiles) {
 
 // persistent deep schedule (gemm_mx_deepp.hip.h): one workgroup per CU walks the tiles; 136 KiB of static LDS
 // ONEFORM: MFMA shape of the one-tile form (grid == tile count, even stage count): 0 = the product's choice (kDeeppOneTile16, gemm_mx_deepp16.hip.h); 32 / 16 force
-// v_mfma_scale_f32_32x32x64 / _16x16x128 (lab: "gemm_variant" 190 / 191, so that both can be timed in one process and small grids reach either)
+// v_mfma_scale_f32_32x32x64 / _16x16x128 (lab: "gemm_variant" 190 / 191, so that both can be timed in one process and small grids reach either); 160 + KL forces the
+// 16x16x128 form with the K loop KL (gemm_mx_deepp16.hip.h KL_ bits; lab: 192 ... 197), 16 is the one the product runs (kDeepp16KLoop)
 template <class C, bool TRACE = false, int ST_AUX = 0, int LAB = 0, int ONEFORM = 0>
 int launch_gemm_deepp(GemmParams p, hipStream_t s) {
   p.tiles_m = (int)cdiv(p.M, C::BM);
@@ -230,9 +231,10 @@ int launch_gemm_deepp(GemmParams p, hipStream_t s) {
   if (odd && one) hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX, true, true>), dim3(grid), dim3(C::THREADS), 0, s, p);
   else if (odd) hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX, true, false>), dim3(grid), dim3(C::THREADS), 0, s, p);
   else if (one) {
-    static_assert(ONEFORM == 0 || ONEFORM == 16 || ONEFORM == 32, "one-tile form");
+    static_assert(ONEFORM == 0 || ONEFORM == 16 || ONEFORM == 32 || (ONEFORM >= 160 && ONEFORM < 168), "one-tile form");
     static_assert(ONEFORM == 0 || QAMD_BENCH, "forced one-tile forms: lab build only");
-    if constexpr (ONEFORM == 16 || (ONEFORM == 0 && kDeeppOneTile16)) hipLaunchKernelGGL((gemm_mx_deepp16_kernel<C, ST_AUX>), dim3(grid), dim3(C::THREADS), 0, s, p);
+    if constexpr (ONEFORM >= 160) hipLaunchKernelGGL((gemm_mx_deepp16_kernel<C, ST_AUX, ONEFORM - 160>), dim3(grid), dim3(C::THREADS), 0, s, p);
+    else if constexpr (ONEFORM == 16 || (ONEFORM == 0 && kDeeppOneTile16)) hipLaunchKernelGGL((gemm_mx_deepp16_kernel<C, ST_AUX>), dim3(grid), dim3(C::THREADS), 0, s, p);
     else hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX, false, true>), dim3(grid), dim3(C::THREADS), 0, s, p);
   }
   else hipLaunchKernelGGL((gemm_mx_deepp_kernel<C, ST_AUX>), dim3(grid), dim3(C::THREADS), 0, s, p);
@@ -778,6 +780,13 @@ int dispatch_lab_variant(int v, const GemmParams& p, hipStream_t s, const char* 
     // 90 with the one-tile form forced (grid == tile count and an even stage count; any other launch runs as 90): 190 = 32x32x64 MFMAs, 191 = 16x16x128 (gemm_mx_deepp16.hip.h)
     if (v == 190) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 32>(p, s);
     if (v == 191) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 16>(p, s);
+    // 191 with the K loop's form forced (gemm_mx_deepp16.hip.h): 192 = the loop before the KL_ forms existed, 193 = KL_SCALES, 194 = KL_DMA, 195 = both, 196 = both + KL_SPREAD, 197 = KL_DMA + KL_SPREAD
+    if (v == 192) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 160>(p, s);
+    if (v == 193) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 160 + KL_SCALES>(p, s);
+    if (v == 194) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 160 + KL_DMA>(p, s);
+    if (v == 195) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 160 + (KL_SCALES | KL_DMA)>(p, s);
+    if (v == 196) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 160 + (KL_SCALES | KL_DMA | KL_SPREAD)>(p, s);
+    if (v == 197) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 17, 0, 160 + (KL_DMA | KL_SPREAD)>(p, s);
     if (v == 91) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, true, 17>(p, s);   //   + phase timestamps of workgroup 0 (qutlass_amd_debug_set_trace_buffer)
     if (v == 92) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 2>(p, s);       //   output stores nt
     if (v == 93) return launch_gemm_deepp<GemmCfg<256, 256, 2, 2, 4, false>, false, 16>(p, s);      //   sc1
