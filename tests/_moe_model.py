@@ -9,7 +9,11 @@ MATHEMATICS instead of with another sequence of this library's ops (tests/test_g
                       a second quantize and GEMM, and moe_combine's definition (an fp32 multiply and add per slot, then bf16).
 The expert weights are quantized HERE by the oracle, as w @ h over the input dimension with the activations' h, and a test uploads their bytes: how a deployment gets
 its weights -- a transposition common to the device quantizers cannot cancel itself out.  The keyword arguments of layer_quantized build deliberately WRONG layers
-(the mutation checks of tests/test_moe_model_cpu.py): the distance a convention error moves the result, in units of the quantization noise |L_q - L_fp64|."""
+(the mutation checks of tests/test_moe_model_cpu.py): the distance a convention error moves the result, in units of the quantization noise |L_q - L_fp64|.
+
+Four more layers -- MXFP8 with SiLU, gpt-oss (clamped SwiGLU, per-expert biases, interleaved gate/up) on MXFP4 and as W4A8 from checkpoint bytes, and the latter over two
+expert-parallel ranks -- live in tests/_moe_model_more.py, with formulas and wrong variants of their own; make_layer, quantize_weights, layer_fp64 and layer_quantized
+here take their names and layers and hand them on."""
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -55,7 +59,9 @@ def _nv_scales():
     return s[np.random.default_rng(5).permutation(4 * E)].reshape(4, E)
 
 
-def make_layer(name: str) -> Layer:
+def make_layer(name: str):
+    if name in MORE_LAYERS:
+        return _more.make_layer(name)
     fmt, method, rot, router, seed = LAYERS[name]
     rng = np.random.default_rng(seed)
     import torch
@@ -135,9 +141,11 @@ def _dequant(layer: Layer, codes, sf):
     return oracle.dequant_fp4(codes, sf, 16 if nv else 32, nv).reshape(rows, -1)
 
 
-def quantize_weights(layer: Layer, acc_model: int = 1):
+def quantize_weights(layer, acc_model: int = 1, **wrong):
     """-> w13q (E, 2 I, H / 2), w13s (E, 2 I, H / group), w2q (E, H, I / 2), w2s (E, H, I / group): every expert's weight rotated as w @ h with the layer's h over its
     input dimension and quantized (NV: under its own global scale) by the oracle"""
+    if isinstance(layer, _more.Layer2):
+        return _more.quantize_weights(layer, acc_model, **wrong)
     out = []
     for w, gs in ((layer.w13, layer.w13_gs), (layer.w2, layer.w2_gs)):
         qs = [_quantize(layer, w[e], layer.h, None if gs is None else gs[e], acc_model) for e in range(E)]
@@ -147,12 +155,19 @@ def quantize_weights(layer: Layer, acc_model: int = 1):
 
 def _gemm(layer: Layer, a_dq, wq, ws, alpha):
     """bf16(fp32(a_dq @ dequant(w)^T) * alpha) as bf16 bits: the block-scaled GEMMs' contract (oracle.gemm_blockscaled: exact sum, one fp32 multiply, bf16 RNE)"""
-    acc = (a_dq @ _dequant(layer, wq, ws).T).astype(np.float32) * np.float32(alpha)
+    return _gemm_dq(a_dq, _dequant(layer, wq, ws), alpha)
+
+
+def _gemm_dq(a_dq, w_dq, alpha):
+    """the same contract on dequantized operands (rows, K) and (N, K) in fp64, whatever their formats"""
+    acc = (a_dq @ w_dq.T).astype(np.float32) * np.float32(alpha)
     return _f64_to_bf16(acc.astype(np.float64))
 
 
 # ---- the two models --------------------------------------------------------------------------------------------------------------------------------------------------
-def layer_fp64(layer: Layer, ids, weights) -> np.ndarray:
+def layer_fp64(layer, ids, weights, **rank) -> np.ndarray:
+    if isinstance(layer, _more.Layer2):
+        return _more.layer_fp64(layer, ids, weights, **rank)
     x = _bf16_to_f64(layer.tok)
     out = np.zeros((T, H))
     for t in range(T):
@@ -164,11 +179,15 @@ def layer_fp64(layer: Layer, ids, weights) -> np.ndarray:
     return out
 
 
-def layer_quantized(layer: Layer, ids, weights, wq, acc_model: int = 1, ha=None, swap_weights: bool = False, swap_gate_up: bool = False,
-                    neighbour_a2: bool = False) -> np.ndarray:
+def layer_quantized(layer, ids, weights, wq, acc_model: int = 1, ha=None, swap_weights: bool = False, swap_gate_up: bool = False,
+                    neighbour_a2: bool = False, **more) -> np.ndarray:
     """The layer as the device chain defines it, (T, H) fp64 holding bf16 values.  wq = quantize_weights(layer).  The wrong variants: ha -- the activations' rotation
     (default layer.h; pass its transpose); swap_weights -- the two routing weights of every token exchanged; swap_gate_up -- the halves of the (rows, 2 I) GEMM
-    output exchanged before the activation; neighbour_a2 -- the second quantizer takes the next expert's a2 global scale while alpha2 stays (NV only)."""
+    output exchanged before the activation; neighbour_a2 -- the second quantizer takes the next expert's a2 global scale while alpha2 stays (NV only).
+    The layers of tests/_moe_model_more.py have flags of their own (**more: see its layer_quantized)."""
+    if isinstance(layer, _more.Layer2):
+        return _more.layer_quantized(layer, ids, weights, wq, acc_model, ha=ha, swap_weights=swap_weights, swap_gate_up=swap_gate_up, **more)
+    assert not more, more
     ha = layer.h if ha is None else np.ascontiguousarray(ha)
     w13q, w13s, w2q, w2s = wq
     y = np.zeros((T, TOPK, H))   # the down projection's rows, by slot
@@ -194,3 +213,8 @@ def layer_quantized(layer: Layer, ids, weights, wq, acc_model: int = 1, ha=None,
 
 def fro(a) -> float:
     return float(np.sqrt((np.asarray(a, dtype=np.float64) ** 2).sum()))
+
+
+# ---- the MXFP8, gpt-oss and W4A8 layers: tests/_moe_model_more.py, reached through make_layer / quantize_weights / layer_fp64 / layer_quantized above ------------------
+MORE_LAYERS = ("mxf8_silu", "oai_mx", "oai_w4a8", "oai_w4a8_ep")
+import _moe_model_more as _more  # noqa: E402  (it imports this module: at the end, where everything it uses is defined)
