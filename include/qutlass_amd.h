@@ -216,6 +216,26 @@ int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, c
                                                  int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
 
 /*
+ * EXTENSION (no counterpart in the reference): grouped W4A16 GEMM for mixture-of-experts layers -- bf16 tokens, unquantised and
+ * without scales, against MXFP4 expert weights as they are stored (gpt-oss checkpoints, fusedQuantizeMx's output), one launch over
+ * E experts.  A: (M, K) bf16 tokens sorted by expert.  B, B_sf, alpha, offs, D, the clamping of the offsets and the rows that are
+ * not written: as qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn.
+ * D[r, n] = bf16(alpha[g] * sum_k A[r, k] * w[g, n, k]), w = e2m1(code) * 2^(B_sf - 127) held as bf16 (exact whenever it is 0 or
+ * 2^-126 <= |w| <= bf16's largest finite value: every code under scale bytes 2 ... 252).  The products are exact in fp32, the
+ * sums are fp32, one fp32 multiply by alpha, one rounding to bf16.  Scale byte 255 gives NaN in every output of that weight row
+ * for the rows of that expert; bytes 0, 1, 253, 254 are outside the exact contract (byte 0 reads as w = 0, byte 1 gives bf16
+ * subnormals, 253 / 254 may overflow to inf).  NaN and inf in A propagate as in fp64 arithmetic.
+ * src_row (may be NULL): device int32[M].  With it A is the UNSORTED (T, K) tokens and row r of D reads A[src_row[r]] -- the
+ * gather of the routed tokens in the GEMM; T * K * 2 must stay below 2 GiB, an index outside [0, T) reads an all-zero token and
+ * never addresses outside A.  T is ignored when src_row is NULL.
+ * K % 128 == 0, N % 8 == 0, 1 <= E <= 1024, M * 2K and N * K/2 (one expert) below 2 GiB; the stack may exceed 2 GiB.
+ * M == 0 returns QAMD_OK without a launch.  Wave-owned 32x32 / 32x16 / 64x32 tiles only, as for W4A8.
+ */
+int qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn(const void* A, const void* B, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                                 const int32_t* offs, const int32_t* src_row, int64_t T, void* D,
+                                                 int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
+
+/*
  * EXTENSION (no counterpart in the reference): grouped NVFP4 GEMM for mixture-of-experts layers, one launch over E experts.
  * A: (M, K/2) packed e2m1 tokens sorted by expert, A_sf: ROW-MAJOR (M, K/16) e4m3 (the quantizer's buffer as it is, no to_blocked).
  * B: (E, N, K/2) stacked expert weights, B_sf: row-major (E, N, K/16).  alpha: device fp32[n_alpha], n_alpha = 1 (shared)

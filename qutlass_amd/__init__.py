@@ -10,6 +10,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
     grouped_matmul_mxf8_mxf4_bf16_tn, matmul_mxf8_mxf4_bf16_tn  (extension: W4A8 -- MXFP8 tokens against MXFP4 expert weights as stored; the dense form is E = 1)
+    grouped_matmul_bf16_mxf4_bf16_tn, matmul_bf16_mxf4_bf16_tn  (extension: W4A16 -- bf16 tokens against the same weights, optionally gathered by src_row in the GEMM)
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
     fusedGatherQuantizeNvGrouped, fusedSiluMulQuantizeNvGrouped  (extension: the two NVFP4 quantizers of the MoE chain with one global scale per expert)
@@ -157,6 +158,58 @@ def matmul_mxf8_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tenso
     _check_w4a8_operands("matmul_mxf8_mxf4_bf16_tn", a, b, a_sf, b_sf, 2)
     offs = torch.full((1,), a.size(0), dtype=torch.int32, device=a.device)
     return _ops_amd.grouped_matmul_mxf8_mxf4(a, b.unsqueeze(0), a_sf, b_sf, alpha, offs)
+
+
+def _check_w4a16_operands(op: str, a: torch.Tensor, b: torch.Tensor, b_sf: torch.Tensor, b_dim: int, src_row: torch.Tensor | None = None) -> None:
+    """the rejections of the W4A16 ops that need no device: raised before the op is dispatched (shapes and dtypes only, so tracing goes through them)"""
+    if a.dtype != torch.bfloat16:
+        raise ValueError(f"{op}: a must be bfloat16 (got {a.dtype}; quantized tokens go to grouped_matmul_mxf8_mxf4_bf16_tn / grouped_matmul_mxf4_bf16_tn)")
+    if b.dtype not in (torch.uint8, torch.float4_e2m1fn_x2):
+        raise ValueError(f"{op}: b must be uint8 or float4_e2m1fn_x2 packed e2m1 (got {b.dtype})")
+    if a.dim() != 2 or b.dim() != b_dim:
+        raise ValueError(f"{op}: a must be 2D ({'T' if src_row is not None else 'M'}, K) and b {b_dim}D ({'E, ' if b_dim == 3 else ''}N, K/2)")
+    if a.size(1) != 2 * b.size(-1):
+        raise ValueError(f"{op}: inner dimensions must match, a is (.., K = {a.size(1)}) and b (.., K/2 = {b.size(-1)})")
+    if b_sf.dtype != torch.float8_e8m0fnu:
+        raise ValueError(f"{op}: b_sf must be float8_e8m0fnu (got {b_sf.dtype})")
+    need = b.numel() // max(b.size(-1), 1) * (a.size(1) // 32)
+    if b_sf.numel() < need:
+        raise ValueError(f"{op}: b_sf has {b_sf.numel()} elements, the row-major scale layout needs {need}")
+    if src_row is not None and (src_row.dtype != torch.int32 or src_row.dim() != 1):
+        raise ValueError(f"{op}: src_row must be a 1D int32 tensor (got {src_row.dtype}, {src_row.dim()}D)")
+
+
+def grouped_matmul_bf16_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor, *,
+                                     src_row: torch.Tensor | None = None) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): grouped W4A16 GEMM for mixture-of-experts layers -- bf16 tokens, unquantized, against MXFP4 expert weights as a
+    checkpoint stores them (gpt-oss; every weight fusedQuantizeMx writes), one launch over all experts.  No quantizer runs in front of it.
+
+    a        (M, K) bfloat16 -- the tokens, sorted by expert; with src_row: the UNSORTED (T, K) tokens
+    b        (E, N, K/2) uint8 / float4_e2m1fn_x2 -- the stacked expert weights: what grouped_matmul_mxf4_bf16_tn reads
+    b_sf     float8_e8m0fnu, >= E*N*K/32 elements, read as row-major (E, N, K/32)
+    alpha    float32, 1 element (shared) or E elements (per expert)
+    offs     int32 (E,): the cumulative END rows of the groups (torch._grouped_mm's convention) -- group g is rows [offs[g-1], offs[g]), offs[-1] := 0
+    src_row  optional int32 (M,): sorted row r reads a[src_row[r]] (moe_sort's / moe_route's src_row as it is) -- the gather of the routed tokens happens in
+             the GEMM's own loads; an index outside [0, T) reads an all-zero token; T * K * 2 bytes below 2 GiB
+
+    Returns out (M, N) bf16 with out[r, n] = bf16(alpha[g] * sum_k x[r, k] * w[g, n, k]), w = e2m1(code) * 2^(b_sf - 127) held as bf16: exact products, fp32
+    sums, one fp32 multiply by alpha, one rounding.  w is exact under scale bytes 2 ... 252; byte 255 gives NaN in every output of that weight row for the rows
+    of that expert; bytes 0, 1, 253, 254 are outside the exact contract (underflow / overflow to inf).  NaN and inf in the tokens propagate.  Empty groups are
+    allowed; rows at or past offs[E-1] are not written; the offsets are read on the device (graph capture, torch.compile), each clamped to [0, M], a decreasing
+    one is an empty group.  K % 128 == 0, N % 8 == 0, 1 <= E <= 1024; the token matrix and one expert's weight below 2 GiB.  M == 0 returns an empty output.
+
+    Wave-owned 32x32 / 32x16 / 64x32 tiles only, as grouped_matmul_mxf8_mxf4_bf16_tn (README, DESIGN.md section 8 for where it loses)."""
+    _check_w4a16_operands("grouped_matmul_bf16_mxf4_bf16_tn", a, b, b_sf, 3, src_row)
+    return _ops_amd.grouped_matmul_bf16_mxf4_bf16_tn(a, b, b_sf, alpha, offs, src_row)
+
+
+def matmul_bf16_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): the dense form of grouped_matmul_bf16_mxf4_bf16_tn -- a (M, K) bfloat16 against ONE MXFP4 weight b (N, K/2)
+    uint8 / float4_e2m1fn_x2 with flat row-major e8m0 scales (N, K/32), alpha float32 with one element.  Returns (M, N) bf16.  The grouped op with E = 1: its offs
+    is a one-element device tensor filled with M, so there is no host sync and no kernel of its own."""
+    _check_w4a16_operands("matmul_bf16_mxf4_bf16_tn", a, b, b_sf, 2)
+    offs = torch.full((1,), a.size(0), dtype=torch.int32, device=a.device)
+    return _ops_amd.grouped_matmul_bf16_mxf4_bf16_tn(a, b.unsqueeze(0), b_sf, alpha, offs, None)
 
 
 def grouped_matmul_nvf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,

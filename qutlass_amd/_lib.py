@@ -25,6 +25,7 @@ SYMBOLS = {
     "qutlass_amd_grouped_matmul_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_mxf8_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     "qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_nvf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_matmul_mxf8_bf16_tn": (_i32, _GEMM_ARGS),
     "qutlass_amd_matmul_mxf8_bf16_nn": (_i32, _GEMM_ARGS[:-1] + [_vp, _i64, _vp]),

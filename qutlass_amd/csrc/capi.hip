@@ -23,6 +23,7 @@
 #include "gemm_mx_ks.hip.h"
 #include "gemm_mx_os.hip.h"
 #include "gemm_mx_os_w4a8.hip.h"
+#include "gemm_mx_os_w4a16.hip.h"
 #include "gemm_mx_fusedq.hip.h"
 #include "gemm_nvf4.hip.h"
 #include "gemm_nvf4_pk.hip.h"
@@ -494,6 +495,53 @@ int launch_grouped_w4a8(int v, const GroupedParams& q, hipStream_t s)
 ;
 #endif
 
+// ---- grouped W4A16 GEMM (gemm_mx_os_w4a16.hip.h): bf16 tokens against MXFP4 expert weights ---------------------------------------------------------------------------
+// Forms: 606 = 32x32 tiles of the bf16-token wave-owned kernel, 607 = 32x16, 608 = 64x32 (one shot while a tile's K extent fits the LDS, wave-owned rings beyond).  No
+// 64x64 ring form, as for W4A8.
+// Measured on the decode and prefill shapes of Qwen3-30B-A3B, Mixtral-8x7B and gpt-oss-20b / 120b and on a sweep of 16 ... 128 rows per expert at K = 512 ... 2944
+// (profiles/calib_grouped_w4a16.txt, taken under the provisional rule -- W4A8's structure with the K threshold at 1024): 607 never leads.  At 16 rows per expert and
+// below 606 leads at every K (K = 768: 139.6 us against 154.8 for 608; K = 2944: 248.6 against 290.0).  From 32 rows per expert on 608 leads at every K from 768
+// (K = 768: 32 rows 168.8 against 199.5, 128 rows 394.9 against 556.0 -- the provisional rule's miss, Qwen3 down prefill 698.4 against 1020.3; K = 2944, 128 rows:
+// 831.4 against 1078.3): it converts each weight fragment once for two m-tiles.  At K = 512 the two are level (32 rows 75.0 for 606 against 82.7; 48 rows 96.5
+// against 91.0; 128 rows 203.7 against 189.1): left with 606.  So: mean rows per group M / E >= 32 and K > 512 -> 608, otherwise 606.  N and the CU count are
+// arguments so that a rule re-taken from more measurements can use them.
+inline int grouped_w4a16_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M >= 32 * E && K > 512) ? 608 : 606;
+}
+// form GRP_BF16_MXF4.form0 + I: the one-shot ladder up to 4 SMAX stages, wave-owned rings of SMAX slots beyond -- 3 slots per wave for the 32-row tiles (one shot up to
+// K = 1536), 2 for the 64-row tile (K = 1024); GATHER: A rows through q.src_row
+template <int I, bool GATHER>
+int launch_grouped_w4a16_os(W4A16Params q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_BF16_MXF4;
+  constexpr int TM = F.tile[I].tm, TN = F.tile[I].tn, SMAX = os_w4a16_smax(TM);
+  static_assert(SMAX == 2 || SMAX == 3, "the ladder below");
+  q.tiles_m = 1;
+  q.tiles_n = (int)cdiv(q.N, TN);
+  const int64_t KT = q.K / 128;
+  const dim3 grid((int)grouped_workgroups(q.M, q.N, q.E, TM, TN)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_w4a16_kernel<OsW4A16Cfg<1, TN, TM>, false, GATHER>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_w4a16_kernel<OsW4A16Cfg<2, TN, TM>, false, GATHER>), grid, block, 0, s, q);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_w4a16_kernel<OsW4A16Cfg<SMAX, TN, TM>, false, GATHER>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_w4a16_kernel<OsW4A16Cfg<SMAX, TN, TM>, true, GATHER>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  return check_launch("gemm_mx_os_w4a16_kernel");
+}
+// form v of the W4A16 op; its kernels ride in the persistent NVFP4 kernel's unit beside W4A8's, still the shortest of the parallel build
+int launch_grouped_w4a16(int v, const W4A16Params& q, hipStream_t s)
+#if QAMD_DEF(8)
+{
+  constexpr const GroupedFormat& F = GRP_BF16_MXF4;
+  static_assert(F.nforms == 3 && F.ebits == 16 && F.ebits_b == 4, "the three wave-owned forms of the bf16-token kernel");
+  const bool gather = q.src_row != nullptr;
+  if (v == F.form0) return gather ? launch_grouped_w4a16_os<0, true>(q, s) : launch_grouped_w4a16_os<0, false>(q, s);
+  if (v == F.form0 + 1) return gather ? launch_grouped_w4a16_os<1, true>(q, s) : launch_grouped_w4a16_os<1, false>(q, s);
+  if (v == F.form0 + 2) return gather ? launch_grouped_w4a16_os<2, true>(q, s) : launch_grouped_w4a16_os<2, false>(q, s);
+  return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+}
+#else
+;
+#endif
+
 // ---- what the grouped entries share: the argument checks, the choice of a form and the parameter fill ----------------------------------------------------------
 // the grouped ops' argument checks, F the format (gemm_mx_grouped.hip.h): every argument is checked before any HIP call; the grid bound covers every form
 inline int grouped_check(const GroupedFormat& F, const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
@@ -504,7 +552,7 @@ inline int grouped_check(const GroupedFormat& F, const char* name, const void* A
   if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
   if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
   if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  const char* rowa = F.row_bytes(K) == K ? "K" : "K/2";
+  const char* rowa = F.row_bytes(K) == 2 * K ? "2K" : F.row_bytes(K) == K ? "K" : "K/2";
   const char* rowb = F.row_bytes_b(K) == K ? "K" : "K/2";
   const int64_t rows_2g = ((1ll << 31) - 1) / F.row_bytes(K) + 1;   // rows of a row's bytes that reach 2 GiB (no product that can overflow)
   const int64_t rows_2g_b = ((1ll << 31) - 1) / F.row_bytes_b(K) + 1;
@@ -1725,6 +1773,24 @@ int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, c
   return launch_grouped_w4a8(grouped_form(F, grouped_w4a8_plan, M, N, K, E), q, (hipStream_t)stream);
 }
 
+// W4A16: A (M, K) bf16 without scales; src_row (M,) int32 or null -- with it A is the unsorted (T, K) tokens and sorted row r reads A[src_row[r]]
+int qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn(const void* A, const void* B, const void* B_sf, const float* alpha, int64_t n_alpha, const int32_t* offs,
+                                                 const int32_t* src_row, int64_t T, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_BF16_MXF4;
+  if (int rc = grouped_check(F, F.name, A, B, /* no A scales */ A, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if (src_row) {   // the descriptor spans all of A: T rows of 2 K bytes
+    if (T < 0) return fail(QAMD_ERR_INVALID, "%s: T must be >= 0 (got %lld)", F.name, (long long)T);
+    if (T >= ((1ll << 31) - 1) / F.row_bytes(K) + 1) return fail(QAMD_ERR_INVALID, "%s: the gathered token matrix (T * 2K bytes, T=%lld K=%lld) must stay below 2 GiB", F.name, (long long)T, (long long)K);
+  }
+  if (M == 0) return QAMD_OK;
+  W4A16Params q;
+  grouped_fill(q, F, A, B, nullptr, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
+  q.sfa_bytes = 0;
+  grouped_mx_defaults(q);
+  q.src_row = src_row; q.T = src_row ? (int)T : 0;
+  return launch_grouped_w4a16(grouped_form(F, grouped_w4a16_plan, M, N, K, E), q, (hipStream_t)stream);
+}
+
 // ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
 // Forms: 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles, 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.
 // Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B and on token counts between them (profiles/calib_grouped_nvf4_r7.txt; these are not the MX
@@ -2680,6 +2746,10 @@ int qutlass_amd_debug_grouped_mxf8_plan(int64_t M, int64_t N, int64_t K, int64_t
 // grouped_matmul_mxf8_mxf4_bf16_tn: 602 = 32x32, 604 = 64x32 tiles of the mixed-width wave-owned kernel
 int qutlass_amd_debug_grouped_mxf8_mxf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
   return debug_grouped_plan(GRP_MXF8_MXF4, "debug_grouped_mxf8_mxf4_plan", grouped_w4a8_plan, M, N, K, E, out);
+}
+// grouped_matmul_bf16_mxf4_bf16_tn: 606 = 32x32, 608 = 64x32 tiles of the bf16-token wave-owned kernel
+int qutlass_amd_debug_grouped_bf16_mxf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  return debug_grouped_plan(GRP_BF16_MXF4, "debug_grouped_bf16_mxf4_plan", grouped_w4a16_plan, M, N, K, E, out);
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel
 int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {

@@ -46,14 +46,16 @@ struct GroupedFormat {
   int nforms = 4;     // forms the op has (tile[0 .. nforms))
   int ebits_b = 0;    // bits per element of B where they differ from A's (0: ebits)
   constexpr bool has(int form) const { return form >= form0 && form < form0 + nforms; }
-  constexpr int64_t row_bytes(int64_t K) const { return K / (8 / ebits); }                             // of an A row
-  constexpr int64_t row_bytes_b(int64_t K) const { return K / (8 / (ebits_b ? ebits_b : ebits)); }     // of a B row
+  constexpr int64_t row_bytes(int64_t K) const { return K / 8 * ebits; }                              // of an A row (K % 8 == 0; ebits may exceed 8, and K * ebits may not overflow)
+  constexpr int64_t row_bytes_b(int64_t K) const { return K / 8 * (ebits_b ? ebits_b : ebits); }      // of a B row
 };
 constexpr GroupedFormat GRP_MXF4{"grouped_matmul_mxf4_bf16_tn", 590, 4, 32, {{32, 32}, {32, 16}, {64, 32}, {64, 64}}};
 constexpr GroupedFormat GRP_MXF8{"grouped_matmul_mxf8_bf16_tn", 594, 8, 32, {{32, 32}, {32, 16}, {64, 32}, {64, 64}}};
 constexpr GroupedFormat GRP_NVF4{"grouped_matmul_nvf4_bf16_tn", 598, 4, 16, {{32, 32}, {64, 32}, {64, 64}, {128, 128}}};
 // W4A8: e4m3 tokens against e2m1 weights (gemm_mx_os_w4a8.hip.h) -- the three wave-owned forms, no ring form
 constexpr GroupedFormat GRP_MXF8_MXF4{"grouped_matmul_mxf8_mxf4_bf16_tn", 602, 8, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
+// W4A16: bf16 tokens WITHOUT scales against e2m1 weights (gemm_mx_os_w4a16.hip.h) -- the three wave-owned forms, no ring form; sgroup is the weights'
+constexpr GroupedFormat GRP_BF16_MXF4{"grouped_matmul_bf16_mxf4_bf16_tn", 606, 16, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
 // workgroups of a grouped launch: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles (grouped_tile: the rest return at once)
 constexpr int64_t grouped_workgroups(int64_t M, int64_t N, int64_t E, int TM, int TN) { return ((M + TM - 1) / TM + E) * ((N + TN - 1) / TN); }
 
@@ -189,13 +191,13 @@ struct GroupedView {
   const uint8_t* SFB;
   const float* alpha;
 };
-// workgroup -> the grouped parts of its tile's view, false: no work (EBITS: element width, 4 = MXFP4, 8 = MXFP8)
+// workgroup -> the grouped parts of its tile's view, false: no work (EBITS: element width of A, 4 = MXFP4, 8 = MXFP8, 16 = bf16)
 template <int TM, int TN, int EBITS = 4>
 __device__ __forceinline__ bool grouped_setup(const GroupedParams& pk, GroupedView& v) {
   GroupTile t;
   if (!grouped_tile(pk.offs, pk.E, pk.M, TM, pk.tiles_n, (int)blockIdx.x, t)) return false;
   const int g = uniform(t.g), gend = uniform(t.row0 + t.rows);
-  const uint32_t rowbytes = EBITS == 8 ? (uint32_t)pk.K : (uint32_t)pk.K >> 1, KB = (uint32_t)pk.K >> 5;
+  const uint32_t rowbytes = EBITS == 16 ? (uint32_t)pk.K << 1 : EBITS == 8 ? (uint32_t)pk.K : (uint32_t)pk.K >> 1, KB = (uint32_t)pk.K >> 5;
   v.M = gend;                                      // stores masked to the group's rows ...
   v.a_bytes = (uint32_t)gend * rowbytes;           // ... and reads past them return zeros
   v.sfa_bytes = (uint32_t)gend * KB;

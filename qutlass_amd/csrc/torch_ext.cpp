@@ -240,6 +240,41 @@ Tensor grouped_matmul_nvf4(const Tensor& A, const Tensor& B, const Tensor& A_sf,
 Tensor grouped_matmul_mxf8(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF8>(A, B, A_sf, B_sf, alpha, offs); }
 Tensor grouped_matmul_mxf8_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF8_MXF4>(A, B, A_sf, B_sf, alpha, offs); }
 
+// EXTENSION: grouped W4A16 GEMM (qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn) -- A (M, K) bf16 tokens sorted by expert and WITHOUT scales, or with src_row (M,) int32 the
+// unsorted (T, K) tokens (row r of the output reads A[src_row[r]]); B (E, N, K/2) packed e2m1 and B_sf row-major (E, N, K/32) e8m0 as grouped_matmul_mxf4's; alpha, offs as
+// there.  Allocates (M, N) bf16; rows at or past offs[E-1] are not written.
+Tensor grouped_matmul_bf16_mxf4(const Tensor& A, const Tensor& B, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs, std::optional<Tensor> src_row) {
+  const char* op = "grouped_matmul_bf16_mxf4_bf16_tn";
+  check_tensors(op, {{A, "A"}, {B, "B"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  STD_TORCH_CHECK(has_dtype(A, ScalarType::BFloat16), op, ": A must be bfloat16");
+  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), op, ": B must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e8m0fnu), "B_sf must be float8_e8m0fnu");
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, "A must be 2D (M, K) and B 3D (E, N, K/2)");
+  STD_TORCH_CHECK(A.size(1) == B.size(2) * 2, "Inner dimensions must match for A @ B[g].T");
+  const int64_t E = B.size(0), N = B.size(1), K = A.size(1), kb = K / 32;
+  int64_t M = A.size(0), T = 0;
+  const int32_t* src = nullptr;
+  if (src_row) {
+    const Named a{A, "A"};
+    check_tensors(op, {{*src_row, "src_row"}}, {}, true, &a);
+    STD_TORCH_CHECK(has_dtype(*src_row, ScalarType::Int) && src_row->dim() == 1, "src_row must be a 1D int32 tensor");
+    T = A.size(0);
+    M = src_row->size(0);
+    src = static_cast<const int32_t*>(src_row->data_ptr());
+  }
+  STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
+  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
+  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
+  STD_TORCH_CHECK(B_sf.numel() >= E * N * kb, "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * kb);
+  Tensor out = torch::stable::new_empty(A, {M, N}, ScalarType::BFloat16);
+  if (M == 0 || N == 0) return out;   // empty batch: nothing to launch
+
+  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
+  check_rc(qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()), alpha.numel(),
+                                                        static_cast<const int32_t*>(offs.data_ptr()), src, T, out.data_ptr(), M, N, K, E, current_stream(A)));
+  return out;
+}
+
 Tensor matmul_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_ada_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::ADA_MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_nvf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::NVF4>(A, B, A_sf, B_sf, alpha); }
@@ -878,6 +913,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // W4A8, inference op: in the minimal library too
+  m.def("grouped_matmul_bf16_mxf4_bf16_tn(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, Tensor? src_row) -> Tensor");   // W4A16, inference op: in the minimal library too
   m.def("grouped_matmul_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
 }
 
@@ -939,12 +975,13 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("grouped_matmul_nvf4", TORCH_BOX(&grouped_matmul_nvf4));
 }
 
-// The functional routing ops are registered for no particular device, like the functional ops of qutlass_amd/ops.py (CompositeExplicitAutograd: one kernel whatever
+// The functional routing ops and the W4A16 grouped GEMM are registered for no particular device, like the functional ops of qutlass_amd/ops.py (CompositeExplicitAutograd: one kernel whatever
 // the tensors' device; their own check_tensors turns a CPU tensor away with the message every op here gives).  The CUDA key stays the list of the ops that fill or
 // allocate one result each, which tests/test_gpu_ext_rejections.py walks.
 STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CompositeExplicitAutograd, m) {
   m.impl("moe_route_fused", TORCH_BOX(&moe_route_fused));
   m.impl("moe_route_grouped_fused", TORCH_BOX(&moe_route_grouped_fused));
+  m.impl("grouped_matmul_bf16_mxf4_bf16_tn", TORCH_BOX(&grouped_matmul_bf16_mxf4));   // (an optional tensor, as theirs)
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module

@@ -95,6 +95,10 @@ def _register_fakes() -> None:
     for name in ("grouped_matmul_mxf4", "grouped_matmul_mxf8", "grouped_matmul_nvf4", "grouped_matmul_mxf8_mxf4"):
         rf(f"qutlass_amd::{name}")(grouped_tn)
 
+    @rf("qutlass_amd::grouped_matmul_bf16_mxf4_bf16_tn")
+    def _(A, B, B_sf, alpha, offs, src_row):   # A (M, K) bf16, or with src_row (M,) the unsorted (T, K) tokens; B (E, N, K/2)
+        return A.new_empty(((A if src_row is None else src_row).size(0), B.size(1)), dtype=torch.bfloat16)
+
     def routed(logits, topk, num_experts):   # the one-launch routing ops allocate their five results, like the grouped GEMMs: weights, ids, src_row, offs, pos
         T, i32 = logits.size(0), torch.int32
         return (logits.new_empty((T, topk), dtype=torch.float32), logits.new_empty((T, topk), dtype=i32), logits.new_empty((T * topk,), dtype=i32),
