@@ -216,6 +216,22 @@ int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, c
                                                  int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
 
 /*
+ * EXTENSION (no counterpart in the reference): grouped W4A6 GEMM for mixture-of-experts layers -- MXFP6 (e2m3) tokens against
+ * MXFP4 expert weights as they are stored, one launch over E experts: W4A8's accuracy class at 3/4 of its token bytes.
+ * A: (M, 3K/4) bytes of packed e2m3 codes, tokens sorted by expert (the MXFP6 operand format at the quantizers below), 16-byte
+ * aligned; A_sf: row-major (M, K/32) e8m0 (fusedQuantizeMxf6 / fusedGatherQuantizeMxf6 write both).  B, B_sf, alpha, offs, D, the
+ * clamping of the offsets and the rows that are not written: as qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn.
+ * D[r] = bf16(alpha[g] * sum_k a[r, k] b[g, n, k]): exact products, fp32 sums, one fp32 multiply by alpha, one rounding.  Scale
+ * bytes 0 ... 254 mean 2^(b - 127); byte 255 on either side makes that row's or column's outputs NaN (e2m3 has no NaN code: the
+ * quantizers mark a group that held a NaN or an infinity with scale byte 255).
+ * K % 128 == 0, N % 8 == 0, 1 <= E <= 1024, M * 3K/4 and N * K/2 (one expert) below 2 GiB; the stack may exceed 2 GiB.
+ * M == 0 returns QAMD_OK without a launch.  Wave-owned 32x32 / 32x16 / 64x32 tiles only, as for W4A8.
+ */
+int qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
+                                                 const float* alpha, int64_t n_alpha, const int32_t* offs, void* D,
+                                                 int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
+
+/*
  * EXTENSION (no counterpart in the reference): grouped W4A16 GEMM for mixture-of-experts layers -- bf16 tokens, unquantised and
  * without scales, against MXFP4 expert weights as they are stored (gpt-oss checkpoints, fusedQuantizeMx's output), one launch over
  * E experts.  A: (M, K) bf16 tokens sorted by expert.  B, B_sf, alpha, offs, D, the clamping of the offsets and the rows that are
@@ -438,6 +454,28 @@ int qutlass_amd_fused_quantize_mxf8_blocked(const void* x, const void* h, int ro
 int qutlass_amd_fused_silu_mul_quantize_mxf8(const void* x, const void* h, int rot, int64_t rows, int64_t inter, int fmt, int blocked, void* out_fp8,
                                              void* out_e8m0, void* stream);
 int qutlass_amd_fused_gather_quantize_mxf8(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, int fmt, void* out_fp8,
+                                           void* out_e8m0, void* stream);
+
+/*
+ * EXTENSION (no reference counterpart): the rotate + quantize family with 6-BIT codes -- the producers of the A operand of
+ * qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn: MXFP6, one e8m0 scale per 32 elements along the row, e2m3 codes.
+ *   The MXFP6 (e2m3) operand format: a row of K elements is 3K/4 bytes; element k occupies bits 6k ... 6k+5 of the row read as one little-endian bit string, so a
+ *   32-element scale block is the 24 bytes 24j ... 24j+23.  A code is sign (bit 5), 2 exponent bits (bias 1), 3 mantissa bits: magnitudes m/8 for exponent 0 and
+ *   (1 + m/8) 2^(e-1) otherwise, up to 7.5; no NaN, no infinity.  Scales are e8m0 bytes, row-major (flat).
+ *   y = x_g . h exactly as qutlass_amd_fused_quantize_mxf8 computes it; rot in {32, 64, 128}.  Then for every 32 consecutive y:
+ *       amax = max |y|  (NaNs ignored)          E = the biased exponent field of the FP32 amax
+ *       e8   = 255 if any of the 32 y is NaN or infinite -- all 32 codes are then 0, the NaN travels in the scale byte, which the GEMM honours;
+ *              127 if amax == 0; else clamp(E - 2, 0, 254)                                               -- the OCP MX rule: the scaled maximum lies in [4, 8)
+ *       q    = min(RNE(|y| * 2^(127 - e8)) on the e2m3 grid, 7.5) with the sign of y                     -- ties to the even code; (7.5, 8) saturates on purpose;
+ *              -0 and negative values that round to zero keep their sign
+ *   Abs-max only; no clip mask, no global scale, flat scales only (the first numel / 32 bytes of out_e8m0).  out_fp6: numel * 3 / 4 bytes.
+ * qutlass_amd_fused_gather_quantize_mxf6 = the plain entry on x[src_row] (an index outside [0, t) gives a zero row: codes 0, scale 127), byte for byte, with the
+ * siblings' limits: x below 2 GiB, numel < 2^31.
+ * Checks: each entry runs its MX sibling's chain in the sibling's order under the name fusedQuantizeMxf6 / fusedGatherQuantizeMxf6 (there is no method and no fmt to
+ * reject); all before any HIP call.
+ */
+int qutlass_amd_fused_quantize_mxf6(const void* x, const void* h, int rot, int64_t numel, void* out_fp6, void* out_e8m0, void* stream);
+int qutlass_amd_fused_gather_quantize_mxf6(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, void* out_fp6,
                                            void* out_e8m0, void* stream);
 
 /*

@@ -10,6 +10,8 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
     grouped_matmul_mxf8_mxf4_bf16_tn, matmul_mxf8_mxf4_bf16_tn  (extension: W4A8 -- MXFP8 tokens against MXFP4 expert weights as stored; the dense form is E = 1)
+    grouped_matmul_mxf6_mxf4_bf16_tn, matmul_mxf6_mxf4_bf16_tn  (extension: W4A6 -- MXFP6 (e2m3) tokens against the same weights: W4A8's accuracy class at 3/4 of its token bytes)
+    fusedQuantizeMxf6, fusedGatherQuantizeMxf6            (extension: the MXFP6 quantizers -- the A operand of the W4A6 GEMM)
     grouped_matmul_bf16_mxf4_bf16_tn, matmul_bf16_mxf4_bf16_tn  (extension: W4A16 -- bf16 tokens against the same weights, optionally gathered by src_row in the GEMM)
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
@@ -160,6 +162,54 @@ def matmul_mxf8_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tenso
     return _ops_amd.grouped_matmul_mxf8_mxf4(a, b.unsqueeze(0), a_sf, b_sf, alpha, offs)
 
 
+def _check_w4a6_operands(op: str, a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, b_dim: int) -> None:
+    """the rejections of the W4A6 ops that need no device, in the manner of _check_w4a8_operands"""
+    if a.dtype != torch.uint8:
+        raise ValueError(f"{op}: a must be uint8, packed e2m3 codes as fusedQuantizeMxf6 writes them (got {a.dtype})")
+    if b.dtype not in (torch.uint8, torch.float4_e2m1fn_x2):
+        raise ValueError(f"{op}: b must be uint8 or float4_e2m1fn_x2 packed e2m1 (got {b.dtype})")
+    if a.dim() != 2 or b.dim() != b_dim:
+        raise ValueError(f"{op}: a must be 2D (M, 3K/4) and b {b_dim}D ({'E, ' if b_dim == 3 else ''}N, K/2)")
+    if a.size(1) * 2 != 3 * b.size(-1):
+        raise ValueError(f"{op}: inner dimensions must match, a is (M, 3K/4 = {a.size(1)}) and b (.., K/2 = {b.size(-1)})")
+    k = 2 * b.size(-1)
+    for name, sf, rows in (("a_sf", a_sf, a.size(0)), ("b_sf", b_sf, b.numel() // max(b.size(-1), 1))):
+        if sf.dtype != torch.float8_e8m0fnu:
+            raise ValueError(f"{op}: {name} must be float8_e8m0fnu (got {sf.dtype})")
+        if sf.numel() < rows * (k // 32):
+            raise ValueError(f"{op}: {name} has {sf.numel()} elements, the row-major scale layout needs {rows * (k // 32)}")
+
+
+def grouped_matmul_mxf6_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,
+                                     alpha: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): grouped W4A6 GEMM for mixture-of-experts layers -- MXFP6 (e2m3) tokens against MXFP4 expert weights as a checkpoint
+    stores them, one launch over all experts.  e2m3 has e4m3's three mantissa bits and the block scale supplies the range it lacks: W4A8's accuracy class
+    (README) at 3/4 of its token bytes.
+
+    a      (M, 3K/4) uint8 -- the tokens, sorted by expert, as fusedQuantizeMxf6 / fusedGatherQuantizeMxf6 write them: element k of a row in bits 6k .. 6k+5 of the
+           row read as one little-endian bit string (a 32-element scale block is 24 bytes); a code is sign, 2 exponent bits (bias 1), 3 mantissa bits
+    b      (E, N, K/2) uint8 / float4_e2m1fn_x2 -- the stacked expert weights: what fusedQuantizeMx writes and grouped_matmul_mxf4_bf16_tn reads
+    a_sf   float8_e8m0fnu, >= M*K/32 elements, read as row-major (M, K/32): the quantizer's flat scale buffer as it is
+    b_sf   float8_e8m0fnu, >= E*N*K/32 elements, read as row-major (E, N, K/32)
+    alpha  float32, 1 element (shared) or E elements (per expert)
+    offs   int32 (E,): the cumulative END rows of the groups, as in grouped_matmul_mxf8_mxf4_bf16_tn
+
+    Returns out (M, N) bf16 = bf16(alpha[g] * sum a b): exact products, fp32 sums, one rounding.  Rows at or past offs[E-1] are not written; each offset is clamped
+    to [0, M] and a decreasing one is an empty group; the offsets are read on the device (graph capture, torch.compile).  Scale bytes 0 .. 254 mean 2^(b - 127);
+    byte 255 on either side makes that row's or column's outputs NaN (the quantizers mark a group that held a NaN or an infinity that way).  K % 128 == 0,
+    N % 8 == 0, 1 <= E <= 1024; the token matrix and one expert's weight below 2 GiB.  Wave-owned 32x32 / 32x16 / 64x32 tiles only, as for W4A8."""
+    _check_w4a6_operands("grouped_matmul_mxf6_mxf4_bf16_tn", a, b, a_sf, b_sf, 3)
+    return _ops_amd.grouped_matmul_mxf6_mxf4(a, b, a_sf, b_sf, alpha, offs)
+
+
+def matmul_mxf6_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): the dense form of grouped_matmul_mxf6_mxf4_bf16_tn -- a (M, 3K/4) uint8 packed e2m3 against ONE MXFP4 weight b
+    (N, K/2), flat row-major e8m0 scales, alpha float32 with one element.  The grouped op with E = 1, as matmul_mxf8_mxf4_bf16_tn is."""
+    _check_w4a6_operands("matmul_mxf6_mxf4_bf16_tn", a, b, a_sf, b_sf, 2)
+    offs = torch.full((1,), a.size(0), dtype=torch.int32, device=a.device)
+    return _ops_amd.grouped_matmul_mxf6_mxf4(a, b.unsqueeze(0), a_sf, b_sf, alpha, offs)
+
+
 def _check_w4a16_operands(op: str, a: torch.Tensor, b: torch.Tensor, b_sf: torch.Tensor, b_dim: int, src_row: torch.Tensor | None = None) -> None:
     """the rejections of the W4A16 ops that need no device: raised before the op is dispatched (shapes and dtypes only, so tracing goes through them)"""
     if a.dtype != torch.bfloat16:
@@ -262,11 +312,11 @@ def _method_code(method) -> int:
 
 
 def _quantize(op: str, *args):
-    """One op of the rotate + quantize family (a row of ops.QUANT_OPS), args as the functional op ``qutlass_amd::<op>`` takes them.  Eager: allocate, then the in-place
+    """One op of the rotate + quantize family (a row of ops.QUANT_OPS or ops.QUANT_OPS_MXF6), args as the functional op ``qutlass_amd::<op>`` takes them.  Eager: allocate, then the in-place
     twin; under torch.compile: the functional op (see ops.py)."""
     if torch.compiler.is_compiling():
         return getattr(_ops_amd, op)(*args)
-    return ops.run_quant(ops.QUANT_OPS[op], *args)
+    return ops.run_quant(ops.QUANT_OPS[op] if op in ops.QUANT_OPS else ops.QUANT_OPS_MXF6[op], *args)
 
 
 def _output(op: str, *args):
@@ -582,6 +632,22 @@ def fusedGatherQuantizeMxf8(x: torch.Tensor, h: torch.Tensor, src_row: torch.Ten
     [0, T) gives a zero row (codes 0, scale 127) and can neither fault nor read another row; the indices are read on the device (graph-capturable).  x below 2 GiB.
     Measured 1.2-2.4x faster than index_select + fusedQuantizeMxf8 at every shape taken."""
     return _quantize("gather_quantize_mxf8", x, h, src_row, ops.mxf8_dtype(dtype))
+
+
+def fusedQuantizeMxf6(a: torch.Tensor, h: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: rotate + quantize to MXFP6 -- e2m3 codes, four in three bytes, with one e8m0 scale per 32 elements: the A operand of
+    grouped_matmul_mxf6_mxf4_bf16_tn.  y = a_group @ h as in fusedQuantizeMxf8 (h: R x R bf16, R in {32, 64, 128}; the identity gives a plain quantizer), then per 32
+    consecutive y: e8 = 255 if any is NaN or infinite (all 32 codes 0 -- the format has no NaN code, the scale byte carries it), 127 if amax == 0, else
+    clamp(E - 2, 0, 254) with E the exponent field of the fp32 amax (the OCP MX rule: the scaled maximum lies in [4, 8)); q = min(RNE(|y| 2^(127 - e8)), 7.5) with
+    the sign of y, ties to the even code, (7.5, 8) saturating on purpose, -0 keeping its sign.  Returns uint8 codes (.., 3K/4) -- element k in bits 6k .. 6k+5 of
+    the row read little-endian -- and float8_e8m0fnu scales (padded_rows, padded_cols), written flat in the first numel / 32 bytes as fusedQuantizeMx's."""
+    return _quantize("quantize_mxf6", a, h)
+
+
+def fusedGatherQuantizeMxf6(x: torch.Tensor, h: torch.Tensor, src_row: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION: ``fusedQuantizeMxf6(x.index_select(0, src_row), h)`` in ONE launch, byte for byte -- the MXFP6 MoE dispatch.  x is (T, K) bf16, contiguous and
+    below 2 GiB, src_row (M,) int32 on the device, K % R == 0; codes (M, 3K/4), flat scales.  An index outside [0, T) gives a zero row: codes 0, scale byte 127."""
+    return _quantize("gather_quantize_mxf6", x, h, src_row)
 
 
 def fusedSiluMulQuantizeMxf8(x: torch.Tensor, h: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:

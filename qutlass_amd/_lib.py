@@ -25,6 +25,7 @@ SYMBOLS = {
     "qutlass_amd_grouped_matmul_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_mxf8_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     "qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_nvf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_matmul_mxf8_bf16_tn": (_i32, _GEMM_ARGS),
@@ -53,6 +54,8 @@ SYMBOLS = {
     "qutlass_amd_fused_quantize_mxf8_blocked": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
     "qutlass_amd_fused_silu_mul_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "qutlass_amd_fused_gather_quantize_mxf8": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "qutlass_amd_fused_quantize_mxf6": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
+    "qutlass_amd_fused_gather_quantize_mxf6": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "qutlass_amd_moe_combine_bf16": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "qutlass_amd_swiglu_oai_mul_bf16": (_i32, [_vp, _i64, _i64, _f32, _f32, _vp, _vp, _i64, _vp, _vp]),
     "qutlass_amd_fused_swiglu_oai_quantize_mx": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),

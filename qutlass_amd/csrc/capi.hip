@@ -24,6 +24,7 @@
 #include "gemm_mx_os.hip.h"
 #include "gemm_mx_os_w4a8.hip.h"
 #include "gemm_mx_os_w4a16.hip.h"
+#include "gemm_mx_os_w4a6.hip.h"
 #include "gemm_mx_fusedq.hip.h"
 #include "gemm_nvf4.hip.h"
 #include "gemm_nvf4_pk.hip.h"
@@ -542,6 +543,57 @@ int launch_grouped_w4a16(int v, const W4A16Params& q, hipStream_t s)
 ;
 #endif
 
+// ---- grouped W4A6 GEMM (gemm_mx_os_w4a6.hip.h): MXFP6 (e2m3) tokens against MXFP4 expert weights --------------------------------------------------------------------
+// Forms: 610 = 32x32 tiles of the 6-bit-token wave-owned kernel, 611 = 32x16, 612 = 64x32 (one shot while a tile's K extent fits the LDS, wave-owned rings beyond).  No
+// 64x64 ring form, as for W4A8.
+// Started from W4A8's rule with its K threshold rescaled by the stage size -- which leaves it at 1536: there 604 takes over where the 32-row tile's stages of a wave stop
+// fitting three slots (3 x 6.5 KiB x 4 waves = 78 KiB, two workgroups per CU); the 5.5 KiB stage keeps three slots up to the same K and a fourth would not let two
+// workgroups share a CU (4 x 5.5 x 4 = 88 KiB > 80).  Measured on the decode and prefill shapes of Qwen3-30B-A3B, Mixtral-8x7B and gpt-oss-20b / 120b and on a sweep of
+// 16 ... 128 rows per expert at K = 768 ... 3712 (profiles/calib_grouped_w4a6.txt, taken under that provisional rule): 611 never leads.  From K = 2048 on 612 leads from
+// 32 rows per expert (K = 2048: 32 rows 199.9 us against 246.8 for 610, 128 rows 517.6 against 710.4; K = 3712, 128 rows: 801.5 against 1110.2), 610 at 16 rows at every K
+// (K = 3712: 256.9 against 259.3; K = 768: 52.6 against 72.5).  At K = 1536 -- the 64-row tile runs three slots per wave, 102 KiB, one workgroup per CU -- 610 leads at
+// every row count (128 rows: 342.9 against 433.5).  Up to K = 1024 the 64-row tile runs at most two slots (68 KiB, two workgroups per CU) and 612 leads from 48 rows on
+// (K = 768: 48 rows 86.7 against 94.9, 128 rows 181.0 against 200.6; K = 1024: 48 rows 91.4 against 105.1; Qwen3 down prefill, K = 768, 256 rows: 313.7 against 358.5 --
+// the provisional rule's one miss), while at 32 rows 610 leads (K = 768: 73.6 against 79.5).  So: mean rows per group M / E >= 32 and K > 1536, or M / E >= 48 and
+// K <= 1024 -> 612; otherwise 610.  N and the CU count are arguments so that a rule re-taken from more measurements can use them.
+inline int grouped_w4a6_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return ((M >= 32 * E && K > 1536) || (M >= 48 * E && K <= 1024)) ? 612 : 610;
+}
+// form GRP_MXF6_MXF4.form0 + I: the one-shot ladder up to 4 SMAX stages, wave-owned rings of SMAX slots beyond -- 7 slots per wave for the 32-row tiles (one shot up to
+// K = 3584), 4 for the 64-row tile (K = 2048)
+template <int I>
+int launch_grouped_w4a6_os(GroupedParams q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_MXF6_MXF4;
+  constexpr int TM = F.tile[I].tm, TN = F.tile[I].tn, SMAX = os_w4a6_smax(TM);
+  static_assert(SMAX >= 4, "the ladder below");
+  q.tiles_m = 1;
+  q.tiles_n = (int)cdiv(q.N, TN);
+  const int64_t KT = q.K / 128;
+  const dim3 grid((int)grouped_workgroups(q.M, q.N, q.E, TM, TN)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_w4a6_kernel<OsW4A6Cfg<1, TN, TM>, false>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_w4a6_kernel<OsW4A6Cfg<2, TN, TM>, false>), grid, block, 0, s, q);
+  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_w4a6_kernel<OsW4A6Cfg<3, TN, TM>, false>), grid, block, 0, s, q);
+  else if (KT <= 16) hipLaunchKernelGGL((gemm_mx_os_w4a6_kernel<OsW4A6Cfg<4, TN, TM>, false>), grid, block, 0, s, q);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_w4a6_kernel<OsW4A6Cfg<SMAX, TN, TM>, false>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_w4a6_kernel<OsW4A6Cfg<SMAX, TN, TM>, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  return check_launch("gemm_mx_os_w4a6_kernel");
+}
+// form v of the W4A6 op; its kernels ride in the persistent NVFP4 kernel's unit beside W4A8's and W4A16's
+int launch_grouped_w4a6(int v, const GroupedParams& q, hipStream_t s)
+#if QAMD_DEF(8)
+{
+  constexpr const GroupedFormat& F = GRP_MXF6_MXF4;
+  static_assert(F.nforms == 3 && F.ebits == 6 && F.ebits_b == 4, "the three wave-owned forms of the 6-bit-token kernel");
+  if (v == F.form0) return launch_grouped_w4a6_os<0>(q, s);
+  if (v == F.form0 + 1) return launch_grouped_w4a6_os<1>(q, s);
+  if (v == F.form0 + 2) return launch_grouped_w4a6_os<2>(q, s);
+  return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+}
+#else
+;
+#endif
+
 // ---- what the grouped entries share: the argument checks, the choice of a form and the parameter fill ----------------------------------------------------------
 // the grouped ops' argument checks, F the format (gemm_mx_grouped.hip.h): every argument is checked before any HIP call; the grid bound covers every form
 inline int grouped_check(const GroupedFormat& F, const char* name, const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
@@ -552,7 +604,7 @@ inline int grouped_check(const GroupedFormat& F, const char* name, const void* A
   if (M < 0 || N <= 0) return fail(QAMD_ERR_INVALID, "%s: M must be >= 0 and N positive (got M=%lld N=%lld)", name, (long long)M, (long long)N);
   if (K < 128 || K % 128) return fail(QAMD_ERR_INVALID, "%s: K must be a positive multiple of 128 (got %lld)", name, (long long)K);
   if (N % 8) return fail(QAMD_ERR_INVALID, "%s: N must be a multiple of 8 (got %lld)", name, (long long)N);
-  const char* rowa = F.row_bytes(K) == 2 * K ? "2K" : F.row_bytes(K) == K ? "K" : "K/2";
+  const char* rowa = F.row_bytes(K) == 2 * K ? "2K" : F.row_bytes(K) == K ? "K" : F.ebits == 6 ? "3K/4" : "K/2";
   const char* rowb = F.row_bytes_b(K) == K ? "K" : "K/2";
   const int64_t rows_2g = ((1ll << 31) - 1) / F.row_bytes(K) + 1;   // rows of a row's bytes that reach 2 GiB (no product that can overflow)
   const int64_t rows_2g_b = ((1ll << 31) - 1) / F.row_bytes_b(K) + 1;
@@ -1400,12 +1452,20 @@ int debug_plan(const char* name, int64_t M, int64_t N, int64_t rowbytes, int gra
 // The _GSCALE kinds are the gated and the gathering quantizer with one global scale per expert (quantize.hip.h, GSCALE): NV abs-max with flat scales and nothing else.
 enum QuantKind { QK_PLAIN, QK_GATED, QK_GATHER, QK_GATED_GSCALE, QK_GATHER_GSCALE };
 
-// FMT: QF_E2M1, or QF_E4M3 / QF_E5M2 for the MXFP8 quantizers (MX abs-max; plain, gated or gathering) -- their own three __global__ wrappers.
+// FMT: QF_E2M1, or QF_E4M3 / QF_E5M2 for the MXFP8 quantizers (MX abs-max; plain, gated or gathering) -- their own three __global__ wrappers --, or QF_E2M3 for the
+// MXFP6 quantizers (plain or gathering, flat scales) -- their own two.
 template <int KIND, int R, bool NV, int METHOD, bool MASK, bool BLK, int FMT = QF_E2M1>
 int launch_quant(const QuantParams& p, hipStream_t s, int grid) {
   static_assert((KIND != QK_GATED_GSCALE && KIND != QK_GATHER_GSCALE) || (NV && METHOD == METHOD_ABSMAX && !MASK && !BLK), "per-expert global scales: NV abs-max, flat scales");
   static_assert(FMT == QF_E2M1 || (KIND == QK_PLAIN || KIND == QK_GATED || KIND == QK_GATHER), "MXFP8: plain, gated or gathering");
-  if constexpr (FMT != QF_E2M1 && KIND == QK_GATED) {
+  static_assert(FMT != QF_E2M3 || (!BLK && (KIND == QK_PLAIN || KIND == QK_GATHER)), "MXFP6: plain or gathering, flat scales");
+  if constexpr (FMT == QF_E2M3 && KIND == QK_GATHER) {
+    hipLaunchKernelGGL((fused_gather_quantize_mxf6_kernel<R>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_gather_quantize_mxf6_kernel");
+  } else if constexpr (FMT == QF_E2M3) {
+    hipLaunchKernelGGL((fused_quantize_mxf6_kernel<R>), dim3(grid), dim3(256), 0, s, p);
+    return check_launch("fused_quantize_mxf6_kernel");
+  } else if constexpr (FMT != QF_E2M1 && KIND == QK_GATED) {
     hipLaunchKernelGGL((fused_silu_mul_quantize_mxf8_kernel<R, FMT, BLK>), dim3(grid), dim3(256), 0, s, p);
     return check_launch("fused_silu_mul_quantize_mxf8_kernel");
   } else if constexpr (FMT != QF_E2M1 && KIND == QK_GATHER) {
@@ -1483,6 +1543,8 @@ QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, false, QF_E4M3) QAMD_QUAN
 QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, true, QF_E4M3) QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, true, QF_E5M2)
 QAMD_QUANT_INST(QK_GATHER, false, METHOD_ABSMAX, false, false, QF_E4M3) QAMD_QUANT_INST(QK_GATHER, false, METHOD_ABSMAX, false, false, QF_E5M2)
 QAMD_QUANT_INST(QK_GATED, false, METHOD_ABSMAX, false, false, QF_E4M3) QAMD_QUANT_INST(QK_GATED, false, METHOD_ABSMAX, false, true, QF_E4M3)
+// MXFP6 (x R = 32, 64, 128 each): plain and gathering, flat scales
+QAMD_QUANT_INST(QK_PLAIN, false, METHOD_ABSMAX, false, false, QF_E2M3) QAMD_QUANT_INST(QK_GATHER, false, METHOD_ABSMAX, false, false, QF_E2M3)
 #undef QAMD_QUANT_FORMATS
 #undef QAMD_QUANT_INST
 #endif
@@ -1594,6 +1656,7 @@ inline int quant_check_method(const char* name, int method) {
 // the kernels' FMT is fmt + 1.  e4m3_only: the gated form.
 inline int quant_check_how(const char* name, const QuantFormat& f, int method, int fmt, bool e4m3_only = false) {
   if (!f.fp8) return quant_check_method(name, method);
+  if (f.fp6) return QAMD_OK;   // MXFP6: one code format, abs-max only -- nothing to choose
   if (fmt == QAMD_FP8_E4M3 || (fmt == QAMD_FP8_E5M2 && !e4m3_only)) return QAMD_OK;
   return fail(QAMD_ERR_INVALID, "%s: invalid fmt %d; expected %s", name, fmt, e4m3_only ? "0 (e4m3)" : "0 (e4m3) or 1 (e5m2)");
 }
@@ -1635,6 +1698,10 @@ inline int quant_check_groups(const char* name, const QuantGroups& g) {
 // fmt8: -1, or the C ABI's fmt of an MXFP8 entry (checked by quant_check_how): MX abs-max with e4m3 / e5m2 codes
 template <int KIND>
 int select_quant(bool nv, int method, bool mask, bool blocked, int rot, const QuantParams& p, hipStream_t s, int grid, const char* name, int fmt8 = -1) {
+  if (fmt8 == QF_E2M3 - 1) {   // MXFP6 (the entries pass the kernels' FMT - 1, as the MXFP8 ones do): plain or gathering, flat scales
+    if constexpr (KIND == QK_PLAIN || KIND == QK_GATHER) return dispatch_quant<KIND, false, METHOD_ABSMAX, false, false, QF_E2M3>(rot, p, s, grid, name);
+    else return fail(QAMD_ERR_INVALID, "%s: no MXFP6 form", name);
+  }
   if (fmt8 >= 0) {
     auto go8 = [&](auto fmt_) {
       using F = decltype(fmt_);
@@ -1771,6 +1838,19 @@ int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, c
   grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
   grouped_mx_defaults(q);
   return launch_grouped_w4a8(grouped_form(F, grouped_w4a8_plan, M, N, K, E), q, (hipStream_t)stream);
+}
+
+// W4A6: A (M, 3K/4) packed e2m3 codes, everything else as W4A8
+int qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                                 const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_MXF6_MXF4;
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if ((uintptr_t)A % 16) return fail(QAMD_ERR_INVALID, "%s: A must be 16-byte aligned", F.name);   // 16-byte LDS-DMA chunks at a 3K/4-byte row pitch
+  if (M == 0) return QAMD_OK;
+  GroupedParams q;
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
+  grouped_mx_defaults(q);
+  return launch_grouped_w4a6(grouped_form(F, grouped_w4a6_plan, M, N, K, E), q, (hipStream_t)stream);
 }
 
 // W4A16: A (M, K) bf16 without scales; src_row (M,) int32 or null -- with it A is the unsorted (T, K) tokens and sorted row r reads A[src_row[r]]
@@ -2115,6 +2195,18 @@ int qutlass_amd_fused_gather_quantize_mxf8(const void* x, const void* h, int rot
                                            void* out_e8m0, void* stream) {
   return fused_gather_quantize_impl("fusedGatherQuantizeMxf8", kQuantMxf8, x, h, rot, t, k, src_row, m, QAMD_METHOD_ABSMAX, nullptr, out_fp8, out_e8m0, stream, nullptr,
                                     fmt);
+}
+
+// ---- MXFP6: the plain and the gathering form with e2m3 codes, four in three bytes (quantize.hip.h, the FP6 arm): the A operand of grouped_matmul_mxf6_mxf4_bf16_tn.
+// Each entry runs its MX sibling's chain under its own name; there is neither a method nor a fmt to check.  out_fp6 takes numel * 3 / 4 bytes.
+int qutlass_amd_fused_quantize_mxf6(const void* x, const void* h, int rot, int64_t numel, void* out_fp6, void* out_e8m0, void* stream) {
+  return fused_quantize_impl("fusedQuantizeMxf6", kQuantMxf6, x, h, rot, numel, 0, QAMD_METHOD_ABSMAX, nullptr, out_fp6, out_e8m0, nullptr, stream, QF_E2M3 - 1);
+}
+
+int qutlass_amd_fused_gather_quantize_mxf6(const void* x, const void* h, int rot, int64_t t, int64_t k, const int32_t* src_row, int64_t m, void* out_fp6,
+                                           void* out_e8m0, void* stream) {
+  return fused_gather_quantize_impl("fusedGatherQuantizeMxf6", kQuantMxf6, x, h, rot, t, k, src_row, m, QAMD_METHOD_ABSMAX, nullptr, out_fp6, out_e8m0, stream, nullptr,
+                                    QF_E2M3 - 1);
 }
 
 // ---- gpt-oss: the clamped SwiGLU with per-expert biases (quantize.hip.h, swiglu_oai_mul8), alone and fused into the MXFP4 and the MXFP8 (e4m3) quantizer; moe_combine with the down bias ----
@@ -2750,6 +2842,10 @@ int qutlass_amd_debug_grouped_mxf8_mxf4_plan(int64_t M, int64_t N, int64_t K, in
 // grouped_matmul_bf16_mxf4_bf16_tn: 606 = 32x32, 608 = 64x32 tiles of the bf16-token wave-owned kernel
 int qutlass_amd_debug_grouped_bf16_mxf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
   return debug_grouped_plan(GRP_BF16_MXF4, "debug_grouped_bf16_mxf4_plan", grouped_w4a16_plan, M, N, K, E, out);
+}
+// grouped_matmul_mxf6_mxf4_bf16_tn: 610 = 32x32, 612 = 64x32 tiles of the 6-bit-token wave-owned kernel
+int qutlass_amd_debug_grouped_mxf6_mxf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  return debug_grouped_plan(GRP_MXF6_MXF4, "debug_grouped_mxf6_mxf4_plan", grouped_w4a6_plan, M, N, K, E, out);
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel
 int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {

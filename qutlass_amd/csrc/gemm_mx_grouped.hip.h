@@ -56,6 +56,8 @@ constexpr GroupedFormat GRP_NVF4{"grouped_matmul_nvf4_bf16_tn", 598, 4, 16, {{32
 constexpr GroupedFormat GRP_MXF8_MXF4{"grouped_matmul_mxf8_mxf4_bf16_tn", 602, 8, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
 // W4A16: bf16 tokens WITHOUT scales against e2m1 weights (gemm_mx_os_w4a16.hip.h) -- the three wave-owned forms, no ring form; sgroup is the weights'
 constexpr GroupedFormat GRP_BF16_MXF4{"grouped_matmul_bf16_mxf4_bf16_tn", 606, 16, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
+// W4A6: e2m3 tokens, four codes in three bytes (an A row is 3 K / 4 bytes), against e2m1 weights (gemm_mx_os_w4a6.hip.h) -- the three wave-owned forms, no ring form
+constexpr GroupedFormat GRP_MXF6_MXF4{"grouped_matmul_mxf6_mxf4_bf16_tn", 610, 6, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
 // workgroups of a grouped launch: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles (grouped_tile: the rest return at once)
 constexpr int64_t grouped_workgroups(int64_t M, int64_t N, int64_t E, int TM, int TN) { return ((M + TM - 1) / TM + E) * ((N + TN - 1) / TN); }
 
@@ -191,13 +193,13 @@ struct GroupedView {
   const uint8_t* SFB;
   const float* alpha;
 };
-// workgroup -> the grouped parts of its tile's view, false: no work (EBITS: element width of A, 4 = MXFP4, 8 = MXFP8, 16 = bf16)
+// workgroup -> the grouped parts of its tile's view, false: no work (EBITS: element width of A, 4 = MXFP4, 6 = MXFP6 -- K % 4 == 0 --, 8 = MXFP8, 16 = bf16)
 template <int TM, int TN, int EBITS = 4>
 __device__ __forceinline__ bool grouped_setup(const GroupedParams& pk, GroupedView& v) {
   GroupTile t;
   if (!grouped_tile(pk.offs, pk.E, pk.M, TM, pk.tiles_n, (int)blockIdx.x, t)) return false;
   const int g = uniform(t.g), gend = uniform(t.row0 + t.rows);
-  const uint32_t rowbytes = EBITS == 16 ? (uint32_t)pk.K << 1 : EBITS == 8 ? (uint32_t)pk.K : (uint32_t)pk.K >> 1, KB = (uint32_t)pk.K >> 5;
+  const uint32_t rowbytes = EBITS == 16 ? (uint32_t)pk.K << 1 : EBITS == 8 ? (uint32_t)pk.K : EBITS == 6 ? ((uint32_t)pk.K >> 2) * 3u : (uint32_t)pk.K >> 1, KB = (uint32_t)pk.K >> 5;
   v.M = gend;                                      // stores masked to the group's rows ...
   v.a_bytes = (uint32_t)gend * rowbytes;           // ... and reads past them return zeros
   v.sfa_bytes = (uint32_t)gend * KB;

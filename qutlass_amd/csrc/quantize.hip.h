@@ -24,7 +24,7 @@
 namespace qamd {
 
 enum { METHOD_QUEST = 0, METHOD_ABSMAX = 1 };
-enum { QF_E2M1 = 0, QF_E4M3 = 1, QF_E5M2 = 2 };   // output code format of the kernels (FMT): 4-bit (MX / NV) or one of the two 8-bit MX formats
+enum { QF_E2M1 = 0, QF_E4M3 = 1, QF_E5M2 = 2, QF_E2M3 = 3 };   // output code format of the kernels (FMT): 4-bit (MX / NV), one of the two 8-bit MX formats or the 6-bit one
 
 // The constants of the clamped SwiGLU (swiglu_oai_mul8 below), made by the host from the caller's alpha and limit (swiglu_oai_act in capi.hip):
 //   alpha * log2 e = c_hi + c_lo in fp64, c_hi of 16 significant bits;  nch = -c_hi,  klo = -ln 2 * c_lo,  tmax = 16 (or -1: every element through fp64)
@@ -36,7 +36,7 @@ enum { ACT_SILU = 0, ACT_OAI = 1, ACT_OAI_BIAS = 2 };   // activation of the GAT
 struct QuantParams {
   const uint16_t* x;   // bf16, numel
   const uint16_t* h;   // bf16, R x R row-major
-  uint8_t* out;        // packed e2m1, numel/2 (FMT e4m3 / e5m2: one byte per element, numel)
+  uint8_t* out;        // packed e2m1, numel/2 (FMT e4m3 / e5m2: one byte per element, numel; FMT e2m3: four codes in three bytes, numel * 3 / 4)
   uint8_t* out_sf;     // e8m0 (MX, numel/32) or e4m3 (NV, numel/16), flat group order
   uint32_t* out_mask;  // MX quest-with-mask: one u32 per 32-group (may be null)
   const float* global_scale;  // NV only
@@ -91,11 +91,13 @@ struct QuantFormat {
   const char* rots;      // that set as the messages spell it
   const char* row_unit;  // the blocked row-length message names its unit "the rotation size" for MX (the unit is R) and gives the bare number for NV (max(R, 32))
   bool fp8 = false;      // MXFP8: one code byte per element (e4m3 or e5m2, the entry's fmt), abs-max only, no clip mask; scales as MX
+  bool fp6 = false;      // MXFP6 (with fp8: the same chains): e2m3 codes, four in three bytes; no fmt argument, flat scales only
   constexpr bool has_rot(int rot) const { return rot >= min_rot && rot <= 128 && (rot & (rot - 1)) == 0; }
 };
 constexpr QuantFormat kQuantMx{false, 32, 32, true, "32, 64, or 128", "the rotation size "};
 constexpr QuantFormat kQuantNv{true, 16, 16, false, "16, 32, 64, or 128", ""};
 constexpr QuantFormat kQuantMxf8{false, 32, 32, false, "32, 64, or 128", "the rotation size ", true};
+constexpr QuantFormat kQuantMxf6{false, 32, 32, false, "32, 64, or 128", "the rotation size ", true, true};
 
 // byte offset of scale (row, col) in the 128x4-tiled block-scale layout (qutlass/utils.py:60-64, :190-193); CB = ceil(cols / 4)
 __device__ __forceinline__ uint32_t blocked_sf_offset(uint32_t row, uint32_t col, uint32_t CB) {
@@ -464,8 +466,9 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
   // x as rows of RP elements (for R = 16 two rotation rows share one 32-element "row")
   const int64_t ngroups = p.numel / (NV ? 16 : 32);
   static_assert(!(GATED && GATHER) && !(GATHER && (BLK || MASK)), "the gathering form: plain operand, flat scales, no clip mask");
-  static_assert(FMT == QF_E2M1 || ((FMT == QF_E4M3 || FMT == QF_E5M2) && !NV && METHOD == METHOD_ABSMAX && !MASK && !GSCALE && R >= 32),
-                "the MXFP8 arm: MX scales (so no R = 16), abs-max, no clip mask");
+  static_assert(FMT == QF_E2M1 || ((FMT == QF_E4M3 || FMT == QF_E5M2 || FMT == QF_E2M3) && !NV && METHOD == METHOD_ABSMAX && !MASK && !GSCALE && R >= 32),
+                "the MXFP8 / MXFP6 arms: MX scales (so no R = 16), abs-max, no clip mask");
+  static_assert(FMT != QF_E2M3 || (!BLK && !GATED), "the MXFP6 arm: plain or gathering, flat scales");
   static_assert(!GSCALE || (NV && METHOD == METHOD_ABSMAX && !BLK && !MASK && (GATED || GATHER)), "per-expert global scales: NV abs-max, flat scales, gathering or gated");
   static_assert(ACT == ACT_SILU || (GATED && !NV && !BLK && !MASK && !GSCALE && (FMT == QF_E2M1 || FMT == QF_E4M3) && R >= 32 && R <= 64),
                 "the clamped SwiGLU: gated MX e2m1 or e4m3, flat scales, R = 32 / 64");
@@ -845,7 +848,66 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
       // acc[4q+e] = y[r_abs][32 jt + 8q + 4 half + e]
       const int64_t grp32 = r_abs * JT + jt;   // 32-element group index in the flat output
 
-      if constexpr (FMT != QF_E2M1) {
+      if constexpr (FMT == QF_E2M3) {
+        // ------------------------------ MXFP6: e8m0 per 32, e2m3 codes, 24 bytes per group -----
+        // amax = max |y| over the group (v_max_f32 drops NaNs), E = the exponent field of the FP32 amax, and
+        //   e8 = 255 if any y of the group is NaN or infinite (all 32 codes 0: the format has no NaN code, the scale byte carries it and the GEMM honours it),
+        //   e8 = 127 if amax == 0, else clamp(E - 2, 0, 254)
+        // -- the OCP MX rule: the scaled maximum lies in [4, 8), and (7.5, 8) saturates to 7.5, the largest e2m3 value.  A NaN input makes every output of its
+        // rotation NaN, an infinite one +-inf or NaN, so a group that holds either has amax 0 (all NaN) or inf: the test for them (nan_risk, as in the e2m1 arm)
+        // runs only behind amax == 0 || amax == inf, which -- all-zero groups aside -- real activations never meet.
+        float m = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m = fmaxf(m, fabsf(acc[r]));
+        m = xhalf_max(m);
+        const int ex = (int)(__float_as_uint(m) >> 23) - 2;   // m >= +0: no sign bit above the exponent field; E <= 254 for a finite m, so e8 <= 252
+        uint32_t e8 = m == 0.f ? 127u : (uint32_t)(ex < 0 ? 0 : ex);
+        bool poison = false;
+        if (__builtin_expect(m == 0.f || !(m < __builtin_inff()), 0)) {
+          uint32_t bad = 0;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) bad |= (__float_as_uint(acc[r]) & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+          bad |= (uint32_t)__shfl_xor((int)bad, 32, 64);   // the other half of the group
+          poison = bad != 0;
+          if (poison) e8 = 255u;
+        }
+        // t = y * 2^(127 - e8), an fp32 MULTIPLY by a normal power of two as in the MXFP8 arm and for its reason (e8 = 0 would make the converters' scale operand
+        // a denormal); exact unless it falls below 2^-126, far under half the smallest e2m3 step (2^-4), where it rounds to (signed) zero either way.
+        // Codes by integer arithmetic: a = min(|t|, 7.5); its e2m3 step is 2^(max(E_a, 127) - 130) -- 1/8 below 2, 1/4 below 4, 1/2 below 8 -- and adding
+        // 1.5 * 2^23 steps rounds a to a whole number n of steps in the sum's low mantissa bits, to nearest, ties to even (the adder's own rounding; n even <=> code
+        // even).  n = 0 .. 16 below 2, 8 .. 16 above: code = n + 8 (max(E_a, 127) - 127), where n = 16 carries into the next exponent as it should.
+        float t[16];
+        scale_pk<16>(acc, 0, __uint_as_float((254u - (poison ? 127u : e8)) << 23), t);
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          uint32_t c4 = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const uint32_t tb = __float_as_uint(t[4 * q + e]);
+            const float a = fminf(__uint_as_float(tb & 0x7fffffffu), 7.5f);
+            const uint32_t er = __float_as_uint(a) >> 23, ea = er < 127u ? 127u : er;
+            const uint32_t magic = ((ea + 20u) << 23) | 0x400000u;
+            const uint32_t n = __float_as_uint(a + __uint_as_float(magic)) - magic;
+            uint32_t code = (n + ((ea - 127u) << 3)) | ((tb >> 31) << 5);
+            code = poison ? 0u : code;
+            c4 |= code << (6 * e);
+          }
+          w[q] = c4;   // elements 8 q + 4 half .. + 3: bytes 6 q + 3 half .. + 2 of the group's 24
+        }
+        // The 24 bytes are eight 3-byte runs that alternate between the lane halves.  One v_permlane32_swap pair, as in the MXFP8 arm: half 0 ends up with
+        // {own w0, partner w0, own w1, partner w1} = bytes 0 .. 11, half 1 with {partner w2, own w2, partner w3, own w3} = bytes 12 .. 23 -- three dwords per lane.
+        auto s0 = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
+        auto s1 = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
+        const uint32_t x0 = s0[0], x1 = s0[1], x2 = s1[0], x3 = s1[1];
+        if (grp32 < ngroups) {
+          uint32_t* o = (uint32_t*)(p.out + grp32 * 24 + half * 12);
+          o[0] = x0 | (x1 << 24);
+          o[1] = (x1 >> 8) | (x2 << 16);
+          o[2] = (x2 >> 16) | (x3 << 8);
+          if (half == 0) p.out_sf[grp32] = (uint8_t)e8;
+        }
+      } else if constexpr (FMT != QF_E2M1) {
         // ------------------------------ MXFP8: e8m0 per 32, e4m3 / e5m2 codes ------------------
         // amax = max |y| over the group (v_max_f32 drops NaNs: a group that is all NaN has amax 0), E = the exponent field of the FP32 amax, and
         //   e8 = 127 if amax == 0, else clamp(E - SH, 0, 254),  SH = 7 (e4m3) / 14 (e5m2)
@@ -1101,6 +1163,15 @@ __global__ __launch_bounds__(256) void fused_silu_mul_quantize_mxf8_kernel(const
 template <int R, int FMT>
 __global__ __launch_bounds__(256) void fused_gather_quantize_mxf8_kernel(const QuantParams p) {
   fused_quantize_body<R, false, METHOD_ABSMAX, false, true, false, true, false, true, false, FMT>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+// the MXFP6 quantizers (fusedQuantizeMxf6, fusedGatherQuantizeMxf6): FMT = QF_E2M3, abs-max, flat scales
+template <int R>
+__global__ __launch_bounds__(256) void fused_quantize_mxf6_kernel(const QuantParams p) {
+  fused_quantize_body<R, false, METHOD_ABSMAX, false, true, false, true, false, false, false, QF_E2M3>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+template <int R>
+__global__ __launch_bounds__(256) void fused_gather_quantize_mxf6_kernel(const QuantParams p) {
+  fused_quantize_body<R, false, METHOD_ABSMAX, false, true, false, true, false, true, false, QF_E2M3>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 // the clamped-SwiGLU form (fusedSwigluOaiQuantizeMxf8): e4m3 with flat scales, R = 32 / 64, with or without the per-expert gate/up bias
 template <int R, bool BIAS>

@@ -187,13 +187,15 @@ Tensor matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor
 //   NVF4: the same operands, e4m3 scales per 16 elements (fusedQuantizeNv's buffer as it is)
 //   MXF8: A (M, K) e4m3 / e5m2 (e5m2 selects the e5m2-A path, as matmul_mxf8_bf16_tn), B (E, N, K) e4m3, e8m0 scales per 32 elements
 //   MXF8_MXF4 (W4A8): A (M, K) e4m3 as MXF8's, B (E, N, K/2) packed e2m1 as MXF4's, e8m0 scales per 32 elements
-enum class Grouped { MXF4, NVF4, MXF8, MXF8_MXF4 };
+//   MXF6_MXF4 (W4A6): A (M, 3K/4) uint8, packed e2m3 codes (include/qutlass_amd.h: the MXFP6 operand format), B and the scales as MXF8_MXF4's
+enum class Grouped { MXF4, NVF4, MXF8, MXF8_MXF4, MXF6_MXF4 };
 
 template <Grouped G>
 Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) {
   constexpr bool w4a8 = G == Grouped::MXF8_MXF4;
   constexpr bool fp8 = G == Grouped::MXF8;
-  const char* op = G == Grouped::MXF4 ? "grouped_matmul_mxf4" : G == Grouped::NVF4 ? "grouped_matmul_nvf4" : w4a8 ? "grouped_matmul_mxf8_mxf4" : "grouped_matmul_mxf8";
+  constexpr bool w4a6 = G == Grouped::MXF6_MXF4;
+  const char* op = G == Grouped::MXF4 ? "grouped_matmul_mxf4" : G == Grouped::NVF4 ? "grouped_matmul_nvf4" : w4a8 ? "grouped_matmul_mxf8_mxf4" : w4a6 ? "grouped_matmul_mxf6_mxf4" : "grouped_matmul_mxf8";
   check_tensors(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
   const ScalarType data_t = fp8 ? ScalarType::Float8_e4m3fn : ScalarType::Byte;                  // either operand
   const ScalarType a_alt = fp8 ? ScalarType::Float8_e5m2 : ScalarType::Float4_e2m1fn_x2;         // ... or, for A
@@ -204,15 +206,18 @@ Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, cons
     STD_TORCH_CHECK(!has_dtype(A, ScalarType::Float8_e5m2), op, ": A must be float8_e4m3fn, float8_e5m2 tokens are not supported");
     STD_TORCH_CHECK(has_dtype(A, ScalarType::Float8_e4m3fn), op, ": A must be float8_e4m3fn");
     STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), op, ": B must be uint8 or float4_e2m1fn_x2");
+  } else if (w4a6) {   // packed e2m3 tokens have no dtype of their own: bytes; the weights as MXF4's
+    STD_TORCH_CHECK(has_dtype(A, ScalarType::Byte), op, ": A must be uint8 (packed e2m3 codes)");
+    STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), op, ": B must be uint8 or float4_e2m1fn_x2");
   } else {
     STD_TORCH_CHECK(has_dtype(A, data_t) || has_dtype(A, a_alt), "A must be ", fp8 ? "float8_e4m3fn or float8_e5m2" : "uint8 or float4_e2m1fn_x2");
     STD_TORCH_CHECK(has_dtype(B, data_t) || has_dtype(B, b_alt), "B must be ", fp8 ? "float8_e4m3fn" : "uint8 or float4_e2m1fn_x2");
   }
   STD_TORCH_CHECK(has_dtype(A_sf, sf_t), "A_sf must be ", sf_n);
   STD_TORCH_CHECK(has_dtype(B_sf, sf_t), "B_sf must be ", sf_n);
-  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, w4a8 ? "A must be 2D (M, K) and B 3D (E, N, K/2)" : fp8 ? "A must be 2D (M, K) and B 3D (E, N, K)" : "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
-  STD_TORCH_CHECK(A.size(1) == B.size(2) * (w4a8 ? 2 : 1), "Inner dimensions must match for A @ B[g].T");
-  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * (fp8 || w4a8 ? 1 : 2), kb = K / (G == Grouped::NVF4 ? 16 : 32);
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, w4a6 ? "A must be 2D (M, 3K/4) and B 3D (E, N, K/2)" : w4a8 ? "A must be 2D (M, K) and B 3D (E, N, K/2)" : fp8 ? "A must be 2D (M, K) and B 3D (E, N, K)" : "A must be 2D (M, K/2) and B 3D (E, N, K/2)");
+  STD_TORCH_CHECK(w4a6 ? A.size(1) * 2 == B.size(2) * 3 : A.size(1) == B.size(2) * (w4a8 ? 2 : 1), "Inner dimensions must match for A @ B[g].T");
+  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = w4a6 ? B.size(2) * 2 : A.size(1) * (fp8 || w4a8 ? 1 : 2), kb = K / (G == Grouped::NVF4 ? 16 : 32);
   STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
   STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
   STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
@@ -228,6 +233,7 @@ Tensor grouped_matmul(const Tensor& A, const Tensor& B, const Tensor& A_sf, cons
   int rc;
   if (G == Grouped::MXF4) rc = qutlass_amd_grouped_matmul_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
   else if (G == Grouped::NVF4) rc = qutlass_amd_grouped_matmul_nvf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
+  else if (w4a6) rc = qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
   else if (w4a8) rc = qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E, s);
   else rc = qutlass_amd_grouped_matmul_mxf8_bf16_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), al, alpha.numel(), of, out.data_ptr(), M, N, K, E,
                                                     has_dtype(A, ScalarType::Float8_e5m2) ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3, s);
@@ -239,6 +245,7 @@ Tensor grouped_matmul_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf,
 Tensor grouped_matmul_nvf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::NVF4>(A, B, A_sf, B_sf, alpha, offs); }
 Tensor grouped_matmul_mxf8(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF8>(A, B, A_sf, B_sf, alpha, offs); }
 Tensor grouped_matmul_mxf8_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF8_MXF4>(A, B, A_sf, B_sf, alpha, offs); }
+Tensor grouped_matmul_mxf6_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs) { return grouped_matmul<Grouped::MXF6_MXF4>(A, B, A_sf, B_sf, alpha, offs); }
 
 // EXTENSION: grouped W4A16 GEMM (qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn) -- A (M, K) bf16 tokens sorted by expert and WITHOUT scales, or with src_row (M,) int32 the
 // unsorted (T, K) tokens (row r of the output reads A[src_row[r]]); B (E, N, K/2) packed e2m1 and B_sf row-major (E, N, K/32) e8m0 as grouped_matmul_mxf4's; alpha, offs as
@@ -319,9 +326,10 @@ int64_t quant_rp(int64_t rot) { return rot < 32 ? 32 : rot; }   // rows are whol
 
 // the C ABI writes numel / 2 bytes of codes and one scale byte per group -- flat, or the padded to_blocked() matrix of the (numel / k, k / group) scales
 // (fp8: the MXFP8 ops -- one code byte per element)
-void quant_check_out(bool nv, const Tensor& OUT, const Tensor& OUT_sf, int64_t numel, int64_t k, bool blocked, bool fp8 = false) {
+// (fp6: the MXFP6 ops -- four codes in three bytes)
+void quant_check_out(bool nv, const Tensor& OUT, const Tensor& OUT_sf, int64_t numel, int64_t k, bool blocked, bool fp8 = false, bool fp6 = false) {
   const int64_t group = nv ? 16 : 32;
-  STD_TORCH_CHECK(nbytes(OUT) >= (fp8 ? numel : numel / 2), "OUT is too small");
+  STD_TORCH_CHECK(nbytes(OUT) >= (fp6 ? numel / 4 * 3 : fp8 ? numel : numel / 2), "OUT is too small");
   STD_TORCH_CHECK(nbytes(OUT_sf) >= (blocked ? (numel / k + 127) / 128 * 128 * ((k / group + 3) / 4 * 4) : numel / group), "OUT_sf is too small",
                   blocked ? " for the blocked scale layout" : "");
 }
@@ -340,19 +348,30 @@ int mxf8_fmt(const Tensor& OUT, const Tensor& OUT_sf, bool e4m3_only = false) {
   return e5m2 ? QAMD_FP8_E5M2 : QAMD_FP8_E4M3;
 }
 
-// OUT_mask != nullptr (MX only): Quest with clip mask (rotation 32 only).  fmt8 >= 0 (MX only): the MXFP8 op, method is not read.
+// The MXFP6 ops (fusedQuantizeMxf6_, fusedGatherQuantizeMxf6_) go through the MXFP8 ops' functions with this value where those carry the C ABI's fmt: OUT is uint8,
+// (.., 3K/4) bytes of packed e2m3 codes
+constexpr int kFmtMxf6 = 2;
+int mxf6_fmt(const Tensor& OUT, const Tensor& OUT_sf) {
+  STD_TORCH_CHECK(has_dtype(OUT, ScalarType::Byte), "OUT must be uint8");
+  STD_TORCH_CHECK(has_dtype(OUT_sf, ScalarType::Float8_e8m0fnu) || has_dtype(OUT_sf, ScalarType::Byte), "OUT_sf must be float8_e8m0fnu or uint8");
+  return kFmtMxf6;
+}
+
+// OUT_mask != nullptr (MX only): Quest with clip mask (rotation 32 only).  fmt8 >= 0 (MX only): the MXFP8 op -- kFmtMxf6: the MXFP6 op --, method is not read.
 void quantize(const char* op, const Tensor& A, const Tensor& R, Tensor& OUT, Tensor& OUT_sf, Tensor* OUT_mask, const Tensor* gscale, int method, int fmt8 = -1) {
   std::vector<Named> ts{{A, "A"}, {R, "B"}, {OUT, "OUT"}, {OUT_sf, "OUT_sf"}};
   if (OUT_mask) ts.push_back({*OUT_mask, "OUT_mask"});
   const int64_t rot = quant_prelude(op, ts, gscale), numel = A.numel();
   STD_TORCH_CHECK(numel % rot == 0, "A must be divisible by", rot);
   quant_check_rot(gscale, rot, OUT_mask);
-  quant_check_out(gscale, OUT, OUT_sf, numel, 0, false, fmt8 >= 0);
+  quant_check_out(gscale, OUT, OUT_sf, numel, 0, false, fmt8 >= 0, fmt8 == kFmtMxf6);
   if (OUT_mask) {
     STD_TORCH_CHECK(nbytes(*OUT_mask) >= numel / 8, "OUT_mask is too small");
   }
   const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
-  if (fmt8 >= 0)
+  if (fmt8 == kFmtMxf6)
+    check_rc(qutlass_amd_fused_quantize_mxf6(A.data_ptr(), R.data_ptr(), (int)rot, numel, OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
+  else if (fmt8 >= 0)
     check_rc(qutlass_amd_fused_quantize_mxf8(A.data_ptr(), R.data_ptr(), (int)rot, numel, fmt8, OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
   else if (gscale)
     check_rc(qutlass_amd_fused_quantize_nv(A.data_ptr(), R.data_ptr(), (int)rot, numel, method, gscale_ptr(gscale), OUT.data_ptr(), OUT_sf.data_ptr(), current_stream(A)));
@@ -498,9 +517,12 @@ void gather_quantize(const char* op, const Tensor& X, const Tensor& R, const Ten
   const int64_t T = X.size(0), K = X.size(1), M = src_row.size(0);
   quant_check_rot(gscale, rot);
   STD_TORCH_CHECK(K % quant_rp(rot) == 0, "the last dimension of A must be divisible by", quant_rp(rot));
-  quant_check_out(gscale, OUT, OUT_sf, M * K, K, false, fmt8 >= 0);
+  quant_check_out(gscale, OUT, OUT_sf, M * K, K, false, fmt8 >= 0, fmt8 == kFmtMxf6);
   const torch::stable::accelerator::DeviceGuard guard(X.get_device_index());
-  if (fmt8 >= 0)
+  if (fmt8 == kFmtMxf6)
+    check_rc(qutlass_amd_fused_gather_quantize_mxf6(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, OUT.data_ptr(),
+                                                    OUT_sf.data_ptr(), current_stream(X)));
+  else if (fmt8 >= 0)
     check_rc(qutlass_amd_fused_gather_quantize_mxf8(X.data_ptr(), R.data_ptr(), (int)rot, T, K, static_cast<const int32_t*>(src_row.data_ptr()), M, fmt8, OUT.data_ptr(),
                                                     OUT_sf.data_ptr(), current_stream(X)));
   else if (offs)
@@ -539,6 +561,15 @@ void fusedSiluMulQuantizeMxf8_(const Tensor& A, const Tensor& R, Tensor OUT, Ten
 }
 void fusedGatherQuantizeMxf8_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf) {
   gather_quantize("fusedGatherQuantizeMxf8", A, R, src_row, OUT, OUT_sf, nullptr, QAMD_METHOD_ABSMAX, nullptr, mxf8_fmt(OUT, OUT_sf));
+}
+
+// ---- EXTENSION: the MXFP6 quantizers -- e2m3 codes, four in three bytes, with one e8m0 scale per 32 elements, abs-max; the plain and the gathering form ------
+// OUT is (.., 3K/4) uint8, OUT_sf as for the MX ops (flat).
+void fusedQuantizeMxf6_(const Tensor& A, const Tensor& R, Tensor OUT, Tensor OUT_sf) {
+  quantize("fusedQuantizeMxf6", A, R, OUT, OUT_sf, nullptr, nullptr, QAMD_METHOD_ABSMAX, mxf6_fmt(OUT, OUT_sf));
+}
+void fusedGatherQuantizeMxf6_(const Tensor& A, const Tensor& R, const Tensor& src_row, Tensor OUT, Tensor OUT_sf) {
+  gather_quantize("fusedGatherQuantizeMxf6", A, R, src_row, OUT, OUT_sf, nullptr, QAMD_METHOD_ABSMAX, nullptr, mxf6_fmt(OUT, OUT_sf));
 }
 
 // ---- EXTENSION: gpt-oss -- the clamped SwiGLU with per-expert gate/up biases, alone and fused into the MXFP4 and the MXFP8 (e4m3) quantizer, and moe_combine with the down bias ------
@@ -913,11 +944,22 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("grouped_matmul_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_mxf8_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // W4A8, inference op: in the minimal library too
+  m.def("grouped_matmul_mxf6_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // W4A6, inference op: in the minimal library too
   m.def("grouped_matmul_bf16_mxf4_bf16_tn(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, Tensor? src_row) -> Tensor");   // W4A16, inference op: in the minimal library too
   m.def("grouped_matmul_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
 }
 
 // CUDA dispatch key only, as the reference (bindings.cpp:516-535); there is no CPU compute path.
+// the in-place twins of the MXFP6 quantizers, in a namespace of their own: the set of output-filling ops of `qutlass_amd` is a pinned list (tests/test_op_tables_cpu.py)
+STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd_mxf6, m) {
+  m.def("fusedQuantizeMxf6_(Tensor A, Tensor R, Tensor(a!) OUT, Tensor(b!) OUT_sf) -> ()");   // OUT (.., 3K/4) uint8: packed e2m3 codes
+  m.def("fusedGatherQuantizeMxf6_(Tensor A, Tensor R, Tensor src_row, Tensor(a!) OUT, Tensor(b!) OUT_sf) -> ()");
+}
+STABLE_TORCH_LIBRARY_IMPL(qutlass_amd_mxf6, CUDA, m) {
+  m.impl("fusedQuantizeMxf6_", TORCH_BOX(&fusedQuantizeMxf6_));
+  m.impl("fusedGatherQuantizeMxf6_", TORCH_BOX(&fusedGatherQuantizeMxf6_));
+}
+
 STABLE_TORCH_LIBRARY_IMPL(_qutlass_C, CUDA, m) {
   m.impl("matmul_mxf4_bf16_tn", TORCH_BOX(&matmul_mxf4_bf16_tn));
   m.impl("matmul_nvf4_bf16_tn", TORCH_BOX(&matmul_nvf4_bf16_tn));
@@ -975,13 +1017,14 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("grouped_matmul_nvf4", TORCH_BOX(&grouped_matmul_nvf4));
 }
 
-// The functional routing ops and the W4A16 grouped GEMM are registered for no particular device, like the functional ops of qutlass_amd/ops.py (CompositeExplicitAutograd: one kernel whatever
+// The functional routing ops and the W4A16 and W4A6 grouped GEMMs are registered for no particular device, like the functional ops of qutlass_amd/ops.py (CompositeExplicitAutograd: one kernel whatever
 // the tensors' device; their own check_tensors turns a CPU tensor away with the message every op here gives).  The CUDA key stays the list of the ops that fill or
 // allocate one result each, which tests/test_gpu_ext_rejections.py walks.
 STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CompositeExplicitAutograd, m) {
   m.impl("moe_route_fused", TORCH_BOX(&moe_route_fused));
   m.impl("moe_route_grouped_fused", TORCH_BOX(&moe_route_grouped_fused));
   m.impl("grouped_matmul_bf16_mxf4_bf16_tn", TORCH_BOX(&grouped_matmul_bf16_mxf4));   // (an optional tensor, as theirs)
+  m.impl("grouped_matmul_mxf6_mxf4", TORCH_BOX(&grouped_matmul_mxf6_mxf4));           // W4A6: its rejections are tests/test_gpu_grouped_w4a6.py's
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module

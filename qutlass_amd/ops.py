@@ -78,6 +78,8 @@ def _register_fakes() -> None:
 
     for row in (*QUANT_OPS.values(), *OUTPUT_OPS.values()):   # every in-place op is the twin of one row: none is called directly
         rf(f"qutlass_amd::{row.twin}")(fills)
+    for row in QUANT_OPS_MXF6.values():   # (their twins live in a namespace of their own: csrc/torch_ext.cpp)
+        rf(f"qutlass_amd_mxf6::{row.twin}")(fills)
 
     @rf("qutlass_amd::to_blocked")
     def _(input_matrix):
@@ -89,10 +91,10 @@ def _register_fakes() -> None:
         k = X.size(-1)
         return X.new_empty((X.numel() // k if k else 0, B.size(0)), dtype=torch.bfloat16)
 
-    def grouped_tn(A, B, A_sf, B_sf, alpha, offs):   # A (M, K/2 or K), B (E, N, K/2 or K)
+    def grouped_tn(A, B, A_sf, B_sf, alpha, offs):   # A (M, K/2, 3K/4 or K), B (E, N, K/2 or K)
         return A.new_empty((A.size(0), B.size(1)), dtype=torch.bfloat16)
 
-    for name in ("grouped_matmul_mxf4", "grouped_matmul_mxf8", "grouped_matmul_nvf4", "grouped_matmul_mxf8_mxf4"):
+    for name in ("grouped_matmul_mxf4", "grouped_matmul_mxf8", "grouped_matmul_nvf4", "grouped_matmul_mxf8_mxf4", "grouped_matmul_mxf6_mxf4"):
         rf(f"qutlass_amd::{name}")(grouped_tn)
 
     @rf("qutlass_amd::grouped_matmul_bf16_mxf4_bf16_tn")
@@ -123,9 +125,9 @@ def _define_functional_ops() -> None:
         return
     from torch.library import custom_op
 
-    for table, run, alloc in ((QUANT_OPS, run_quant, alloc_quant), (OUTPUT_OPS, run_output, lambda row, *args: row.alloc(*args))):
+    for table, run, alloc in ((QUANT_OPS, run_quant, alloc_quant), (QUANT_OPS_MXF6, run_quant, alloc_quant), (OUTPUT_OPS, run_output, lambda row, *args: row.alloc(*args))):
         for name, row in table.items():
-            if not hasattr(torch.ops.qutlass_amd, row.twin):   # QUTLASS_MINIMAL_BUILD: inference ops only
+            if not hasattr(torch.ops.qutlass_amd_mxf6 if table is QUANT_OPS_MXF6 else torch.ops.qutlass_amd, row.twin):   # QUTLASS_MINIMAL_BUILD: inference ops only
                 continue
             op = custom_op(f"qutlass_amd::{name}", mutates_args=(), schema=row.schema)(lambda *args, _row=row, _run=run: _run(_row, *args))
             op.register_fake(lambda *args, _row=row, _alloc=alloc: _alloc(_row, *args))   # the fake IS the row's allocator
@@ -164,7 +166,8 @@ def _gathered(A, R, src_row):   # MoE dispatch: the operand is A[src_row], (M, K
 
 
 _OAI_OPTIONAL = ((4, None), (5, torch.int32))   # bias in A's dtype, offs
-QUANT_FORMATS = {"mx": (32, torch.float8_e8m0fnu), "nv": (16, torch.float8_e4m3fn), "mxf8": (32, torch.float8_e8m0fnu)}   # elements per scale, scale dtype
+QUANT_FORMATS = {"mx": (32, torch.float8_e8m0fnu), "nv": (16, torch.float8_e4m3fn), "mxf8": (32, torch.float8_e8m0fnu),
+                 "mxf6": (32, torch.float8_e8m0fnu)}   # elements per scale, scale dtype
 MXF8_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2)   # code dtypes of the "mxf8" ops; "mx" and "nv" pack two e2m1 codes per uint8
 QUANT_OPS = {
     "quantize_mx": QuantOp("(Tensor A, Tensor R, int method) -> (Tensor, Tensor)", "fusedQuantizeMx_", 2, _same, "mx", False),
@@ -192,6 +195,12 @@ QUANT_OPS = {
     "swiglu_oai_quantize_mxf8": QuantOp("(Tensor A, Tensor R, float alpha, float limit, Tensor? bias, Tensor? offs) -> (Tensor, Tensor)", "fusedSwigluOaiQuantizeMxf8_", 2,
                                         _act, "mxf8", False, torch.float8_e4m3fn, _OAI_OPTIONAL),
 }
+# MXFP6: e2m3 codes, four in three bytes of a uint8 tensor (torch has no fp6 dtype), one e8m0 scale per 32 elements, abs-max, flat scales.  Rows of the same kind in
+# a table of their own: the family's table above is enumerated, row for row, by the tests of the 4- and 8-bit ops.
+QUANT_OPS_MXF6 = {
+    "quantize_mxf6": QuantOp("(Tensor A, Tensor R) -> (Tensor, Tensor)", "fusedQuantizeMxf6_", 2, _same, "mxf6", False),
+    "gather_quantize_mxf6": QuantOp("(Tensor A, Tensor R, Tensor src_row) -> (Tensor, Tensor)", "fusedGatherQuantizeMxf6_", 3, _gathered, "mxf6", False),
+}
 
 
 def mxf8_dtype(dtype) -> torch.dtype:
@@ -201,14 +210,18 @@ def mxf8_dtype(dtype) -> torch.dtype:
 
 
 def alloc_quant(row: QuantOp, *args):
-    """The results of one family op, uninitialised: packed e2m1 (.., K / 2) uint8 -- "mxf8": (.., K) codes in the dtype asked for -- and the scales -- (padded_rows,
+    """The results of one family op, uninitialised: packed e2m1 (.., K / 2) uint8 -- "mxf8": (.., K) codes in the dtype asked for; "mxf6": packed e2m3
+    (.., 3 K / 4) uint8 -- and the scales -- (padded_rows,
     padded_cols), or their product flat when blocked -- of the operand (.., K); args as the functional op takes them.  The one allocator of the fake kernels, the
     functional ops and the eager wrappers."""
     shape = row.operand(*args[:row.lead])
     group, sf_dtype = QUANT_FORMATS[row.fmt]
     pr, pc = padded_scale_shape(math.prod(shape) // shape[-1], shape[-1], group)
     blocked = args[-1] if row.blocked is None else row.blocked
-    codes = args[0].new_empty(shape, dtype=row.dtype or mxf8_dtype(args[row.lead])) if row.fmt == "mxf8" else args[0].new_empty((*shape[:-1], shape[-1] // 2), dtype=torch.uint8)
+    if row.fmt == "mxf8":
+        codes = args[0].new_empty(shape, dtype=row.dtype or mxf8_dtype(args[row.lead]))
+    else:
+        codes = args[0].new_empty((*shape[:-1], shape[-1] * 3 // 4 if row.fmt == "mxf6" else shape[-1] // 2), dtype=torch.uint8)
     return codes, args[0].new_empty((pr * pc,) if blocked else (pr, pc), dtype=sf_dtype)
 
 
@@ -231,7 +244,7 @@ def run_quant(row: QuantOp, *args):
     if row.optional:
         args = _no_none(args, row.optional)
     lead = row.lead
-    getattr(_AMD, row.twin)(*args[:lead], o[0], o[1], *args[lead + (row.fmt == "mxf8" and row.dtype is None):])
+    getattr(torch.ops.qutlass_amd_mxf6 if row.fmt == "mxf6" else _AMD, row.twin)(*args[:lead], o[0], o[1], *args[lead + (row.fmt == "mxf8" and row.dtype is None):])
     return o
 
 
