@@ -10,6 +10,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_mxf8_bf16_tn                      (extension: the same for MXFP8, e4m3 or e5m2 tokens)
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
     grouped_matmul_mxf8_mxf4_bf16_tn, matmul_mxf8_mxf4_bf16_tn  (extension: W4A8 -- MXFP8 tokens against MXFP4 expert weights as stored; the dense form is E = 1)
+    grouped_matmul_mxf8_mxf4_silu_mxf8_tn, grouped_matmul_mxf8_mxf4_swiglu_oai_mxf8_tn  (extension: the W4A8 gate/up GEMM with the activation and the MXFP8 quantizer fused in)
     grouped_matmul_mxf6_mxf4_bf16_tn, matmul_mxf6_mxf4_bf16_tn  (extension: W4A6 -- MXFP6 (e2m3) tokens against the same weights: W4A8's accuracy class at 3/4 of its token bytes)
     fusedQuantizeMxf6, fusedGatherQuantizeMxf6            (extension: the MXFP6 quantizers -- the A operand of the W4A6 GEMM)
     grouped_matmul_bf16_mxf4_bf16_tn, matmul_bf16_mxf4_bf16_tn  (extension: W4A16 -- bf16 tokens against the same weights, optionally gathered by src_row in the GEMM)
@@ -160,6 +161,67 @@ def matmul_mxf8_mxf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tenso
     _check_w4a8_operands("matmul_mxf8_mxf4_bf16_tn", a, b, a_sf, b_sf, 2)
     offs = torch.full((1,), a.size(0), dtype=torch.int32, device=a.device)
     return _ops_amd.grouped_matmul_mxf8_mxf4(a, b.unsqueeze(0), a_sf, b_sf, alpha, offs)
+
+
+def _check_w4a8_act(op: str, a, b, a_sf, b_sf, bias=None) -> None:
+    """the rejections of the fused gate/up W4A8 ops that need no device, in the manner of _check_w4a8_operands (which they start with)"""
+    _check_w4a8_operands(op, a, b, a_sf, b_sf, 3)
+    if b.size(1) % 64:
+        raise ValueError(f"{op}: b must be (E, 2 * I, K/2) with I a multiple of 32, whole scale groups of the output (got 2 * I = {b.size(1)})")
+    if a.size(1) % 128:
+        raise ValueError(f"{op}: K must be a multiple of 128 (got {a.size(1)})")
+    if not 1 <= b.size(0) <= 1024:
+        raise ValueError(f"{op}: the number of experts must be in [1, 1024] (got {b.size(0)})")
+    if bias is not None:
+        if bias.dtype != torch.bfloat16:
+            raise ValueError(f"{op}: bias must be bfloat16 (got {bias.dtype})")
+        if bias.dim() != 2 or tuple(bias.shape) != (b.size(0), b.size(1)):
+            raise ValueError(f"{op}: bias must be (E, 2 * I) = ({b.size(0)}, {b.size(1)}) (got {tuple(bias.shape)})")
+
+
+def grouped_matmul_mxf8_mxf4_silu_mxf8_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor,
+                                          offs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): the gate/up GEMM of a W4A8 expert layer with silu(gate) * up and the MXFP8 quantizer fused into its epilogue, ONE launch.
+    For well-formed offs the result equals, byte for byte in every row below offs[E-1], the chain
+
+        fusedSiluMulQuantizeMxf8(grouped_matmul_mxf8_mxf4_bf16_tn(a, b, a_sf, b_sf, alpha, offs), eye(32))
+
+    and the (M, 2 I) bf16 tensor between those two launches is never written.  Operands as grouped_matmul_mxf8_mxf4_bf16_tn's, with b (E, 2 I, K/2): rows [0, I) of an
+    expert the gate projection, rows [I, 2 I) the up projection (utils.split_interleaved_gate_up's halves).  Returns (codes, scales): float8_e4m3fn (M, I) and
+    float8_e8m0fnu (padded_rows, padded_cols) as fusedQuantizeMxf8 allocates them for an (M, I) tensor -- scales flat in the first M * I / 32 bytes -- so the pair is
+    the down GEMM's A operand as it is.  Rows at or past offs[E-1] are written in neither; both are allocated without a fill.  An activation of -0 is stored as the
+    +0 code, as the chain's rotation leaves it.  Outside the equality (never a fault): groups whose activations are not finite (the chain's rotation spreads a NaN over
+    the group of 32), and malformed offs.  I % 32 == 0, K % 128 == 0, 1 <= E <= 1024, e4m3 tokens only; the sizes as the GEMM op's.  The offsets are read on the
+    device: no host sync, graph-capturable, traces under torch.compile.
+
+    A workgroup owns 32 activation columns -- the 32 gate and the 32 up weight rows -- over 32 or 64 token rows.  Measured against the two
+    launches (profiles/bench_grouped_w4a8_act_mi355x.txt; 16 / 64 / 4096 tokens): gpt-oss-20b 1.03-1.11 / 1.01 / 1.33-1.34x, gpt-oss-120b 1.17-1.38 / 1.01-1.07 /
+    1.33-1.34x, Qwen3-30B-A3B 1.32-1.47 / 1.18-1.25 / 1.43x, Mixtral-8x7B 1.16-1.18 / 1.18-1.22 / 1.36x.  **SLOWER than the two launches in five cells of
+    the sweep** (profiles/calib_grouped_w4a8_act.txt, 128 experts, I = 1024: **0.69 / 0.88 / 0.99x at K = 1280 and 16 / 32 / 64 rows per expert, 0.70 / 0.91x at
+    K = 1536 and 16 / 32 rows**; 48 and 128 rows win at both K: three 8.5 KiB slots per wave leave one workgroup per CU where the GEMM op keeps two) and level at K = 768 / 1024 (1.00-1.04x);
+    at gpt-oss-20b decode it is slower than the GEMM op ALONE (0.94x) and ahead only by the launch it saves.  DESIGN.md section 8 item 17."""
+    _check_w4a8_act("grouped_matmul_mxf8_mxf4_silu_mxf8_tn", a, b, a_sf, b_sf)
+    return _ops_amd.grouped_matmul_mxf8_mxf4_act_mxf8(a, b, a_sf, b_sf, alpha, offs, 0, 1.0, 1.0, None)
+
+
+def grouped_matmul_mxf8_mxf4_swiglu_oai_mxf8_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor, *,
+                                                act_alpha: float = 1.702, limit: float = 7.0, bias: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): grouped_matmul_mxf8_mxf4_silu_mxf8_tn with gpt-oss's clamped SwiGLU in place of silu * up.  For well-formed offs the
+    result equals, byte for byte in every row below offs[E-1], the chain
+
+        fusedSwigluOaiQuantizeMxf8(grouped_matmul_mxf8_mxf4_bf16_tn(a, b, a_sf, b_sf, alpha, offs), eye(32), alpha=act_alpha, limit=limit, bias=bias, offs=offs)
+
+    bias (E, 2 I) bf16 in the weight's [gate | up] halves, or None; the bias row is that of the tile's expert (for well-formed offs: the row's).  act_alpha finite
+    and > 0, limit > 0 and exact in bf16, as in swiglu_oai_and_mul.  Everything else -- operands, results, the rows that are not written, signed zero, what lies
+    outside the equality, the measurements and the cells where it LOSES -- as grouped_matmul_mxf8_mxf4_silu_mxf8_tn."""
+    op = "grouped_matmul_mxf8_mxf4_swiglu_oai_mxf8_tn"
+    _check_w4a8_act(op, a, b, a_sf, b_sf, bias)
+    act_alpha, limit = float(act_alpha), float(limit)
+    if not (act_alpha > 0 and act_alpha < float("inf")):
+        raise ValueError(f"{op}: act_alpha must be finite and > 0 (got {act_alpha})")
+    if not (limit > 0 and limit < float("inf") and _bf16_exact(limit)):
+        raise ValueError(f"{op}: limit must be > 0, finite and exactly representable in bf16 (got {limit})")
+    return _ops_amd.grouped_matmul_mxf8_mxf4_act_mxf8(a, b, a_sf, b_sf, alpha, offs, 1, act_alpha, limit, bias)
 
 
 def _check_w4a6_operands(op: str, a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, b_dim: int) -> None:

@@ -25,6 +25,7 @@
 #include "gemm_mx_os_w4a8.hip.h"
 #include "gemm_mx_os_w4a16.hip.h"
 #include "gemm_mx_os_w4a6.hip.h"
+#include "gemm_mx_os_w4a8_act.hip.h"
 #include "gemm_mx_fusedq.hip.h"
 #include "gemm_nvf4.hip.h"
 #include "gemm_nvf4_pk.hip.h"
@@ -589,6 +590,54 @@ int launch_grouped_w4a6(int v, const GroupedParams& q, hipStream_t s)
   if (v == F.form0 + 1) return launch_grouped_w4a6_os<1>(q, s);
   if (v == F.form0 + 2) return launch_grouped_w4a6_os<2>(q, s);
   return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+}
+#else
+;
+#endif
+
+// ---- gate/up W4A8 GEMM with fused activation and MXFP8 output (gemm_mx_os_w4a8_act.hip.h) ------------------------------------------------------------------------------
+// Forms: 614 = 32 rows x 32 activation columns, 615 = 64 x 32 (a workgroup owns the 32 gate AND the 32 up weight rows of its columns; one shot while a tile's K extent
+// fits the LDS, wave-owned rings beyond).  N is the weight's 2 I rows.
+// Started from W4A8's structure (grouped_w4a8_plan) with its K threshold rescaled by the stage size -- there 604 takes over where the 32-row tile's stages of a wave stop
+// fitting two workgroups per CU (three slots of 6.5 KiB x 4 waves = 78 KiB); the 8.5 KiB stage of this kernel keeps two workgroups up to two slots, K = 1024 (68 KiB;
+// three are 102 KiB).  Measured with both forms forced on the gate/up cells of gpt-oss-20b / 120b, Qwen3-30B-A3B and Mixtral-8x7B and on a sweep of 16 ... 128 rows per
+// expert at K = 768 ... 2944 (profiles/calib_grouped_w4a8_act.txt, taken under that rule): it picks the faster form in every cell but one -- up to K = 1024 614 leads at
+// every row count (K = 1024, 128 rows: 265.6 us against 306.1), from K = 1280 on 615 leads from 32 rows (K = 1280: 141.1 against 176.9; Mixtral prefill 3220.6 against
+// 5224.5) and 614 at 16 rows (K = 2944: 193.5 against 200.5); the one miss is Mixtral decode64 skewed (614 at 224.2 against 218.1, 2.8 %).  So the rule stayed:
+// mean rows per group M / E >= 32 and K > 1024 -> 615, otherwise 614.
+inline int grouped_w4a8_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M >= 32 * E && K > 1024) ? 615 : 614;
+}
+// form GRP_MXF8_MXF4_ACT.form0 + I with activation ACT: the one-shot ladder up to 4 SMAX stages, wave-owned rings of SMAX slots beyond -- 4 slots per wave for the 32-row
+// tile (one shot up to K = 2048), 3 for the 64-row tile (K = 1536)
+template <int I, int ACT>
+int launch_grouped_w4a8_act_os(W4A8ActParams q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_MXF8_MXF4_ACT;
+  constexpr int TM = F.tile[I].tm, SMAX = os_w4a8_act_smax(TM);
+  static_assert(F.tile[I].tn == 32 && (SMAX == 3 || SMAX == 4), "one scale group of activation columns; the ladder below");
+  q.tiles_m = 1;
+  q.tiles_n = q.inter / 32;
+  const int64_t KT = q.K / 128;
+  const dim3 grid((int)grouped_workgroups(q.M, q.inter, q.E, TM, 32)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_w4a8_act_kernel<OsW4A8ActCfg<1, TM>, ACT, false>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_w4a8_act_kernel<OsW4A8ActCfg<2, TM>, ACT, false>), grid, block, 0, s, q);
+  else if (KT <= 12) hipLaunchKernelGGL((gemm_mx_os_w4a8_act_kernel<OsW4A8ActCfg<3, TM>, ACT, false>), grid, block, 0, s, q);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_w4a8_act_kernel<OsW4A8ActCfg<SMAX, TM>, ACT, false>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_w4a8_act_kernel<OsW4A8ActCfg<SMAX, TM>, ACT, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  return check_launch("gemm_mx_os_w4a8_act_kernel");
+}
+// form v of the fused op, act = ACT_SILU / ACT_OAI / ACT_OAI_BIAS (quantize.hip.h); its kernels ride in the persistent NVFP4 kernel's unit beside W4A8's, W4A16's and W4A6's
+int launch_grouped_w4a8_act(int v, int act, const W4A8ActParams& q, hipStream_t s)
+#if QAMD_DEF(8)
+{
+  constexpr const GroupedFormat& F = GRP_MXF8_MXF4_ACT;
+  static_assert(F.nforms == 2 && F.ebits == 8 && F.ebits_b == 4, "the two forms of the fused gate/up kernel");
+  if (v != F.form0 && v != F.form0 + 1) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+  const bool tall = v == F.form0 + 1;
+  if (act == ACT_SILU) return tall ? launch_grouped_w4a8_act_os<1, ACT_SILU>(q, s) : launch_grouped_w4a8_act_os<0, ACT_SILU>(q, s);
+  if (act == ACT_OAI) return tall ? launch_grouped_w4a8_act_os<1, ACT_OAI>(q, s) : launch_grouped_w4a8_act_os<0, ACT_OAI>(q, s);
+  return tall ? launch_grouped_w4a8_act_os<1, ACT_OAI_BIAS>(q, s) : launch_grouped_w4a8_act_os<0, ACT_OAI_BIAS>(q, s);
 }
 #else
 ;
@@ -1840,6 +1889,37 @@ int qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn(const void* A, const void* B, c
   return launch_grouped_w4a8(grouped_form(F, grouped_w4a8_plan, M, N, K, E), q, (hipStream_t)stream);
 }
 
+// the gate/up W4A8 GEMM whose output is the down GEMM's A operand: B (E, N = 2 I, K/2) [gate | up], act 0 = silu(gate) * up, 1 = the clamped SwiGLU with act_alpha, limit
+// and the optional bias (E, 2 I) bf16 (both unread for act 0); out_fp8 (M, I) e4m3, out_e8m0 flat (M, I / 32)
+static int swiglu_oai_act(const char* name, float alpha, float limit, SwigluOaiAct& a);   // (the OAI quantizer entry's checks, below)
+static int swiglu_oai_check_bias(const char* name, const void* bias, const int32_t* offs, int64_t e);
+int qutlass_amd_grouped_matmul_mxf8_mxf4_act_mxf8_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                                     const int32_t* offs, int act, float act_alpha, float limit, const void* bias, void* out_fp8, void* out_e8m0,
+                                                     int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_MXF8_MXF4_ACT;
+  if (!out_e8m0) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", F.name);
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, out_fp8, M, N, K, E)) return rc;
+  if (N % 64) return fail(QAMD_ERR_INVALID, "%s: N = 2 * I must be a multiple of 64, whole scale groups of 32 activation columns (got %lld)", F.name, (long long)N);
+  if (act != 0 && act != 1) return fail(QAMD_ERR_INVALID, "%s: invalid act %d; expected 0 (silu) or 1 (swiglu_oai)", F.name, act);
+  if ((uintptr_t)out_fp8 % 8) return fail(QAMD_ERR_INVALID, "%s: out_fp8 must be 8-byte aligned", F.name);
+  W4A8ActParams q;
+  q.oai = {};
+  if (act == 1) {
+    if (int rc = swiglu_oai_act(F.name, act_alpha, limit, q.oai)) return rc;
+    if (bias) {
+      if (int rc = swiglu_oai_check_bias(F.name, bias, offs, E)) return rc;
+      if (E * N >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: bias (E * N * 2 = %lld bytes) must stay below 2 GiB", F.name, (long long)(E * N * 2));
+    }
+  } else if (bias) {
+    return fail(QAMD_ERR_INVALID, "%s: act 0 (silu) takes no bias", F.name);
+  }
+  if (M == 0) return QAMD_OK;
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, out_fp8, M, N, K, E);
+  grouped_mx_defaults(q);
+  q.codes = (uint8_t*)out_fp8; q.out_sf = (uint8_t*)out_e8m0; q.bias = (const uint16_t*)bias; q.inter = (int)(N / 2);
+  return launch_grouped_w4a8_act(grouped_form(F, grouped_w4a8_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI, q, (hipStream_t)stream);
+}
+
 // W4A6: A (M, 3K/4) packed e2m3 codes, everything else as W4A8
 int qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
                                                  const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
@@ -2846,6 +2926,15 @@ int qutlass_amd_debug_grouped_bf16_mxf4_plan(int64_t M, int64_t N, int64_t K, in
 // grouped_matmul_mxf6_mxf4_bf16_tn: 610 = 32x32, 612 = 64x32 tiles of the 6-bit-token wave-owned kernel
 int qutlass_amd_debug_grouped_mxf6_mxf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
   return debug_grouped_plan(GRP_MXF6_MXF4, "debug_grouped_mxf6_mxf4_plan", grouped_w4a6_plan, M, N, K, E, out);
+}
+// grouped_matmul_mxf8_mxf4_act_mxf8_tn: 614 = 32 rows x 32 activation columns, 615 = 64 x 32; out[0] = (cdiv(M, TM) + E) * (I / 32) workgroups, N = 2 I
+int qutlass_amd_debug_grouped_mxf8_mxf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  constexpr const GroupedFormat& F = GRP_MXF8_MXF4_ACT;
+  alignas(16) static char dummy[16];
+  if (grouped_check(F, "debug_grouped_mxf8_mxf4_act_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E) || N % 64) return -1;
+  const int v = grouped_w4a8_act_plan(M, N, K, E, 256);
+  if (out) out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
+  return v;
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel
 int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {

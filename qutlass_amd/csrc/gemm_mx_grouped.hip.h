@@ -58,6 +58,9 @@ constexpr GroupedFormat GRP_MXF8_MXF4{"grouped_matmul_mxf8_mxf4_bf16_tn", 602, 8
 constexpr GroupedFormat GRP_BF16_MXF4{"grouped_matmul_bf16_mxf4_bf16_tn", 606, 16, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
 // W4A6: e2m3 tokens, four codes in three bytes (an A row is 3 K / 4 bytes), against e2m1 weights (gemm_mx_os_w4a6.hip.h) -- the three wave-owned forms, no ring form
 constexpr GroupedFormat GRP_MXF6_MXF4{"grouped_matmul_mxf6_mxf4_bf16_tn", 610, 6, 32, {{32, 32}, {32, 16}, {64, 32}, {0, 0}}, 3, 4};
+// gate/up W4A8 with fused activation and MXFP8 output (gemm_mx_os_w4a8_act.hip.h): two forms, the tile width counts ACTIVATION columns (a workgroup reads the 32 gate and
+// the 32 up weight rows that go with them); 613 stays free as W4A6's fourth slot
+constexpr GroupedFormat GRP_MXF8_MXF4_ACT{"grouped_matmul_mxf8_mxf4_act_mxf8_tn", 614, 8, 32, {{32, 32}, {64, 32}, {0, 0}, {0, 0}}, 2, 4};
 // workgroups of a grouped launch: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles (grouped_tile: the rest return at once)
 constexpr int64_t grouped_workgroups(int64_t M, int64_t N, int64_t E, int TM, int TN) { return ((M + TM - 1) / TM + E) * ((N + TN - 1) / TN); }
 

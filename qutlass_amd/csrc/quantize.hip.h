@@ -256,6 +256,17 @@ __device__ __forceinline__ float e4m3_decode_pos(uint32_t b) {
   return e ? __uint_as_float(((e + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
 }
 
+// The MXFP8 block scale of a group whose abs-max is m >= +0 (NaNs already dropped): e8 = 127 if m == 0, else max(E - SH, 0) with E the exponent field of the FP32 m and
+// SH = 7 (e4m3) / 14 (e5m2); returns the multiplier 2^(127 - e8), a normal number for every e8 the rule gives.  ONE definition for the FP8 arm of the quantizers and for
+// the GEMM epilogue that writes the same bytes (gemm_mx_os_w4a8_act.hip.h).
+template <int FMT>
+__device__ __forceinline__ float mxf8_block_scale(float m, uint32_t& e8) {
+  constexpr int SH = FMT == QF_E4M3 ? 7 : 14;
+  const int ex = (int)(__float_as_uint(m) >> 23) - SH;   // m >= +0: no sign bit above the exponent field
+  e8 = m == 0.f ? 127u : (uint32_t)(ex < 0 ? 0 : ex);
+  return __uint_as_float((254u - e8) << 23);
+}
+
 // --- gated-MLP activation --------------------------------------------------------------------------
 // act = bf16_rne(float(s) * float(u)), s = bf16_rne(g / (1 + exp(-g))): what a model that runs `silu(gate) * up` in bf16 computes.  s is the CORRECTLY rounded bf16 of
 // silu(g): a mis-rounded s (fp32 arithmetic misses a bf16 tie about once in 2^11 values) is off by up to 2^-8 of its value, which can come out as TWO bf16 steps of
@@ -917,16 +928,15 @@ __device__ __forceinline__ void fused_quantize_body(const QuantParams& p, const 
 #pragma unroll
         for (int r = 0; r < 16; ++r) m = fmaxf(m, fabsf(acc[r]));
         m = xhalf_max(m);
-        constexpr int SH = FMT == QF_E4M3 ? 7 : 14;
-        const int ex = (int)(__float_as_uint(m) >> 23) - SH;   // m >= +0: no sign bit above the exponent field
-        const uint32_t e8 = m == 0.f ? 127u : (uint32_t)(ex < 0 ? 0 : ex);
+        uint32_t e8;
+        const float mul8 = mxf8_block_scale<FMT>(m, e8);
         // q = RNE(y * 2^(127 - e8)).  The scaling is an fp32 MULTIPLY in front of a unit-scale convert, not the converter's scale operand: that operand would be
         // 2^(e8 - 127), which for e8 = 0 (a group whose maximum is below 2^-120 / 2^-113) is 2^-127, an fp32 DENORMAL -- and what the converter makes of a
         // denormal scale is not pinned by anything in this tree (tests/native/cvt_scale_probe.hip covers the fp4 converter with normal scales only).  The
         // multiplier 2^(127 - e8) is a normal number for every e8 the rule can give (e8 in [0, 248]: 2^127 ... 2^-121), so the product is exact unless it
         // falls below 2^-126 -- far under half the formats' smallest subnormals (2^-10, 2^-17), where it rounds to (signed) zero either way.  -0 keeps its sign.
         float t[16];
-        scale_pk<16>(acc, 0, __uint_as_float((254u - e8) << 23), t);
+        scale_pk<16>(acc, 0, mul8, t);
         // acc[4 q + e] = element 8 q + 4 half + e of the group: dword 2 q + half of its 32 bytes.  Half 0 keeps its dwords 0 and 2 and takes 1 and 3 from the
         // partner lane, half 1 keeps 5 and 7 and takes 4 and 6: 8 of a lane's 16 bytes change hands, 4 per v_permlane32_swap each way -- two swaps (the e2m1 arm
         // moves 4 of 8 bytes and needs one), then one 16-byte store per lane: the group is one 32-byte run.
