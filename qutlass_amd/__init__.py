@@ -11,6 +11,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_nvf4_bf16_tn                      (extension: the same for NVFP4, row-major e4m3 scales per 16 elements)
     grouped_matmul_mxf8_mxf4_bf16_tn, matmul_mxf8_mxf4_bf16_tn  (extension: W4A8 -- MXFP8 tokens against MXFP4 expert weights as stored; the dense form is E = 1)
     grouped_matmul_mxf8_mxf4_silu_mxf8_tn, grouped_matmul_mxf8_mxf4_swiglu_oai_mxf8_tn  (extension: the W4A8 gate/up GEMM with the activation and the MXFP8 quantizer fused in)
+    grouped_matmul_mxf4_silu_mxf4_tn, grouped_matmul_mxf4_swiglu_oai_mxf4_tn  (extension: the MXFP4 (W4A4) gate/up GEMM with the activation, the rotation and the MXFP4 quantizer fused in)
     grouped_matmul_mxf6_mxf4_bf16_tn, matmul_mxf6_mxf4_bf16_tn  (extension: W4A6 -- MXFP6 (e2m3) tokens against the same weights: W4A8's accuracy class at 3/4 of its token bytes)
     fusedQuantizeMxf6, fusedGatherQuantizeMxf6            (extension: the MXFP6 quantizers -- the A operand of the W4A6 GEMM)
     grouped_matmul_bf16_mxf4_bf16_tn, matmul_bf16_mxf4_bf16_tn  (extension: W4A16 -- bf16 tokens against the same weights, optionally gathered by src_row in the GEMM)
@@ -222,6 +223,91 @@ def grouped_matmul_mxf8_mxf4_swiglu_oai_mxf8_tn(a: torch.Tensor, b: torch.Tensor
     if not (limit > 0 and limit < float("inf") and _bf16_exact(limit)):
         raise ValueError(f"{op}: limit must be > 0, finite and exactly representable in bf16 (got {limit})")
     return _ops_amd.grouped_matmul_mxf8_mxf4_act_mxf8(a, b, a_sf, b_sf, alpha, offs, 1, act_alpha, limit, bias)
+
+
+def _check_mxf4_act(op: str, a, b, a_sf, b_sf, h, method, bias=None) -> None:
+    """the rejections of the fused gate/up MXFP4 ops that need no device, in the manner of _check_w4a8_act"""
+    for name, t in (("a", a), ("b", b)):
+        if t.dtype not in (torch.uint8, torch.float4_e2m1fn_x2):
+            raise ValueError(f"{op}: {name} must be uint8 or float4_e2m1fn_x2 packed e2m1 (got {t.dtype})")
+    if a.dim() != 2 or b.dim() != 3:
+        raise ValueError(f"{op}: a must be 2D (M, K/2) and b 3D (E, 2 * I, K/2)")
+    if a.size(1) != b.size(2):
+        raise ValueError(f"{op}: inner dimensions must match, a is (M, K/2 = {a.size(1)}) and b (.., K/2 = {b.size(2)})")
+    K = 2 * a.size(1)
+    for name, sf, rows in (("a_sf", a_sf, a.size(0)), ("b_sf", b_sf, b.size(0) * b.size(1))):
+        if sf.dtype != torch.float8_e8m0fnu:
+            raise ValueError(f"{op}: {name} must be float8_e8m0fnu (got {sf.dtype})")
+        if sf.numel() < rows * (K // 32):
+            raise ValueError(f"{op}: {name} has {sf.numel()} elements, the row-major scale layout needs {rows * (K // 32)}")
+    if b.size(1) % 64:
+        raise ValueError(f"{op}: b must be (E, 2 * I, K/2) with I a multiple of 32, whole scale groups of the output (got 2 * I = {b.size(1)})")
+    if K % 128:
+        raise ValueError(f"{op}: K must be a multiple of 128 (got {K})")
+    if not 1 <= b.size(0) <= 1024:
+        raise ValueError(f"{op}: the number of experts must be in [1, 1024] (got {b.size(0)})")
+    if h.dtype != torch.bfloat16:
+        raise ValueError(f"{op}: h must be bfloat16 (got {h.dtype})")
+    if h.dim() != 2 or tuple(h.shape) != (32, 32):
+        raise ValueError(f"{op}: h must be a 32 x 32 rotation (got {tuple(h.shape)}); for any other size run grouped_matmul_mxf4_bf16_tn followed by "
+                         "fusedSiluMulQuantizeMx / fusedSwigluOaiQuantizeMx")
+    if method not in _METHOD_CODE:
+        raise ValueError(f"{op}: invalid method {method!r}; use 'quest' or 'abs_max'")
+    if bias is not None:
+        if bias.dtype != torch.bfloat16:
+            raise ValueError(f"{op}: bias must be bfloat16 (got {bias.dtype})")
+        if bias.dim() != 2 or tuple(bias.shape) != (b.size(0), b.size(1)):
+            raise ValueError(f"{op}: bias must be (E, 2 * I) = ({b.size(0)}, {b.size(1)}) (got {tuple(bias.shape)})")
+
+
+def grouped_matmul_mxf4_silu_mxf4_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor,
+                                     h: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): the gate/up GEMM of an MXFP4 (W4A4) expert layer with silu(gate) * up, the rotation h and the MXFP4 quantizer fused into
+    its epilogue, ONE launch.  For well-formed offs the result equals, byte for byte in every row below offs[E-1], the chain
+
+        fusedSiluMulQuantizeMx(grouped_matmul_mxf4_bf16_tn(a, b, a_sf, b_sf, alpha, offs), h, method=method)
+
+    wherever the GEMM's fp32 sums do not depend on their order, and the (M, 2 I) bf16 tensor between those two launches is never written.  OUTSIDE THAT REGIME a
+    gate/up value may differ from the chain's by one fp32 rounding before its rounding to bf16: the chain's GEMM usually runs its 64x64 ring form, which sums K in
+    sequence, while this kernel adds four wave-owned partial sums as ((w0 + w1) + w2) + w3 (as that GEMM's own small-tile forms do); everything after the bf16
+    gate/up value -- activation, rotation, group statistic, scale, codes -- is the quantizer's arithmetic bit for bit.  Operands as grouped_matmul_mxf4_bf16_tn's,
+    with b (E, 2 I, K/2): rows [0, I) of an expert the gate projection, rows [I, 2 I) the up projection.  h: the quantizer's rotation, bf16, 32 x 32 ONLY (other sizes:
+    the two launches); method "quest" or "abs_max"; no clip mask, no blocked scales.  Returns (codes, scales): uint8 (M, I / 2) packed e2m1 and float8_e8m0fnu
+    (padded_rows, padded_cols) as fusedQuantizeMx allocates them for an (M, I) tensor -- scales flat in the first M * I / 32 bytes -- so the pair is the down GEMM's A
+    operand as it is.  Rows at or past offs[E-1] are written in neither; both are allocated without a fill.  Outside the equality (never a fault): groups whose
+    activations are not finite, and malformed offs.  I % 32 == 0, K % 128 == 0, 1 <= E <= 1024; the sizes as the GEMM op's.  The offsets are read on the device: no
+    host sync, graph-capturable, traces under torch.compile.
+
+    A workgroup owns 32 activation columns -- the 32 gate and the 32 up weight rows -- over 32 or 64 token rows.  Measured against the two
+    launches (profiles/bench_grouped_mxf4_act_mi355x.txt; time of the two launches / time of this op, 16 / 64 / 4096 tokens): **SLOWER ON EVERY MODEL CELL** -- gpt-oss-20b
+    0.72-0.75 / 0.81 / 0.69x, gpt-oss-120b 0.65-0.74 / 0.75-0.78 / 0.72x, Qwen3-30B-A3B 0.68 / 0.68-0.70 / 0.72-0.74x, Mixtral-8x7B 0.80-0.87 / 0.77-0.83 / 0.76-0.77x -- and
+    slower there than the GEMM op ALONE (0.59-0.84x): that op runs its 64x64 ring form on those shapes, this one has decode-sized wave-owned tiles only and one
+    workgroup per CU once K > 1024.  It WINS only at K <= 1024 with up to 32 rows per expert (profiles/calib_grouped_mxf4_act.txt, 128 experts, I = 1024: 1.20-1.23x;
+    64 rows 0.91-1.00x, 128 rows 0.85-0.94x; K >= 1280: 0.54-0.83x).  Use it there, or where the (M, 2 I) bf16 tensor's memory matters more than time.  DESIGN.md
+    section 8 item 18."""
+    _check_mxf4_act("grouped_matmul_mxf4_silu_mxf4_tn", a, b, a_sf, b_sf, h, method)
+    return _ops_amd.grouped_matmul_mxf4_act_mxf4(a, b, a_sf, b_sf, alpha, offs, 0, 1.0, 1.0, None, h, _METHOD_CODE[method])
+
+
+def grouped_matmul_mxf4_swiglu_oai_mxf4_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor,
+                                           h: torch.Tensor, *, method: Literal["quest", "abs_max"] = "quest", act_alpha: float = 1.702, limit: float = 7.0,
+                                           bias: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): grouped_matmul_mxf4_silu_mxf4_tn with gpt-oss's clamped SwiGLU in place of silu * up.  For well-formed offs the result
+    equals, byte for byte in every row below offs[E-1] and in the same regime of exact fp32 sums, the chain
+
+        fusedSwigluOaiQuantizeMx(grouped_matmul_mxf4_bf16_tn(a, b, a_sf, b_sf, alpha, offs), h, method=method, alpha=act_alpha, limit=limit, bias=bias, offs=offs)
+
+    bias (E, 2 I) bf16 in the weight's [gate | up] halves, or None; the bias row is that of the tile's expert (for well-formed offs: the row's).  act_alpha finite
+    and > 0, limit > 0 and exact in bf16, as in swiglu_oai_and_mul.  Everything else -- operands, h, method, results, the rows that are not written, the one fp32
+    rounding outside the exact regime, what lies outside the equality, the measurements and the cells where it LOSES -- as grouped_matmul_mxf4_silu_mxf4_tn."""
+    op = "grouped_matmul_mxf4_swiglu_oai_mxf4_tn"
+    _check_mxf4_act(op, a, b, a_sf, b_sf, h, method, bias)
+    act_alpha, limit = float(act_alpha), float(limit)
+    if not (act_alpha > 0 and act_alpha < float("inf")):
+        raise ValueError(f"{op}: act_alpha must be finite and > 0 (got {act_alpha})")
+    if not (limit > 0 and limit < float("inf") and _bf16_exact(limit)):
+        raise ValueError(f"{op}: limit must be > 0, finite and exactly representable in bf16 (got {limit})")
+    return _ops_amd.grouped_matmul_mxf4_act_mxf4(a, b, a_sf, b_sf, alpha, offs, 1, act_alpha, limit, bias, h, _METHOD_CODE[method])
 
 
 def _check_w4a6_operands(op: str, a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, b_dim: int) -> None:

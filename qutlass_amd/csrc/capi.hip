@@ -26,6 +26,7 @@
 #include "gemm_mx_os_w4a16.hip.h"
 #include "gemm_mx_os_w4a6.hip.h"
 #include "gemm_mx_os_w4a8_act.hip.h"
+#include "gemm_mx_os_mxf4_act.hip.h"
 #include "gemm_mx_fusedq.hip.h"
 #include "gemm_nvf4.hip.h"
 #include "gemm_nvf4_pk.hip.h"
@@ -638,6 +639,59 @@ int launch_grouped_w4a8_act(int v, int act, const W4A8ActParams& q, hipStream_t 
   if (act == ACT_SILU) return tall ? launch_grouped_w4a8_act_os<1, ACT_SILU>(q, s) : launch_grouped_w4a8_act_os<0, ACT_SILU>(q, s);
   if (act == ACT_OAI) return tall ? launch_grouped_w4a8_act_os<1, ACT_OAI>(q, s) : launch_grouped_w4a8_act_os<0, ACT_OAI>(q, s);
   return tall ? launch_grouped_w4a8_act_os<1, ACT_OAI_BIAS>(q, s) : launch_grouped_w4a8_act_os<0, ACT_OAI_BIAS>(q, s);
+}
+#else
+;
+#endif
+
+// ---- gate/up MXFP4 GEMM (W4A4) with fused activation, rotation and MXFP4 output (gemm_mx_os_mxf4_act.hip.h) -------------------------------------------------------------
+// Forms: 616 = 32 rows x 32 activation columns, 617 = 64 x 32 (a workgroup owns the 32 gate AND the 32 up weight rows of its columns; one shot while a tile's K extent
+// fits the LDS, wave-owned rings beyond).  N is the weight's 2 I rows.
+// Started from the slot ladder alone (that header): the fused W4A8 rule's structure -- 617 fetches each weight row once for two m-tiles, so it needs groups that fill its
+// 64 rows halfway -- with the K threshold where the 32-row tile stops fitting more than one workgroup per CU: one 12.75 KiB slot per wave is 51 KiB (three per CU), two are
+// 102 KiB (one per CU), so K = 1024.  Measured with both forms forced on the gate/up cells of gpt-oss-20b / 120b, Qwen3-30B-A3B and Mixtral-8x7B and on a sweep of
+// 16 ... 128 rows per expert at K = 768 ... 3328 (profiles/calib_grouped_mxf4_act.txt, taken under that rule): from K = 1280 on 617 leads from 32 rows (K = 1280: 117.6 us
+// against 146.2; gpt-oss-20b prefill 943.7 against 1397.7) and 616 at 16 rows (K = 3072: 148.2 against 169.4); up to K = 1024 616 leads up to 64 rows (K = 768, 32 rows:
+// 54.7 against 60.3) -- but at 128 rows 617 is ahead there too (K = 768: 140.5 against 145.3; K = 1024: 148.9 against 154.9), which the started rule missed.  Refitted:
+// mean rows per group M / E >= 128, or M / E >= 32 and K > 1024 -> 617, otherwise 616.  One miss is left: Mixtral decode64 skewed (616 at 180.3 against 174.8, 3 %).
+inline int grouped_mxf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M >= 128 * E || (M >= 32 * E && K > 1024)) ? 617 : 616;
+}
+// form GRP_MXF4_ACT.form0 + I with activation ACT and quantizer METHOD: the one-shot ladder up to 4 SMAX stages of 256 elements, wave-owned rings of SMAX slots beyond -- 3
+// slots per wave for the 32-row tile (one shot up to K = 3072), 2 for the 64-row tile (K = 2048)
+template <int I, int ACT, int METHOD>
+int launch_grouped_mxf4_act_os(Mxf4ActParams q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_MXF4_ACT;
+  constexpr int TM = F.tile[I].tm, SMAX = os_mxf4_act_smax(TM);
+  static_assert(F.tile[I].tn == 32 && (SMAX == 2 || SMAX == 3), "one scale group of activation columns; the ladder below");
+  q.tiles_m = 1;
+  q.tiles_n = q.inter / 32;
+  const int64_t KT = cdiv(q.K, 256);
+  const dim3 grid((int)grouped_workgroups(q.M, q.inter, q.E, TM, 32)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_mxf4_act_kernel<OsMxf4ActCfg<1, TM>, ACT, METHOD, false>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_mxf4_act_kernel<OsMxf4ActCfg<2, TM>, ACT, METHOD, false>), grid, block, 0, s, q);
+  else if (KT <= 4 * SMAX) hipLaunchKernelGGL((gemm_mx_os_mxf4_act_kernel<OsMxf4ActCfg<SMAX, TM>, ACT, METHOD, false>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_mxf4_act_kernel<OsMxf4ActCfg<SMAX, TM>, ACT, METHOD, true>), grid, block, 0, s, q);   // wave-owned rings of SMAX slots
+  return check_launch("gemm_mx_os_mxf4_act_kernel");
+}
+// form v of the fused op, act = ACT_SILU / ACT_OAI / ACT_OAI_BIAS, method = METHOD_QUEST / METHOD_ABSMAX (quantize.hip.h); its kernels ride in the MXFP8
+// variants' unit (3), the shortest of the parallel build
+int launch_grouped_mxf4_act(int v, int act, int method, const Mxf4ActParams& q, hipStream_t s)
+#if QAMD_DEF(3)
+{
+  constexpr const GroupedFormat& F = GRP_MXF4_ACT;
+  static_assert(F.nforms == 2 && F.ebits == 4 && F.ebits_b == 0, "the two forms of the fused gate/up kernel");
+  if (v != F.form0 && v != F.form0 + 1) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+  const bool tall = v == F.form0 + 1;
+  auto go = [&](auto a, auto m) {
+    constexpr int A = decltype(a)::value, Mth = decltype(m)::value;
+    return tall ? launch_grouped_mxf4_act_os<1, A, Mth>(q, s) : launch_grouped_mxf4_act_os<0, A, Mth>(q, s);
+  };
+  auto by_method = [&](auto a) { return method == METHOD_QUEST ? go(a, std::integral_constant<int, METHOD_QUEST>{}) : go(a, std::integral_constant<int, METHOD_ABSMAX>{}); };
+  if (act == ACT_SILU) return by_method(std::integral_constant<int, ACT_SILU>{});
+  if (act == ACT_OAI) return by_method(std::integral_constant<int, ACT_OAI>{});
+  return by_method(std::integral_constant<int, ACT_OAI_BIAS>{});
 }
 #else
 ;
@@ -1920,6 +1974,40 @@ int qutlass_amd_grouped_matmul_mxf8_mxf4_act_mxf8_tn(const void* A, const void* 
   return launch_grouped_w4a8_act(grouped_form(F, grouped_w4a8_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI, q, (hipStream_t)stream);
 }
 
+// the gate/up MXFP4 GEMM whose output is the down GEMM's A operand: everything of the fused W4A8 entry above, plus the quantizer's rotation h (rot x rot bf16, rot = 32
+// only) and method; out_e2m1 (M, I / 2) e2m1, out_e8m0 flat (M, I / 32)
+int qutlass_amd_grouped_matmul_mxf4_act_mxf4_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                                const int32_t* offs, int act, float act_alpha, float limit, const void* bias, const void* h, int rot, int method,
+                                                void* out_e2m1, void* out_e8m0, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_MXF4_ACT;
+  if (!out_e8m0 || !h) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", F.name);
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, out_e2m1, M, N, K, E)) return rc;
+  if (N % 64) return fail(QAMD_ERR_INVALID, "%s: N = 2 * I must be a multiple of 64, whole scale groups of 32 activation columns (got %lld)", F.name, (long long)N);
+  if (rot != 32)
+    return fail(QAMD_ERR_INVALID, "%s: rotation size %d is not supported; expected 32 (use grouped_matmul_mxf4_bf16_tn followed by the fused activation quantizer)", F.name, rot);
+  if (int rc = quant_check_method(F.name, method)) return rc;
+  if (act != 0 && act != 1) return fail(QAMD_ERR_INVALID, "%s: invalid act %d; expected 0 (silu) or 1 (swiglu_oai)", F.name, act);
+  if ((uintptr_t)out_e2m1 % 8) return fail(QAMD_ERR_INVALID, "%s: out_e2m1 must be 8-byte aligned", F.name);
+  if ((uintptr_t)h % 2) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 2-byte aligned", F.name);
+  Mxf4ActParams q;
+  q.oai = {};
+  if (act == 1) {
+    if (int rc = swiglu_oai_act(F.name, act_alpha, limit, q.oai)) return rc;
+    if (bias) {
+      if (int rc = swiglu_oai_check_bias(F.name, bias, offs, E)) return rc;
+      if (E * N >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: bias (E * N * 2 = %lld bytes) must stay below 2 GiB", F.name, (long long)(E * N * 2));
+    }
+  } else if (bias) {
+    return fail(QAMD_ERR_INVALID, "%s: act 0 (silu) takes no bias", F.name);
+  }
+  if (M == 0) return QAMD_OK;
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, out_e2m1, M, N, K, E);
+  grouped_mx_defaults(q);
+  q.codes = (uint8_t*)out_e2m1; q.out_sf = (uint8_t*)out_e8m0; q.bias = (const uint16_t*)bias; q.h = (const uint16_t*)h; q.inter = (int)(N / 2);
+  return launch_grouped_mxf4_act(grouped_form(F, grouped_mxf4_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI,
+                                 method == QAMD_METHOD_QUEST ? METHOD_QUEST : METHOD_ABSMAX, q, (hipStream_t)stream);
+}
+
 // W4A6: A (M, 3K/4) packed e2m3 codes, everything else as W4A8
 int qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
                                                  const int32_t* offs, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
@@ -2934,6 +3022,20 @@ int qutlass_amd_debug_grouped_mxf8_mxf4_act_plan(int64_t M, int64_t N, int64_t K
   if (grouped_check(F, "debug_grouped_mxf8_mxf4_act_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E) || N % 64) return -1;
   const int v = grouped_w4a8_act_plan(M, N, K, E, 256);
   if (out) out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
+  return v;
+}
+// grouped_matmul_mxf4_act_mxf4_tn: 616 = 32 rows x 32 activation columns, 617 = 64 x 32; out[0] = (cdiv(M, TM) + E) * (I / 32) workgroups, N = 2 I; out[1], out[2] =
+// the largest K forms 616 and 617 run in one shot (their rings start at the next multiple of 128)
+int qutlass_amd_debug_grouped_mxf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  constexpr const GroupedFormat& F = GRP_MXF4_ACT;
+  alignas(16) static char dummy[16];
+  if (grouped_check(F, "debug_grouped_mxf4_act_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E) || N % 64) return -1;
+  const int v = grouped_mxf4_act_plan(M, N, K, E, 256);
+  if (out) {
+    out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
+    out[1] = os_mxf4_act_one_shot_k(F.tile[0].tm);
+    out[2] = os_mxf4_act_one_shot_k(F.tile[1].tm);
+  }
   return v;
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel

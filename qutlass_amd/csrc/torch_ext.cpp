@@ -326,6 +326,51 @@ std::tuple<Tensor, Tensor> grouped_matmul_mxf8_mxf4_act_mxf8(const Tensor& A, co
   return {codes, scales};
 }
 
+// EXTENSION: the gate/up MXFP4 (W4A4) grouped GEMM with fused activation, rotation and MXFP4 output (qutlass_amd_grouped_matmul_mxf4_act_mxf4_tn) -- A, B (E, 2 I, K/2), the
+// scales, alpha, offs as grouped_matmul_mxf4's; act, act_alpha, limit, bias as grouped_matmul_mxf8_mxf4_act_mxf8's; h the quantizer's (R, R) bf16 rotation, R = 32 only;
+// method 0 = quest, 1 = abs_max.  Allocates, without a fill, the codes (M, I / 2) uint8 and the scales as fusedQuantizeMx allocates them for an (M, I) tensor.
+std::tuple<Tensor, Tensor> grouped_matmul_mxf4_act_mxf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs,
+                                                        int64_t act, double act_alpha, double limit, std::optional<Tensor> bias, const Tensor& h, int64_t method) {
+  const char* op = "grouped_matmul_mxf4_act_mxf4";
+  check_tensors(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}, {h, "h"}});
+  STD_TORCH_CHECK(has_dtype(A, ScalarType::Byte) || has_dtype(A, ScalarType::Float4_e2m1fn_x2), op, ": A must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), op, ": B must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(A_sf, ScalarType::Float8_e8m0fnu), "A_sf must be float8_e8m0fnu");
+  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e8m0fnu), "B_sf must be float8_e8m0fnu");
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, "A must be 2D (M, K/2) and B 3D (E, 2I, K/2)");
+  STD_TORCH_CHECK(A.size(1) == B.size(2), "Inner dimensions must match for A @ B[g].T");
+  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * 2, kb = K / 32, I = N / 2;
+  STD_TORCH_CHECK(N > 0 && N % 64 == 0, op, ": B must have 2 * I rows per expert with I a multiple of 32 (got ", N, ")");
+  STD_TORCH_CHECK(E >= 1 && E <= 1024, "the number of experts must be in [1, 1024] (got ", E, ")");
+  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, "offs must be an int32 tensor of E = ", E, " elements");
+  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), "alpha must be a float32 tensor of 1 or E = ", E, " elements");
+  STD_TORCH_CHECK(A_sf.numel() >= M * kb, "A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * kb);
+  STD_TORCH_CHECK(B_sf.numel() >= E * N * kb, "B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * kb);
+  STD_TORCH_CHECK(has_dtype(h, ScalarType::BFloat16), op, ": h must be bf16");
+  STD_TORCH_CHECK(h.dim() == 2 && h.size(0) == h.size(1), op, ": h must be a square matrix");
+  STD_TORCH_CHECK(act == 0 || act == 1, op, ": act must be 0 (silu) or 1 (swiglu_oai)");
+  STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, "method must be 0 (quest) or 1 (abs_max)");
+  const void* bp = nullptr;
+  if (bias) {
+    STD_TORCH_CHECK(act == 1, op, ": act 0 (silu) takes no bias");
+    const Named a{A, "A"};
+    check_tensors(op, {{*bias, "bias"}}, {}, true, &a);
+    STD_TORCH_CHECK(has_dtype(*bias, ScalarType::BFloat16), "bias must be bf16");
+    STD_TORCH_CHECK(bias->dim() == 2 && bias->size(0) == E && bias->size(1) == N, "bias must be (E, 2I) = (", E, ", ", N, ")");
+    bp = bias->data_ptr();
+  }
+  Tensor codes = torch::stable::new_empty(A, {M, I / 2}, ScalarType::Byte);
+  Tensor scales = torch::stable::new_empty(A_sf, {(M + 127) / 128 * 128, (I / 32 + 3) / 4 * 4});
+  STD_TORCH_CHECK(h.size(0) == 32, op, ": rotation size ", h.size(0), " is not supported; expected 32 (use grouped_matmul_mxf4 followed by the fused activation quantizer)");
+  if (M == 0) return {codes, scales};   // empty batch: nothing to launch
+
+  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
+  check_rc(qutlass_amd_grouped_matmul_mxf4_act_mxf4_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()), alpha.numel(),
+                                                       static_cast<const int32_t*>(offs.data_ptr()), (int)act, (float)act_alpha, (float)limit, bp, h.data_ptr(), (int)h.size(0),
+                                                       (int)method, codes.data_ptr(), scales.data_ptr(), M, N, K, E, current_stream(A)));
+  return {codes, scales};
+}
+
 Tensor matmul_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_ada_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::ADA_MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_nvf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::NVF4>(A, B, A_sf, B_sf, alpha); }
@@ -991,6 +1036,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("grouped_matmul_mxf6_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // W4A6, inference op: in the minimal library too
   m.def("grouped_matmul_bf16_mxf4_bf16_tn(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, Tensor? src_row) -> Tensor");   // W4A16, inference op: in the minimal library too
   m.def("grouped_matmul_mxf8_mxf4_act_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias) -> (Tensor, Tensor)");   // W4A8 gate/up with fused activation, inference op: in the minimal library too
+  m.def("grouped_matmul_mxf4_act_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias, Tensor h, int method) -> (Tensor, Tensor)");   // W4A4 gate/up with fused activation, inference op: in the minimal library too
   m.def("grouped_matmul_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
 }
 
@@ -1062,7 +1108,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CUDA, m) {
   m.impl("grouped_matmul_nvf4", TORCH_BOX(&grouped_matmul_nvf4));
 }
 
-// The functional routing ops, the W4A16 and W4A6 grouped GEMMs and the fused gate/up W4A8 GEMM are registered for no particular device, like the functional ops of qutlass_amd/ops.py (CompositeExplicitAutograd: one kernel whatever
+// The functional routing ops, the W4A16 and W4A6 grouped GEMMs and the fused gate/up W4A8 and W4A4 GEMMs are registered for no particular device, like the functional ops of qutlass_amd/ops.py (CompositeExplicitAutograd: one kernel whatever
 // the tensors' device; their own check_tensors turns a CPU tensor away with the message every op here gives).  The CUDA key stays the list of the ops that fill or
 // allocate one result each, which tests/test_gpu_ext_rejections.py walks.
 STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CompositeExplicitAutograd, m) {
@@ -1071,6 +1117,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CompositeExplicitAutograd, m) {
   m.impl("grouped_matmul_bf16_mxf4_bf16_tn", TORCH_BOX(&grouped_matmul_bf16_mxf4));   // (an optional tensor, as theirs)
   m.impl("grouped_matmul_mxf6_mxf4", TORCH_BOX(&grouped_matmul_mxf6_mxf4));           // W4A6: its rejections are tests/test_gpu_grouped_w4a6.py's
   m.impl("grouped_matmul_mxf8_mxf4_act_mxf8", TORCH_BOX(&grouped_matmul_mxf8_mxf4_act_mxf8));   // its rejections are tests/test_grouped_w4a8_act_cpu.py's
+  m.impl("grouped_matmul_mxf4_act_mxf4", TORCH_BOX(&grouped_matmul_mxf4_act_mxf4));             // its rejections are tests/test_grouped_mxf4_act_cpu.py's
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module
