@@ -26,6 +26,7 @@
 #include "gemm_mx_os_w4a16.hip.h"
 #include "gemm_mx_os_w4a6.hip.h"
 #include "gemm_mx_os_w4a8_act.hip.h"
+#include "gemm_mx_os_w4a16_act.hip.h"
 #include "gemm_mx_os_mxf4_act.hip.h"
 #include "gemm_mx_fusedq.hip.h"
 #include "gemm_nvf4.hip.h"
@@ -692,6 +693,61 @@ int launch_grouped_mxf4_act(int v, int act, int method, const Mxf4ActParams& q, 
   if (act == ACT_SILU) return by_method(std::integral_constant<int, ACT_SILU>{});
   if (act == ACT_OAI) return by_method(std::integral_constant<int, ACT_OAI>{});
   return by_method(std::integral_constant<int, ACT_OAI_BIAS>{});
+}
+#else
+;
+#endif
+
+// ---- gate/up W4A16 GEMM with fused activation and bf16 output (gemm_mx_os_w4a16_act.hip.h) ------------------------------------------------------------------------------
+// Forms: 618 = 32 rows x 32 activation columns, 619 = 64 x 32 (a workgroup owns the 32 gate AND the 32 up weight rows of its columns; one shot up to K = 1024, wave-owned
+// rings of two slots beyond).  N is the weight's 2 I rows.
+// Started from W4A16's rule (mean rows per group M / E >= 32 and K > 512 -> the 64-row form).  Measured with both forms forced on the gate/up cells of gpt-oss-20b / 120b,
+// Qwen3-30B-A3B and Mixtral-8x7B and on a sweep of 16 ... 128 rows per expert at K = 512 ... 2944 (profiles/calib_grouped_w4a16_act.txt, taken under that rule): it was
+// wrong in most of the sweep.  With the weights in registers the 64-row form's second slot costs 128 KiB and one workgroup per CU, and 618 leads at every K up to 128
+// rows per expert (K = 768, 32 rows: 78.9 us against 112.1; K = 1280, 128 rows: 330.6 against 372.1; K = 2944, 64 rows: 308.7 against 335.5, 128 rows: 523.4 against
+// 550.6; gpt-oss-120b prefill, 128 rows: 1518.9 against 1589.6) except 48 rows at K >= 2048, where the two are level (K = 2048: 212.1 against 200.9; K = 2944: 255.2
+// against 251.2).  619 -- each weight fragment converted once for two m-tiles -- leads where the groups are long: Qwen3 prefill (256 rows, K = 2048) 585.7 against
+// 600.7, Mixtral prefill (1024 rows, K = 4096) 3583.4 against 4050.1; gpt-oss-20b prefill (512 rows, K = 2944) is level, 1260.2 against 1245.6.  At K = 512 only 128
+// rows and fewer were measured (618 leads: 117.5 against 136.3), so the K bound of the started rule stays.  Refitted: M / E >= 256 and K > 512 -> 619, otherwise 618.
+// Misses left: gpt-oss-20b prefill (1.2 %) and the two 48-row cells (5 % and 2 %).
+inline int grouped_w4a16_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M >= 256 * E && K > 512) ? 619 : 618;
+}
+// form GRP_BF16_MXF4_ACT.form0 + I with activation ACT: one slot per wave up to K = 512, two up to K = 1024, wave-owned rings of two slots beyond; GATHER: A rows
+// through q.src_row
+template <int I, int ACT, bool GATHER>
+int launch_grouped_w4a16_act_os(W4A16ActParams q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_BF16_MXF4_ACT;
+  constexpr int TM = F.tile[I].tm, SMAX = os_w4a16_act_smax(TM);
+  static_assert(F.tile[I].tn == 32 && SMAX == 2, "32 activation columns; the ladder below");
+  q.tiles_m = 1;
+  q.tiles_n = q.inter / 32;
+  const int64_t KT = q.K / 128;
+  const dim3 grid((int)grouped_workgroups(q.M, q.inter, q.E, TM, 32)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_mx_os_w4a16_act_kernel<OsW4A16ActCfg<1, TM>, ACT, false, GATHER>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_mx_os_w4a16_act_kernel<OsW4A16ActCfg<2, TM>, ACT, false, GATHER>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_mx_os_w4a16_act_kernel<OsW4A16ActCfg<2, TM>, ACT, true, GATHER>), grid, block, 0, s, q);   // wave-owned rings of two slots
+  return check_launch("gemm_mx_os_w4a16_act_kernel");
+}
+// form v of the fused op, act = ACT_SILU / ACT_OAI / ACT_OAI_BIAS (quantize.hip.h); its kernels ride in the persistent NVFP4 kernel's unit beside
+// W4A8's, W4A16's and W4A6's -- the shortest before (22 s compiled alone; 32 s with them, beside 27 s and 30 s for units 5 and 3 and more for 1, 4 and 2: not the
+// longest, so no unit of their own)
+int launch_grouped_w4a16_act(int v, int act, const W4A16ActParams& q, hipStream_t s)
+#if QAMD_DEF(8)
+{
+  constexpr const GroupedFormat& F = GRP_BF16_MXF4_ACT;
+  static_assert(F.nforms == 2 && F.ebits == 16 && F.ebits_b == 4, "the two forms of the fused gate/up kernel");
+  if (v != F.form0 && v != F.form0 + 1) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+  const bool tall = v == F.form0 + 1, gather = q.src_row != nullptr;
+  auto go = [&](auto a) {
+    constexpr int A = decltype(a)::value;
+    if (gather) return tall ? launch_grouped_w4a16_act_os<1, A, true>(q, s) : launch_grouped_w4a16_act_os<0, A, true>(q, s);
+    return tall ? launch_grouped_w4a16_act_os<1, A, false>(q, s) : launch_grouped_w4a16_act_os<0, A, false>(q, s);
+  };
+  if (act == ACT_SILU) return go(std::integral_constant<int, ACT_SILU>{});
+  if (act == ACT_OAI) return go(std::integral_constant<int, ACT_OAI>{});
+  return go(std::integral_constant<int, ACT_OAI_BIAS>{});
 }
 #else
 ;
@@ -2039,6 +2095,39 @@ int qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn(const void* A, const void* B, c
   return launch_grouped_w4a16(grouped_form(F, grouped_w4a16_plan, M, N, K, E), q, (hipStream_t)stream);
 }
 
+// the gate/up W4A16 GEMM whose output is the down GEMM's A operand: A, src_row, T as for the W4A16 entry above, B (E, N = 2 I, K/2) [gate | up], act 0 = silu(gate) * up,
+// 1 = the clamped SwiGLU with act_alpha, limit and the optional bias (E, 2 I) bf16 (both unread for act 0); D (M, I) bf16
+int qutlass_amd_grouped_matmul_bf16_mxf4_act_bf16_tn(const void* A, const void* B, const void* B_sf, const float* alpha, int64_t n_alpha, const int32_t* offs,
+                                                     const int32_t* src_row, int64_t T, int act, float act_alpha, float limit, const void* bias, void* D, int64_t M,
+                                                     int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_BF16_MXF4_ACT;
+  if (int rc = grouped_check(F, F.name, A, B, /* no A scales */ A, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if (N % 64) return fail(QAMD_ERR_INVALID, "%s: N = 2 * I must be a multiple of 64, whole tiles of 32 activation columns (got %lld)", F.name, (long long)N);
+  if (act != 0 && act != 1) return fail(QAMD_ERR_INVALID, "%s: invalid act %d; expected 0 (silu) or 1 (swiglu_oai)", F.name, act);
+  if ((uintptr_t)D % 16) return fail(QAMD_ERR_INVALID, "%s: D must be 16-byte aligned", F.name);
+  if (src_row) {   // the descriptor spans all of A: T rows of 2 K bytes
+    if (T < 0) return fail(QAMD_ERR_INVALID, "%s: T must be >= 0 (got %lld)", F.name, (long long)T);
+    if (T >= ((1ll << 31) - 1) / F.row_bytes(K) + 1) return fail(QAMD_ERR_INVALID, "%s: the gathered token matrix (T * 2K bytes, T=%lld K=%lld) must stay below 2 GiB", F.name, (long long)T, (long long)K);
+  }
+  W4A16ActParams q;
+  q.oai = {};
+  if (act == 1) {
+    if (int rc = swiglu_oai_act(F.name, act_alpha, limit, q.oai)) return rc;
+    if (bias) {
+      if (int rc = swiglu_oai_check_bias(F.name, bias, offs, E)) return rc;
+      if (E * N >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: bias (E * N * 2 = %lld bytes) must stay below 2 GiB", F.name, (long long)(E * N * 2));
+    }
+  } else if (bias) {
+    return fail(QAMD_ERR_INVALID, "%s: act 0 (silu) takes no bias", F.name);
+  }
+  if (M == 0) return QAMD_OK;
+  grouped_fill(q, F, A, B, nullptr, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
+  q.sfa_bytes = 0; q.ldd = (int)(N / 2);
+  grouped_mx_defaults(q);
+  q.src_row = src_row; q.T = src_row ? (int)T : 0; q.bias = (const uint16_t*)bias; q.inter = (int)(N / 2);
+  return launch_grouped_w4a16_act(grouped_form(F, grouped_w4a16_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI, q, (hipStream_t)stream);
+}
+
 // ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
 // Forms: 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles, 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.
 // Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B and on token counts between them (profiles/calib_grouped_nvf4_r7.txt; these are not the MX
@@ -3036,6 +3125,15 @@ int qutlass_amd_debug_grouped_mxf4_act_plan(int64_t M, int64_t N, int64_t K, int
     out[1] = os_mxf4_act_one_shot_k(F.tile[0].tm);
     out[2] = os_mxf4_act_one_shot_k(F.tile[1].tm);
   }
+  return v;
+}
+// grouped_matmul_bf16_mxf4_act_bf16_tn: 618 = 32 rows x 32 activation columns, 619 = 64 x 32; out[0] = (cdiv(M, TM) + E) * (I / 32) workgroups, N = 2 I
+int qutlass_amd_debug_grouped_bf16_mxf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  constexpr const GroupedFormat& F = GRP_BF16_MXF4_ACT;
+  alignas(16) static char dummy[16];
+  if (grouped_check(F, "debug_grouped_bf16_mxf4_act_plan", dummy, dummy, dummy, dummy, (const float*)dummy, 1, (const int32_t*)dummy, dummy, M, N, K, E) || N % 64) return -1;
+  const int v = grouped_w4a16_act_plan(M, N, K, E, 256);
+  if (out) out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
   return v;
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel

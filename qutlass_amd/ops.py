@@ -101,6 +101,10 @@ def _register_fakes() -> None:
     def _(A, B, B_sf, alpha, offs, src_row):   # A (M, K) bf16, or with src_row (M,) the unsorted (T, K) tokens; B (E, N, K/2)
         return A.new_empty(((A if src_row is None else src_row).size(0), B.size(1)), dtype=torch.bfloat16)
 
+    @rf("qutlass_amd::grouped_matmul_bf16_mxf4_act_bf16")
+    def _(A, B, B_sf, alpha, offs, act, act_alpha, limit, bias, src_row):   # B (E, 2 I, K/2): (M, I) bf16, M = src_row's rows when it is given
+        return A.new_empty(((A if src_row is None else src_row).size(0), B.size(1) // 2), dtype=torch.bfloat16)
+
     @rf("qutlass_amd::grouped_matmul_mxf8_mxf4_act_mxf8")
     def _(A, B, A_sf, B_sf, alpha, offs, act, act_alpha, limit, bias):   # B (E, 2 I, K/2): the codes (M, I) and the scales fusedQuantizeMxf8 allocates for them
         M, I = A.size(0), B.size(1) // 2
