@@ -311,6 +311,25 @@ int qutlass_amd_grouped_matmul_bf16_mxf4_act_bf16_tn(const void* A, const void* 
                                                      int64_t N, int64_t K, int64_t E, void* stream);
 
 /*
+ * EXTENSION (no counterpart in the reference): grouped W4A16 GEMM on NVFP4 expert weights -- bf16 tokens, unquantised and without
+ * scales, against NVFP4 weights as a checkpoint stores them, one launch over E experts.
+ * A, src_row, T, offs, the clamping of the offsets and the rows that are not written: as
+ * qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn.  B: (E, N, K/2) packed e2m1.  B_sf: e4m3 (OCP e4m3fn), row-major (E, N, K/16),
+ * 8-byte aligned -- the buffer qutlass_amd_grouped_matmul_nvf4_bf16_tn reads.  alpha: device fp32[n_alpha], n_alpha = 1 or E;
+ * for a checkpoint alpha[g] = 1 / weight_global_scale[g].  D: (M, N) bf16, 16-byte aligned.
+ *   D[r, n] = bf16(alpha[g] * sum_k A[r, k] * w[g, n, k]),  w[g, n, k] = e2m1(code[g, n, k]) * e4m3(B_sf[g, n, k / 16]) held as bf16.
+ * w is exact in bf16 for every finite scale byte of either sign (at most 2 x 4 = 6 significant bits, magnitudes in [2^-10, 2688]:
+ * all normal bf16; no excluded scale bytes).  The products are exact in fp32, the sums are fp32, one fp32 multiply by alpha[g],
+ * one rounding to bf16.  Scale bytes 0x7f and 0xff (the e4m3fn NaN) give NaN in every output of that weight row for the rows of
+ * that expert; 0x00 and 0x80 give w = 0.  NaN and inf in A propagate as in fp64 arithmetic.
+ * K % 128 == 0, N % 8 == 0, 1 <= E <= 1024, M * 2K, T * 2K and N * K/2 (one expert) below 2 GiB; the stack may exceed 2 GiB.
+ * Every argument is checked before any HIP call.  M == 0 returns QAMD_OK without a launch.  Wave-owned 32x32 / 64x32 tiles.
+ */
+int qutlass_amd_grouped_matmul_bf16_nvf4_bf16_tn(const void* A, const void* B, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                                 const int32_t* offs, const int32_t* src_row, int64_t T, void* D,
+                                                 int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
+
+/*
  * EXTENSION (no counterpart in the reference): grouped NVFP4 GEMM for mixture-of-experts layers, one launch over E experts.
  * A: (M, K/2) packed e2m1 tokens sorted by expert, A_sf: ROW-MAJOR (M, K/16) e4m3 (the quantizer's buffer as it is, no to_blocked).
  * B: (E, N, K/2) stacked expert weights, B_sf: row-major (E, N, K/16).  alpha: device fp32[n_alpha], n_alpha = 1 (shared)

@@ -32,6 +32,7 @@
 #include "gemm_nvf4.hip.h"
 #include "gemm_nvf4_pk.hip.h"
 #include "gemm_nvf4_os.hip.h"
+#include "gemm_nvf4_os_w4a16.hip.h"
 #include "quantize.hip.h"
 #include "moe_route.hip.h"
 #include "to_blocked.hip.h"
@@ -748,6 +749,50 @@ int launch_grouped_w4a16_act(int v, int act, const W4A16ActParams& q, hipStream_
   if (act == ACT_SILU) return go(std::integral_constant<int, ACT_SILU>{});
   if (act == ACT_OAI) return go(std::integral_constant<int, ACT_OAI>{});
   return go(std::integral_constant<int, ACT_OAI_BIAS>{});
+}
+#else
+;
+#endif
+
+// ---- grouped W4A16 GEMM on NVFP4 weights (gemm_nvf4_os_w4a16.hip.h): bf16 tokens against e2m1 codes with e4m3 group scales -------------------------------------------------
+// Forms: 620 = 32x32 tiles, 621 = 64x32 (weights from memory straight into registers, tokens through LDS; one shot up to K = 1024, wave-owned rings of two slots beyond).
+// Started from M / E >= 64 -> 621 (each weight fragment is converted once for two m-tiles).  Measured with both forms forced on the decode and prefill cells of
+// Qwen3-30B-A3B, Mixtral-8x7B and gpt-oss-20b / 120b (profiles/calib_grouped_bf16_nvf4.txt, taken under that rule): it was wrong in most prefill cells.  620 leads at
+// every cell up to 512 rows per expert (decode, 4-16 rows: 95.7 us against 170.2, 50.8 against 100.5; Qwen3 prefill, 256 rows: 854.9 against 894.9 and 602.2 against
+// 731.3; gpt-oss-120b prefill, 128 rows: 2105.8 against 2254.8; gpt-oss-20b prefill, 512 rows: 1710.1 against 1756.7 and 813.9 against 894.1) -- two slots of the
+// 64-row form are 128 KiB, one workgroup per CU --, and 621 only at Mixtral's 1024 rows per expert (gate/up 5108.2 against 5334.0, down 2148.8 against 2523.1).
+// Refitted: mean rows per group M / E >= 1024 -> 621, otherwise 620; nothing was measured between 512 and 1024 rows.  N, K and the CU count are arguments so that
+// a rule re-taken from more measurements can use them.
+inline int grouped_bf16_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)K; (void)cus;
+  return M >= 1024 * E ? 621 : 620;
+}
+// form GRP_BF16_NVF4.form0 + I: one slot per wave up to K = 512, two up to K = 1024, wave-owned rings of two slots beyond; GATHER: A rows through q.src_row
+template <int I, bool GATHER>
+int launch_grouped_bf16_nvf4_os(W4A16Params q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_BF16_NVF4;
+  constexpr int TM = F.tile[I].tm;
+  static_assert(F.tile[I].tn == 32, "32 columns");
+  q.tiles_m = 1;
+  q.tiles_n = (int)cdiv(q.N, 32);
+  const int64_t KT = q.K / 128;
+  const dim3 grid((int)grouped_workgroups(q.M, q.N, q.E, TM, 32)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_nvf4_os_w4a16_kernel<OsNvW4A16Cfg<1, TM>, false, GATHER>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os_w4a16_kernel<OsNvW4A16Cfg<2, TM>, false, GATHER>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_nvf4_os_w4a16_kernel<OsNvW4A16Cfg<2, TM>, true, GATHER>), grid, block, 0, s, q);   // wave-owned rings of two slots
+  return check_launch("gemm_nvf4_os_w4a16_kernel");
+}
+// form v of the op; its twelve kernels ride in the persistent NVFP4 kernel's unit (8) beside the W4A8, W4A16 and W4A6 families (DESIGN.md section 5 has the unit's
+// compile time before and after)
+int launch_grouped_bf16_nvf4(int v, const W4A16Params& q, hipStream_t s)
+#if QAMD_DEF(8)
+{
+  constexpr const GroupedFormat& F = GRP_BF16_NVF4;
+  static_assert(F.nforms == 2 && F.ebits == 16 && F.ebits_b == 4 && F.sgroup == 16, "the two forms of the bf16-token NVFP4 kernel");
+  if (v != F.form0 && v != F.form0 + 1) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+  const bool tall = v == F.form0 + 1, gather = q.src_row != nullptr;
+  if (gather) return tall ? launch_grouped_bf16_nvf4_os<1, true>(q, s) : launch_grouped_bf16_nvf4_os<0, true>(q, s);
+  return tall ? launch_grouped_bf16_nvf4_os<1, false>(q, s) : launch_grouped_bf16_nvf4_os<0, false>(q, s);
 }
 #else
 ;
@@ -2128,6 +2173,27 @@ int qutlass_amd_grouped_matmul_bf16_mxf4_act_bf16_tn(const void* A, const void* 
   return launch_grouped_w4a16_act(grouped_form(F, grouped_w4a16_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI, q, (hipStream_t)stream);
 }
 
+// W4A16 on NVFP4 weights: A, src_row, T as for the MXFP4 W4A16 entry above; B (E, N, K/2) e2m1, B_sf row-major (E, N, K/16) e4m3 (8-byte aligned: one 8-byte load per
+// row and stage), alpha[g] carries the expert's global scale; D (M, N) bf16, 16-byte aligned
+int qutlass_amd_grouped_matmul_bf16_nvf4_bf16_tn(const void* A, const void* B, const void* B_sf, const float* alpha, int64_t n_alpha, const int32_t* offs,
+                                                 const int32_t* src_row, int64_t T, void* D, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_BF16_NVF4;
+  if (int rc = grouped_check(F, F.name, A, B, /* no A scales */ A, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if ((uintptr_t)D % 16) return fail(QAMD_ERR_INVALID, "%s: D must be 16-byte aligned", F.name);
+  if ((uintptr_t)B_sf % 8) return fail(QAMD_ERR_INVALID, "%s: B_sf must be 8-byte aligned", F.name);
+  if (src_row) {   // the descriptor spans all of A: T rows of 2 K bytes
+    if (T < 0) return fail(QAMD_ERR_INVALID, "%s: T must be >= 0 (got %lld)", F.name, (long long)T);
+    if (T >= ((1ll << 31) - 1) / F.row_bytes(K) + 1) return fail(QAMD_ERR_INVALID, "%s: the gathered token matrix (T * 2K bytes, T=%lld K=%lld) must stay below 2 GiB", F.name, (long long)T, (long long)K);
+  }
+  if (M == 0) return QAMD_OK;
+  W4A16Params q;
+  grouped_fill(q, F, A, B, nullptr, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
+  q.sfa_bytes = 0;
+  grouped_mx_defaults(q);
+  q.src_row = src_row; q.T = src_row ? (int)T : 0;
+  return launch_grouped_bf16_nvf4(grouped_form(F, grouped_bf16_nvf4_plan, M, N, K, E), q, (hipStream_t)stream);
+}
+
 // ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
 // Forms: 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles, 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.
 // Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B and on token counts between them (profiles/calib_grouped_nvf4_r7.txt; these are not the MX
@@ -3135,6 +3201,10 @@ int qutlass_amd_debug_grouped_bf16_mxf4_act_plan(int64_t M, int64_t N, int64_t K
   const int v = grouped_w4a16_act_plan(M, N, K, E, 256);
   if (out) out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
   return v;
+}
+// grouped_matmul_bf16_nvf4_bf16_tn: 620 = 32x32, 621 = 64x32 tiles of the bf16-token NVFP4 kernel; out[0] = (cdiv(M, TM) + E) * cdiv(N, 32) workgroups
+int qutlass_amd_debug_grouped_bf16_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  return debug_grouped_plan(GRP_BF16_NVF4, "debug_grouped_bf16_nvf4_plan", grouped_bf16_nvf4_plan, M, N, K, E, out);
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel
 int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
