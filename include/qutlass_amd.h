@@ -330,6 +330,25 @@ int qutlass_amd_grouped_matmul_bf16_nvf4_bf16_tn(const void* A, const void* B, c
                                                  int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
 
 /*
+ * EXTENSION (no counterpart in the reference): the gate/up GEMM of a W4A16 expert layer on NVFP4 weights with the activation
+ * fused into its epilogue -- what it writes is the down GEMM's A operand, (M, I) bf16; the (M, N) bf16 tensor between is never
+ * stored.  A, B_sf (8-byte aligned), alpha, n_alpha, offs, src_row, T, the scale bytes (every finite e4m3 byte exact, 0x7f /
+ * 0xff poison their weight row), the clamping of the offsets: as qutlass_amd_grouped_matmul_bf16_nvf4_bf16_tn.
+ * B: (E, N = 2 I, K/2) packed e2m1, rows [0, I) of an expert the gate projection, rows [I, 2 I) the up projection.
+ * act, act_alpha, limit, bias: as qutlass_amd_grouped_matmul_bf16_mxf4_act_bf16_tn.
+ * D: (M, I) bf16, 16-byte aligned.  For every row r < offs[E - 1] its bits are those of qutlass_amd_silu_mul_bf16 /
+ * qutlass_amd_swiglu_oai_mul_bf16 on the bf16 output of qutlass_amd_grouped_matmul_bf16_nvf4_bf16_tn, for any operands (well-formed
+ * offs: the bias row is the tile's own expert); a poisoned gate or up row is a NaN column of D for that expert's rows.  Rows at
+ * or past offs[E - 1] are not written.  Reads A (or the T rows src_row names), B, B_sf, alpha, offs, bias; writes D only.
+ * K % 128 == 0, N % 64 == 0, 1 <= E <= 1024, the sizes as there.  Every argument is checked before any HIP call.  M == 0
+ * returns QAMD_OK without a launch.
+ */
+int qutlass_amd_grouped_matmul_bf16_nvf4_act_bf16_tn(const void* A, const void* B, const void* B_sf, const float* alpha,
+                                                     int64_t n_alpha, const int32_t* offs, const int32_t* src_row, int64_t T,
+                                                     int act, float act_alpha, float limit, const void* bias, void* D, int64_t M,
+                                                     int64_t N, int64_t K, int64_t E, void* stream);
+
+/*
  * EXTENSION (no counterpart in the reference): grouped NVFP4 GEMM for mixture-of-experts layers, one launch over E experts.
  * A: (M, K/2) packed e2m1 tokens sorted by expert, A_sf: ROW-MAJOR (M, K/16) e4m3 (the quantizer's buffer as it is, no to_blocked).
  * B: (E, N, K/2) stacked expert weights, B_sf: row-major (E, N, K/16).  alpha: device fp32[n_alpha], n_alpha = 1 (shared)

@@ -17,6 +17,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_bf16_mxf4_bf16_tn, matmul_bf16_mxf4_bf16_tn  (extension: W4A16 -- bf16 tokens against the same weights, optionally gathered by src_row in the GEMM)
     grouped_matmul_bf16_nvf4_bf16_tn, matmul_bf16_nvf4_bf16_tn  (extension: W4A16 on NVFP4 weights -- bf16 tokens against e2m1 codes with e4m3 group scales)
     grouped_matmul_bf16_mxf4_silu_bf16_tn, grouped_matmul_bf16_mxf4_swiglu_oai_bf16_tn  (extension: the W4A16 gate/up GEMM with the activation fused in, bf16 output)
+    grouped_matmul_bf16_nvf4_silu_bf16_tn, grouped_matmul_bf16_nvf4_swiglu_oai_bf16_tn  (extension: the same fusion on NVFP4 weights)
     silu_and_mul, fusedSiluMulQuantizeMx / Nv [Blocked]  (extension: the gated-MLP activation, alone and fused into the quantizers)
     moe_sort, fusedGatherQuantizeMx / Nv, moe_combine     (extension: MoE dispatch and combine around the grouped GEMMs)
     fusedGatherQuantizeNvGrouped, fusedSiluMulQuantizeNvGrouped  (extension: the two NVFP4 quantizers of the MoE chain with one global scale per expert)
@@ -523,6 +524,66 @@ def grouped_matmul_bf16_mxf4_swiglu_oai_bf16_tn(a: torch.Tensor, b: torch.Tensor
     if not (limit > 0 and limit < float("inf") and _bf16_exact(limit)):
         raise ValueError(f"{op}: limit must be > 0, finite and exactly representable in bf16 (got {limit})")
     return _ops_amd.grouped_matmul_bf16_mxf4_act_bf16(a, b, b_sf, alpha, offs, 1, act_alpha, limit, bias, src_row)
+
+
+def _check_bf16_nvf4_act(op: str, a, b, b_sf, src_row, bias=None) -> None:
+    """the rejections of the fused gate/up W4A16 ops on NVFP4 weights that need no device: _check_bf16_nvf4_operands, then _check_w4a16_act's own"""
+    _check_bf16_nvf4_operands(op, a, b, b_sf, 3, src_row)
+    if b.size(1) % 64:
+        raise ValueError(f"{op}: b must be (E, 2 * I, K/2) with I a multiple of 32, whole tiles of the output (got 2 * I = {b.size(1)})")
+    if a.size(1) % 128:
+        raise ValueError(f"{op}: K must be a multiple of 128 (got {a.size(1)})")
+    if not 1 <= b.size(0) <= 1024:
+        raise ValueError(f"{op}: the number of experts must be in [1, 1024] (got {b.size(0)})")
+    if bias is not None:
+        if bias.dtype != torch.bfloat16:
+            raise ValueError(f"{op}: bias must be bfloat16 (got {bias.dtype})")
+        if bias.dim() != 2 or tuple(bias.shape) != (b.size(0), b.size(1)):
+            raise ValueError(f"{op}: bias must be (E, 2 * I) = ({b.size(0)}, {b.size(1)}) (got {tuple(bias.shape)})")
+
+
+def grouped_matmul_bf16_nvf4_silu_bf16_tn(a: torch.Tensor, b: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor, *,
+                                          src_row: torch.Tensor | None = None) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): the gate/up GEMM of a W4A16 expert layer on NVFP4 weights with silu(gate) * up fused into its epilogue, ONE launch.
+    For well-formed offs the result equals, bit for bit in every row below offs[E-1] and for any operands, the chain
+
+        silu_and_mul(grouped_matmul_bf16_nvf4_bf16_tn(a, b, b_sf, alpha, offs, src_row=src_row))
+
+    and the (M, 2 I) bf16 tensor between those two launches is never written.  Operands as grouped_matmul_bf16_nvf4_bf16_tn's -- src_row, every finite e4m3 scale
+    byte exact, 0x7f / 0xff poisoning their weight row (a poisoned gate or up row is a NaN activation column for that expert's rows), NaN and inf, the clamping of
+    the offsets included -- with b (E, 2 I, K/2): rows [0, I) of an expert the gate projection, rows [I, 2 I) the up projection, and b_sf row-major (E, 2 I, K/16).
+    Returns (M, I) bf16, the down GEMM's A operand as it is, allocated without a fill; rows at or past offs[E-1] are not written.  I % 32 == 0, K % 128 == 0,
+    1 <= E <= 1024; the sizes as the GEMM op's.  The offsets are read on the device: no host sync, graph-capturable, traces under torch.compile.
+
+    A workgroup owns 32 activation columns -- the 32 gate and the 32 up weight rows -- over 32 or 64 token rows; the weights go from memory straight into registers,
+    are dequantized there, and only the tokens pass through LDS.  Measured against the two launches
+    (profiles/bench_grouped_bf16_nvf4_act_mi355x.txt; 16 / 64 / 4096 tokens): gpt-oss-20b 1.22-1.32 / 1.14-1.16 / 1.32x, gpt-oss-120b 1.29-1.42 / 1.20-1.24 / 1.34x,
+    Qwen3-30B-A3B 1.40-1.44 / 1.35-1.36 / 1.40x, Mixtral-8x7B 1.13-1.17 / 1.17-1.24 / 1.29x, the same with src_row; 1.25-1.59x on a sweep of 16 ... 128 rows per expert at
+    K = 512 ... 2944.  It lost in no measured cell and is faster than the GEMM op alone in all of them (1.10-1.47x), so there is no measured shape where the two
+    launches should be kept.  DESIGN.md section 8 item 21."""
+    _check_bf16_nvf4_act("grouped_matmul_bf16_nvf4_silu_bf16_tn", a, b, b_sf, src_row)
+    return _ops_amd.grouped_matmul_bf16_nvf4_act_bf16(a, b, b_sf, alpha, offs, 0, 1.0, 1.0, None, src_row)
+
+
+def grouped_matmul_bf16_nvf4_swiglu_oai_bf16_tn(a: torch.Tensor, b: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor, *,
+                                                act_alpha: float = 1.702, limit: float = 7.0, bias: torch.Tensor | None = None,
+                                                src_row: torch.Tensor | None = None) -> torch.Tensor:
+    """EXTENSION (no reference counterpart): grouped_matmul_bf16_nvf4_silu_bf16_tn with gpt-oss's clamped SwiGLU in place of silu * up.  For well-formed offs the
+    result equals, bit for bit in every row below offs[E-1], the chain
+
+        swiglu_oai_and_mul(grouped_matmul_bf16_nvf4_bf16_tn(a, b, b_sf, alpha, offs, src_row=src_row), alpha=act_alpha, limit=limit, bias=bias, offs=offs)
+
+    bias (E, 2 I) bf16 in the weight's [gate | up] halves, or None; the bias row is that of the tile's expert (for well-formed offs: the row's).  act_alpha finite
+    and > 0, limit > 0 and exact in bf16, as in swiglu_oai_and_mul.  Everything else -- operands, the result, the rows that are not written and the measurements --
+    as grouped_matmul_bf16_nvf4_silu_bf16_tn."""
+    op = "grouped_matmul_bf16_nvf4_swiglu_oai_bf16_tn"
+    _check_bf16_nvf4_act(op, a, b, b_sf, src_row, bias)
+    act_alpha, limit = float(act_alpha), float(limit)
+    if not (act_alpha > 0 and act_alpha < float("inf")):
+        raise ValueError(f"{op}: act_alpha must be finite and > 0 (got {act_alpha})")
+    if not (limit > 0 and limit < float("inf") and _bf16_exact(limit)):
+        raise ValueError(f"{op}: limit must be > 0, finite and exactly representable in bf16 (got {limit})")
+    return _ops_amd.grouped_matmul_bf16_nvf4_act_bf16(a, b, b_sf, alpha, offs, 1, act_alpha, limit, bias, src_row)
 
 
 def grouped_matmul_nvf4_bf16_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor,

@@ -33,6 +33,7 @@
 #include "gemm_nvf4_pk.hip.h"
 #include "gemm_nvf4_os.hip.h"
 #include "gemm_nvf4_os_w4a16.hip.h"
+#include "gemm_nvf4_os_w4a16_act.hip.h"
 #include "quantize.hip.h"
 #include "moe_route.hip.h"
 #include "to_blocked.hip.h"
@@ -793,6 +794,60 @@ int launch_grouped_bf16_nvf4(int v, const W4A16Params& q, hipStream_t s)
   const bool tall = v == F.form0 + 1, gather = q.src_row != nullptr;
   if (gather) return tall ? launch_grouped_bf16_nvf4_os<1, true>(q, s) : launch_grouped_bf16_nvf4_os<0, true>(q, s);
   return tall ? launch_grouped_bf16_nvf4_os<1, false>(q, s) : launch_grouped_bf16_nvf4_os<0, false>(q, s);
+}
+#else
+;
+#endif
+
+// ---- gate/up W4A16 GEMM on NVFP4 weights with fused activation and bf16 output (gemm_nvf4_os_w4a16_act.hip.h) ----------------------------------------------------------
+// Forms: 622 = 32 rows x 32 activation columns, 623 = 64 x 32 (a workgroup owns the 32 gate AND the 32 up weight rows of its columns; one shot up to K = 1024, wave-owned
+// rings of two slots beyond).  N is the weight's 2 I rows.
+// Started from the MXFP4 fusion's refitted rule (mean rows per group M / E >= 256 and K > 512 -> the 64-row form).  Measured with both forms forced on the gate/up cells of
+// gpt-oss-20b / 120b, Qwen3-30B-A3B and Mixtral-8x7B and on a sweep of 16 ... 128 rows per expert at K = 512 ... 2944 (profiles/calib_grouped_bf16_nvf4_act.txt, taken
+// under that rule): it was wrong in the four prefill cells of 256 and 512 rows per expert.  622 leads in every cell up to 512 rows (decode, 2-16 rows: 67.7 us against
+// 127.7, 52.7 against 91.7; the sweep at every K, closest at 48 rows: K = 2048 225.8 against 229.4, K = 2944 281.3 against 297.0; gpt-oss-120b prefill, 128 rows:
+// 1638.1 against 1836.9; Qwen3 prefill, 256 rows: 631.8 against 679.3; gpt-oss-20b prefill, 512 rows: 1358.5 against 1461.7) -- two slots of the 64-row form are
+// 128 KiB, one workgroup per CU, and the converts it saves are hidden behind the MFMAs of two workgroups of the 32-row form --, and 623 only at Mixtral's 1024 rows per
+// expert (4081.2 against 4240.3, 4095.7 against 4261.6).  Refitted: M / E >= 1024 and K > 512 -> 623, otherwise 622: the unfused NVFP4 op's row threshold.  No miss is
+// left among the 54 measured cells; nothing was measured between 512 and 1024 rows per expert, nor above 128 rows at K <= 512 (the K bound of the started rule stays).
+inline int grouped_bf16_nvf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)cus;
+  return (M >= 1024 * E && K > 512) ? 623 : 622;
+}
+// form GRP_BF16_NVF4_ACT.form0 + I with activation ACT: one slot per wave up to K = 512, two up to K = 1024, wave-owned rings of two slots beyond; GATHER: A rows
+// through q.src_row
+template <int I, int ACT, bool GATHER>
+int launch_grouped_bf16_nvf4_act_os(W4A16ActParams q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_BF16_NVF4_ACT;
+  constexpr int TM = F.tile[I].tm;
+  static_assert(F.tile[I].tn == 32, "32 activation columns");
+  q.tiles_m = 1;
+  q.tiles_n = q.inter / 32;
+  const int64_t KT = q.K / 128;
+  const dim3 grid((int)grouped_workgroups(q.M, q.inter, q.E, TM, 32)), block(256);
+  if (KT <= 4) hipLaunchKernelGGL((gemm_nvf4_os_w4a16_act_kernel<OsNvW4A16ActCfg<1, TM>, ACT, false, GATHER>), grid, block, 0, s, q);
+  else if (KT <= 8) hipLaunchKernelGGL((gemm_nvf4_os_w4a16_act_kernel<OsNvW4A16ActCfg<2, TM>, ACT, false, GATHER>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((gemm_nvf4_os_w4a16_act_kernel<OsNvW4A16ActCfg<2, TM>, ACT, true, GATHER>), grid, block, 0, s, q);   // wave-owned rings of two slots
+  return check_launch("gemm_nvf4_os_w4a16_act_kernel");
+}
+// form v of the fused op, act = ACT_SILU / ACT_OAI / ACT_OAI_BIAS (quantize.hip.h); its 36 kernels ride in the NVFP4 unit (4).  Beside the kernel they derive from,
+// in unit 8, they made that unit the longest (compiled alone 45 s before, 54 s with them; 68 s against unit 2's 50 s with all six units compiling at once), so they moved to the then-shortest unit that keeps the GEMM units' AGPR accumulators (unit 5 is shorter
+// but compiles with the rotation quantizers' VGPR-form flag)
+int launch_grouped_bf16_nvf4_act(int v, int act, const W4A16ActParams& q, hipStream_t s)
+#if QAMD_DEF(4)
+{
+  constexpr const GroupedFormat& F = GRP_BF16_NVF4_ACT;
+  static_assert(F.nforms == 2 && F.ebits == 16 && F.ebits_b == 4 && F.sgroup == 16, "the two forms of the fused gate/up NVFP4 kernel");
+  if (v != F.form0 && v != F.form0 + 1) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+  const bool tall = v == F.form0 + 1, gather = q.src_row != nullptr;
+  auto go = [&](auto a) {
+    constexpr int A = decltype(a)::value;
+    if (gather) return tall ? launch_grouped_bf16_nvf4_act_os<1, A, true>(q, s) : launch_grouped_bf16_nvf4_act_os<0, A, true>(q, s);
+    return tall ? launch_grouped_bf16_nvf4_act_os<1, A, false>(q, s) : launch_grouped_bf16_nvf4_act_os<0, A, false>(q, s);
+  };
+  if (act == ACT_SILU) return go(std::integral_constant<int, ACT_SILU>{});
+  if (act == ACT_OAI) return go(std::integral_constant<int, ACT_OAI>{});
+  return go(std::integral_constant<int, ACT_OAI_BIAS>{});
 }
 #else
 ;
@@ -2194,6 +2249,40 @@ int qutlass_amd_grouped_matmul_bf16_nvf4_bf16_tn(const void* A, const void* B, c
   return launch_grouped_bf16_nvf4(grouped_form(F, grouped_bf16_nvf4_plan, M, N, K, E), q, (hipStream_t)stream);
 }
 
+// the gate/up NVFP4 W4A16 GEMM whose output is the down GEMM's A operand: A, B_sf, alpha, src_row, T as for the NVFP4 W4A16 entry above, B (E, N = 2 I, K/2) [gate | up];
+// act, act_alpha, limit, bias as for the MXFP4 fused entry; D (M, I) bf16
+int qutlass_amd_grouped_matmul_bf16_nvf4_act_bf16_tn(const void* A, const void* B, const void* B_sf, const float* alpha, int64_t n_alpha, const int32_t* offs,
+                                                     const int32_t* src_row, int64_t T, int act, float act_alpha, float limit, const void* bias, void* D, int64_t M,
+                                                     int64_t N, int64_t K, int64_t E, void* stream) {
+  constexpr const GroupedFormat& F = GRP_BF16_NVF4_ACT;
+  if (int rc = grouped_check(F, F.name, A, B, /* no A scales */ A, B_sf, alpha, n_alpha, offs, D, M, N, K, E)) return rc;
+  if (N % 64) return fail(QAMD_ERR_INVALID, "%s: N = 2 * I must be a multiple of 64, whole tiles of 32 activation columns (got %lld)", F.name, (long long)N);
+  if (act != 0 && act != 1) return fail(QAMD_ERR_INVALID, "%s: invalid act %d; expected 0 (silu) or 1 (swiglu_oai)", F.name, act);
+  if ((uintptr_t)D % 16) return fail(QAMD_ERR_INVALID, "%s: D must be 16-byte aligned", F.name);
+  if ((uintptr_t)B_sf % 8) return fail(QAMD_ERR_INVALID, "%s: B_sf must be 8-byte aligned", F.name);
+  if (src_row) {   // the descriptor spans all of A: T rows of 2 K bytes
+    if (T < 0) return fail(QAMD_ERR_INVALID, "%s: T must be >= 0 (got %lld)", F.name, (long long)T);
+    if (T >= ((1ll << 31) - 1) / F.row_bytes(K) + 1) return fail(QAMD_ERR_INVALID, "%s: the gathered token matrix (T * 2K bytes, T=%lld K=%lld) must stay below 2 GiB", F.name, (long long)T, (long long)K);
+  }
+  W4A16ActParams q;
+  q.oai = {};
+  if (act == 1) {
+    if (int rc = swiglu_oai_act(F.name, act_alpha, limit, q.oai)) return rc;
+    if (bias) {
+      if (int rc = swiglu_oai_check_bias(F.name, bias, offs, E)) return rc;
+      if (E * N >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: bias (E * N * 2 = %lld bytes) must stay below 2 GiB", F.name, (long long)(E * N * 2));
+    }
+  } else if (bias) {
+    return fail(QAMD_ERR_INVALID, "%s: act 0 (silu) takes no bias", F.name);
+  }
+  if (M == 0) return QAMD_OK;
+  grouped_fill(q, F, A, B, nullptr, B_sf, alpha, n_alpha, offs, D, M, N, K, E);
+  q.sfa_bytes = 0; q.ldd = (int)(N / 2);
+  grouped_mx_defaults(q);
+  q.src_row = src_row; q.T = src_row ? (int)T : 0; q.bias = (const uint16_t*)bias; q.inter = (int)(N / 2);
+  return launch_grouped_bf16_nvf4_act(grouped_form(F, grouped_bf16_nvf4_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI, q, (hipStream_t)stream);
+}
+
 // ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
 // Forms: 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles, 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.
 // Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B and on token counts between them (profiles/calib_grouped_nvf4_r7.txt; these are not the MX
@@ -3205,6 +3294,15 @@ int qutlass_amd_debug_grouped_bf16_mxf4_act_plan(int64_t M, int64_t N, int64_t K
 // grouped_matmul_bf16_nvf4_bf16_tn: 620 = 32x32, 621 = 64x32 tiles of the bf16-token NVFP4 kernel; out[0] = (cdiv(M, TM) + E) * cdiv(N, 32) workgroups
 int qutlass_amd_debug_grouped_bf16_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
   return debug_grouped_plan(GRP_BF16_NVF4, "debug_grouped_bf16_nvf4_plan", grouped_bf16_nvf4_plan, M, N, K, E, out);
+}
+// grouped_matmul_bf16_nvf4_act_bf16_tn: 622 = 32 rows x 32 activation columns, 623 = 64 x 32; N = 2 I, so the workgroups are counted over I = N / 2 columns:
+// out[0] = (cdiv(M, TM) + E) * (I / 32)
+int qutlass_amd_debug_grouped_bf16_nvf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  constexpr const GroupedFormat& F = GRP_BF16_NVF4_ACT;
+  const int v = debug_grouped_plan(F, "debug_grouped_bf16_nvf4_act_plan", grouped_bf16_nvf4_act_plan, M, N, K, E, nullptr);
+  if (v < 0 || N % 64) return -1;
+  if (out) out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
+  return v;
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel
 int qutlass_amd_debug_grouped_nvf4_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {

@@ -316,6 +316,53 @@ Tensor grouped_matmul_bf16_nvf4(const Tensor& A, const Tensor& B, const Tensor& 
   return out;
 }
 
+// EXTENSION: the gate/up W4A16 grouped GEMM on NVFP4 weights with fused activation and bf16 output (qutlass_amd_grouped_matmul_bf16_nvf4_act_bf16_tn) -- A, B_sf, alpha,
+// offs, src_row as grouped_matmul_bf16_nvf4's with B (E, 2 I, K/2) [gate | up]; act 0 = silu * up, 1 = the clamped SwiGLU with act_alpha, limit and the optional bias
+// (E, 2 I) bf16.  Allocates (M, I) bf16 without a fill; rows at or past offs[E-1] are not written.
+Tensor grouped_matmul_bf16_nvf4_act_bf16(const Tensor& A, const Tensor& B, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs, int64_t act, double act_alpha,
+                                         double limit, std::optional<Tensor> bias, std::optional<Tensor> src_row) {
+  const char* op = "grouped_matmul_bf16_nvf4_act_bf16";
+  check_tensors(op, {{A, "A"}, {B, "B"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}});
+  STD_TORCH_CHECK(has_dtype(A, ScalarType::BFloat16), op, ": A must be bfloat16");
+  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), op, ": B must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e4m3fn), op, ": B_sf must be float8_e4m3fn");
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, op, ": A must be 2D (M, K) and B 3D (E, 2I, K/2)");
+  STD_TORCH_CHECK(A.size(1) == B.size(2) * 2, op, ": inner dimensions must match for A @ B[g].T");
+  const int64_t E = B.size(0), N = B.size(1), K = A.size(1), kb = K / 16, I = N / 2;
+  int64_t M = A.size(0), T = 0;
+  const int32_t* src = nullptr;
+  const Named a{A, "A"};
+  if (src_row) {
+    check_tensors(op, {{*src_row, "src_row"}}, {}, true, &a);
+    STD_TORCH_CHECK(has_dtype(*src_row, ScalarType::Int) && src_row->dim() == 1, op, ": src_row must be a 1D int32 tensor");
+    T = A.size(0);
+    M = src_row->size(0);
+    src = static_cast<const int32_t*>(src_row->data_ptr());
+  }
+  STD_TORCH_CHECK(N > 0 && N % 64 == 0, op, ": B must have 2 * I rows per expert with I a multiple of 32 (got ", N, ")");
+  STD_TORCH_CHECK(E >= 1 && E <= 1024, op, ": the number of experts must be in [1, 1024] (got ", E, ")");
+  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, op, ": offs must be an int32 tensor of E = ", E, " elements");
+  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), op, ": alpha must be a float32 tensor of 1 or E = ", E, " elements");
+  STD_TORCH_CHECK(B_sf.numel() >= E * N * kb, op, ": B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * kb);
+  STD_TORCH_CHECK(act == 0 || act == 1, op, ": act must be 0 (silu) or 1 (swiglu_oai)");
+  const void* bp = nullptr;
+  if (bias) {
+    STD_TORCH_CHECK(act == 1, op, ": act 0 (silu) takes no bias");
+    check_tensors(op, {{*bias, "bias"}}, {}, true, &a);
+    STD_TORCH_CHECK(has_dtype(*bias, ScalarType::BFloat16), op, ": bias must be bf16");
+    STD_TORCH_CHECK(bias->dim() == 2 && bias->size(0) == E && bias->size(1) == N, op, ": bias must be (E, 2I) = (", E, ", ", N, ")");
+    bp = bias->data_ptr();
+  }
+  Tensor out = torch::stable::new_empty(A, {M, I}, ScalarType::BFloat16);
+  if (M == 0) return out;   // empty batch: nothing to launch
+
+  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
+  check_rc(qutlass_amd_grouped_matmul_bf16_nvf4_act_bf16_tn(A.data_ptr(), B.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()), alpha.numel(),
+                                                            static_cast<const int32_t*>(offs.data_ptr()), src, T, (int)act, (float)act_alpha, (float)limit, bp,
+                                                            out.data_ptr(), M, N, K, E, current_stream(A)));
+  return out;
+}
+
 // EXTENSION: the gate/up W4A16 grouped GEMM with fused activation and bf16 output (qutlass_amd_grouped_matmul_bf16_mxf4_act_bf16_tn) -- A, B (E, 2 I, K/2), B_sf, alpha,
 // offs, src_row as grouped_matmul_bf16_mxf4's; act 0 = silu * up, 1 = the clamped SwiGLU with act_alpha, limit and the optional bias (E, 2 I) bf16.  Allocates (M, I)
 // bf16 without a fill; rows at or past offs[E-1] are not written.
@@ -1121,6 +1168,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("grouped_matmul_mxf4_act_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias, Tensor h, int method) -> (Tensor, Tensor)");   // W4A4 gate/up with fused activation, inference op: in the minimal library too
   m.def("grouped_matmul_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_bf16_nvf4_bf16_tn(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, Tensor? src_row) -> Tensor");   // W4A16 on NVFP4 weights, inference op: in the minimal library too
+  m.def("grouped_matmul_bf16_nvf4_act_bf16(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias, Tensor? src_row) -> Tensor");   // its gate/up form with fused activation, inference op: in the minimal library too
 }
 
 // CUDA dispatch key only, as the reference (bindings.cpp:516-535); there is no CPU compute path.
@@ -1203,6 +1251,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CompositeExplicitAutograd, m) {
   m.impl("grouped_matmul_mxf8_mxf4_act_mxf8", TORCH_BOX(&grouped_matmul_mxf8_mxf4_act_mxf8));   // its rejections are tests/test_grouped_w4a8_act_cpu.py's
   m.impl("grouped_matmul_mxf4_act_mxf4", TORCH_BOX(&grouped_matmul_mxf4_act_mxf4));             // its rejections are tests/test_grouped_mxf4_act_cpu.py's
   m.impl("grouped_matmul_bf16_nvf4_bf16_tn", TORCH_BOX(&grouped_matmul_bf16_nvf4));             // its rejections are tests/test_grouped_bf16_nvf4_cpu.py's
+  m.impl("grouped_matmul_bf16_nvf4_act_bf16", TORCH_BOX(&grouped_matmul_bf16_nvf4_act_bf16));   // its rejections are tests/test_grouped_bf16_nvf4_act_cpu.py's
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module

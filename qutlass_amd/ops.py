@@ -105,6 +105,10 @@ def _register_fakes() -> None:
     def _(A, B, B_sf, alpha, offs, src_row):   # the same shapes on NVFP4 weights: (M or len(src_row), N) bf16
         return A.new_empty(((A if src_row is None else src_row).size(0), B.size(1)), dtype=torch.bfloat16)
 
+    @rf("qutlass_amd::grouped_matmul_bf16_nvf4_act_bf16")
+    def _(A, B, B_sf, alpha, offs, act, act_alpha, limit, bias, src_row):   # the same on NVFP4 weights: (M or len(src_row), I) bf16
+        return A.new_empty(((A if src_row is None else src_row).size(0), B.size(1) // 2), dtype=torch.bfloat16)
+
     @rf("qutlass_amd::grouped_matmul_bf16_mxf4_act_bf16")
     def _(A, B, B_sf, alpha, offs, act, act_alpha, limit, bias, src_row):   # B (E, 2 I, K/2): (M, I) bf16, M = src_row's rows when it is given
         return A.new_empty(((A if src_row is None else src_row).size(0), B.size(1) // 2), dtype=torch.bfloat16)
