@@ -258,6 +258,31 @@ int qutlass_amd_grouped_matmul_mxf4_act_mxf4_tn(const void* A, const void* B, co
                                                 void* out_e8m0, int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
 
 /*
+ * EXTENSION (no counterpart in the reference): the gate/up GEMM of an NVFP4 (W4A4) expert layer with the activation, the rotation
+ * and the NVFP4 quantizer fused into its epilogue -- what it writes is the down GEMM's A operand; the (M, N) bf16 tensor between
+ * is never stored.
+ * A, A_sf, B_sf, alpha, n_alpha, offs, the clamping of the offsets: as qutlass_amd_grouped_matmul_nvf4_bf16_tn.
+ * B: (E, N = 2 I, K/2) packed e2m1, rows [0, I) of an expert the gate projection, rows [I, 2 I) the up projection.
+ * act, act_alpha, limit, bias: as qutlass_amd_grouped_matmul_mxf8_mxf4_act_mxf8_tn.
+ * h: h_size x h_size bf16, row-major; h_size must be 32 (QAMD_ERR_INVALID otherwise, the message names the composition).
+ * global_scales: E floats, the down projection's per-expert input scale, as qutlass_amd_fused_silu_mul_quantize_nv_grouped takes
+ * it; a row takes the scale (and the bias) of its TILE's expert.  Read by QAMD_METHOD_ABSMAX only.
+ * method: QAMD_METHOD_QUEST / QAMD_METHOD_ABSMAX.  No clip mask, no blocked scales.
+ * Footprint: writes out_e2m1, (M, I / 2) packed e2m1 codes, 4-byte aligned, and out_e4m3, flat (M, I / 16) e4m3 scales, in rows
+ * r < offs[E - 1] only; reads nothing beyond the operands' stated extents.  For those rows the bytes of both are those of the
+ * grouped NVFP4 activation quantizers (h, 32, method, flat scales) on the bf16 output of
+ * qutlass_amd_grouped_matmul_nvf4_bf16_tn, for any finite operands, whenever that GEMM runs the 64x64 / 128x128 tile form this
+ * kernel is built on (the same MFMA order per accumulator); where its rule picks the wave-owned form, wherever the fp32 sums do
+ * not depend on their order.  Groups whose activations are not finite, and malformed offs, are outside that equality.
+ * K % 128 == 0, N % 64 == 0, 1 <= E <= 1024, the sizes as there.  M == 0 returns QAMD_OK without a launch.
+ */
+int qutlass_amd_grouped_matmul_nvf4_act_nvf4_tn(const void* A, const void* B, const void* A_sf, const void* B_sf,
+                                                const float* alpha, int64_t n_alpha, const int32_t* offs, int act, float act_alpha,
+                                                float limit, const void* bias, const void* h, int h_size,
+                                                const float* global_scales, int method, void* out_e2m1, void* out_e4m3, int64_t M,
+                                                int64_t N, int64_t K, int64_t E, void* stream);
+
+/*
  * EXTENSION (no counterpart in the reference): grouped W4A6 GEMM for mixture-of-experts layers -- MXFP6 (e2m3) tokens against
  * MXFP4 expert weights as they are stored, one launch over E experts: W4A8's accuracy class at 3/4 of its token bytes.
  * A: (M, 3K/4) bytes of packed e2m3 codes, tokens sorted by expert (the MXFP6 operand format at the quantizers below), 16-byte

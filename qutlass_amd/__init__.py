@@ -12,6 +12,7 @@ meaning, defaults and Python-level error behaviour):
     grouped_matmul_mxf8_mxf4_bf16_tn, matmul_mxf8_mxf4_bf16_tn  (extension: W4A8 -- MXFP8 tokens against MXFP4 expert weights as stored; the dense form is E = 1)
     grouped_matmul_mxf8_mxf4_silu_mxf8_tn, grouped_matmul_mxf8_mxf4_swiglu_oai_mxf8_tn  (extension: the W4A8 gate/up GEMM with the activation and the MXFP8 quantizer fused in)
     grouped_matmul_mxf4_silu_mxf4_tn, grouped_matmul_mxf4_swiglu_oai_mxf4_tn  (extension: the MXFP4 (W4A4) gate/up GEMM with the activation, the rotation and the MXFP4 quantizer fused in)
+    grouped_matmul_nvf4_silu_nvf4_tn, grouped_matmul_nvf4_swiglu_oai_nvf4_tn  (extension: the same fusion for NVFP4 (W4A4), on the tile bodies the NVFP4 GEMM op runs)
     grouped_matmul_mxf6_mxf4_bf16_tn, matmul_mxf6_mxf4_bf16_tn  (extension: W4A6 -- MXFP6 (e2m3) tokens against the same weights: W4A8's accuracy class at 3/4 of its token bytes)
     fusedQuantizeMxf6, fusedGatherQuantizeMxf6            (extension: the MXFP6 quantizers -- the A operand of the W4A6 GEMM)
     grouped_matmul_bf16_mxf4_bf16_tn, matmul_bf16_mxf4_bf16_tn  (extension: W4A16 -- bf16 tokens against the same weights, optionally gathered by src_row in the GEMM)
@@ -311,6 +312,95 @@ def grouped_matmul_mxf4_swiglu_oai_mxf4_tn(a: torch.Tensor, b: torch.Tensor, a_s
     if not (limit > 0 and limit < float("inf") and _bf16_exact(limit)):
         raise ValueError(f"{op}: limit must be > 0, finite and exactly representable in bf16 (got {limit})")
     return _ops_amd.grouped_matmul_mxf4_act_mxf4(a, b, a_sf, b_sf, alpha, offs, 1, act_alpha, limit, bias, h, _METHOD_CODE[method])
+
+
+def _check_nvf4_act(op: str, a, b, a_sf, b_sf, alpha, offs, h, global_scales, method, bias=None) -> None:
+    """the rejections of the fused gate/up NVFP4 ops that need no device, in the manner of _check_mxf4_act"""
+    for name, t in (("a", a), ("b", b)):
+        if t.dtype not in (torch.uint8, torch.float4_e2m1fn_x2):
+            raise ValueError(f"{op}: {name} must be uint8 or float4_e2m1fn_x2 packed e2m1 (got {t.dtype})")
+    if a.dim() != 2 or b.dim() != 3:
+        raise ValueError(f"{op}: a must be 2D (M, K/2) and b 3D (E, 2 * I, K/2)")
+    if a.size(1) != b.size(2):
+        raise ValueError(f"{op}: inner dimensions must match, a is (M, K/2 = {a.size(1)}) and b (.., K/2 = {b.size(2)})")
+    K, E = 2 * a.size(1), b.size(0)
+    for name, sf, rows in (("a_sf", a_sf, a.size(0)), ("b_sf", b_sf, E * b.size(1))):
+        if sf.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"{op}: {name} must be float8_e4m3fn (got {sf.dtype})")
+        if sf.numel() < rows * (K // 16):
+            raise ValueError(f"{op}: {name} has {sf.numel()} elements, the row-major scale layout needs {rows * (K // 16)}")
+    if b.size(1) % 64:
+        raise ValueError(f"{op}: b must be (E, 2 * I, K/2) with I a multiple of 32, whole rotation blocks of the output (got 2 * I = {b.size(1)})")
+    if K % 128:
+        raise ValueError(f"{op}: K must be a multiple of 128 (got {K})")
+    if not 1 <= E <= 1024:
+        raise ValueError(f"{op}: the number of experts must be in [1, 1024] (got {E})")
+    if alpha.dtype != torch.float32 or alpha.numel() not in (1, E):
+        raise ValueError(f"{op}: alpha must be float32 with 1 or E = {E} elements (got {alpha.dtype}, {alpha.numel()})")
+    if offs.dtype != torch.int32 or offs.dim() != 1 or offs.numel() != E:
+        raise ValueError(f"{op}: offs must be a 1D int32 tensor of E = {E} elements (got {offs.dtype}, {tuple(offs.shape)})")
+    if h.dtype != torch.bfloat16:
+        raise ValueError(f"{op}: h must be bfloat16 (got {h.dtype})")
+    if h.dim() != 2 or tuple(h.shape) != (32, 32):
+        raise ValueError(f"{op}: h must be a 32 x 32 rotation (got {tuple(h.shape)}); for any other size run grouped_matmul_nvf4_bf16_tn followed by "
+                         "fusedSiluMulQuantizeNvGrouped / swiglu_oai_and_mul and fusedGatherQuantizeNvGrouped")
+    if global_scales.dtype != torch.float32 or global_scales.dim() != 1 or global_scales.numel() != E:
+        raise ValueError(f"{op}: global_scales must be a 1D float32 tensor of E = {E} elements (got {global_scales.dtype}, {tuple(global_scales.shape)})")
+    if method not in _METHOD_CODE:
+        raise ValueError(f"{op}: invalid method {method!r}; use 'quest' or 'abs_max'")
+    if bias is not None:
+        if bias.dtype != torch.bfloat16:
+            raise ValueError(f"{op}: bias must be bfloat16 (got {bias.dtype})")
+        if bias.dim() != 2 or tuple(bias.shape) != (E, b.size(1)):
+            raise ValueError(f"{op}: bias must be (E, 2 * I) = ({E}, {b.size(1)}) (got {tuple(bias.shape)})")
+
+
+def grouped_matmul_nvf4_silu_nvf4_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor,
+                                     h: torch.Tensor, global_scales: torch.Tensor, *, method: Literal["quest", "abs_max"] = "abs_max") -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): the gate/up GEMM of an NVFP4 (W4A4) expert layer with silu(gate) * up, the rotation h and the NVFP4 quantizer fused into
+    its epilogue, ONE launch.  For well-formed offs the result equals, byte for byte in every row below offs[E-1], the chain
+
+        fusedSiluMulQuantizeNvGrouped(grouped_matmul_nvf4_bf16_tn(a, b, a_sf, b_sf, alpha, offs), h, global_scales, offs, method=method)
+
+    FOR ANY FINITE OPERANDS whenever that GEMM runs its 64x64 or 128x128 tile form -- everywhere but at most 16 rows per expert with K >= 8192 --: this kernel is built
+    on those tile bodies and keeps their MFMA order, alpha multiply and bf16 rounding per accumulator, and everything after the bf16 gate/up value -- activation,
+    rotation, group statistic, scale, codes -- is the quantizer's arithmetic bit for bit.  Where the GEMM's rule picks its wave-owned form instead, the equality holds
+    wherever the GEMM's fp32 sums do not depend on their order; OUTSIDE THAT REGIME a gate/up value may there differ from the chain's by one fp32 rounding before its
+    rounding to bf16.  The (M, 2 I) bf16 tensor between the launches is never written.  Operands as grouped_matmul_nvf4_bf16_tn's, with b (E, 2 I, K/2): rows [0, I) of
+    an expert the gate projection, rows [I, 2 I) the up projection.  h: the quantizer's rotation, bf16, 32 x 32 ONLY (other sizes: the launches above);
+    global_scales (E,) float32: the down projection's per-expert input scale, as in fusedSiluMulQuantizeNvGrouped (a row takes its tile's expert's; "quest" reads
+    none); method "quest" or "abs_max"; no blocked scales.  Returns (codes, scales): uint8 (M, I / 2) packed e2m1 and float8_e4m3fn (padded_rows, padded_cols) as
+    fusedQuantizeNv allocates them for an (M, I) tensor -- scales flat in the first M * I / 16 bytes -- so the pair is the down GEMM's A operand as it is.  Rows at or
+    past offs[E-1] are written in neither; both are allocated without a fill.  Outside the equality (never a fault): groups whose activations are not finite, and
+    malformed offs.  I % 32 == 0, K % 128 == 0, 1 <= E <= 1024; the sizes as the GEMM op's.  The offsets are read on the device: no host sync, graph-capturable,
+    traces under torch.compile.
+
+    A workgroup owns 64 token rows x 32 activation columns (up to a mean of 48 rows per expert) or 128 x 64 (beyond) -- the gate and the up weight rows of those
+    columns.  Measurements, and the cells where it loses: DESIGN.md section 8 item 21, profiles/bench_grouped_nvf4_act_mi355x.txt."""
+    _check_nvf4_act("grouped_matmul_nvf4_silu_nvf4_tn", a, b, a_sf, b_sf, alpha, offs, h, global_scales, method)
+    return _ops_amd.grouped_matmul_nvf4_act_nvf4(a, b, a_sf, b_sf, alpha, offs, 0, 1.0, 1.0, None, h, global_scales, _METHOD_CODE[method])
+
+
+def grouped_matmul_nvf4_swiglu_oai_nvf4_tn(a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, alpha: torch.Tensor, offs: torch.Tensor,
+                                           h: torch.Tensor, global_scales: torch.Tensor, *, method: Literal["quest", "abs_max"] = "abs_max", act_alpha: float = 1.702,
+                                           limit: float = 7.0, bias: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION (no reference counterpart): grouped_matmul_nvf4_silu_nvf4_tn with gpt-oss's clamped SwiGLU in place of silu * up.  For well-formed offs the result
+    equals, byte for byte in every row below offs[E-1] and under the same conditions, the three launches
+
+        y = grouped_matmul_nvf4_bf16_tn(a, b, a_sf, b_sf, alpha, offs)
+        fusedGatherQuantizeNvGrouped(swiglu_oai_and_mul(y, alpha=act_alpha, limit=limit, bias=bias, offs=offs), h, global_scales, arange(M), offs, method=method)
+
+    bias (E, 2 I) bf16 in the weight's [gate | up] halves, or None; the bias row is that of the tile's expert (for well-formed offs: the row's).  act_alpha finite
+    and > 0, limit > 0 and exact in bf16, as in swiglu_oai_and_mul.  Everything else -- operands, h, global_scales, method, results, the rows that are not written,
+    what lies outside the equality, the measurements -- as grouped_matmul_nvf4_silu_nvf4_tn."""
+    op = "grouped_matmul_nvf4_swiglu_oai_nvf4_tn"
+    _check_nvf4_act(op, a, b, a_sf, b_sf, alpha, offs, h, global_scales, method, bias)
+    act_alpha, limit = float(act_alpha), float(limit)
+    if not (act_alpha > 0 and act_alpha < float("inf")):
+        raise ValueError(f"{op}: act_alpha must be finite and > 0 (got {act_alpha})")
+    if not (limit > 0 and limit < float("inf") and _bf16_exact(limit)):
+        raise ValueError(f"{op}: limit must be > 0, finite and exactly representable in bf16 (got {limit})")
+    return _ops_amd.grouped_matmul_nvf4_act_nvf4(a, b, a_sf, b_sf, alpha, offs, 1, act_alpha, limit, bias, h, global_scales, _METHOD_CODE[method])
 
 
 def _check_w4a6_operands(op: str, a: torch.Tensor, b: torch.Tensor, a_sf: torch.Tensor, b_sf: torch.Tensor, b_dim: int) -> None:

@@ -27,6 +27,7 @@ SYMBOLS = {
     "qutlass_amd_grouped_matmul_mxf8_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_mxf8_mxf4_act_mxf8_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_mxf4_act_mxf4_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "qutlass_amd_grouped_matmul_nvf4_act_nvf4_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_mxf6_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_bf16_mxf4_act_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "qutlass_amd_grouped_matmul_bf16_mxf4_bf16_tn": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),

@@ -34,6 +34,7 @@
 #include "gemm_nvf4_os.hip.h"
 #include "gemm_nvf4_os_w4a16.hip.h"
 #include "gemm_nvf4_os_w4a16_act.hip.h"
+#include "gemm_nvf4_act.hip.h"
 #include "quantize.hip.h"
 #include "moe_route.hip.h"
 #include "to_blocked.hip.h"
@@ -848,6 +849,52 @@ int launch_grouped_bf16_nvf4_act(int v, int act, const W4A16ActParams& q, hipStr
   if (act == ACT_SILU) return go(std::integral_constant<int, ACT_SILU>{});
   if (act == ACT_OAI) return go(std::integral_constant<int, ACT_OAI>{});
   return go(std::integral_constant<int, ACT_OAI_BIAS>{});
+}
+#else
+;
+#endif
+
+// ---- gate/up NVFP4 GEMM (W4A4) with fused activation, rotation and NVFP4 output (gemm_nvf4_act.hip.h) ------------------------------------------------------------------
+// Forms: 624 = 64 rows x 32 activation columns on form 600's 64x64 body, 625 = 128 x 64 on form 601's 128x128 body (a workgroup owns the gate AND the up weight rows of
+// its columns).  N is the weight's 2 I rows.  Started from the chain's GEMM rule (grouped_nv_plan without its wave-owned corner) -- 624 up to a mean of 48 rows per
+// expert, 625 beyond -- so that the op runs the tile body the chain's GEMM runs and the two agree bit for bit.  Measured with both forms forced on the gate/up cells of
+// gpt-oss-20b / 120b, Qwen3-30B-A3B and Mixtral-8x7B and on a sweep of 16 ... 128 rows per expert at K = 768 ... 3328 (profiles/calib_grouped_nvf4_act.txt, the first
+// kernel; the forced columns of profiles/bench_grouped_nvf4_act_mi355x.txt, the final one): 624 leads in every cell up to 48 rows (gpt-oss-20b decode 85.4 us against
+// 117.9; 48 rows at K = 3328: 198.4 against 220.1), 625 in every cell from 64 rows (K = 768: 70.0 against 80.1; K = 3328: 229.7 against 271.2; Mixtral prefill 2032
+// against 3034).  The refit leaves the rule where it started; no miss above 1 % among the 44 cells of either take.  Nothing was measured between 48 and 64 rows.
+inline int grouped_nvf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int cus) {
+  (void)N; (void)K; (void)cus;
+  return M <= 48 * E ? 624 : 625;
+}
+// form GRP_NVF4_ACT.form0 + I with activation ACT and quantizer METHOD
+template <int I, int ACT, int METHOD>
+int launch_grouped_nvf4_act_tile(NvActParams q, hipStream_t s) {
+  constexpr const GroupedFormat& F = GRP_NVF4_ACT;
+  using C = NvActCfg<F.tile[I].tm>;
+  static_assert(C::TM == F.tile[I].tm && C::TN == F.tile[I].tn, "forms 624 / 625");
+  q.tiles_m = 1;
+  q.tiles_n = (int)cdiv(q.inter, C::TN);
+  const dim3 grid((int)grouped_workgroups(q.M, q.inter, q.E, C::TM, C::TN)), block(C::THREADS);
+  hipLaunchKernelGGL((gemm_nvf4_act_kernel<C, ACT, METHOD>), grid, block, 0, s, q);
+  return check_launch("gemm_nvf4_act_kernel");
+}
+// form v of the fused op, act = ACT_SILU / ACT_OAI / ACT_OAI_BIAS, method = METHOD_QUEST / METHOD_ABSMAX (quantize.hip.h); its 12 kernels ride in the MXFP8 variants'
+// unit (3), the shortest of the GEMM units (README, build line)
+int launch_grouped_nvf4_act(int v, int act, int method, const NvActParams& q, hipStream_t s)
+#if QAMD_DEF(3)
+{
+  constexpr const GroupedFormat& F = GRP_NVF4_ACT;
+  static_assert(F.nforms == 2 && F.ebits == 4 && F.ebits_b == 0 && F.sgroup == 16, "the two forms of the fused gate/up NVFP4 kernel");
+  if (v != F.form0 && v != F.form0 + 1) return fail(QAMD_ERR_INVALID, "%s: unknown form %d", F.name, v);
+  const bool big = v == F.form0 + 1;
+  auto go = [&](auto a, auto m) {
+    constexpr int A = decltype(a)::value, Mth = decltype(m)::value;
+    return big ? launch_grouped_nvf4_act_tile<1, A, Mth>(q, s) : launch_grouped_nvf4_act_tile<0, A, Mth>(q, s);
+  };
+  auto by_method = [&](auto a) { return method == METHOD_QUEST ? go(a, std::integral_constant<int, METHOD_QUEST>{}) : go(a, std::integral_constant<int, METHOD_ABSMAX>{}); };
+  if (act == ACT_SILU) return by_method(std::integral_constant<int, ACT_SILU>{});
+  if (act == ACT_OAI) return by_method(std::integral_constant<int, ACT_OAI>{});
+  return by_method(std::integral_constant<int, ACT_OAI_BIAS>{});
 }
 #else
 ;
@@ -2283,6 +2330,41 @@ int qutlass_amd_grouped_matmul_bf16_nvf4_act_bf16_tn(const void* A, const void* 
   return launch_grouped_bf16_nvf4_act(grouped_form(F, grouped_bf16_nvf4_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI, q, (hipStream_t)stream);
 }
 
+// the gate/up NVFP4 GEMM whose output is the down GEMM's A operand: everything of the fused MXFP4 entry (A_sf / B_sf row-major e4m3, one per 16), plus global_scales (E,)
+// float32, the down projection's per-expert input scale as fusedSiluMulQuantizeNvGrouped takes it (read by method abs_max only); out_e2m1 (M, I / 2) e2m1, out_e4m3 flat
+// (M, I / 16)
+int qutlass_amd_grouped_matmul_nvf4_act_nvf4_tn(const void* A, const void* B, const void* A_sf, const void* B_sf, const float* alpha, int64_t n_alpha,
+                                                const int32_t* offs, int act, float act_alpha, float limit, const void* bias, const void* h, int h_size,
+                                                const float* global_scales, int method, void* out_e2m1, void* out_e4m3, int64_t M, int64_t N, int64_t K, int64_t E,
+                                                void* stream) {
+  constexpr const GroupedFormat& F = GRP_NVF4_ACT;
+  if (!out_e4m3 || !h || !global_scales) return fail(QAMD_ERR_INVALID, "%s: null pointer argument", F.name);
+  if (int rc = grouped_check(F, F.name, A, B, A_sf, B_sf, alpha, n_alpha, offs, out_e2m1, M, N, K, E)) return rc;
+  if (N % 64) return fail(QAMD_ERR_INVALID, "%s: N = 2 * I must be a multiple of 64, whole rotation blocks of 32 activation columns (got %lld)", F.name, (long long)N);
+  if (h_size != 32)
+    return fail(QAMD_ERR_INVALID, "%s: rotation size %d is not supported; expected 32 (use grouped_matmul_nvf4_bf16_tn followed by the fused activation quantizer)", F.name, h_size);
+  if (int rc = quant_check_method(F.name, method)) return rc;
+  if (act != 0 && act != 1) return fail(QAMD_ERR_INVALID, "%s: invalid act %d; expected 0 (silu) or 1 (swiglu_oai)", F.name, act);
+  if ((uintptr_t)out_e2m1 % 4) return fail(QAMD_ERR_INVALID, "%s: out_e2m1 must be 4-byte aligned", F.name);
+  if ((uintptr_t)h % 2) return fail(QAMD_ERR_INVALID, "%s: the rotation matrix must be 2-byte aligned", F.name);
+  if ((uintptr_t)global_scales % 4) return fail(QAMD_ERR_INVALID, "%s: global_scales must be 4-byte aligned", F.name);
+  NvActParams q{};
+  if (act == 1) {
+    if (int rc = swiglu_oai_act(F.name, act_alpha, limit, q.oai)) return rc;
+    if (bias) {
+      if (int rc = swiglu_oai_check_bias(F.name, bias, offs, E)) return rc;
+      if (E * N >= (1ll << 30)) return fail(QAMD_ERR_INVALID, "%s: bias (E * N * 2 = %lld bytes) must stay below 2 GiB", F.name, (long long)(E * N * 2));
+    }
+  } else if (bias) {
+    return fail(QAMD_ERR_INVALID, "%s: act 0 (silu) takes no bias", F.name);
+  }
+  if (M == 0) return QAMD_OK;
+  grouped_fill(q, F, A, B, A_sf, B_sf, alpha, n_alpha, offs, out_e2m1, M, N, K, E);
+  q.codes = (uint8_t*)out_e2m1; q.out_sf = (uint8_t*)out_e4m3; q.bias = (const uint16_t*)bias; q.h = (const uint16_t*)h; q.gscale = global_scales; q.inter = (int)(N / 2);
+  return launch_grouped_nvf4_act(grouped_form(F, grouped_nvf4_act_plan, M, N, K, E), act == 0 ? ACT_SILU : bias ? ACT_OAI_BIAS : ACT_OAI,
+                                 method == QAMD_METHOD_QUEST ? METHOD_QUEST : METHOD_ABSMAX, q, (hipStream_t)stream);
+}
+
 // ---- grouped NVFP4 GEMM (gemm_nvf4.hip.h, gemm_nvf4_os.hip.h; the kernels live in the NVFP4 unit: launch_nvf4_grouped) -----------------------------------------------
 // Forms: 598 = 32x32 tiles of the wave-owned kernel, 599 = its 64x32 tiles, 600 = 64x64 tiles, 601 = 128x128 tiles of gemm_nvf4_kernel with row-major scale fetch.
 // Measured on the decode and prefill shapes of Qwen3-30B-A3B and Mixtral-8x7B and on token counts between them (profiles/calib_grouped_nvf4_r7.txt; these are not the MX
@@ -3302,6 +3384,18 @@ int qutlass_amd_debug_grouped_bf16_nvf4_act_plan(int64_t M, int64_t N, int64_t K
   const int v = debug_grouped_plan(F, "debug_grouped_bf16_nvf4_act_plan", grouped_bf16_nvf4_act_plan, M, N, K, E, nullptr);
   if (v < 0 || N % 64) return -1;
   if (out) out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
+  return v;
+}
+// grouped_matmul_nvf4_act_nvf4_tn: 624 = 64 rows x 32 activation columns, 625 = 128 x 64; N = 2 I, so the workgroups are counted over I = N / 2 columns:
+// out[0] = (cdiv(M, TM) + E) * cdiv(I, TN); out[1] = the smallest K that fills the K loop's ring once
+int qutlass_amd_debug_grouped_nvf4_act_plan(int64_t M, int64_t N, int64_t K, int64_t E, int64_t* out) {
+  constexpr const GroupedFormat& F = GRP_NVF4_ACT;
+  const int v = debug_grouped_plan(F, "debug_grouped_nvf4_act_plan", grouped_nvf4_act_plan, M, N, K, E, nullptr);
+  if (v < 0 || N % 64) return -1;
+  if (out) {
+    out[0] = M == 0 ? 0 : grouped_grid(F, v, M, N / 2, E);
+    out[1] = nvf4_act_ring_k();
+  }
   return v;
 }
 // grouped_matmul_nvf4_bf16_tn: 598 / 599 = 32x32 / 64x32 tiles of the wave-owned kernel, 600 / 601 = 64x64 / 128x128 tiles of the tile kernel

@@ -70,6 +70,9 @@ constexpr GroupedFormat GRP_BF16_MXF4_ACT{"grouped_matmul_bf16_mxf4_act_bf16_tn"
 constexpr GroupedFormat GRP_BF16_NVF4{"grouped_matmul_bf16_nvf4_bf16_tn", 620, 16, 16, {{32, 32}, {64, 32}, {0, 0}, {0, 0}}, 2, 4};
 // gate/up W4A16 on NVFP4 weights with fused activation and bf16 output (gemm_nvf4_os_w4a16_act.hip.h): two forms, the tile width counts ACTIVATION columns as above
 constexpr GroupedFormat GRP_BF16_NVF4_ACT{"grouped_matmul_bf16_nvf4_act_bf16_tn", 622, 16, 16, {{32, 32}, {64, 32}, {0, 0}, {0, 0}}, 2, 4};
+// gate/up NVFP4 (W4A4) with fused activation, rotation and NVFP4 output (gemm_nvf4_act.hip.h): two forms on the 64x64 / 128x128 tile bodies of forms 600 / 601, the tile
+// width counts ACTIVATION columns as above
+constexpr GroupedFormat GRP_NVF4_ACT{"grouped_matmul_nvf4_act_nvf4_tn", 624, 4, 16, {{64, 32}, {128, 64}, {0, 0}, {0, 0}}, 2};
 // workgroups of a grouped launch: (m-tile slots cdiv(M, TM) + E) x column tiles -- the host's upper bound of the real tiles (grouped_tile: the rest return at once)
 constexpr int64_t grouped_workgroups(int64_t M, int64_t N, int64_t E, int TM, int TN) { return ((M + TM - 1) / TM + E) * ((N + TN - 1) / TN); }
 

@@ -499,6 +499,54 @@ std::tuple<Tensor, Tensor> grouped_matmul_mxf4_act_mxf4(const Tensor& A, const T
   return {codes, scales};
 }
 
+// EXTENSION: the gate/up NVFP4 (W4A4) grouped GEMM with fused activation, rotation and NVFP4 output (qutlass_amd_grouped_matmul_nvf4_act_nvf4_tn) -- A, B (E, 2 I, K/2), the
+// scales, alpha, offs as grouped_matmul_nvf4's; act, act_alpha, limit, bias, h, method as grouped_matmul_mxf4_act_mxf4's; global_scales (E,) float32 as
+// fusedSiluMulQuantizeNvGrouped_'s.  Allocates, without a fill, the codes (M, I / 2) uint8 and the scales as fusedQuantizeNv allocates them for an (M, I) tensor.
+std::tuple<Tensor, Tensor> grouped_matmul_nvf4_act_nvf4(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha, const Tensor& offs,
+                                                        int64_t act, double act_alpha, double limit, std::optional<Tensor> bias, const Tensor& h, const Tensor& global_scales,
+                                                        int64_t method) {
+  const char* op = "grouped_matmul_nvf4_act_nvf4";
+  check_tensors(op, {{A, "A"}, {B, "B"}, {A_sf, "A_sf"}, {B_sf, "B_sf"}, {alpha, "alpha"}, {offs, "offs"}, {h, "h"}, {global_scales, "global_scales"}});
+  STD_TORCH_CHECK(has_dtype(A, ScalarType::Byte) || has_dtype(A, ScalarType::Float4_e2m1fn_x2), op, ": A must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(B, ScalarType::Byte) || has_dtype(B, ScalarType::Float4_e2m1fn_x2), op, ": B must be uint8 or float4_e2m1fn_x2");
+  STD_TORCH_CHECK(has_dtype(A_sf, ScalarType::Float8_e4m3fn), op, ": A_sf must be float8_e4m3fn");
+  STD_TORCH_CHECK(has_dtype(B_sf, ScalarType::Float8_e4m3fn), op, ": B_sf must be float8_e4m3fn");
+  STD_TORCH_CHECK(A.dim() == 2 && B.dim() == 3, op, ": A must be 2D (M, K/2) and B 3D (E, 2I, K/2)");
+  STD_TORCH_CHECK(A.size(1) == B.size(2), op, ": inner dimensions must match for A @ B[g].T");
+  const int64_t M = A.size(0), E = B.size(0), N = B.size(1), K = A.size(1) * 2, kb = K / 16, I = N / 2;
+  STD_TORCH_CHECK(N > 0 && N % 64 == 0, op, ": B must have 2 * I rows per expert with I a multiple of 32 (got ", N, ")");
+  STD_TORCH_CHECK(E >= 1 && E <= 1024, op, ": the number of experts must be in [1, 1024] (got ", E, ")");
+  STD_TORCH_CHECK(has_dtype(offs, ScalarType::Int) && offs.numel() == E, op, ": offs must be an int32 tensor of E = ", E, " elements");
+  STD_TORCH_CHECK(has_dtype(alpha, ScalarType::Float) && (alpha.numel() == 1 || alpha.numel() == E), op, ": alpha must be a float32 tensor of 1 or E = ", E, " elements");
+  STD_TORCH_CHECK(has_dtype(global_scales, ScalarType::Float) && global_scales.numel() == E, op, ": global_scales must be a float32 tensor of E = ", E, " elements");
+  STD_TORCH_CHECK(A_sf.numel() >= M * kb, op, ": A_sf has ", A_sf.numel(), " elements, the row-major scale layout of A needs ", M * kb);
+  STD_TORCH_CHECK(B_sf.numel() >= E * N * kb, op, ": B_sf has ", B_sf.numel(), " elements, the row-major scale layout of B needs ", E * N * kb);
+  STD_TORCH_CHECK(has_dtype(h, ScalarType::BFloat16), op, ": h must be bf16");
+  STD_TORCH_CHECK(h.dim() == 2 && h.size(0) == h.size(1), op, ": h must be a square matrix");
+  STD_TORCH_CHECK(act == 0 || act == 1, op, ": act must be 0 (silu) or 1 (swiglu_oai)");
+  STD_TORCH_CHECK(method == QAMD_METHOD_QUEST || method == QAMD_METHOD_ABSMAX, op, ": method must be 0 (quest) or 1 (abs_max)");
+  const void* bp = nullptr;
+  if (bias) {
+    STD_TORCH_CHECK(act == 1, op, ": act 0 (silu) takes no bias");
+    const Named a{A, "A"};
+    check_tensors(op, {{*bias, "bias"}}, {}, true, &a);
+    STD_TORCH_CHECK(has_dtype(*bias, ScalarType::BFloat16), op, ": bias must be bf16");
+    STD_TORCH_CHECK(bias->dim() == 2 && bias->size(0) == E && bias->size(1) == N, op, ": bias must be (E, 2I) = (", E, ", ", N, ")");
+    bp = bias->data_ptr();
+  }
+  Tensor codes = torch::stable::new_empty(A, {M, I / 2}, ScalarType::Byte);
+  Tensor scales = torch::stable::new_empty(A_sf, {(M + 127) / 128 * 128, (I / 16 + 3) / 4 * 4});   // (no 8-bit float ScalarType in the stable ABI: A_sf's e4m3)
+  STD_TORCH_CHECK(h.size(0) == 32, op, ": rotation size ", h.size(0), " is not supported; expected 32 (use grouped_matmul_nvf4 followed by the fused activation quantizer)");
+  if (M == 0) return {codes, scales};   // empty batch: nothing to launch
+
+  const torch::stable::accelerator::DeviceGuard guard(A.get_device_index());
+  check_rc(qutlass_amd_grouped_matmul_nvf4_act_nvf4_tn(A.data_ptr(), B.data_ptr(), A_sf.data_ptr(), B_sf.data_ptr(), static_cast<const float*>(alpha.data_ptr()), alpha.numel(),
+                                                       static_cast<const int32_t*>(offs.data_ptr()), (int)act, (float)act_alpha, (float)limit, bp, h.data_ptr(), (int)h.size(0),
+                                                       static_cast<const float*>(global_scales.data_ptr()), (int)method, codes.data_ptr(), scales.data_ptr(), M, N, K, E,
+                                                       current_stream(A)));
+  return {codes, scales};
+}
+
 Tensor matmul_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_ada_mxf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::ADA_MXF4>(A, B, A_sf, B_sf, alpha); }
 Tensor matmul_nvf4_bf16_tn(const Tensor& A, const Tensor& B, const Tensor& A_sf, const Tensor& B_sf, const Tensor& alpha) { return matmul<Gemm::NVF4>(A, B, A_sf, B_sf, alpha); }
@@ -1166,6 +1214,7 @@ STABLE_TORCH_LIBRARY_FRAGMENT(qutlass_amd, m) {
   m.def("grouped_matmul_bf16_mxf4_act_bf16(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias, Tensor? src_row) -> Tensor");   // W4A16 gate/up with fused activation, inference op: in the minimal library too
   m.def("grouped_matmul_mxf8_mxf4_act_mxf8(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias) -> (Tensor, Tensor)");   // W4A8 gate/up with fused activation, inference op: in the minimal library too
   m.def("grouped_matmul_mxf4_act_mxf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias, Tensor h, int method) -> (Tensor, Tensor)");   // W4A4 gate/up with fused activation, inference op: in the minimal library too
+  m.def("grouped_matmul_nvf4_act_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias, Tensor h, Tensor global_scales, int method) -> (Tensor, Tensor)");   // NVFP4 W4A4 gate/up with fused activation, inference op: in the minimal library too
   m.def("grouped_matmul_nvf4(Tensor A, Tensor B, Tensor A_sf, Tensor B_sf, Tensor alpha, Tensor offs) -> Tensor");   // inference op: in the minimal library too
   m.def("grouped_matmul_bf16_nvf4_bf16_tn(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, Tensor? src_row) -> Tensor");   // W4A16 on NVFP4 weights, inference op: in the minimal library too
   m.def("grouped_matmul_bf16_nvf4_act_bf16(Tensor A, Tensor B, Tensor B_sf, Tensor alpha, Tensor offs, int act, float act_alpha, float limit, Tensor? bias, Tensor? src_row) -> Tensor");   // its gate/up form with fused activation, inference op: in the minimal library too
@@ -1252,6 +1301,7 @@ STABLE_TORCH_LIBRARY_IMPL(qutlass_amd, CompositeExplicitAutograd, m) {
   m.impl("grouped_matmul_mxf4_act_mxf4", TORCH_BOX(&grouped_matmul_mxf4_act_mxf4));             // its rejections are tests/test_grouped_mxf4_act_cpu.py's
   m.impl("grouped_matmul_bf16_nvf4_bf16_tn", TORCH_BOX(&grouped_matmul_bf16_nvf4));             // its rejections are tests/test_grouped_bf16_nvf4_cpu.py's
   m.impl("grouped_matmul_bf16_nvf4_act_bf16", TORCH_BOX(&grouped_matmul_bf16_nvf4_act_bf16));   // its rejections are tests/test_grouped_bf16_nvf4_act_cpu.py's
+  m.impl("grouped_matmul_nvf4_act_nvf4", TORCH_BOX(&grouped_matmul_nvf4_act_nvf4));             // its rejections are tests/test_grouped_nvf4_act_cpu.py's
 }
 
 // `import qutlass._CUDA` (reference: include/registration.h REGISTER_EXTENSION(_CUDA), bindings.cpp:537-540): an empty module

@@ -123,6 +123,11 @@ def _register_fakes() -> None:
         M, I = A.size(0), B.size(1) // 2
         return A.new_empty((M, I // 2), dtype=torch.uint8), A.new_empty(padded_scale_shape(M, I, 32), dtype=torch.float8_e8m0fnu)
 
+    @rf("qutlass_amd::grouped_matmul_nvf4_act_nvf4")
+    def _(A, B, A_sf, B_sf, alpha, offs, act, act_alpha, limit, bias, h, global_scales, method):   # the codes (M, I / 2) and the scales fusedQuantizeNv allocates for (M, I)
+        M, I = A.size(0), B.size(1) // 2
+        return A.new_empty((M, I // 2), dtype=torch.uint8), A.new_empty(padded_scale_shape(M, I, 16), dtype=torch.float8_e4m3fn)
+
     def routed(logits, topk, num_experts):   # the one-launch routing ops allocate their five results, like the grouped GEMMs: weights, ids, src_row, offs, pos
         T, i32 = logits.size(0), torch.int32
         return (logits.new_empty((T, topk), dtype=torch.float32), logits.new_empty((T, topk), dtype=i32), logits.new_empty((T * topk,), dtype=i32),
